@@ -2,17 +2,21 @@
 """bench.py - headline benchmark of the MI355X NDT scan matcher (driver contract).
 
     python bench.py --gpus N --steps K --warmup W           # any N: for N > 1 this process starts its own N ranks
+    python bench.py --gpus 1 --steps K --warmup W --full    # N = 1: every leg beside the headline as well
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 ... bench.py --gpus N ...
 
-Metric (BASELINE.json): NDT Gauss-Newton iterations/sec @ 1M-point target, plus the
-converged-pose error against the CPU reference (here: this repo's oracle - the reference
-implementation is unavailable, /root/reference/README.md:1).
+Metric (BASELINE.json): NDT Gauss-Newton iterations/sec @ 1M-point target, plus (with --full)
+the converged-pose error against the CPU reference (here: this repo's oracle - the reference
+implementation is unavailable).
 
 N = 1  value = BASELINE config 3: one pair, 1M-point submap target vs 100k-point scan.
        A step = one alignment of fixed K_GN = 30 Gauss-Newton iterations with the target grid
-       cached and all inputs resident in HBM (the grid build is timed separately and
-       reported as grid_build).  value = steps * 30 / elapsed.  The line also carries, under
-       `batch`, the single-GPU figure of BASELINE config 4 (512 candidate pairs x 100k points).
+       cached and all inputs resident in HBM.  value = steps * 30 / elapsed.  A plain run sets
+       up, warms up, times the steps and prints the line, nothing else.  With --full the line
+       also carries the grid build (grid_build), the converged-pose error against the oracle,
+       the CPU baseline, the multi-start / multi-scan chains, the stream-copy ceiling and, under
+       `batch`, the single-GPU figure of BASELINE config 4 (512 candidate pairs x 100k points),
+       config 5 (3D) and configs 1 and 2.
 N > 1  one process per GPU (RCCL).  A single alignment does not shard, so
        `value` is the N = 1 workload as one independent replica per GPU ("value_kind": "replicas":
        linear by construction, it exercises no multi-GPU code).  The path that DOES shard is in
@@ -20,12 +24,17 @@ N > 1  one process per GPU (RCCL).  A single alignment does not shard (DESIGN.md
        over the ranks with no data-path collective and ONE RCCL all_gather of the result rows
        inside every timed step.  batch.value = pair-iterations of all ranks / max-over-ranks
        time: read the 1 -> 8 scaling of the multi-GPU path from batch.value against the N = 1
-       line's batch.value.
+       --full line's batch.value.  --full changes nothing at N > 1.
 
 Started without WORLD_SIZE in the environment and with --gpus N > 1, this script launches
 `python -m torch.distributed.run --nproc-per-node N` on itself as a CHILD process before any
 GPU call, relays rank 0's JSON line and exits with the child's code (a process that has
 touched the GPU is never re-executed).
+
+--dump-outputs DIR writes what the timed path returned in its last step, the AlignResult of the
+config-3 alignment (rank 0's replica at N > 1), as DIR/<field>.npy in float64 for the fields pose,
+H, g, score, iterations, n_hit and status, right after the timed steps.  The inputs are seeded,
+so two builds can be compared file for file.
 
 One JSON line is printed by rank 0.  roofline / cpu_baseline are described in DESIGN.md section 7.
 """
@@ -55,6 +64,12 @@ def parse():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=50)
     ap.add_argument("--warmup", type=int, default=5)
+    ap.add_argument("--full", action="store_true",
+                    help="N=1: also run every leg beside the headline (grid build, parity against the oracle, CPU baselines, "
+                         "batches, 3D, multi-start / multi-scan, configs 1-2, stream-copy ceiling); the options below that "
+                         "add or drop legs apply to this run")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the last step's result as DIR/<field>.npy (float64)")
     ap.add_argument("--pairs-per-rank", type=int, default=512)
     ap.add_argument("--batch-points", type=int, default=100_000)
     ap.add_argument("--no-cpu-baseline", action="store_true")
@@ -84,6 +99,8 @@ def parse():
     ap.add_argument("--force-dist", action="store_true",
                     help="rehearsal: run the N>1 code path (process group + all_gather) even with one rank")
     a = ap.parse_args()
+    if a.gpus == 1 and not a.full and (a.all_configs or a.host_path or a.converged_batch):
+        ap.error("--all-configs, --host-path and --converged-batch add legs to the --full run: give --full as well")
     if a.headline_only:
         a.no_latency = True
         a.no_batch_4096 = True
@@ -868,6 +885,15 @@ def run_batch_3d(a, dev, dev_index, n_pairs=256, check=True):
                                  "(DESIGN.md section 5.5)"}}
 
 
+def dump_outputs(path: str, r) -> None:
+    """--dump-outputs: the AlignResult of the timed path's last step, one float64 .npy per field (a few hundred bytes)."""
+    os.makedirs(path, exist_ok=True)
+    fields = {"pose": r.pose, "H": r.H, "g": r.g, "score": [r.score], "iterations": [r.iterations], "n_hit": [r.n_hit],
+              "status": [r.status]}
+    for name, v in fields.items():
+        np.save(os.path.join(path, f"{name}.npy"), np.asarray(v, dtype=np.float64))
+
+
 def free_port() -> int:
     import socket
     with socket.socket(socket.AF_INET, socket.SOCK_STREAM) as s:
@@ -887,8 +913,11 @@ def self_launch(a) -> int:
             print(f"bench.py: --gpus {a.gpus} but only {have} device(s) visible "
                   "(a one-GPU rehearsal of the N > 1 flow needs --rehearse-on-one-gpu)", file=sys.stderr)
             return 2
+    argv = sys.argv[1:]
+    if a.dump_outputs:                 # the ranks run from the repository root: the directory goes to them as an absolute path
+        argv = [*argv, "--dump-outputs", os.path.abspath(a.dump_outputs)]
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", f"--nproc-per-node={a.gpus}",
-           "--master-addr", "127.0.0.1", "--master-port", str(free_port()), os.path.abspath(__file__), *sys.argv[1:]]
+           "--master-addr", "127.0.0.1", "--master-port", str(free_port()), os.path.abspath(__file__), *argv]
     env = dict(os.environ)
     env.setdefault("HSA_ENABLE_IPC_MODE_LEGACY", "0")        # dmabuf IPC only on this pool (RCCL needs it)
     line = None
@@ -907,6 +936,106 @@ def self_launch(a) -> int:
         return 1
     print(line, flush=True)
     return 0
+
+
+def full_legs(a, out, d, tx, ty, sx, sy, dev, dev_index, barrier):
+    """--full, N = 1: every leg beside the config-3 headline, added to `out` after the timed steps (none of them touches
+    the headline's figures): parity against the oracle and the converged-mode latency, the multi-start / multi-scan
+    chains, the host-pointer path, the CPU baseline, the config-4 batches, config 5, configs 1 and 2, the --all-configs
+    legs and the stream-copy ceiling."""
+    from gtsam_ndt_amd.matcher import NdtMatcher2D
+    # converged-pose error vs the CPU oracle (outside the timed region)
+    from oracle import ndt2d as oracle
+    rc = ref = perr = conv_ms = relaxed = None
+    if not a.headline_only:
+        mc = NdtMatcher2D(device=dev_index)
+        mc.set_target(tx, ty)
+        rc = mc.align(sx, sy, d["init"])
+        # what a caller sees per scan in converged mode: host call -> result on the host
+        lat = []
+        for _ in range(0 if a.no_latency else 20):
+            t1 = time.perf_counter(); rl = mc.align(sx, sy, d["init"]); lat.append(time.perf_counter() - t1)
+            assert rl.pose == rc.pose
+        conv_ms = 1e3 * float(np.median(lat)) if lat else None
+        mc.close()
+        if not a.no_latency:
+            # the same call with over-relaxed steps (params.step_scale = 3, DESIGN.md section 2.5)
+            mr = NdtMatcher2D(device=dev_index, step_scale=3.0)
+            mr.set_target(tx, ty)
+            lat = []
+            for _ in range(20):
+                t1 = time.perf_counter(); rr = mr.align(sx, sy, d["init"]); lat.append(time.perf_counter() - t1)
+            mr.close()
+            relaxed = {"step_scale": 3.0, "ms_per_call": round(1e3 * float(np.median(lat)), 4), "iterations": rr.iterations,
+                       "status": rr.status,
+                       "pose_diff_vs_plain": [abs(u - v) for u, v in zip(rr.pose, rc.pose)]}
+        prm = oracle.NdtParams()
+        ref = oracle.align(oracle.build_grid(d["tx"], d["ty"], prm), d["sx"], d["sy"], d["init"], prm)
+        perr = np.abs(np.array(rc.pose) - np.array(ref["pose"]))
+    out["converged_align"] = None if rc is None else {
+        "ms_per_call": None if conv_ms is None else round(conv_ms, 4), "iterations": rc.iterations,
+        "note": "ndt2d_align_dev in converged mode, host call to result in host memory "
+                "(8-launch chunks, progress and done flag written to pinned host memory); median of 20",
+        "relaxed": relaxed}
+    out["pose_err_vs_cpu_ref"] = None if perr is None else {
+        "dx_m": float(perr[0]), "dy_m": float(perr[1]), "dtheta_rad": float(perr[2]),
+        "gpu_iterations": rc.iterations, "cpu_iterations": ref["iterations"],
+        "cpu_ref": "oracle/ndt2d.py float64 (reference implementation unavailable)"}
+    if not a.headline_only:
+        out["multi_start"] = {
+            "note": "the same 1M-point target and 100k-point scan, m starts per launch chain (ndt2d_align_multi_start_dev); "
+                    "reported beside the single-start headline, never instead of it; bytes = N x (8 + 24 m)",
+            "runs": [multi_start_rate(dev_index, tx, ty, sx, sy, d["init"], mm_, max(5, a.steps // 2), a.warmup)
+                     for mm_ in [int(v) for v in a.multi_starts.split(",") if v]]}
+    if not a.headline_only:
+        out["multi_scan"] = {
+            "note": "the same 1M-point target, m different 100k-point scans per launch chain (ndt2d_align_multi_scan_dev); "
+                    "beside the single-scan headline, never instead of it; bytes = m x N x 32 B",
+            "runs": [multi_scan_rate(dev, dev_index, tx, ty, mm_, max(5, a.steps // 2), a.warmup) for mm_ in (8, 64)]}
+    if a.host_path:
+        mh = NdtMatcher2D(device=dev_index, fixed_iterations=K_GN)
+        lt, la = [], []
+        for _ in range(5):
+            t1 = time.perf_counter(); mh.set_target(d["tx"], d["ty"]); lt.append(time.perf_counter() - t1)
+        for _ in range(10):
+            t1 = time.perf_counter(); rh = mh.align(d["sx"], d["sy"], d["init"]); la.append(time.perf_counter() - t1)
+        mh.close()
+        assert rh.iterations == K_GN
+        out["host_path"] = {"set_target_ms_incl_pcie": round(1e3 * float(np.median(lt[1:])), 4),
+                            "align_ms_incl_pcie": round(1e3 * float(np.median(la[1:])), 4),
+                            "iters_per_s_incl_pcie": round(K_GN / float(np.median(la[1:])), 1),
+                            "note": "ndt2d_set_target / ndt2d_align with pageable host arrays (8 MB / 0.8 MB "
+                                    "uploads included); reported beside value, never as value"}
+    if not a.no_cpu_baseline:
+        out["cpu_baseline"] = cpu_baseline(d, a.cpu_seconds)
+    if not a.no_batch:
+        out["batch"] = run_batch(a, dev, dev_index, 0, 1, None, barrier)
+        if a.converged_batch:
+            out["batch_converged"] = run_batch(a, dev, dev_index, 0, 1, None, barrier, steps=max(3, min(a.steps, 10)), converged=True)
+        if not a.no_batch_4096:
+            # all 4096 candidates of BASELINE config 4 on this one GPU (6.55 GB resident): the
+            # anchor for reading the N > 1 lines (512 pairs per GPU) as strong scaling as well
+            out["batch_4096"] = run_batch(a, dev, dev_index, 0, 1, None, barrier, ppr=4096, steps=max(3, min(a.steps, 10)))
+    if not a.no_3d:
+        out["3d"] = run_3d(a, dev, dev_index)
+        out["batch_3d"] = run_batch_3d(a, dev, dev_index, check=not a.headline_only)   # profile mode: timed launches only
+    # the other single-pair configs of BASELINE.json beside the headline (parity-test cases; cheap to time)
+    if not a.headline_only:
+        out["configs_1_2"] = [single_pair_rate(dev, dev_index, c, a.steps, a.warmup) for c in (1, 2)]
+    if a.all_configs:
+        out["batch_lidar_sized"] = lidar_batch_rate(dev, dev_index)
+        out["batch_overlap_grids"] = overlap_batch_rate(dev, dev_index)
+        out["grid_build_ordered"] = ordered_build_leg(dev, dev_index)
+        # the same kernel with enough work per launch to leave the latency regime: a 1M-point source
+        out["config3_with_1M_point_source"] = single_pair_rate(dev, dev_index, 3, max(5, a.steps // 5), 2, n_src=1_000_000)
+        if not a.no_3d:
+            out["scan_loop_3d"] = scan_loop_3d(dev, dev_index)
+    copy_peak = stream_copy_GBps(dev)
+    out["roofline"]["stream_copy_GBps"] = round(copy_peak, 1)
+    out["roofline"]["frac_of_stream_copy"] = round(out["roofline"]["achieved"] / copy_peak, 4)
+    if "batch" in out:
+        out["batch"]["roofline"]["stream_copy_GBps"] = round(copy_peak, 1)
+        out["batch"]["roofline"]["frac_of_stream_copy"] = round(out["batch"]["roofline"]["achieved"] / copy_peak, 4)
 
 
 def main():
@@ -953,8 +1082,8 @@ def main():
         tx, ty, sx, sy = (torch.from_numpy(d[k]).to(dev) for k in ("tx", "ty", "sx", "sy"))
         torch.cuda.synchronize()
         m = NdtMatcher2D(device=dev_index, fixed_iterations=K_GN)
-        grid_build, submap_update = build_legs(m, tx, ty, sx, sy, d["pose"])
-        grid_ms = grid_build["ms_per_call"]
+        if a.full:
+            grid_build, submap_update = build_legs(m, tx, ty, sx, sy, d["pose"])
         m.set_target(tx, ty)                   # (the timed alignments run against the plain 1M-point submap again)
         n_src = int(sx.numel())
 
@@ -971,6 +1100,8 @@ def main():
         barrier()
         elapsed = time.perf_counter() - t0
         assert r.iterations == K_GN
+        if a.dump_outputs:
+            dump_outputs(a.dump_outputs, r)
         iters = a.steps * K_GN
         launches = a.steps * (K_GN + 1)
         value = iters / elapsed
@@ -987,34 +1118,6 @@ def main():
                     "avg_launch_us": round(launch_us, 3),
                     "timing": "HIP events on the handle's stream over the timed region / launches "
                               "(kernel + launch boundary)"}
-        # converged-pose error vs the CPU oracle (outside the timed region)
-        from oracle import ndt2d as oracle
-        rc = ref = perr = conv_ms = relaxed = None
-        if not a.headline_only:
-            mc = NdtMatcher2D(device=dev_index)
-            mc.set_target(tx, ty)
-            rc = mc.align(sx, sy, d["init"])
-            # what a caller sees per scan in converged mode: host call -> result on the host
-            lat = []
-            for _ in range(0 if a.no_latency else 20):
-                t1 = time.perf_counter(); rl = mc.align(sx, sy, d["init"]); lat.append(time.perf_counter() - t1)
-                assert rl.pose == rc.pose
-            conv_ms = 1e3 * float(np.median(lat)) if lat else None
-            mc.close()
-            if not a.no_latency:
-                # the same call with over-relaxed steps (params.step_scale = 3)
-                mr = NdtMatcher2D(device=dev_index, step_scale=3.0)
-                mr.set_target(tx, ty)
-                lat = []
-                for _ in range(20):
-                    t1 = time.perf_counter(); rr = mr.align(sx, sy, d["init"]); lat.append(time.perf_counter() - t1)
-                mr.close()
-                relaxed = {"step_scale": 3.0, "ms_per_call": round(1e3 * float(np.median(lat)), 4), "iterations": rr.iterations,
-                           "status": rr.status,
-                           "pose_diff_vs_plain": [abs(u - v) for u, v in zip(rr.pose, rc.pose)]}
-            prm = oracle.NdtParams()
-            ref = oracle.align(oracle.build_grid(d["tx"], d["ty"], prm), d["sx"], d["sy"], d["init"], prm)
-            perr = np.abs(np.array(rc.pose) - np.array(ref["pose"]))
         out = {
             "metric": METRIC, "value": round(value, 1), "unit": "iters/s", "n_gpus": 1,
             "steps": a.steps, "warmup": a.warmup, "ms_per_step": round(1e3 * elapsed / a.steps, 4),
@@ -1025,78 +1128,17 @@ def main():
                        "n_target": int(tx.numel()), "n_source": n_src, "cell_size": 0.5,
                        "gn_iterations_per_step": K_GN, "hessian": "gauss-newton"},
             "roofline": roofline,
-            "grid_build_ms": round(grid_ms, 4),
-            "grid_build": grid_build,
-            "submap_update": submap_update,
-            "submap_update_ms": submap_update["ms_per_call"],
-            "converged_align": None if rc is None else {"ms_per_call": None if conv_ms is None else round(conv_ms, 4), "iterations": rc.iterations,
-                                "note": "ndt2d_align_dev in converged mode, host call to result in host memory "
-                                        "(8-launch chunks, progress and done flag written to pinned host memory); median of 20",
-                                "relaxed": relaxed},
             "scaling_note": "N > 1 lines carry this workload as one independent replica per GPU in `value` (a single "
                             "alignment does not shard) and the sharded loop-closure batch of config 4 in `batch`: "
                             "read value against value and batch.value against batch.value.",
-            "pose_err_vs_cpu_ref": None if perr is None else {
-                "dx_m": float(perr[0]), "dy_m": float(perr[1]), "dtheta_rad": float(perr[2]),
-                "gpu_iterations": rc.iterations, "cpu_iterations": ref["iterations"],
-                "cpu_ref": "oracle/ndt2d.py float64 (reference implementation unavailable)"},
         }
         m.close()
-        if not a.headline_only:
-            out["multi_start"] = {
-                "note": "the same 1M-point target and 100k-point scan, m starts per launch chain (ndt2d_align_multi_start_dev); "
-                        "reported beside the single-start headline, never instead of it; bytes = N x (8 + 24 m)",
-                "runs": [multi_start_rate(dev_index, tx, ty, sx, sy, d["init"], mm_, max(5, a.steps // 2), a.warmup)
-                         for mm_ in [int(v) for v in a.multi_starts.split(",") if v]]}
-        if not a.headline_only:
-            out["multi_scan"] = {
-                "note": "the same 1M-point target, m different 100k-point scans per launch chain (ndt2d_align_multi_scan_dev); "
-                        "beside the single-scan headline, never instead of it; bytes = m x N x 32 B",
-                "runs": [multi_scan_rate(dev, dev_index, tx, ty, mm_, max(5, a.steps // 2), a.warmup) for mm_ in (8, 64)]}
-        if a.host_path:
-            mh = NdtMatcher2D(device=dev_index, fixed_iterations=K_GN)
-            lt, la = [], []
-            for _ in range(5):
-                t1 = time.perf_counter(); mh.set_target(d["tx"], d["ty"]); lt.append(time.perf_counter() - t1)
-            for _ in range(10):
-                t1 = time.perf_counter(); rh = mh.align(d["sx"], d["sy"], d["init"]); la.append(time.perf_counter() - t1)
-            mh.close()
-            assert rh.iterations == K_GN
-            out["host_path"] = {"set_target_ms_incl_pcie": round(1e3 * float(np.median(lt[1:])), 4),
-                                "align_ms_incl_pcie": round(1e3 * float(np.median(la[1:])), 4),
-                                "iters_per_s_incl_pcie": round(K_GN / float(np.median(la[1:])), 1),
-                                "note": "ndt2d_set_target / ndt2d_align with pageable host arrays (8 MB / 0.8 MB "
-                                        "uploads included); reported beside value, never as value"}
-        if not a.no_cpu_baseline:
-            out["cpu_baseline"] = cpu_baseline(d, a.cpu_seconds)
-        if not a.no_batch:
-            out["batch"] = run_batch(a, dev, dev_index, 0, 1, None, barrier)
-            if a.converged_batch:
-                out["batch_converged"] = run_batch(a, dev, dev_index, 0, 1, None, barrier, steps=max(3, min(a.steps, 10)), converged=True)
-            if not a.no_batch_4096:
-                # all 4096 candidates of BASELINE config 4 on this one GPU (6.55 GB resident): the
-                # anchor for reading the N > 1 lines (512 pairs per GPU) as strong scaling as well
-                out["batch_4096"] = run_batch(a, dev, dev_index, 0, 1, None, barrier, ppr=4096, steps=max(3, min(a.steps, 10)))
-        if not a.no_3d:
-            out["3d"] = run_3d(a, dev, dev_index)
-            out["batch_3d"] = run_batch_3d(a, dev, dev_index, check=not a.headline_only)   # profile mode: timed launches only
-        # the other single-pair configs of BASELINE.json beside the headline (parity-test cases; cheap to time)
-        if not a.headline_only:
-            out["configs_1_2"] = [single_pair_rate(dev, dev_index, c, a.steps, a.warmup) for c in (1, 2)]
-        if a.all_configs:
-            out["batch_lidar_sized"] = lidar_batch_rate(dev, dev_index)
-            out["batch_overlap_grids"] = overlap_batch_rate(dev, dev_index)
-            out["grid_build_ordered"] = ordered_build_leg(dev, dev_index)
-            # the same kernel with enough work per launch to leave the latency regime: a 1M-point source
-            out["config3_with_1M_point_source"] = single_pair_rate(dev, dev_index, 3, max(5, a.steps // 5), 2, n_src=1_000_000)
-            if not a.no_3d:
-                out["scan_loop_3d"] = scan_loop_3d(dev, dev_index)
-        copy_peak = stream_copy_GBps(dev)
-        out["roofline"]["stream_copy_GBps"] = round(copy_peak, 1)
-        out["roofline"]["frac_of_stream_copy"] = round(out["roofline"]["achieved"] / copy_peak, 4)
-        if "batch" in out:
-            out["batch"]["roofline"]["stream_copy_GBps"] = round(copy_peak, 1)
-            out["batch"]["roofline"]["frac_of_stream_copy"] = round(out["batch"]["roofline"]["achieved"] / copy_peak, 4)
+        if a.full:
+            out["grid_build_ms"] = round(grid_build["ms_per_call"], 4)
+            out["grid_build"] = grid_build
+            out["submap_update"] = submap_update
+            out["submap_update_ms"] = submap_update["ms_per_call"]
+            full_legs(a, out, d, tx, ty, sx, sy, dev, dev_index, barrier)
     else:
         # N > 1.  A single alignment is never split across GPUs (it would need an all-reduce per ~5 us iteration,
         # DESIGN.md section 8), so the line's `value` is the headline workload as ONE INDEPENDENT REPLICA PER GPU - the
@@ -1127,6 +1169,8 @@ def main():
         barrier()
         elapsed = nd.max_over_ranks(time.perf_counter() - t0, device=dev)
         assert r.iterations == K_GN and r.status == 0
+        if a.dump_outputs and rank == 0:
+            dump_outputs(a.dump_outputs, r)          # rank 0's replica: the same files as the N = 1 line
         m.close()
         launch_us = 1e3 * ev_ms / (a.steps * (K_GN + 1))
         alg_bytes = n_src * BYTES_PER_POINT_ITER

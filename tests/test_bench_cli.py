@@ -30,3 +30,12 @@ def test_bench_without_a_gpu_fails_instead_of_measuring_something_else():
                        capture_output=True, text=True, timeout=300, env=env, cwd=ROOT)
     assert r.returncode != 0
     assert '"metric"' not in r.stdout
+
+
+def test_bench_extra_legs_need_full():
+    """--all-configs / --host-path / --converged-batch add to the --full run: a plain N = 1 run refuses them before it
+    touches a device instead of quietly dropping them."""
+    for flag in ("--all-configs", "--host-path", "--converged-batch"):
+        r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "1", "--warmup", "0", flag],
+                           capture_output=True, text=True, timeout=300, cwd=ROOT)
+        assert r.returncode == 2 and "--full" in r.stderr and '"metric"' not in r.stdout

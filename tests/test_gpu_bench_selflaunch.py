@@ -25,8 +25,11 @@ def _run(extra):
     return json.loads(lines[0])
 
 
-def test_bench_starts_its_own_ranks(gpu_lib):
-    out = _run(["--converged-batch"])
+def test_bench_starts_its_own_ranks(gpu_lib, tmp_path):
+    out = _run(["--converged-batch", "--dump-outputs", str(tmp_path / "out")])
+    import numpy as np
+    pose, its = np.load(tmp_path / "out" / "pose.npy"), np.load(tmp_path / "out" / "iterations.npy")   # rank 0's replica
+    assert pose.dtype == np.float64 and pose.shape == (3,) and its.tolist() == [30.0]
     assert out["n_gpus"] == 2 and out["steps"] == 2 and out["warmup"] == 1
     assert out["metric"].startswith("NDT Gauss-Newton iters/sec") and out["unit"] == "iters/s"
     assert out["config"]["replicas"] == 2 and out["value"] > 0 and "replicas" in out["value_kind"]
