@@ -98,6 +98,16 @@ class MapHeader(C.Structure):
 MAP_MAGIC = 0x4d54444e
 
 
+class SearchWindow2D(C.Structure):
+    """ndt2d_search_window: the (x, y, theta) lattice of an exhaustive pose search and the hits' separation."""
+    _fields_ = [("center", C.c_double * 3), ("half_extent", C.c_double * 3), ("step", C.c_double * 3),
+                ("min_sep_trans", C.c_double), ("min_sep_rot", C.c_double)]
+
+
+class SearchHit2D(C.Structure):
+    _fields_ = [("pose", C.c_double * 3), ("score", C.c_float), ("index", C.c_int32)]
+
+
 class Result3D(C.Structure):
     _fields_ = [("pose", C.c_double * 6), ("H", C.c_double * 36), ("g", C.c_double * 6), ("score", C.c_double),
                 ("iterations", C.c_int32), ("n_hit", C.c_int32), ("status", C.c_int32), ("reserved", C.c_int32)]
@@ -147,6 +157,14 @@ SIGNATURES = {
     "ndt2d_align_trace": (C.c_int32, [_vp, _vp, _vp, C.c_size_t, _dp, _vp, C.c_int32, C.POINTER(C.c_int32), _vp]),
     "ndt2d_align_multi_scan_dev": (C.c_int32, [_vp, _vp, _vp, _vp, _vp, C.c_int32, _vp]),
     "ndt2d_align_multi_start_dev": (C.c_int32, [_vp, _vp, _vp, C.c_size_t, _vp, C.c_int32, _vp]),
+    "ndt2d_search_lattice_size": (C.c_int32, [C.POINTER(SearchWindow2D), _vp]),
+    "ndt2d_search": (C.c_int32, [_vp, _vp, _vp, C.c_size_t, C.POINTER(SearchWindow2D), C.c_int32, _vp,
+                                 C.POINTER(C.c_int32)]),
+    "ndt2d_search_dev": (C.c_int32, [_vp, _vp, _vp, C.c_size_t, C.POINTER(SearchWindow2D), C.c_int32, _vp,
+                                     C.POINTER(C.c_int32)]),
+    "ndt2d_search_scores_dev": (C.c_int32, [_vp, _vp, _vp, C.c_size_t, C.POINTER(SearchWindow2D), _vp]),
+    "ndt2d_search_align_dev": (C.c_int32, [_vp, _vp, _vp, C.c_size_t, C.POINTER(SearchWindow2D), C.c_int32, _vp, _vp,
+                                           C.POINTER(C.c_int32)]),
     "ndt2d_stream": (_vp, [_vp]),
     "ndt2d_set_tuning": (C.c_int32, [_vp, C.c_int32, C.c_int64]),
     "ndt2d_batch_set_tuning": (C.c_int32, [_vp, C.c_int32, C.c_int64]),

@@ -18,6 +18,7 @@ from dataclasses import dataclass
 import numpy as np
 
 from . import _lib as L
+from .search import SearchHit
 
 
 @dataclass
@@ -92,6 +93,7 @@ class NdtMatcher2D:
         h = C.c_void_p()
         L.check(self._lib.ndt2d_create(C.byref(self.params), int(device), C.byref(h)), "ndt2d_create")
         self._h = h
+        self._device = int(device)
         self._keep = None
         for k, v in (tuning or {}).items():
             self.set_tuning(k, v)
@@ -260,6 +262,70 @@ class NdtMatcher2D:
         L.check(self._lib.ndt2d_align_multi_scan_dev(self._h, px, py, nn, poses.ctypes.data, m, C.cast(out, C.c_void_p)),
                 "ndt2d_align_multi_scan_dev")
         return [_to_result(r) for r in out]
+
+    # ---- exhaustive pose search over an (x, y, theta) window (ndt2d_search_*; gtsam_ndt_amd/search.py restates it)
+    @staticmethod
+    def _window(center, half_extent, step, min_sep=(0.0, 0.0)) -> L.SearchWindow2D:
+        w = L.SearchWindow2D()
+        for a in range(3):
+            w.center[a], w.half_extent[a], w.step[a] = float(center[a]), float(half_extent[a]), float(step[a])
+        w.min_sep_trans, w.min_sep_rot = float(min_sep[0]), float(min_sep[1])
+        return w
+
+    def _on_device(self, sx, sy):
+        """(sx, sy) as CUDA tensors on the handle's device (numpy arrays are uploaded), after wait_stream."""
+        if not _is_dev(sx):
+            import torch
+            sx = torch.from_numpy(_host_f32(sx)).to(f"cuda:{self._device}")
+            sy = torch.from_numpy(_host_f32(sy)).to(f"cuda:{self._device}")
+        self.wait_stream()
+        return sx, sy
+
+    def search(self, sx, sy, center, half_extent, step, k: int = 8, min_sep=(0.5, 0.1)):
+        """The best k (1..64) well-separated peaks of the NDT score over the lattice of the window (ndt2d_search /
+        ndt2d_search_dev): a list of SearchHit, best first."""
+        w = self._window(center, half_extent, step, min_sep)
+        hits = (L.SearchHit2D * max(int(k), 1))()
+        nh = C.c_int32(0)
+        if _is_dev(sx):
+            n = sx.numel()
+            self.wait_stream()
+            st = self._lib.ndt2d_search_dev(self._h, _dev_ptr(sx, n), _dev_ptr(sy, n), n, C.byref(w), int(k),
+                                            C.cast(hits, C.c_void_p), C.byref(nh))
+        else:
+            sx, sy = _host_f32(sx), _host_f32(sy)
+            st = self._lib.ndt2d_search(self._h, sx.ctypes.data, sy.ctypes.data, sx.size, C.byref(w), int(k),
+                                        C.cast(hits, C.c_void_p), C.byref(nh))
+        L.check(st, "ndt2d_search")
+        return [SearchHit(tuple(h.pose), float(h.score), int(h.index)) for h in hits[:nh.value]]
+
+    def search_scores(self, sx, sy, center, half_extent, step):
+        """The score volume of the window's lattice (ndt2d_search_scores_dev): a float32 CUDA tensor [n_theta, n_y, n_x]."""
+        import torch
+        w = self._window(center, half_extent, step)
+        dims = (C.c_int32 * 3)()
+        L.check(self._lib.ndt2d_search_lattice_size(C.byref(w), C.cast(dims, C.c_void_p)), "ndt2d_search_lattice_size")
+        sx, sy = self._on_device(sx, sy)
+        out = torch.empty(tuple(dims), dtype=torch.float32, device=sx.device)
+        n = sx.numel()
+        L.check(self._lib.ndt2d_search_scores_dev(self._h, _dev_ptr(sx, n), _dev_ptr(sy, n), n, C.byref(w),
+                                                  C.c_void_p(out.data_ptr())), "ndt2d_search_scores_dev")
+        return out
+
+    def search_align(self, sx, sy, center, half_extent, step, k: int = 8, min_sep=(0.5, 0.1)):
+        """search(), then align_multi_start() from the hits' poses (ndt2d_search_align_dev): a list of
+        (SearchHit, AlignResult), best lattice score first."""
+        w = self._window(center, half_extent, step, min_sep)
+        hits = (L.SearchHit2D * max(int(k), 1))()
+        res = (L.Result2D * max(int(k), 1))()
+        nh = C.c_int32(0)
+        sx, sy = self._on_device(sx, sy)
+        n = sx.numel()
+        L.check(self._lib.ndt2d_search_align_dev(self._h, _dev_ptr(sx, n), _dev_ptr(sy, n), n, C.byref(w), int(k),
+                                                 C.cast(hits, C.c_void_p), C.cast(res, C.c_void_p), C.byref(nh)),
+                "ndt2d_search_align_dev")
+        return [(SearchHit(tuple(h.pose), float(h.score), int(h.index)), _to_result(r))
+                for h, r in zip(hits[:nh.value], res[:nh.value])]
 
     def align_async(self, sx, sy, init_pose=(0.0, 0.0, 0.0), producer_complete: bool = False):
         """Enqueue the whole loop on the handle's stream (device tensors only).  producer_complete=True:

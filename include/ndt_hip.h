@@ -243,6 +243,50 @@ int32_t ndt2d_align_trace(ndt2d_handle* h, const float* sx, const float* sy, siz
  * workgroup), every start still bit for bit its single alignment with the option. */
 int32_t ndt2d_align_multi_start_dev(ndt2d_handle* h, const float* d_sx, const float* d_sy, size_t n,
                                     const double* init_poses, int32_t m, ndt2d_result* results);
+/* Exhaustive pose search (docs/ALGORITHM.md "Exhaustive pose search"): the NDT score of the scan at every pose of an
+ * (x, y, theta) lattice around a poor guess, against the cached grid, then the best well-separated peaks - for a
+ * loop-closure candidate whose odometry has drifted by metres, or a robot relocalising in a map.
+ * Lattice: n_x = 2 floor(hx/sx + 1e-9) + 1 poses at cx + i sx, i = -(n_x-1)/2 .. (n_x-1)/2, the same for y and for
+ * theta when h_theta < pi; h_theta >= pi is a full turn: n_theta = max(1, floor(2 pi/s_theta + 0.5)) headings c_theta + j 2pi/n_theta,
+ * j = 0 .. n_theta-1, a cyclic axis.  Headings are wrapped to (-pi, pi].  Flat index ((j n_y) + iy) n_x + ix; at most
+ * 2^25 poses (NDT_ERR_CAPACITY above).  The score at a pose is the score ndt2d_evaluate_dev reports there (the same
+ * float32 terms per point, summed in another order; overlap_grids honoured).
+ * Peaks: score > 0 and beating every in-window neighbour of the 3x3x3 block (higher score, or equal score and lower
+ * index; theta wraps on a cyclic axis only).  Hits: the best min(#peaks, 4096) peaks by (score desc, index asc),
+ * walked in that order; a peak is dropped when an accepted hit lies closer than min_sep_trans in translation AND
+ * closer than min_sep_rot in wrapped heading; at most k (1..64) hits.  Deterministic: the same inputs give the same
+ * volume and hits bit for bit.  A window that misses the map returns NDT_OK with *n_hits = 0. */
+typedef struct ndt2d_search_window {
+  double center[3];       /* x, y, theta of the lattice's middle pose */
+  double half_extent[3];  /* metres, metres, radians (>= 0; 0 pins the axis); theta >= pi: a full turn */
+  double step[3];         /* lattice step per axis, > 0 */
+  double min_sep_trans;   /* hits closer than this in translation ... */
+  double min_sep_rot;     /* ... AND in rotation than an accepted hit are dropped (both >= 0) */
+} ndt2d_search_window;
+
+typedef struct ndt2d_search_hit {
+  double pose[3];         /* lattice pose, theta wrapped to (-pi, pi] */
+  float score;            /* the lattice score (float32, as in the volume) */
+  int32_t index;          /* flat lattice index */
+} ndt2d_search_hit;
+
+/* dims = n_theta, n_y, n_x of the window's lattice (CPU only; the same validation as the searches) */
+int32_t ndt2d_search_lattice_size(const ndt2d_search_window* w, int32_t dims[3]);
+/* hits[0 .. *n_hits) (hits has room for k), best first.  Synchronous in the hits (host memory). */
+int32_t ndt2d_search_dev(ndt2d_handle* h, const float* d_sx, const float* d_sy, size_t n,
+                         const ndt2d_search_window* w, int32_t k, ndt2d_search_hit* hits, int32_t* n_hits);
+/* the same with a host scan */
+int32_t ndt2d_search(ndt2d_handle* h, const float* sx, const float* sy, size_t n,
+                     const ndt2d_search_window* w, int32_t k, ndt2d_search_hit* hits, int32_t* n_hits);
+/* the score volume itself into d_scores (device memory, n_theta x n_y x n_x floats, flat index order); returns once
+ * it is written */
+int32_t ndt2d_search_scores_dev(ndt2d_handle* h, const float* d_sx, const float* d_sy, size_t n,
+                                const ndt2d_search_window* w, float* d_scores);
+/* ndt2d_search_dev, then ndt2d_align_multi_start_dev from the hits' poses: results[i] is bit for bit what
+ * ndt2d_align_multi_start_dev returns for those poses (results has room for k) */
+int32_t ndt2d_search_align_dev(ndt2d_handle* h, const float* d_sx, const float* d_sy, size_t n,
+                               const ndt2d_search_window* w, int32_t k, ndt2d_search_hit* hits,
+                               ndt2d_result* results, int32_t* n_hits);
 /* Execution-strategy knobs of a handle.  They choose between kernels that compute the same alignment
  * (results agree up to float32 summation order; the tests pin each pair of choices against each other
  * and against the oracle); the defaults are the measured best, nothing reads the environment.

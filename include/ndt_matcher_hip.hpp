@@ -196,6 +196,51 @@ class NdtMatcherHip {
     for (const ndt2d_result& q : r) out.push_back(to_match_result(q, mode_));
     return out;
   }
+  // Exhaustive pose search over an (x, y, theta) window against the cached grid (ndt2d_search_dev; lattice, peaks and
+  // separation: ndt_hip.h): the best k (1..64) well-separated lattice poses, best first.  For a loop-closure candidate
+  // or a relocalisation whose guess is metres and tens of degrees off, where alignDev's basin (about one cell) is too
+  // narrow.  producer_stream as in alignMultiStartDev.
+  struct SearchHit {
+    Pose2 pose;            // the lattice pose, theta wrapped to (-pi, pi]
+    float score = 0.f;     // the lattice score
+    int32_t index = 0;     // flat lattice index
+  };
+  struct SearchMatch {
+    SearchHit hit;
+    MatchResult result;    // alignMultiStartDev's result from hit.pose
+  };
+  std::vector<SearchHit> searchDev(const float* d_sx, const float* d_sy, size_t n, const ndt2d_search_window& window, int k,
+                                   void* producer_stream, bool complete = false) {
+    if (!complete) check(ndt2d_wait_stream(h_, producer_stream), "ndt2d_wait_stream");
+    std::vector<ndt2d_search_hit> hits(k > 0 ? (size_t)k : 1);
+    int32_t n_hits = 0;
+    check(ndt2d_search_dev(h_, d_sx, d_sy, n, &window, (int32_t)k, hits.data(), &n_hits), "ndt2d_search_dev");
+    std::vector<SearchHit> out;
+    for (int32_t i = 0; i < n_hits; ++i) out.push_back(to_search_hit(hits[i]));
+    return out;
+  }
+  // searchDev, then one alignment from every hit in one launch chain (ndt2d_search_align_dev): result i is bit for bit
+  // what alignMultiStartDev returns from the hits' poses.  The best match is usually the converged result of highest
+  // score.
+  std::vector<SearchMatch> searchAlignDev(const float* d_sx, const float* d_sy, size_t n, const ndt2d_search_window& window,
+                                          int k, void* producer_stream, bool complete = false) {
+    if (!complete) check(ndt2d_wait_stream(h_, producer_stream), "ndt2d_wait_stream");
+    std::vector<ndt2d_search_hit> hits(k > 0 ? (size_t)k : 1);
+    std::vector<ndt2d_result> r(hits.size());
+    int32_t n_hits = 0;
+    check(ndt2d_search_align_dev(h_, d_sx, d_sy, n, &window, (int32_t)k, hits.data(), r.data(), &n_hits),
+          "ndt2d_search_align_dev");
+    std::vector<SearchMatch> out;
+    for (int32_t i = 0; i < n_hits; ++i) out.push_back(SearchMatch{to_search_hit(hits[i]), to_match_result(r[i], mode_)});
+    return out;
+  }
+  static SearchHit to_search_hit(const ndt2d_search_hit& h) {
+    SearchHit s;
+    s.pose = {h.pose[0], h.pose[1], h.pose[2]};
+    s.score = h.score;
+    s.index = h.index;
+    return s;
+  }
   // one evaluation at a fixed pose, for callers with their own optimiser
   ndt2d_eval evaluate(const float* sx, const float* sy, size_t n, const Pose2& at) {
     const double p[3] = {at.x, at.y, at.theta};
