@@ -37,7 +37,7 @@ struct ndt2d_handle {
   unsigned int* d_bounds = nullptr;        // [4]
   int* d_counters = nullptr;               // [2] valid cells, overflowed cells
   unsigned long long* d_outside = nullptr; // [1]
-  void* h_small = nullptr;                 // pinned scratch (256 B: counter shards at 0, the outside count at 128)
+  void* h_small = nullptr;                 // pinned scratch (kSmallBytes: counter shards at 0, the outside count at 128, a flag)
   // staging for host-pointer entry points
   float* d_tx = nullptr; float* d_ty = nullptr; size_t tcap = 0;
   float* d_sx = nullptr; float* d_sy = nullptr; size_t scap = 0;
@@ -72,7 +72,7 @@ struct ndt2d_handle {
   unsigned char* d_acc2 = nullptr;
   int acc_parity = 0;
   bool acc_clean = false;                  // both halves known to be zero where the next build needs it
-  int publish_seq = 0;                     // k_build_publish's flag value of the build in flight (h_small + 192)
+  int publish_seq = 0;                     // k_build_publish's flag value of the build in flight (small_flag(h_small))
   // hipGraph of the launch chain (launch-bound inner loop: one replay instead of K+1 launches)
   ChainGraphCache graphs;
   hipGraphExec_t graph_exec = nullptr;     // the one ensure_graph selected last (owned by `graphs`)
@@ -127,18 +127,6 @@ int32_t check_params(const ndt2d_params* p) {
   return NDT_OK;
 }
 
-int32_t ensure_points(float** dx, float** dy, size_t* cap, size_t n) {
-  if (n <= *cap) return NDT_OK;
-  if (*dx) (void)hipFree(*dx);
-  if (*dy) (void)hipFree(*dy);
-  *dx = *dy = nullptr; *cap = 0;
-  const size_t want = n + n / 4 + 1024;
-  HIP_TRY(hipMalloc((void**)dx, want * sizeof(float)));
-  HIP_TRY(hipMalloc((void**)dy, want * sizeof(float)));
-  *cap = want;
-  return NDT_OK;
-}
-
 int blocks_for(size_t) { return kMaxBlocks; }   // one workgroup per CU, always (see k_iterate)
 
 // k_bounds ends in four same-address atomics per block (about 10 ns each, serialised): few blocks
@@ -186,45 +174,25 @@ bool plan_sorted(size_t n, long long ntile, SortPlan* sp) {
   }
 }
 
-int32_t ensure_sorted_buffers(ndt2d_handle* h, const SortPlan& sp, size_t ntile) {
-  const size_t need_pts = (size_t)sp.nchunks * sp.chunk, need_tab = ntile * (size_t)sp.nchunks;
-  if (need_pts > h->bxy_cap) {
-    if (h->d_bxy) (void)hipFree(h->d_bxy);
-    h->d_bxy = nullptr; h->bxy_cap = 0;
-    const size_t want = need_pts + need_pts / 4 + 4096;
-    HIP_TRY(hipMalloc((void**)&h->d_bxy, want * sizeof(float2)));
-    h->bxy_cap = want;
-  }
-  if (need_tab > h->table_cap) {
-    if (h->d_table) (void)hipFree(h->d_table);
-    h->d_table = nullptr; h->table_cap = 0;
-    const size_t want = need_tab + need_tab / 4 + 1024;
-    HIP_TRY(hipMalloc((void**)&h->d_table, want * sizeof(unsigned int)));
-    h->table_cap = want;
-  }
-  return NDT_OK;
-}
-
-// the buffers the workgroups that share a tile use (ndt2d_build_sorted.hpp: SplitBufs), sized for `tiles` tiles and n points
-int32_t ensure_split_buffers(ndt2d_handle* h, size_t n, int tiles, SplitBufs* sb) {
+// the chunk-sorted build's buffers for n points over `tiles` tiles: the sorted copy of the cloud, the run table and the
+// buffers the workgroups that share a tile use (ndt2d_build_sorted.hpp: SplitBufs)
+int32_t ensure_sorted_buffers(ndt2d_handle* h, const SortPlan& sp, size_t n, int tiles, SplitBufs* sb) {
+  const size_t need_pts = (size_t)sp.nchunks * sp.chunk, need_tab = (size_t)tiles * sp.nchunks;
+  HIP_TRY(grow(&h->d_bxy, &h->bxy_cap, need_pts, need_pts + need_pts / 4 + 4096));
+  HIP_TRY(grow(&h->d_table, &h->table_cap, need_tab, need_tab + need_tab / 4 + 1024));
   const size_t pool_entries = n < (size_t)tiles * kGatherSplit * kTileCells ? n : (size_t)tiles * kGatherSplit * kTileCells;
   const size_t off_touched = ((size_t)tiles + 1) * sizeof(unsigned int);
   const size_t off_part = (off_touched + (size_t)tiles * sizeof(unsigned int) + 15) / 16 * 16;
   const size_t off_pool = off_part + (size_t)tiles * kGatherSplit * sizeof(uint2);
   const size_t need = off_pool + (pool_entries + 1) * sizeof(CellAcc);
-  if (need > h->split_cap) {
-    if (h->d_split) (void)hipFree(h->d_split);
-    h->d_split = nullptr; h->split_cap = 0;
-    const size_t want = need + need / 4;
-    HIP_TRY(hipMalloc((void**)&h->d_split, want));
-    HIP_TRY(hipMemsetAsync(h->d_split, 0, want, h->stream));       // (the touched numbers must not start as garbage)
-    h->split_cap = want;
-    h->build_seq = 0;
-  }
-  if (++h->build_seq == 0u) {                                      // wrapped: start the numbers over
+  bool grew = false;
+  HIP_TRY(grow(&h->d_split, &h->split_cap, need, need + need / 4, &grew));
+  if (grew) h->build_seq = 0xFFFFFFFFu;                            // (the touched numbers must not start as garbage)
+  if (h->build_seq == 0xFFFFFFFFu) {                               // new memory, or the numbers would wrap: start them over
     HIP_TRY(hipMemsetAsync(h->d_split, 0, h->split_cap, h->stream));
-    h->build_seq = 1u;
+    h->build_seq = 0u;
   }
+  ++h->build_seq;
   sb->ticket = reinterpret_cast<unsigned int*>(h->d_split);
   sb->touched = reinterpret_cast<unsigned int*>(h->d_split + off_touched);
   sb->part = reinterpret_cast<uint2*>(h->d_split + off_part);
@@ -233,8 +201,8 @@ int32_t ensure_split_buffers(ndt2d_handle* h, size_t n, int tiles, SplitBufs* sb
   sb->seq = h->build_seq;
   // a tile is shared so that no workgroup sums much more than a CU's share of the cloud; clouds too small to fill the
   // chip are cut finer, down to 1024 points per workgroup
-  size_t sp = n / 200;
-  sb->split_points = (int)(sp < 1024 ? 1024 : (sp > (size_t)1 << 24 ? (size_t)1 << 24 : sp));
+  const size_t share = n / 200;
+  sb->split_points = (int)(share < 1024 ? 1024 : (share > (size_t)1 << 24 ? (size_t)1 << 24 : share));
   return NDT_OK;
 }
 
@@ -269,20 +237,81 @@ int launch_bounds_parts(ndt2d_handle* h, const float* d_x, const float* d_y, siz
 }
 
 // The read-back of a sorted build: k_build_publish writes `nwords` words from device memory into pinned host memory and
-// raises the flag at h_small + 192; the host spins on it.  If the flag does not come (a stream error, or a second of
-// silence), a plain copy after a stream synchronisation is the safety net.
-int32_t publish_and_wait(ndt2d_handle* h, const void* d_src, void* h_dst, int nwords) {
-  int* flag = reinterpret_cast<int*>(static_cast<char*>(h->h_small) + 192);
-  h->publish_seq = h->publish_seq == 0x7fffffff ? 1 : h->publish_seq + 1;
-  hipLaunchKernelGGL(k_build_publish, dim3(1), dim3(64), 0, h->stream, (const unsigned int*)d_src, (unsigned int*)h_dst, nwords, flag,
-                     h->publish_seq);
-  HIP_TRY(hipGetLastError());
+// raises the flag in h_small (publish_and_wait).  If the flag does not come, a plain copy after a stream synchronisation
+// is the safety net.
+int32_t read_back(ndt2d_handle* h, const void* d_src, void* h_dst, int nwords) {
+  int* flag = small_flag(h->h_small);
   bool seen = false;
-  const int want = h->publish_seq;
-  HIP_TRY(spin_until(h->stream, [&]() { return __atomic_load_n(flag, __ATOMIC_ACQUIRE) == want; }, &seen));
+  HIP_TRY(publish_and_wait(h->stream, &h->publish_seq, flag, [&](int seq) {
+    hipLaunchKernelGGL(k_build_publish, dim3(1), dim3(64), 0, h->stream, (const unsigned int*)d_src, (unsigned int*)h_dst, nwords, flag, seq);
+  }, &seen));
   if (!seen) {
     HIP_TRY(hipMemcpyAsync(h_dst, d_src, (size_t)nwords * 4, hipMemcpyDeviceToHost, h->stream));
     HIP_TRY(hipStreamSynchronize(h->stream));
+  }
+  return NDT_OK;
+}
+
+// The two binned builds below enqueue the same launches for a geometry the host knows (the grids of h->grid) and for one
+// the device decides in the same stream (set_target_single_sync); `tiles` is the grid's tile count or the launch bound.
+// They add the counter shards and the outside count into d_cnt and d_out.
+
+// Chunk-sorted build (ndt2d_build_sorted.hpp): sort every chunk of the cloud by tile, then one workgroup per tile gathers
+// its runs.  Host geometry: ga = {} (merge = add to the cached sums; the last grid's gather clears `clear_next`, the
+// accumulator half of the next build).  Device geometry: ga, whose chunk sort prologue decides it into ga.out.
+int32_t enqueue_sorted_build(ndt2d_handle* h, const float* d_x, const float* d_y, size_t n, const SortPlan& sp, const SplitBufs& sb,
+                             int tiles, bool merge, const MoveArgs& mv, const GeomArgs& ga, int* d_cnt, unsigned long long* d_out,
+                             unsigned int* clear_next) {
+  const GridDev& g = h->grid;
+  const GeomDev* dg = ga.out;
+  const int ngrid = dg ? 1 : g.ngrid;
+  const int ntx = dg ? 0 : (g.W + kTile - 1) >> kTileShift;
+  const int split = gather_split(n, tiles);
+  for (int q = 0; q < ngrid; ++q) {
+    const BinGeom bg = dg ? BinGeom{} : BinGeom{g.gx[q], g.gy[q], g.inv_c, g.W, g.H, ntx, tiles};
+    launch_chunk_sort(h, sp, d_x, d_y, n, bg, tiles, mv, q == 0 ? d_out : (unsigned long long*)nullptr, ga, sb);
+    hipLaunchKernelGGL(k_tile_gather, dim3(tiles, split), dim3(kGatherThreads), 0, h->stream, (const float2*)h->d_bxy,
+                       (const unsigned int*)h->d_table, sp.nchunks, sp.chunk, g, q, ntx, merge ? 1 : 0, h->prm.min_points,
+                       h->prm.eig_ratio, d_cnt, dg, (const GridDev*)ga.grid, sb, q == ngrid - 1 ? clear_next : (unsigned int*)nullptr);
+    HIP_TRY(hipGetLastError());
+  }
+  return NDT_OK;
+}
+
+// the round-1 binned build's scratch for n points over `tiles` tiles: the binned cloud and the tile tables
+int32_t ensure_binned_buffers(ndt2d_handle* h, size_t n, int tiles) {
+  HIP_TRY(grow({grow_buf(&h->d_bx), grow_buf(&h->d_by)}, &h->bcap, n, n + n / 4 + 1024));
+  const size_t tneed = 3 * (size_t)tiles + 4;
+  HIP_TRY(grow(&h->d_tiles, &h->tile_cap, tneed, tneed));
+  return NDT_OK;
+}
+
+// Round-1 binned build (ndt2d_build.hpp): per grid count -> scan -> scatter -> accumulate.  Host geometry: dg = null (merge =
+// add to the cached sums).  Device geometry: dg and dgrid, decided by k_geometry behind the caller's k_build_init, which
+// cleared the tile totals.
+int32_t enqueue_binned_build(ndt2d_handle* h, const float* d_x, const float* d_y, size_t n, int tiles, bool merge, const GeomDev* dg,
+                             const GridDev* dgrid, int* d_cnt, unsigned long long* d_out) {
+  const GridDev& g = h->grid;
+  const int ngrid = dg ? 1 : g.ngrid;
+  const int ntx = dg ? 0 : (g.W + kTile - 1) >> kTileShift;
+  // tile tables laid out for `tiles`: total[tiles] | start[tiles + 1] | cursor[tiles]
+  unsigned int* d_total = h->d_tiles;
+  unsigned int* d_start = h->d_tiles + tiles;
+  unsigned int* d_cursor = h->d_tiles + 2 * tiles + 1;
+  const size_t chunk = (size_t)kBinThreads * kBinPerThread;
+  size_t nb = (n + chunk - 1) / chunk;
+  if (nb > 1024) nb = 1024;
+  for (int q = 0; q < ngrid; ++q) {
+    const BinGeom bg = dg ? BinGeom{} : BinGeom{g.gx[q], g.gy[q], g.inv_c, g.W, g.H, ntx, tiles};
+    if (!dg) HIP_TRY(hipMemsetAsync(d_total, 0, tiles * sizeof(unsigned int), h->stream));
+    hipLaunchKernelGGL(k_tile_count, dim3((unsigned)nb), dim3(kBinThreads), tiles * sizeof(unsigned int), h->stream,
+                       d_x, d_y, n, bg, d_total, q == 0 ? d_out : (unsigned long long*)nullptr, dg);
+    hipLaunchKernelGGL(k_tile_scan, dim3(1), dim3(1024), 0, h->stream, d_total, d_start, d_cursor, dg ? 0 : tiles, dg);
+    hipLaunchKernelGGL(k_tile_scatter, dim3((unsigned)nb), dim3(kBinThreads), 2 * tiles * sizeof(unsigned int),
+                       h->stream, d_x, d_y, n, bg, d_cursor, h->d_bx, h->d_by, dg);
+    hipLaunchKernelGGL(k_tile_accumulate, dim3(tiles), dim3(kBinThreads), 0, h->stream, h->d_bx, h->d_by, d_start, g, q,
+                       ntx, merge ? 1 : 0, h->prm.min_points, h->prm.eig_ratio, d_cnt, dg, dgrid);
+    HIP_TRY(hipGetLastError());
   }
   return NDT_OK;
 }
@@ -299,34 +328,23 @@ int32_t accumulate_and_finalise(ndt2d_handle* h, const float* d_x, const float* 
   const long long ntile_ll = (long long)ntx * nty;
   SortPlan sp;
   if (h->use_binned_build && h->build_variant == 1 && ntile_ll <= kBinMaxTiles && plan_sorted(n, ntile_ll, &sp)) {
-    // chunk-sorted build: sort every chunk of the cloud by tile, then one workgroup per tile gathers its runs
     const int ntile = (int)ntile_ll;
-    { const int32_t es = ensure_sorted_buffers(h, sp, (size_t)ntile); if (es != NDT_OK) return es; }
     SplitBufs sb{};
-    { const int32_t es = ensure_split_buffers(h, n, ntile, &sb); if (es != NDT_OK) return es; }
-    const int split = gather_split(n, ntile);
+    { const int32_t es = ensure_sorted_buffers(h, sp, n, ntile, &sb); if (es != NDT_OK) return es; }
     if (!h->acc_clean) HIP_TRY(hipMemsetAsync(h->d_acc2, 0, 512, h->stream));      // (first build, or one that failed half-way)
     h->acc_clean = false;
     unsigned char* cur = h->d_acc2 + 256 * h->acc_parity;
     unsigned char* nxt = h->d_acc2 + 256 * (1 - h->acc_parity);
-    int* d_cnt = reinterpret_cast<int*>(cur);
-    unsigned long long* d_out = reinterpret_cast<unsigned long long*>(cur + 128);
     const MoveArgs none{1.f, 0.f, 0.f, 0.f, 0};
-    for (int q = 0; q < g.ngrid; ++q) {
-      BinGeom bg{g.gx[q], g.gy[q], g.inv_c, g.W, g.H, ntx, ntile};
-      launch_chunk_sort(h, sp, d_x, d_y, n, bg, ntile, move ? *move : none, q == 0 ? d_out : (unsigned long long*)nullptr,
-                        GeomArgs{}, sb);
-      hipLaunchKernelGGL(k_tile_gather, dim3(ntile, split), dim3(kGatherThreads), 0, h->stream, (const float2*)h->d_bxy, (const unsigned int*)h->d_table,
-                         sp.nchunks, sp.chunk, g, q, ntx, merge ? 1 : 0, h->prm.min_points, h->prm.eig_ratio, d_cnt,
-                         (const GeomDev*)nullptr, (const GridDev*)nullptr, sb,
-                         q == g.ngrid - 1 ? reinterpret_cast<unsigned int*>(nxt) : (unsigned int*)nullptr);
-      HIP_TRY(hipGetLastError());
-    }
+    { const int32_t bs = enqueue_sorted_build(h, d_x, d_y, n, sp, sb, ntile, merge, move ? *move : none, GeomArgs{},
+                                              reinterpret_cast<int*>(cur), reinterpret_cast<unsigned long long*>(cur + 128),
+                                              reinterpret_cast<unsigned int*>(nxt));
+      if (bs != NDT_OK) return bs; }
     h->last_ntile = ntile;
     int* hc = (int*)h->h_small;
     unsigned long long* ho = (unsigned long long*)((char*)h->h_small + 128);
     static_assert(ndt::kCountInts * sizeof(int) == 128, "the accumulator halves mirror h_small: counters at 0, outside at 128");
-    { const int32_t ps = publish_and_wait(h, cur, hc, 34); if (ps != NDT_OK) return ps; }   // counter shards + outside count
+    { const int32_t ps = read_back(h, cur, hc, 34); if (ps != NDT_OK) return ps; }   // counter shards + outside count
     h->acc_parity ^= 1;
     h->acc_clean = true;
     int n_valid_sum = 0, n_over_sum = 0;
@@ -338,8 +356,7 @@ int32_t accumulate_and_finalise(ndt2d_handle* h, const float* d_x, const float* 
   }
   // the other paths take the points as they are: move them into the map frame first
   if (move && move->use) {
-    const int32_t st = ensure_points(&h->d_tx, &h->d_ty, &h->tcap, n);
-    if (st != NDT_OK) return st;
+    HIP_TRY(grow({grow_buf(&h->d_tx), grow_buf(&h->d_ty)}, &h->tcap, n, n + n / 4 + 1024));
     hipLaunchKernelGGL(k_transform_points, dim3((unsigned)((n + kBlock - 1) / kBlock)), dim3(kBlock), 0, h->stream, d_x, d_y,
                        n, move->cs, move->sn, move->tx, move->ty, h->d_tx, h->d_ty);
     HIP_TRY(hipGetLastError());
@@ -348,42 +365,10 @@ int32_t accumulate_and_finalise(ndt2d_handle* h, const float* d_x, const float* 
   HIP_TRY(hipMemsetAsync(h->d_outside, 0, sizeof(unsigned long long), h->stream));
   if (h->use_binned_build && ntile_ll <= kBinMaxTiles && n <= 0xFFFFFFFFull) {
     const int ntile = (int)ntile_ll;
-    if (n > h->bcap) {
-      if (h->d_bx) (void)hipFree(h->d_bx);
-      if (h->d_by) (void)hipFree(h->d_by);
-      h->d_bx = h->d_by = nullptr; h->bcap = 0;
-      const size_t want = n + n / 4 + 1024;
-      HIP_TRY(hipMalloc((void**)&h->d_bx, want * sizeof(float)));
-      HIP_TRY(hipMalloc((void**)&h->d_by, want * sizeof(float)));
-      h->bcap = want;
-    }
-    const size_t tneed = 3 * (size_t)ntile + 4;
-    if (tneed > h->tile_cap) {
-      if (h->d_tiles) (void)hipFree(h->d_tiles);
-      h->d_tiles = nullptr; h->tile_cap = 0;
-      HIP_TRY(hipMalloc((void**)&h->d_tiles, tneed * sizeof(unsigned int)));
-      h->tile_cap = tneed;
-    }
-    unsigned int* d_total = h->d_tiles;
-    unsigned int* d_start = h->d_tiles + ntile;
-    unsigned int* d_cursor = h->d_tiles + 2 * ntile + 1;
+    { const int32_t es = ensure_binned_buffers(h, n, ntile); if (es != NDT_OK) return es; }
     HIP_TRY(hipMemsetAsync(h->d_counters, 0, ndt::kCountInts * sizeof(int), h->stream));
-    const size_t chunk = (size_t)kBinThreads * kBinPerThread;
-    size_t nb = (n + chunk - 1) / chunk;
-    if (nb > 1024) nb = 1024;
-    for (int q = 0; q < g.ngrid; ++q) {
-      BinGeom bg{g.gx[q], g.gy[q], g.inv_c, g.W, g.H, ntx, ntile};
-      HIP_TRY(hipMemsetAsync(d_total, 0, ntile * sizeof(unsigned int), h->stream));
-      hipLaunchKernelGGL(k_tile_count, dim3((unsigned)nb), dim3(kBinThreads), ntile * sizeof(unsigned int), h->stream,
-                         d_x, d_y, n, bg, d_total, q == 0 ? h->d_outside : (unsigned long long*)nullptr, (const GeomDev*)nullptr);
-      hipLaunchKernelGGL(k_tile_scan, dim3(1), dim3(1024), 0, h->stream, d_total, d_start, d_cursor, ntile, (const GeomDev*)nullptr);
-      hipLaunchKernelGGL(k_tile_scatter, dim3((unsigned)nb), dim3(kBinThreads), 2 * ntile * sizeof(unsigned int),
-                         h->stream, d_x, d_y, n, bg, d_cursor, h->d_bx, h->d_by, (const GeomDev*)nullptr);
-      hipLaunchKernelGGL(k_tile_accumulate, dim3(ntile), dim3(kBinThreads), 0, h->stream, h->d_bx, h->d_by, d_start, g, q,
-                         ntx, merge ? 1 : 0, h->prm.min_points, h->prm.eig_ratio, h->d_counters, (const GeomDev*)nullptr,
-                         (const GridDev*)nullptr);
-      HIP_TRY(hipGetLastError());
-    }
+    { const int32_t bs = enqueue_binned_build(h, d_x, d_y, n, ntile, merge, nullptr, nullptr, h->d_counters, h->d_outside);
+      if (bs != NDT_OK) return bs; }
     h->last_ntile = ntile;
     int* hc = (int*)h->h_small;
     unsigned long long* ho = (unsigned long long*)((char*)h->h_small + 128);
@@ -406,6 +391,12 @@ int32_t accumulate_and_finalise(ndt2d_handle* h, const float* d_x, const float* 
   const int32_t st = finalise_grid(h);
   if (h_outside) *h_outside = *ho;
   return st;
+}
+
+// storage for ncell cells (all grids): a 32-byte record (two float4) and the sums of each
+int32_t ensure_cells(ndt2d_handle* h, size_t ncell) {
+  HIP_TRY(grow({grow_buf(&h->grid.rec, 2), grow_buf(&h->grid.acc)}, &h->cell_capacity, ncell, ncell + ncell / 8));
+  return NDT_OK;
 }
 
 // Grid geometry for a bounding box (oracle/ndt2d.py grid_geometry) and storage for its cells.
@@ -438,16 +429,7 @@ int32_t setup_geometry(ndt2d_handle* h, float xmin, float xmax, float ymin, floa
   g.fix_scale = std::ldexp(1.0, kFixShift) / c;
   const size_t ncell = (size_t)g.W * g.H * g.ngrid;     // all grids, back to back
   if (ncell > kMaxCells) { set_error("target extent / cell_size needs more than 2^27 cells"); return NDT_ERR_CAPACITY; }
-  if (ncell > h->cell_capacity) {
-    if (g.rec) (void)hipFree(g.rec);
-    if (g.acc) (void)hipFree(g.acc);
-    g.rec = nullptr; g.acc = nullptr; h->cell_capacity = 0;
-    const size_t want = ncell + ncell / 8;
-    HIP_TRY(hipMalloc((void**)&g.rec, 2 * want * sizeof(float4)));
-    HIP_TRY(hipMalloc((void**)&g.acc, want * sizeof(CellAcc)));
-    h->cell_capacity = want;
-  }
-  return NDT_OK;
+  return ensure_cells(h, ncell);
 }
 
 // ndt2d_set_target with ONE host round trip: bounds -> geometry (k_geometry, on the device, into d_static) ->
@@ -464,71 +446,37 @@ int32_t set_target_single_sync(ndt2d_handle* h, const float* d_x, const float* d
   long long tb = 2ll * h->last_ntile + 16;
   if (tb > kBinMaxTiles) tb = kBinMaxTiles;
   const int tile_bound = (int)tb;
-  if (!h->d_geom) {
-    HIP_TRY(hipMalloc((void**)&h->d_geom, sizeof(GeomDev)));
-    HIP_TRY(hipHostMalloc((void**)&h->h_geom, sizeof(GeomDev), hipHostMallocDefault));
-  }
+  if (!h->d_geom) HIP_TRY(hipMalloc((void**)&h->d_geom, sizeof(GeomDev)));
+  if (!h->h_geom) HIP_TRY(pinned_alloc(&h->h_geom, sizeof(GeomDev)));
   GeomDev* dg = h->d_geom;
+  GridDev* dgrid = &h->d_static->grid;
   SortPlan sp;
   if (h->build_variant == 1 && plan_sorted(n, tile_bound, &sp)) {
     // chunk-sorted build: bounds partials -> chunk sort (reduce + geometry in its prologue) -> one workgroup per tile
-    { const int32_t es = ensure_sorted_buffers(h, sp, (size_t)tile_bound); if (es != NDT_OK) return es; }
     SplitBufs sb{};
-    { const int32_t es = ensure_split_buffers(h, n, tile_bound, &sb); if (es != NDT_OK) return es; }
-    const int split = gather_split(n, tile_bound);
+    { const int32_t es = ensure_sorted_buffers(h, sp, n, tile_bound, &sb); if (es != NDT_OK) return es; }
     const int nparts = launch_bounds_parts(h, d_x, d_y, n, dg);
-    const BinGeom none{};
-    const MoveArgs stay{1.f, 0.f, 0.f, 0.f, 0};
     GeomArgs ga{};
     ga.parts = h->d_parts; ga.nparts = nparts; ga.tile_bound = tile_bound; ga.cell = h->prm.cell_size;
-    ga.cell_capacity = (unsigned long long)h->cell_capacity; ga.grid = &h->d_static->grid; ga.out = dg;
-    launch_chunk_sort(h, sp, d_x, d_y, n, none, tile_bound, stay, &dg->n_outside, ga, sb);
-    hipLaunchKernelGGL(k_tile_gather, dim3(tile_bound, split), dim3(kGatherThreads), 0, h->stream, (const float2*)h->d_bxy,
-                       (const unsigned int*)h->d_table, sp.nchunks, sp.chunk, h->grid, 0, 0, 0, h->prm.min_points, h->prm.eig_ratio,
-                       &dg->counters[0], (const GeomDev*)dg, (const GridDev*)&h->d_static->grid, sb, (unsigned int*)nullptr);
+    ga.cell_capacity = (unsigned long long)h->cell_capacity; ga.grid = dgrid; ga.out = dg;
+    const MoveArgs stay{1.f, 0.f, 0.f, 0.f, 0};
+    { const int32_t bs = enqueue_sorted_build(h, d_x, d_y, n, sp, sb, tile_bound, false, stay, ga, &dg->counters[0], &dg->n_outside,
+                                              nullptr);
+      if (bs != NDT_OK) return bs; }
   } else {
-  if (n > h->bcap) {
-    if (h->d_bx) (void)hipFree(h->d_bx);
-    if (h->d_by) (void)hipFree(h->d_by);
-    h->d_bx = h->d_by = nullptr; h->bcap = 0;
-    const size_t want = n + n / 4 + 1024;
-    HIP_TRY(hipMalloc((void**)&h->d_bx, want * sizeof(float)));
-    HIP_TRY(hipMalloc((void**)&h->d_by, want * sizeof(float)));
-    h->bcap = want;
+    // round-1 binned build: clear counters and tile totals -> bounds -> geometry -> count, scan, scatter, accumulate
+    { const int32_t es = ensure_binned_buffers(h, n, tile_bound); if (es != NDT_OK) return es; }
+    hipLaunchKernelGGL(k_build_init, dim3(1), dim3(1024), 0, h->stream, dg, h->d_tiles, tile_bound);
+    hipLaunchKernelGGL(k_bounds, dim3(stream_blocks(n) > kBoundsBlocks ? kBoundsBlocks : stream_blocks(n)), dim3(kBlock), 0, h->stream,
+                       d_x, d_y, n, &dg->bounds[0]);
+    hipLaunchKernelGGL(k_geometry, dim3(1), dim3(64), 0, h->stream, h->prm.cell_size, (unsigned long long)h->cell_capacity, tile_bound,
+                       dgrid, dg);
+    { const int32_t bs = enqueue_binned_build(h, d_x, d_y, n, tile_bound, false, dg, dgrid, &dg->counters[0], &dg->n_outside);
+      if (bs != NDT_OK) return bs; }
   }
-  const size_t tneed = 3 * (size_t)tile_bound + 4;
-  if (tneed > h->tile_cap) {
-    if (h->d_tiles) (void)hipFree(h->d_tiles);
-    h->d_tiles = nullptr; h->tile_cap = 0;
-    HIP_TRY(hipMalloc((void**)&h->d_tiles, tneed * sizeof(unsigned int)));
-    h->tile_cap = tneed;
-  }
-  // tile tables laid out for the bound: total[tb] | start[tb+1] | cursor[tb]
-  unsigned int* d_total = h->d_tiles;
-  unsigned int* d_start = h->d_tiles + tile_bound;
-  unsigned int* d_cursor = h->d_tiles + 2 * tile_bound + 1;
-  hipLaunchKernelGGL(k_build_init, dim3(1), dim3(1024), 0, h->stream, dg, d_total, tile_bound);
-  hipLaunchKernelGGL(k_bounds, dim3(stream_blocks(n) > kBoundsBlocks ? kBoundsBlocks : stream_blocks(n)), dim3(kBlock), 0, h->stream,
-                     d_x, d_y, n, &dg->bounds[0]);
-  hipLaunchKernelGGL(k_geometry, dim3(1), dim3(64), 0, h->stream, h->prm.cell_size, (unsigned long long)h->cell_capacity, tile_bound,
-                     &h->d_static->grid, dg);
-  const size_t chunk = (size_t)kBinThreads * kBinPerThread;
-  size_t nb = (n + chunk - 1) / chunk;
-  if (nb > 1024) nb = 1024;
-  const BinGeom none{};
-  hipLaunchKernelGGL(k_tile_count, dim3((unsigned)nb), dim3(kBinThreads), tile_bound * sizeof(unsigned int), h->stream, d_x, d_y, n,
-                     none, d_total, &dg->n_outside, (const GeomDev*)dg);
-  hipLaunchKernelGGL(k_tile_scan, dim3(1), dim3(1024), 0, h->stream, d_total, d_start, d_cursor, 0, (const GeomDev*)dg);
-  hipLaunchKernelGGL(k_tile_scatter, dim3((unsigned)nb), dim3(kBinThreads), 2 * tile_bound * sizeof(unsigned int), h->stream, d_x,
-                     d_y, n, none, d_cursor, h->d_bx, h->d_by, (const GeomDev*)dg);
-  hipLaunchKernelGGL(k_tile_accumulate, dim3(tile_bound), dim3(kBinThreads), 0, h->stream, h->d_bx, h->d_by, d_start, h->grid, 0, 0,
-                     0, h->prm.min_points, h->prm.eig_ratio, &dg->counters[0], (const GeomDev*)dg,
-                     (const GridDev*)&h->d_static->grid);
-  }
-  HIP_TRY(hipGetLastError());
   GeomDev* hg = h->h_geom;
   static_assert(sizeof(GeomDev) % 4 == 0, "GeomDev travels to the host word by word");
-  { const int32_t ps = publish_and_wait(h, dg, hg, (int)(sizeof(GeomDev) / 4)); if (ps != NDT_OK) return ps; }
+  { const int32_t ps = read_back(h, dg, hg, (int)(sizeof(GeomDev) / 4)); if (ps != NDT_OK) return ps; }
   const int* hc = hg->counters;
   for (int j = 0; j < 4; ++j) hb_out[j] = hg->bounds[j];
   *have_bounds = true;
@@ -659,7 +607,7 @@ int32_t ensure_graph(ndt2d_handle* h, int launches, int blocks) {
 // Wait for a single-workgroup alignment: its last thread raises the flag in pinned host memory
 // after writing the state there, so the result is on the host the moment the spin ends.
 int32_t ensure_multi_buffers(ndt2d_handle* h) {
-  if (!h->h_state_multi) HIP_TRY(hipHostMalloc((void**)&h->h_state_multi, kMaxStarts * sizeof(IterState), hipHostMallocDefault));
+  if (!h->h_state_multi) HIP_TRY(pinned_alloc(&h->h_state_multi, kMaxStarts * sizeof(IterState)));
   return NDT_OK;
 }
 
@@ -929,12 +877,11 @@ int32_t ndt2d_create(const ndt2d_params* p, int32_t device_id, ndt2d_handle** ou
   if (hipMalloc((void**)&h->d_static, sizeof(AlignStatic)) != hipSuccess) return fail(NDT_ERR_ALLOC);
   if (hipMalloc((void**)&h->d_call, sizeof(AlignCall)) != hipSuccess) return fail(NDT_ERR_ALLOC);
   if (hipMalloc((void**)&h->d_dyn, sizeof(AlignDyn)) != hipSuccess) return fail(NDT_ERR_ALLOC);
-  if (hipHostMalloc((void**)&h->h_static, sizeof(AlignStatic), hipHostMallocDefault) != hipSuccess) return fail(NDT_ERR_ALLOC);
-  if (hipHostMalloc((void**)&h->h_state, sizeof(IterState), hipHostMallocDefault) != hipSuccess) return fail(NDT_ERR_ALLOC);
-  if (hipHostMalloc((void**)&h->h_flag, 64, hipHostMallocDefault) != hipSuccess) return fail(NDT_ERR_ALLOC);
+  if (pinned_alloc(&h->h_static, sizeof(AlignStatic)) != hipSuccess) return fail(NDT_ERR_ALLOC);
+  if (pinned_alloc(&h->h_state, sizeof(IterState)) != hipSuccess) return fail(NDT_ERR_ALLOC);
+  if (pinned_alloc(&h->h_flag, 64) != hipSuccess) return fail(NDT_ERR_ALLOC);
   if (hipEventCreateWithFlags(&h->upload_ev, hipEventDisableTiming) != hipSuccess) return fail(NDT_ERR_HIP);
-  *h->h_flag = 0;
-  if (hipHostMalloc(&h->h_small, 256, hipHostMallocDefault) != hipSuccess) return fail(NDT_ERR_ALLOC);
+  if (pinned_alloc(&h->h_small, kSmallBytes) != hipSuccess) return fail(NDT_ERR_ALLOC);
   if (hipMemset(h->d_dyn, 0, sizeof(AlignDyn)) != hipSuccess) return fail(NDT_ERR_HIP);
   *out = h;
   return NDT_OK;
@@ -990,8 +937,7 @@ int32_t ndt2d_set_target(ndt2d_handle* h, const float* x, const float* y, size_t
   if (!h || !x || !y || n == 0) return NDT_ERR_INVALID_ARG;
   HIP_TRY(hipSetDevice(h->device));
   { const int32_t fs = finish_chunk_run(h); if (fs != NDT_OK) return fs; }
-  const int32_t st = ensure_points(&h->d_tx, &h->d_ty, &h->tcap, n);
-  if (st != NDT_OK) return st;
+  HIP_TRY(grow({grow_buf(&h->d_tx), grow_buf(&h->d_ty)}, &h->tcap, n, n + n / 4 + 1024));
   HIP_TRY(hipMemcpyAsync(h->d_tx, x, n * sizeof(float), hipMemcpyHostToDevice, h->stream));
   HIP_TRY(hipMemcpyAsync(h->d_ty, y, n * sizeof(float), hipMemcpyHostToDevice, h->stream));
   return set_target_impl(h, h->d_tx, h->d_ty, n);
@@ -1047,8 +993,7 @@ int32_t ndt2d_add_target_points(ndt2d_handle* h, const float* x, const float* y,
   if (!h->has_target) return NDT_ERR_NO_TARGET;
   HIP_TRY(hipSetDevice(h->device));
   { const int32_t fs = finish_chunk_run(h); if (fs != NDT_OK) return fs; }
-  const int32_t st = ensure_points(&h->d_tx, &h->d_ty, &h->tcap, n);
-  if (st != NDT_OK) return st;
+  HIP_TRY(grow({grow_buf(&h->d_tx), grow_buf(&h->d_ty)}, &h->tcap, n, n + n / 4 + 1024));
   HIP_TRY(hipMemcpyAsync(h->d_tx, x, n * sizeof(float), hipMemcpyHostToDevice, h->stream));
   HIP_TRY(hipMemcpyAsync(h->d_ty, y, n * sizeof(float), hipMemcpyHostToDevice, h->stream));
   unsigned long long outside = 0;
@@ -1105,11 +1050,10 @@ int32_t ndt2d_evaluate(ndt2d_handle* h, const float* sx, const float* sy, size_t
   if (!h || !sx || !sy || !pose || !out || n == 0) return NDT_ERR_INVALID_ARG;
   if (!h->has_target) return NDT_ERR_NO_TARGET;
   HIP_TRY(hipSetDevice(h->device));
-  int32_t st = ensure_points(&h->d_sx, &h->d_sy, &h->scap, n);
-  if (st != NDT_OK) return st;
+  HIP_TRY(grow({grow_buf(&h->d_sx), grow_buf(&h->d_sy)}, &h->scap, n, n + n / 4 + 1024));
   HIP_TRY(hipMemcpyAsync(h->d_sx, sx, n * sizeof(float), hipMemcpyHostToDevice, h->stream));
   HIP_TRY(hipMemcpyAsync(h->d_sy, sy, n * sizeof(float), hipMemcpyHostToDevice, h->stream));
-  st = run_align(h, h->d_sx, h->d_sy, n, pose, /*fixed_override=*/1, /*check_every=*/0);
+  int32_t st = run_align(h, h->d_sx, h->d_sy, n, pose, /*fixed_override=*/1, /*check_every=*/0);
   if (st != NDT_OK) return st;
   st = fetch_state(h);
   if (st != NDT_OK) return st;
@@ -1155,8 +1099,7 @@ int32_t ndt2d_align_trace(ndt2d_handle* h, const float* sx, const float* sy, siz
     if (out) *out = rows[0];
     return NDT_OK;
   }
-  const int32_t st = ensure_points(&h->d_sx, &h->d_sy, &h->scap, n);
-  if (st != NDT_OK) return st;
+  HIP_TRY(grow({grow_buf(&h->d_sx), grow_buf(&h->d_sy)}, &h->scap, n, n + n / 4 + 1024));
   HIP_TRY(hipMemcpyAsync(h->d_sx, sx, n * sizeof(float), hipMemcpyHostToDevice, h->stream));
   HIP_TRY(hipMemcpyAsync(h->d_sy, sy, n * sizeof(float), hipMemcpyHostToDevice, h->stream));
   // the launch-per-iteration kernels, one plain launch and one state fetch per iteration
@@ -1219,8 +1162,7 @@ int32_t ndt2d_align(ndt2d_handle* h, const float* sx, const float* sy, size_t n,
   if (!h || !sx || !sy || !init_pose || !out || n == 0) return NDT_ERR_INVALID_ARG;
   if (!h->has_target) return NDT_ERR_NO_TARGET;
   HIP_TRY(hipSetDevice(h->device));
-  const int32_t st = ensure_points(&h->d_sx, &h->d_sy, &h->scap, n);
-  if (st != NDT_OK) return st;
+  HIP_TRY(grow({grow_buf(&h->d_sx), grow_buf(&h->d_sy)}, &h->scap, n, n + n / 4 + 1024));
   HIP_TRY(hipMemcpyAsync(h->d_sx, sx, n * sizeof(float), hipMemcpyHostToDevice, h->stream));
   HIP_TRY(hipMemcpyAsync(h->d_sy, sy, n * sizeof(float), hipMemcpyHostToDevice, h->stream));
   const int32_t rs = run_align(h, h->d_sx, h->d_sy, n, init_pose, -1, h->check_every, /*wait=*/true, /*own_source=*/true);

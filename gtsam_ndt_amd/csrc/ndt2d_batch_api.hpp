@@ -74,15 +74,7 @@ int32_t batch_launch(ndt2d_batch* b, const float* d_tx, const float* d_ty, const
   // the small variant keeps two workgroups resident per CU
   const size_t small_max = 2 * (size_t)b->n_cu;
   const int blocks_small = (int)(n_pairs < small_max ? n_pairs : small_max);
-  if (n_pairs > b->marks_cap) {
-    if (b->d_marks) (void)hipFree(b->d_marks);
-    if (b->d_fb_list) (void)hipFree(b->d_fb_list);
-    b->d_marks = b->d_fb_list = nullptr; b->marks_cap = 0;
-    const size_t want = n_pairs + n_pairs / 4 + 64;
-    HIP_TRY(hipMalloc((void**)&b->d_marks, want * sizeof(int)));
-    HIP_TRY(hipMalloc((void**)&b->d_fb_list, want * sizeof(int)));
-    b->marks_cap = want;
-  }
+  HIP_TRY(ndt::grow({ndt::grow_buf(&b->d_marks), ndt::grow_buf(&b->d_fb_list)}, &b->marks_cap, n_pairs, n_pairs + n_pairs / 4 + 64));
   grow_global_slabs(b, &b->d_slab, ndt::BatchGlobal::kTabBytes, b->n_cu < ndt::kBatchGlobalBlocks ? b->n_cu : ndt::kBatchGlobalBlocks, st);
   a.slab = b->d_slab;
   a.fb_marks = b->d_fb_list;
@@ -151,16 +143,6 @@ int32_t batch_launch(ndt2d_batch* b, const float* d_tx, const float* d_ty, const
   return NDT_OK;
 }
 
-template <typename T>
-int32_t ensure_dev(T** p, size_t* cap, size_t n) {
-  if (n <= *cap) return NDT_OK;
-  if (*p) (void)hipFree(*p);
-  *p = nullptr; *cap = 0;
-  HIP_TRY(hipMalloc((void**)p, (n + n / 4 + 64) * sizeof(T)));
-  *cap = n + n / 4 + 64;
-  return NDT_OK;
-}
-
 }  // namespace
 
 extern "C" {
@@ -212,8 +194,7 @@ int32_t ndt2d_batch_create_pyramid(const ndt2d_params* levels, int32_t n_levels,
   if (any_overlap) b->global_blocks = b->n_cu < ndt::kBatchGlobalBlocks ? b->n_cu : ndt::kBatchGlobalBlocks;
   if (hipMalloc((void**)&b->d_queue, 16) != hipSuccess) return fail(NDT_ERR_ALLOC);
   if (hipMalloc((void**)&b->d_slab, (size_t)b->global_blocks * ndt::BatchGlobal::kTabBytes) != hipSuccess) return fail(NDT_ERR_ALLOC);
-  if (hipHostMalloc((void**)&b->h_fb_seen, 64, hipHostMallocDefault) != hipSuccess) return fail(NDT_ERR_ALLOC);
-  *b->h_fb_seen = 0;
+  if (ndt::pinned_alloc(&b->h_fb_seen, 64) != hipSuccess) return fail(NDT_ERR_ALLOC);
   // more than 64 KiB of dynamic LDS needs an explicit opt-in per kernel
   if (hipFuncSetAttribute(reinterpret_cast<const void*>(&ndt::k_batch<0, ndt::BatchSmall>), hipFuncAttributeMaxDynamicSharedMemorySize,
                           ndt::BatchSmall::kLdsBytes) != hipSuccess) return fail(NDT_ERR_HIP);
@@ -308,14 +289,15 @@ int32_t ndt2d_batch_align(ndt2d_batch* b, const float* tx, const float* ty, cons
         soff[k + 1] - soff[k] > (size_t)ndt::kBatchMaxCloud) return NDT_ERR_INVALID_ARG;
   }
   int32_t st;
-  if ((st = ensure_dev(&b->d_tx, &b->cap_tx, nt)) != NDT_OK) return st;
-  if ((st = ensure_dev(&b->d_ty, &b->cap_ty, nt)) != NDT_OK) return st;
-  if ((st = ensure_dev(&b->d_sx, &b->cap_sx, ns)) != NDT_OK) return st;
-  if ((st = ensure_dev(&b->d_sy, &b->cap_sy, ns)) != NDT_OK) return st;
-  if ((st = ensure_dev(&b->d_toff, &b->cap_toff, n_pairs + 1)) != NDT_OK) return st;
-  if ((st = ensure_dev(&b->d_soff, &b->cap_soff, n_pairs + 1)) != NDT_OK) return st;
-  if ((st = ensure_dev(&b->d_init, &b->cap_init, 3 * (n_pairs + 1))) != NDT_OK) return st;
-  if ((st = ensure_dev(&b->d_out, &b->cap_out, n_pairs + 1)) != NDT_OK) return st;
+  auto slack = [](size_t k) { return k + k / 4 + 64; };   // the staging buffers' room to grow
+  HIP_TRY(ndt::grow(&b->d_tx, &b->cap_tx, nt, slack(nt)));
+  HIP_TRY(ndt::grow(&b->d_ty, &b->cap_ty, nt, slack(nt)));
+  HIP_TRY(ndt::grow(&b->d_sx, &b->cap_sx, ns, slack(ns)));
+  HIP_TRY(ndt::grow(&b->d_sy, &b->cap_sy, ns, slack(ns)));
+  HIP_TRY(ndt::grow(&b->d_toff, &b->cap_toff, n_pairs + 1, slack(n_pairs + 1)));
+  HIP_TRY(ndt::grow(&b->d_soff, &b->cap_soff, n_pairs + 1, slack(n_pairs + 1)));
+  HIP_TRY(ndt::grow(&b->d_init, &b->cap_init, 3 * (n_pairs + 1), slack(3 * (n_pairs + 1))));
+  HIP_TRY(ndt::grow(&b->d_out, &b->cap_out, n_pairs + 1, slack(n_pairs + 1)));
   hipStream_t s = b->stream;
   HIP_TRY(hipMemcpyAsync(b->d_tx, tx, nt * sizeof(float), hipMemcpyHostToDevice, s));
   HIP_TRY(hipMemcpyAsync(b->d_ty, ty, nt * sizeof(float), hipMemcpyHostToDevice, s));

@@ -368,17 +368,6 @@ int32_t search_walk(const SearchSel& sel, const std::vector<double>* ax, const S
   return m;
 }
 
-template <typename T>
-int32_t search_grow(T** p, size_t* cap, size_t want) {
-  if (want <= *cap) return NDT_OK;
-  if (*p) (void)hipFree(*p);
-  *p = nullptr; *cap = 0;
-  const size_t n = want + want / 4;
-  HIP_TRY(hipMalloc((void**)p, n * sizeof(T)));
-  *cap = n;
-  return NDT_OK;
-}
-
 // The whole search on the handle's stream.  d_scores != null: only the volume, into the caller's buffer; else the hits.
 int32_t search_run(ndt2d_handle* h, const float* d_sx, const float* d_sy, size_t n, const ndt2d_search_window* w,
                    int32_t k, ndt2d_search_hit* hits, int32_t* n_hits, float* d_scores) {
@@ -393,16 +382,9 @@ int32_t search_run(ndt2d_handle* h, const float* d_sx, const float* d_sy, size_t
   const size_t N = (size_t)L.nx * L.ny * L.nt;
   // axes on the device: headings (double) | x (float) | y (float)
   const size_t axes_bytes = 8 * (size_t)L.nt + 4 * ((size_t)L.nx + L.ny);
-  { const int32_t gs = search_grow(&h->d_srch_axes, &h->srch_axes_cap, axes_bytes); if (gs != NDT_OK) return gs; }
-  if (axes_bytes > h->h_srch_axes_cap) {
-    HIP_TRY(hipStreamSynchronize(h->stream));
-    if (h->h_srch_axes) (void)hipHostFree(h->h_srch_axes);
-    h->h_srch_axes = nullptr; h->h_srch_axes_cap = 0;
-    HIP_TRY(hipHostMalloc((void**)&h->h_srch_axes, axes_bytes + axes_bytes / 4, hipHostMallocDefault));
-    h->h_srch_axes_cap = axes_bytes + axes_bytes / 4;
-  } else {
-    HIP_TRY(hipStreamSynchronize(h->stream));        // the pinned buffer's last copy has left it
-  }
+  HIP_TRY(grow(&h->d_srch_axes, &h->srch_axes_cap, axes_bytes, axes_bytes + axes_bytes / 4));
+  HIP_TRY(hipStreamSynchronize(h->stream));          // the pinned buffer's last copy has left it
+  HIP_TRY(grow({grow_buf(&h->h_srch_axes)}, &h->h_srch_axes_cap, axes_bytes, axes_bytes + axes_bytes / 4, nullptr, /*pinned=*/true));
   double* hth = reinterpret_cast<double*>(h->h_srch_axes);
   float* hx = reinterpret_cast<float*>(hth + L.nt);
   float* hy = hx + L.nx;
@@ -416,7 +398,7 @@ int32_t search_run(ndt2d_handle* h, const float* d_sx, const float* d_sy, size_t
 
   float* vol = d_scores;
   if (!vol) {
-    { const int32_t gs = search_grow(&h->d_srch_vol, &h->srch_vol_cap, N); if (gs != NDT_OK) return gs; }
+    HIP_TRY(grow(&h->d_srch_vol, &h->srch_vol_cap, N, N + N / 4));
     vol = h->d_srch_vol;
   }
   const long long tiles = (long long)((L.nx + kSearchTile - 1) / kSearchTile) * ((L.ny + kSearchTile - 1) / kSearchTile);
@@ -437,9 +419,9 @@ int32_t search_run(ndt2d_handle* h, const float* d_sx, const float* d_sy, size_t
 
   // peaks: at most one in every 2 x 2 x 2 block of the lattice (two neighbours cannot both beat each other)
   const size_t cap = (size_t)((L.nx + 1) / 2) * ((L.ny + 1) / 2) * ((L.nt + 1) / 2);
-  { const int32_t gs = search_grow(&h->d_srch_keys, &h->srch_keys_cap, cap); if (gs != NDT_OK) return gs; }
+  HIP_TRY(grow(&h->d_srch_keys, &h->srch_keys_cap, cap, cap + cap / 4));
   if (!h->d_srch_sel) HIP_TRY(hipMalloc((void**)&h->d_srch_sel, sizeof(SearchSel)));
-  if (!h->h_srch_sel) HIP_TRY(hipHostMalloc((void**)&h->h_srch_sel, sizeof(SearchSel), hipHostMallocDefault));
+  if (!h->h_srch_sel) HIP_TRY(pinned_alloc(&h->h_srch_sel, sizeof(SearchSel)));
   SearchSel* sel = h->d_srch_sel;
   const unsigned hb = (unsigned)std::min<size_t>(std::max<size_t>((cap + 255) / 256, 1), 1024);
   hipLaunchKernelGGL(k_search_sel_clear, dim3(1), dim3(256), 0, h->stream, sel);
@@ -496,8 +478,7 @@ int32_t ndt2d_search(ndt2d_handle* h, const float* sx, const float* sy, size_t n
   if (!h->has_target) return NDT_ERR_NO_TARGET;
   HIP_TRY(hipSetDevice(h->device));
   { const int32_t fs = finish_chunk_run(h); if (fs != NDT_OK) return fs; }
-  st = ensure_points(&h->d_sx, &h->d_sy, &h->scap, n);
-  if (st != NDT_OK) return st;
+  HIP_TRY(grow({grow_buf(&h->d_sx), grow_buf(&h->d_sy)}, &h->scap, n, n + n / 4 + 1024));
   HIP_TRY(hipMemcpyAsync(h->d_sx, sx, n * sizeof(float), hipMemcpyHostToDevice, h->stream));
   HIP_TRY(hipMemcpyAsync(h->d_sy, sy, n * sizeof(float), hipMemcpyHostToDevice, h->stream));
   return search_run(h, h->d_sx, h->d_sy, n, w, k, hits, n_hits, nullptr);

@@ -6,6 +6,9 @@
 #include "ndt3d_build.hpp"
 #include "ndt3d_multi.hpp"
 
+// h_pub3, the pinned read-back of a single-sync build: the accumulator block's first 64 words, then the flag
+constexpr int kPub3FlagWord = 64, kPub3Words = kPub3FlagWord + 16;
+
 struct ndt3d_handle {
   int device = 0;
   hipStream_t stream = nullptr;
@@ -16,14 +19,14 @@ struct ndt3d_handle {
   int n_valid = 0;
   unsigned int* d_bounds = nullptr;   // [6]
   int* d_counters = nullptr;          // counter shards of ndt3d_load_map's finalise (the builds keep theirs in d_tiles)
-  int publish_seq = 0;                // k_build_publish's flag value of the build in flight (h_small + 192)
+  int publish_seq = 0;                // the flag value of the read-back in flight (publish_and_wait)
   float* d_parts3 = nullptr;          // [256][8]: per-workgroup partial bounding boxes (k_bounds3_parts)
-  void* h_small = nullptr;            // pinned 256 B (counter shards at 0, the outside count at 128)
+  void* h_small = nullptr;            // pinned kSmallBytes (counter shards at 0, the outside count at 128, a flag)
   float *d_t[3] = {nullptr, nullptr, nullptr}; size_t tcap = 0;
   float *d_b[3] = {nullptr, nullptr, nullptr}; size_t bcap = 0;      // binned build scratch
   unsigned int* d_tiles = nullptr; size_t tile_cap = 0;
   int last_ntile = 0;                 // tiles of the grid the handle holds (0: none): the launch bound of a single-sync build
-  unsigned int* h_pub3 = nullptr;     // pinned [64 + 16]: the accumulator block's first 64 words of a single-sync build, flag at [64]
+  unsigned int* h_pub3 = nullptr;     // pinned [kPub3Words]: the accumulator block's first 64 words of a single-sync build, then the flag
   bool one_round_trip = true;
   size_t tiles_clean = 0;             // leading words of d_tiles known to be zero (the last build's publish cleared them)
   unsigned char* d_split3 = nullptr; size_t split3_cap = 0;   // shared tiles' hand-off (ndt3d_build.hpp Split3Bufs): the slab pool
@@ -49,16 +52,6 @@ struct ndt3d_handle {
 };
 
 namespace {
-
-int32_t ensure3(float** d, size_t* cap, size_t n) {
-  if (n <= *cap) return NDT_OK;
-  for (int a = 0; a < 3; ++a) { if (d[a]) (void)hipFree(d[a]); d[a] = nullptr; }
-  *cap = 0;
-  const size_t want = n + n / 4 + 1024;
-  for (int a = 0; a < 3; ++a) HIP_TRY(hipMalloc((void**)&d[a], want * sizeof(float)));
-  *cap = want;
-  return NDT_OK;
-}
 
 int32_t upload_static3(ndt3d_handle* h) {
   // as upload_static in 2D: the copy is left in flight (whatever reads d_static is ordered behind it on the same
@@ -92,13 +85,9 @@ int32_t ensure_build3_bufs(ndt3d_handle* h, size_t n, int ntile, bool binned, Bu
   using namespace ndt;
   B->wg_bound = (size_t)ntile + n / (size_t)kTile3SubMin + 1;
   const size_t tneed = 64 + 4 * (size_t)ntile + 4 + 1 + B->wg_bound;
-  if (tneed > h->tile_cap) {
-    if (h->d_tiles) (void)hipFree(h->d_tiles);
-    h->d_tiles = nullptr; h->tile_cap = 0;
-    HIP_TRY(hipMalloc((void**)&h->d_tiles, tneed * sizeof(unsigned int)));
-    h->tile_cap = tneed;
-    h->tiles_clean = 0;
-  }
+  bool grew = false;
+  HIP_TRY(grow(&h->d_tiles, &h->tile_cap, tneed, tneed, &grew));
+  if (grew) h->tiles_clean = 0;
   B->d_cnt = reinterpret_cast<int*>(h->d_tiles);
   B->d_out = reinterpret_cast<unsigned long long*>(h->d_tiles + 32);
   B->d_total = h->d_tiles + 64;
@@ -110,18 +99,53 @@ int32_t ensure_build3_bufs(ndt3d_handle* h, size_t n, int ntile, bool binned, Bu
   B->zero_words = 64 + 2 * (size_t)ntile;
   B->sb = Split3Bufs{};
   if (!binned) return NDT_OK;
-  { const int32_t st = ensure3(h->d_b, &h->bcap, n); if (st != NDT_OK) return st; }
+  HIP_TRY(grow({grow_buf(&h->d_b[0]), grow_buf(&h->d_b[1]), grow_buf(&h->d_b[2])}, &h->bcap, n, n + n / 4 + 1024));
   // the shared tiles' slabs: one per workgroup of the tile kernel's launch (only the shares of shared tiles use theirs)
   const size_t slabs = B->wg_bound;
   const size_t need = slabs * kSlabWords * sizeof(unsigned long long);
-  if (need > h->split3_cap) {
-    if (h->d_split3) (void)hipFree(h->d_split3);
-    h->d_split3 = nullptr; h->split3_cap = 0;
-    HIP_TRY(hipMalloc((void**)&h->d_split3, need + need / 4));
-    h->split3_cap = need + need / 4;
-  }
+  HIP_TRY(grow(&h->d_split3, &h->split3_cap, need, need + need / 4));
   B->sb.pool = reinterpret_cast<unsigned long long*>(h->d_split3);
   B->sb.capacity = (unsigned int)(slabs > 0xFFFFFFF0ull ? 0xFFFFFFF0ull : slabs);
+  return NDT_OK;
+}
+
+// The binned build (ndt3d_build.hpp) of `tiles` tiles into the block of B: count (the scan runs in its last workgroup) ->
+// scatter -> tile kernel, for a geometry the host knows (ga = {}: the grid of h->grid; merge = add to the cached sums, mv =
+// the motion applied on the way in) or for one the count kernel's prologue decides into ga.out (set_target3_single_sync).
+int32_t enqueue_binned_build3(ndt3d_handle* h, const float* dx, const float* dy, const float* dz, size_t n, int tiles,
+                              const Build3Bufs& B, bool merge, const ndt::Move3Args& mv, const ndt::Geom3Args& ga) {
+  using namespace ndt;
+  const Grid3Dev& g = h->grid;
+  const GeomDev3* dg = ga.out;
+  const int ntx = dg ? 0 : (g.W + (1 << kT3x) - 1) >> kT3x, nty = dg ? 0 : (g.H + (1 << kT3y) - 1) >> kT3y;
+  const BinGeom3 bg = dg ? BinGeom3{} : BinGeom3{g.ox, g.oy, g.oz, g.inv_c, g.W, g.H, g.D, ntx, nty, tiles};
+  size_t nb = (n + kBinThreads * 4 - 1) / (kBinThreads * 4);
+  if (nb > 1024) nb = 1024;
+  hipLaunchKernelGGL(k_tile_count3, dim3((unsigned)nb), dim3(kBinThreads), tiles * sizeof(unsigned int), h->stream, dx, dy, dz, n,
+                     bg, B.d_total, B.d_out, ga, Scan3Out{h->d_tiles + 41, B.d_start, B.d_cursor, B.d_wgtotal, B.d_wgmap}, mv);
+  hipLaunchKernelGGL(k_tile_scatter3, dim3((unsigned)nb), dim3(kBinThreads), 2 * tiles * sizeof(unsigned int), h->stream, dx, dy, dz,
+                     n, bg, B.d_cursor, h->d_b[0], h->d_b[1], h->d_b[2], dg, mv);
+  // (no fill of the grid's sums: the workgroup that finishes a tile writes every voxel's sums, empty ones included)
+  hipLaunchKernelGGL(k_tile_accumulate3, dim3((unsigned)B.wg_bound), dim3(kBinThreads), 0, h->stream, h->d_b[0], h->d_b[1], h->d_b[2],
+                     B.d_start, g, ntx, nty, merge ? 1 : 0, h->prm.min_points, h->prm.eig_ratio, B.d_cnt, B.d_ticket, B.sb,
+                     (const unsigned int*)B.d_wgtotal, (const unsigned int*)B.d_wgmap, dg, (const Grid3Dev*)ga.grid);
+  HIP_TRY(hipGetLastError());
+  return NDT_OK;
+}
+
+// The read-back of a build's accumulator block (k_build_publish_clear3 through publish_and_wait): its first `nwords` words
+// into pinned memory at h_dst, then `flag` raised; the kernel clears the block's first zero_words words behind it.  The
+// kernel's own stores are the only copy, so a flag that has not come even after a synchronisation is an error.
+int32_t read_back3(ndt3d_handle* h, unsigned int* h_dst, int nwords, int* flag, size_t zero_words) {
+  bool seen = false;
+  HIP_TRY(publish_and_wait(h->stream, &h->publish_seq, flag, [&](int seq) {
+    hipLaunchKernelGGL(ndt::k_build_publish_clear3, dim3(1), dim3(256), 0, h->stream, h->d_tiles, h_dst, nwords, flag, seq, (int)zero_words);
+  }, &seen));
+  if (!seen) {
+    HIP_TRY(hipStreamSynchronize(h->stream));
+    if (!flag_raised(flag, h->publish_seq)) { set_error("the voxel-grid build did not report its end"); return NDT_ERR_HIP; }
+  }
+  h->tiles_clean = zero_words;
   return NDT_OK;
 }
 
@@ -139,72 +163,45 @@ int32_t accumulate3(ndt3d_handle* h, const float* dx, const float* dy, const flo
   const int ntile = binned ? (int)ntile_ll : 0;
   Build3Bufs B{};
   { const int32_t bs = ensure_build3_bufs(h, n, ntile, binned, &B); if (bs != NDT_OK) return bs; }
-  int* d_cnt = B.d_cnt;
-  unsigned long long* d_out = B.d_out;
-  unsigned int *d_total = B.d_total, *d_ticket = B.d_ticket, *d_start = B.d_start, *d_cursor = B.d_cursor, *d_wgtotal = B.d_wgtotal,
-               *d_wgmap = B.d_wgmap;
-  const size_t wg_bound = B.wg_bound;
-  const Split3Bufs sb = B.sb;
   // (the publish of the build before cleared the block, unless this one needs more of it or that one did not finish)
   const bool clean = h->tiles_clean >= B.zero_words;
   h->tiles_clean = 0;
   if (!clean) HIP_TRY(hipMemsetAsync(h->d_tiles, 0, B.zero_words * sizeof(unsigned int), h->stream));
   if (binned) {
-    // binned build (ndt3d_build.hpp)
-    const BinGeom3 bg{g.ox, g.oy, g.oz, g.inv_c, g.W, g.H, g.D, ntx, nty, ntile};
     Move3Args mv{};
     if (move) { mv.T = *move; mv.use = 1; }
-    size_t nb = (n + kBinThreads * 4 - 1) / (kBinThreads * 4);
-    if (nb > 1024) nb = 1024;
-    hipLaunchKernelGGL(k_tile_count3, dim3((unsigned)nb), dim3(kBinThreads), ntile * sizeof(unsigned int), h->stream, dx, dy,
-                       dz, n, bg, d_total, d_out, Geom3Args{}, Scan3Out{h->d_tiles + 41, d_start, d_cursor, d_wgtotal, d_wgmap}, mv);
-    hipLaunchKernelGGL(k_tile_scatter3, dim3((unsigned)nb), dim3(kBinThreads), 2 * ntile * sizeof(unsigned int), h->stream,
-                       dx, dy, dz, n, bg, d_cursor, h->d_b[0], h->d_b[1], h->d_b[2], (const GeomDev3*)nullptr, mv);
-    // (no fill of the grid's sums: the workgroup that finishes a tile writes every voxel's sums, empty ones included)
-    hipLaunchKernelGGL(k_tile_accumulate3, dim3((unsigned)wg_bound), dim3(kBinThreads), 0, h->stream, h->d_b[0], h->d_b[1],
-                       h->d_b[2], d_start, g, ntx, nty, merge ? 1 : 0, h->prm.min_points, h->prm.eig_ratio, d_cnt, d_ticket, sb,
-                       (const unsigned int*)d_wgtotal, (const unsigned int*)d_wgmap, (const GeomDev3*)nullptr, (const Grid3Dev*)nullptr);
-    HIP_TRY(hipGetLastError());
+    { const int32_t bs = enqueue_binned_build3(h, dx, dy, dz, n, ntile, B, merge, mv, Geom3Args{}); if (bs != NDT_OK) return bs; }
     h->last_ntile = ntile;
   } else {
     if (move) {                                      // this path takes the points as they are: move them first
-      const int32_t st = ensure3(h->d_t, &h->tcap, n);
-      if (st != NDT_OK) return st;
+      HIP_TRY(grow({grow_buf(&h->d_t[0]), grow_buf(&h->d_t[1]), grow_buf(&h->d_t[2])}, &h->tcap, n, n + n / 4 + 1024));
       hipLaunchKernelGGL(k_transform_points3, dim3((unsigned)((n + kBlock - 1) / kBlock)), dim3(kBlock), 0, h->stream, dx, dy, dz, n, *move,
                          h->d_t[0], h->d_t[1], h->d_t[2]);
       HIP_TRY(hipGetLastError());
       dx = h->d_t[0]; dy = h->d_t[1]; dz = h->d_t[2];
     }
     if (!merge) HIP_TRY(hipMemsetAsync(g.acc, 0, ncell * sizeof(CellAcc3), h->stream));
-    hipLaunchKernelGGL(k_accumulate3, dim3(stream_blocks(n)), dim3(kBlock), 0, h->stream, dx, dy, dz, n, g, d_out);
+    hipLaunchKernelGGL(k_accumulate3, dim3(stream_blocks(n)), dim3(kBlock), 0, h->stream, dx, dy, dz, n, g, B.d_out);
     HIP_TRY(hipGetLastError());
     hipLaunchKernelGGL(k_finalise3, dim3((unsigned)((ncell + kBlock - 1) / kBlock)), dim3(kBlock), 0, h->stream, g,
-                       h->prm.min_points, h->prm.eig_ratio, d_cnt);
+                       h->prm.min_points, h->prm.eig_ratio, B.d_cnt);
     HIP_TRY(hipGetLastError());
   }
-  // counter shards and outside count to the host through pinned memory and a flag (k_build_publish, as the 2D build)
+  // counter shards and outside count to the host through pinned memory and a flag (as the 2D build)
   int* hc = (int*)h->h_small;
   unsigned long long* ho = (unsigned long long*)((char*)h->h_small + 128);
-  {
-    int* flag = reinterpret_cast<int*>(static_cast<char*>(h->h_small) + 192);
-    h->publish_seq = h->publish_seq == 0x7fffffff ? 1 : h->publish_seq + 1;
-    hipLaunchKernelGGL(k_build_publish_clear3, dim3(1), dim3(256), 0, h->stream, h->d_tiles, (unsigned int*)hc, 34, flag, h->publish_seq,
-                       (int)B.zero_words);
-    HIP_TRY(hipGetLastError());
-    bool seen = false;
-    const int want = h->publish_seq;
-    HIP_TRY(spin_until(h->stream, [&]() { return __atomic_load_n(flag, __ATOMIC_ACQUIRE) == want; }, &seen));
-    if (!seen) {       // a second of silence: the kernel's own stores are the only copy (it clears the block behind them)
-      HIP_TRY(hipStreamSynchronize(h->stream));
-      if (__atomic_load_n(flag, __ATOMIC_ACQUIRE) != want) { set_error("the voxel-grid build did not report its end"); return NDT_ERR_HIP; }
-    }
-  }
-  h->tiles_clean = B.zero_words;
+  { const int32_t rs = read_back3(h, (unsigned int*)hc, 34, small_flag(h->h_small), B.zero_words); if (rs != NDT_OK) return rs; }
   if (h_outside) *h_outside = *ho;
   int n_valid_sum = 0, n_over_sum = 0;
   sum_count_shards(hc, &n_valid_sum, &n_over_sum);
   h->n_valid = n_valid_sum;
   if (n_over_sum > 0) { set_error("a target cell holds more than 2^20 points"); return NDT_ERR_CAPACITY; }
+  return NDT_OK;
+}
+
+// storage for ncell voxels: a 64-byte record (four float4) and the sums of each
+int32_t ensure_cells3(ndt3d_handle* h, size_t ncell) {
+  HIP_TRY(grow({grow_buf(&h->grid.rec, 4), grow_buf(&h->grid.acc)}, &h->cell_capacity, ncell, ncell + ncell / 8));
   return NDT_OK;
 }
 
@@ -232,16 +229,7 @@ int32_t setup_geometry3(ndt3d_handle* h, const float lo[3], const float hi[3]) {
   g.W = dims[0]; g.H = dims[1]; g.D = dims[2]; g.pad = 0;
   g.fix_scale = std::ldexp(1.0, kFixShift) / c;
   const size_t ncell = (size_t)g.W * g.H * g.D;
-  if (ncell > h->cell_capacity) {
-    void* old[] = {g.rec, g.acc};
-    for (void* p : old) if (p) (void)hipFree(p);
-    g.rec = nullptr; g.acc = nullptr; h->cell_capacity = 0;
-    const size_t want = ncell + ncell / 8;
-    HIP_TRY(hipMalloc((void**)&g.rec, 4 * want * sizeof(float4)));
-    HIP_TRY(hipMalloc((void**)&g.acc, want * sizeof(CellAcc3)));
-    h->cell_capacity = want;
-  }
-  return NDT_OK;
+  return ensure_cells3(h, ncell);
 }
 
 // ndt3d_set_target with ONE host round trip (the 3D twin of the 2D build's set_target_single_sync): a handle that already
@@ -259,48 +247,23 @@ int32_t set_target3_single_sync(ndt3d_handle* h, const float* dx, const float* d
   long long tb = 2ll * h->last_ntile + 16;
   if (tb > kBinMaxTiles) tb = kBinMaxTiles;
   const int tile_bound = (int)tb;
-  if (!h->h_pub3) HIP_TRY(hipHostMalloc((void**)&h->h_pub3, 80 * sizeof(unsigned int), hipHostMallocDefault));
+  if (!h->h_pub3) HIP_TRY(pinned_alloc(&h->h_pub3, kPub3Words * sizeof(unsigned int)));
   if (!h->d_parts3) HIP_TRY(hipMalloc((void**)&h->d_parts3, 256 * 8 * sizeof(float)));
   Build3Bufs B{};
   { const int32_t bs = ensure_build3_bufs(h, n, tile_bound, true, &B); if (bs != NDT_OK) return bs; }
   h->tiles_clean = 0;                                      // (k_bounds3_parts clears the block for this build)
   int sbk = stream_blocks(n);
   if (sbk > 256) sbk = 256;
-  const GeomDev3* dg = reinterpret_cast<const GeomDev3*>(h->d_tiles + kGeom3Word);
-  Grid3Dev* dgrid = &h->d_static->grid;
   HIP_TRY(hipEventSynchronize(h->upload_ev));              // (an upload of d_static still in flight would overwrite the header)
   hipLaunchKernelGGL(k_bounds3_parts, dim3(sbk), dim3(kBlock), 0, h->stream, dx, dy, dz, n, h->d_parts3, h->d_tiles, (int)B.zero_words,
                      kGeom3Word, (int)(sizeof(GeomDev3) / 4));
   Geom3Args ga{};
   ga.parts = h->d_parts3; ga.nparts = sbk; ga.tile_bound = tile_bound; ga.cell = h->prm.cell_size;
-  ga.cell_capacity = (unsigned long long)h->cell_capacity; ga.grid = dgrid;
+  ga.cell_capacity = (unsigned long long)h->cell_capacity; ga.grid = &h->d_static->grid;
   ga.out = reinterpret_cast<GeomDev3*>(h->d_tiles + kGeom3Word);
-  const BinGeom3 none{};
-  size_t nb = (n + kBinThreads * 4 - 1) / (kBinThreads * 4);
-  if (nb > 1024) nb = 1024;
-  hipLaunchKernelGGL(k_tile_count3, dim3((unsigned)nb), dim3(kBinThreads), tile_bound * sizeof(unsigned int), h->stream, dx, dy, dz, n,
-                     none, B.d_total, B.d_out, ga, Scan3Out{h->d_tiles + 41, B.d_start, B.d_cursor, B.d_wgtotal, B.d_wgmap}, Move3Args{});
-  hipLaunchKernelGGL(k_tile_scatter3, dim3((unsigned)nb), dim3(kBinThreads), 2 * tile_bound * sizeof(unsigned int), h->stream, dx, dy, dz,
-                     n, none, B.d_cursor, h->d_b[0], h->d_b[1], h->d_b[2], dg, Move3Args{});
-  hipLaunchKernelGGL(k_tile_accumulate3, dim3((unsigned)B.wg_bound), dim3(kBinThreads), 0, h->stream, h->d_b[0], h->d_b[1], h->d_b[2],
-                     B.d_start, h->grid, 0, 0, 0, h->prm.min_points, h->prm.eig_ratio, B.d_cnt, B.d_ticket, B.sb,
-                     (const unsigned int*)B.d_wgtotal, (const unsigned int*)B.d_wgmap, dg, (const Grid3Dev*)dgrid);
-  HIP_TRY(hipGetLastError());
+  { const int32_t bs = enqueue_binned_build3(h, dx, dy, dz, n, tile_bound, B, false, Move3Args{}, ga); if (bs != NDT_OK) return bs; }
   unsigned int* hp = h->h_pub3;
-  {
-    int* flag = reinterpret_cast<int*>(hp + 64);
-    h->publish_seq = h->publish_seq == 0x7fffffff ? 1 : h->publish_seq + 1;
-    hipLaunchKernelGGL(k_build_publish_clear3, dim3(1), dim3(256), 0, h->stream, h->d_tiles, hp, 64, flag, h->publish_seq, (int)B.zero_words);
-    HIP_TRY(hipGetLastError());
-    bool seen = false;
-    const int want = h->publish_seq;
-    HIP_TRY(spin_until(h->stream, [&]() { return __atomic_load_n(flag, __ATOMIC_ACQUIRE) == want; }, &seen));
-    if (!seen) {
-      HIP_TRY(hipStreamSynchronize(h->stream));
-      if (__atomic_load_n(flag, __ATOMIC_ACQUIRE) != want) { set_error("the voxel-grid build did not report its end"); return NDT_ERR_HIP; }
-    }
-  }
-  h->tiles_clean = B.zero_words;
+  { const int32_t rs = read_back3(h, hp, 64, reinterpret_cast<int*>(hp + kPub3FlagWord), B.zero_words); if (rs != NDT_OK) return rs; }
   const GeomDev3* hg = reinterpret_cast<const GeomDev3*>(hp + kGeom3Word);
   for (int j = 0; j < 6; ++j) hb_out[j] = hg->bounds[j];
   *have_bounds = true;
@@ -339,14 +302,12 @@ int32_t set_target3_impl(ndt3d_handle* h, const float* dx, const float* dy, cons
     if (!h->d_parts3) HIP_TRY(hipMalloc((void**)&h->d_parts3, 256 * 8 * sizeof(float)));
     int sb = stream_blocks(n);
     if (sb > 256) sb = 256;
-    int* flag = reinterpret_cast<int*>(static_cast<char*>(h->h_small) + 192);
-    h->publish_seq = h->publish_seq == 0x7fffffff ? 1 : h->publish_seq + 1;
+    int* flag = small_flag(h->h_small);
     hipLaunchKernelGGL(k_bounds3_parts, dim3(sb), dim3(kBlock), 0, h->stream, dx, dy, dz, n, h->d_parts3, (unsigned int*)nullptr, 0, 0, 0);
-    hipLaunchKernelGGL(k_bounds3_publish, dim3(1), dim3(64), 0, h->stream, (const float*)h->d_parts3, sb, hb, flag, h->publish_seq);
-    HIP_TRY(hipGetLastError());
     bool seen = false;
-    const int want = h->publish_seq;
-    HIP_TRY(spin_until(h->stream, [&]() { return __atomic_load_n(flag, __ATOMIC_ACQUIRE) == want; }, &seen));
+    HIP_TRY(publish_and_wait(h->stream, &h->publish_seq, flag, [&](int seq) {
+      hipLaunchKernelGGL(k_bounds3_publish, dim3(1), dim3(64), 0, h->stream, (const float*)h->d_parts3, sb, hb, flag, seq);
+    }, &seen));
     if (!seen) {                                           // safety net: the atomic form with a copy each way
       for (int a = 0; a < 3; ++a) { hb[2 * a] = 0xFFFFFFFFu; hb[2 * a + 1] = 0u; }
       HIP_TRY(hipMemcpyAsync(h->d_bounds, hb, 24, hipMemcpyHostToDevice, h->stream));
@@ -465,7 +426,7 @@ int32_t multi_align3(ndt3d_handle* h, const float* const* sxs, const float* cons
     }
     return NDT_OK;
   }
-  if (!h->h_state_multi) HIP_TRY(hipHostMalloc((void**)&h->h_state_multi, kMaxStarts3 * sizeof(IterState3), hipHostMallocDefault));
+  if (!h->h_state_multi) HIP_TRY(pinned_alloc(&h->h_state_multi, kMaxStarts3 * sizeof(IterState3)));
   if (!h->d_dyn_multi) {
     HIP_TRY(hipMalloc((void**)&h->d_dyn_multi, sizeof(AlignDynMulti3)));
     HIP_TRY(hipMemsetAsync(h->d_dyn_multi, 0, sizeof(AlignDynMulti3), h->stream));
@@ -557,12 +518,11 @@ int32_t ndt3d_create(const ndt3d_params* p, int32_t device_id, ndt3d_handle** ou
   if (hipMalloc((void**)&h->d_static, sizeof(ndt::AlignStatic3)) != hipSuccess) return fail(NDT_ERR_ALLOC);
   if (hipMalloc((void**)&h->d_call, sizeof(ndt::AlignCall3)) != hipSuccess) return fail(NDT_ERR_ALLOC);
   if (hipMalloc((void**)&h->d_dyn, sizeof(ndt::AlignDyn3)) != hipSuccess) return fail(NDT_ERR_ALLOC);
-  if (hipHostMalloc((void**)&h->h_static, sizeof(ndt::AlignStatic3), hipHostMallocDefault) != hipSuccess) return fail(NDT_ERR_ALLOC);
+  if (ndt::pinned_alloc(&h->h_static, sizeof(ndt::AlignStatic3)) != hipSuccess) return fail(NDT_ERR_ALLOC);
   if (hipEventCreateWithFlags(&h->upload_ev, hipEventDisableTiming) != hipSuccess) return fail(NDT_ERR_HIP);
-  if (hipHostMalloc((void**)&h->h_state, sizeof(ndt::IterState3), hipHostMallocDefault) != hipSuccess) return fail(NDT_ERR_ALLOC);
-  if (hipHostMalloc((void**)&h->h_flag, 64, hipHostMallocDefault) != hipSuccess) return fail(NDT_ERR_ALLOC);
-  *h->h_flag = 0;
-  if (hipHostMalloc(&h->h_small, 256, hipHostMallocDefault) != hipSuccess) return fail(NDT_ERR_ALLOC);
+  if (ndt::pinned_alloc(&h->h_state, sizeof(ndt::IterState3)) != hipSuccess) return fail(NDT_ERR_ALLOC);
+  if (ndt::pinned_alloc(&h->h_flag, 64) != hipSuccess) return fail(NDT_ERR_ALLOC);
+  if (ndt::pinned_alloc(&h->h_small, ndt::kSmallBytes) != hipSuccess) return fail(NDT_ERR_ALLOC);
   if (hipMemset(h->d_dyn, 0, sizeof(ndt::AlignDyn3)) != hipSuccess) return fail(NDT_ERR_HIP);
   *out = h;
   return NDT_OK;
@@ -603,8 +563,7 @@ int32_t ndt3d_add_target_points(ndt3d_handle* h, const float* x, const float* y,
   if (!h->has_target) return NDT_ERR_NO_TARGET;
   HIP_TRY(hipSetDevice(h->device));
   { const int32_t fs = finish_align3(h); if (fs != NDT_OK) return fs; }
-  const int32_t st = ensure3(h->d_t, &h->tcap, n);
-  if (st != NDT_OK) return st;
+  HIP_TRY(grow({grow_buf(&h->d_t[0]), grow_buf(&h->d_t[1]), grow_buf(&h->d_t[2])}, &h->tcap, n, n + n / 4 + 1024));
   const float* src[3] = {x, y, z};
   for (int a = 0; a < 3; ++a) HIP_TRY(hipMemcpyAsync(h->d_t[a], src[a], n * sizeof(float), hipMemcpyHostToDevice, h->stream));
   unsigned long long outside = 0;
@@ -688,8 +647,7 @@ int32_t ndt3d_set_target(ndt3d_handle* h, const float* x, const float* y, const 
   if (!h || !x || !y || !z || n == 0) return NDT_ERR_INVALID_ARG;
   HIP_TRY(hipSetDevice(h->device));
   { const int32_t fs = finish_align3(h); if (fs != NDT_OK) return fs; }
-  const int32_t st = ensure3(h->d_t, &h->tcap, n);
-  if (st != NDT_OK) return st;
+  HIP_TRY(grow({grow_buf(&h->d_t[0]), grow_buf(&h->d_t[1]), grow_buf(&h->d_t[2])}, &h->tcap, n, n + n / 4 + 1024));
   const float* src[3] = {x, y, z};
   for (int a = 0; a < 3; ++a) HIP_TRY(hipMemcpyAsync(h->d_t[a], src[a], n * sizeof(float), hipMemcpyHostToDevice, h->stream));
   return set_target3_impl(h, h->d_t[0], h->d_t[1], h->d_t[2], n);
@@ -732,8 +690,7 @@ int32_t ndt3d_get_grid(ndt3d_handle* h, int32_t* count, float* mean_xyz, float* 
 
 static int32_t upload_source3(ndt3d_handle* h, const float* sx, const float* sy, const float* sz, size_t n) {
   { const int32_t fs = finish_align3(h); if (fs != NDT_OK) return fs; }
-  const int32_t st = ensure3(h->d_s, &h->scap, n);
-  if (st != NDT_OK) return st;
+  HIP_TRY(grow({grow_buf(&h->d_s[0]), grow_buf(&h->d_s[1]), grow_buf(&h->d_s[2])}, &h->scap, n, n + n / 4 + 1024));
   const float* src[3] = {sx, sy, sz};
   for (int a = 0; a < 3; ++a) HIP_TRY(hipMemcpyAsync(h->d_s[a], src[a], n * sizeof(float), hipMemcpyHostToDevice, h->stream));
   return NDT_OK;

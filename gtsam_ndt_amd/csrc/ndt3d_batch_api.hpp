@@ -51,13 +51,7 @@ int32_t batch3_launch(ndt3d_batch* b, const float* const d_t[3], const unsigned 
   a.n_pairs = (int)n_pairs;
   const int blocks = (int)(n_pairs < (size_t)b->n_cu ? n_pairs : (size_t)b->n_cu);
   const int blocks_fb = (int)(n_pairs < (size_t)b->global_blocks ? n_pairs : (size_t)b->global_blocks);
-  if (n_pairs > b->fb_cap) {
-    if (b->d_fb) (void)hipFree(b->d_fb);
-    b->d_fb = nullptr; b->fb_cap = 0;
-    const size_t want = n_pairs + n_pairs / 4 + 64;
-    HIP_TRY(hipMalloc((void**)&b->d_fb, want * sizeof(int)));
-    b->fb_cap = want;
-  }
+  HIP_TRY(ndt::grow(&b->d_fb, &b->fb_cap, n_pairs, n_pairs + n_pairs / 4 + 64));
   a.fb_marks = b->d_fb;
   for (size_t lv = 0; lv < b->levels.size(); ++lv) {
     const ndt3d_params& p = b->levels[lv];
@@ -135,8 +129,7 @@ int32_t ndt3d_batch_create_pyramid(const ndt3d_params* levels, int32_t n_levels,
   if (hipMalloc((void**)&b->d_queue, 16) != hipSuccess) return fail(NDT_ERR_ALLOC);
   if (hipMalloc((void**)&b->d_slab, (size_t)b->n_cu * ndt::kB3SlabBytes) != hipSuccess) return fail(NDT_ERR_ALLOC);
   if (hipMalloc((void**)&b->d_gslab, (size_t)b->global_blocks * ndt::kG3SlabBytes) != hipSuccess) return fail(NDT_ERR_ALLOC);
-  if (hipHostMalloc((void**)&b->h_fb_seen, 64, hipHostMallocDefault) != hipSuccess) return fail(NDT_ERR_ALLOC);
-  *b->h_fb_seen = 0;
+  if (ndt::pinned_alloc(&b->h_fb_seen, 64) != hipSuccess) return fail(NDT_ERR_ALLOC);
   // more than 64 KiB of dynamic LDS needs an explicit opt-in per kernel
   if (hipFuncSetAttribute(reinterpret_cast<const void*>(&ndt::k_batch3<0>), hipFuncAttributeMaxDynamicSharedMemorySize,
                           ndt::kB3LdsBytes) != hipSuccess) return fail(NDT_ERR_HIP);
@@ -204,17 +197,18 @@ int32_t ndt3d_batch_align(ndt3d_batch* b, const float* tx, const float* ty, cons
         soff[k + 1] - soff[k] > (size_t)ndt::kBatchMaxCloud) return NDT_ERR_INVALID_ARG;
   }
   int32_t st;
+  auto slack = [](size_t k) { return k + k / 4 + 64; };   // the staging buffers' room to grow
   const float* th[3] = {tx, ty, tz};
   const float* sh[3] = {sx, sy, sz};
   hipStream_t s = b->stream;
   for (int c = 0; c < 3; ++c) {
-    if ((st = ensure_dev(&b->d_t[c], &b->cap_t[c], nt)) != NDT_OK) return st;
-    if ((st = ensure_dev(&b->d_s[c], &b->cap_s[c], ns)) != NDT_OK) return st;
+    HIP_TRY(ndt::grow(&b->d_t[c], &b->cap_t[c], nt, slack(nt)));
+    HIP_TRY(ndt::grow(&b->d_s[c], &b->cap_s[c], ns, slack(ns)));
   }
-  if ((st = ensure_dev(&b->d_toff, &b->cap_toff, n_pairs + 1)) != NDT_OK) return st;
-  if ((st = ensure_dev(&b->d_soff, &b->cap_soff, n_pairs + 1)) != NDT_OK) return st;
-  if ((st = ensure_dev(&b->d_init, &b->cap_init, 6 * (n_pairs + 1))) != NDT_OK) return st;
-  if ((st = ensure_dev(&b->d_out, &b->cap_out, n_pairs + 1)) != NDT_OK) return st;
+  HIP_TRY(ndt::grow(&b->d_toff, &b->cap_toff, n_pairs + 1, slack(n_pairs + 1)));
+  HIP_TRY(ndt::grow(&b->d_soff, &b->cap_soff, n_pairs + 1, slack(n_pairs + 1)));
+  HIP_TRY(ndt::grow(&b->d_init, &b->cap_init, 6 * (n_pairs + 1), slack(6 * (n_pairs + 1))));
+  HIP_TRY(ndt::grow(&b->d_out, &b->cap_out, n_pairs + 1, slack(n_pairs + 1)));
   for (int c = 0; c < 3; ++c) {
     HIP_TRY(hipMemcpyAsync(b->d_t[c], th[c], nt * sizeof(float), hipMemcpyHostToDevice, s));
     HIP_TRY(hipMemcpyAsync(b->d_s[c], sh[c], ns * sizeof(float), hipMemcpyHostToDevice, s));

@@ -1,12 +1,15 @@
 // Host-side helpers shared by the C-ABI translation units: per-thread error text, the HIP_TRY
-// macro that turns a hipError_t into NDT_ERR_HIP without throwing, launch-chain graphs and their
-// cache, and the host half of the converged-mode protocol (flags in pinned host memory).
+// macro that turns a hipError_t into NDT_ERR_HIP without throwing, buffer growth and pinned
+// allocation, launch-chain graphs and their cache, and the host half of the converged-mode and
+// build read-back protocols (flags in pinned host memory).
 #pragma once
 #include <hip/hip_runtime.h>
 
 #include <sched.h>
 
 #include <atomic>
+#include <cstring>
+#include <initializer_list>
 #include <string>
 
 #include "ndt_dyn.hpp"
@@ -18,6 +21,46 @@ inline std::string& last_error() {
   return e;
 }
 inline void set_error(const char* msg) { last_error() = msg ? msg : ""; }
+
+// One buffer of a group that grows together (grow below): `unit` bytes per element of the group's capacity.
+struct GrowBuf { void** p; size_t unit; };
+template <class T>
+inline GrowBuf grow_buf(T** p, size_t per = 1) { return {reinterpret_cast<void**>(p), per * sizeof(T)}; }
+
+// Makes the buffers of a group, which share the capacity *cap (in elements), hold `need` elements.  If they hold fewer,
+// each is freed and allocated again with `want` elements (the caller's slack rule; want >= need): the contents are lost.
+// On failure *cap is 0 and the buffers not allocated yet are null, so the next call tries again.
+// *grew (optional): the group was reallocated.  pinned: host memory (hipHostMalloc) instead of device memory.
+inline hipError_t grow(std::initializer_list<GrowBuf> bufs, size_t* cap, size_t need, size_t want, bool* grew = nullptr,
+                       bool pinned = false) {
+  if (grew) *grew = false;
+  if (need <= *cap) return hipSuccess;
+  *cap = 0;
+  for (const GrowBuf& b : bufs) {
+    if (*b.p) (void)(pinned ? hipHostFree(*b.p) : hipFree(*b.p));
+    *b.p = nullptr;
+  }
+  for (const GrowBuf& b : bufs) {
+    const hipError_t e = pinned ? hipHostMalloc(b.p, want * b.unit, hipHostMallocDefault) : hipMalloc(b.p, want * b.unit);
+    if (e != hipSuccess) return e;
+  }
+  *cap = want;
+  if (grew) *grew = true;
+  return hipSuccess;
+}
+template <class T>
+inline hipError_t grow(T** p, size_t* cap, size_t need, size_t want, bool* grew = nullptr) {
+  return grow({grow_buf(p)}, cap, need, want, grew);
+}
+
+// Pinned host memory of a fixed size, zeroed: a word the host compares with a sequence number (publish_and_wait) must not
+// start out equal to one.
+template <class T>
+inline hipError_t pinned_alloc(T** p, size_t bytes) {
+  const hipError_t e = hipHostMalloc(reinterpret_cast<void**>(p), bytes, hipHostMallocDefault);
+  if (e == hipSuccess) std::memset(*p, 0, bytes);
+  return e;
+}
 
 }  // namespace ndt
 
@@ -281,6 +324,28 @@ inline hipError_t run_chunks_until_flag(hipGraphExec_t exec, hipStream_t stream,
   const hipError_t e = chunk_run_begin(r, exec, stream, chunk, max_launches);
   if (e != hipSuccess) { *seen = false; (void)hipStreamSynchronize(stream); return e; }
   return chunk_run_finish(r, stream, flag, seen);
+}
+
+// The pinned 256-byte block of a handle (h_small): counter shards at 0, the outside count at 128, the flag of a build's
+// read-back (publish_and_wait) at byte kSmallFlagByte.
+constexpr size_t kSmallBytes = 256, kSmallFlagByte = 192;
+inline int* small_flag(void* h_small) { return reinterpret_cast<int*>(static_cast<char*>(h_small) + kSmallFlagByte); }
+
+inline bool flag_raised(const int* flag, int seq) { return __atomic_load_n(flag, __ATOMIC_ACQUIRE) == seq; }
+
+// The read-back of a build through pinned memory: advances *seq (1 .. 2^31 - 1, never 0: pinned blocks start zeroed) and
+// calls launch(seq), which enqueues the publish kernel (k_build_publish, k_build_publish_clear3 or k_bounds3_publish): it
+// writes its words into pinned memory, then raises *flag to seq.  The host spins on the flag.  *seen = false: it did not
+// come (a stream error, or a second of silence) - the caller's fallback decides what that means.
+template <class Launch>
+inline hipError_t publish_and_wait(hipStream_t stream, int* seq, const int* flag, Launch&& launch, bool* seen) {
+  *seq = *seq == 0x7fffffff ? 1 : *seq + 1;
+  const int want = *seq;
+  *seen = false;
+  launch(want);
+  const hipError_t e = hipGetLastError();
+  if (e != hipSuccess) return e;
+  return spin_until(stream, [&]() { return flag_raised(flag, want); }, seen);
 }
 
 }  // namespace ndt

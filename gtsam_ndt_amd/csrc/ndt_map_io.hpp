@@ -138,15 +138,7 @@ int32_t ndt2d_load_map(ndt2d_handle* h, const void* buf, size_t bytes) {
   g.ox = g.gx[0]; g.oy = g.gy[0];
   g.fix_scale = std::ldexp(1.0, kFixShift) / c;
   const size_t ncell = (size_t)m.n_cells;
-  if (ncell > h->cell_capacity) {
-    if (g.rec) (void)hipFree(g.rec);
-    if (g.acc) (void)hipFree(g.acc);
-    g.rec = nullptr; g.acc = nullptr; h->cell_capacity = 0;
-    const size_t want = ncell + ncell / 8;
-    HIP_TRY(hipMalloc((void**)&g.rec, 2 * want * sizeof(float4)));
-    HIP_TRY(hipMalloc((void**)&g.acc, want * sizeof(CellAcc)));
-    h->cell_capacity = want;
-  }
+  { const int32_t es = ensure_cells(h, ncell); if (es != NDT_OK) return es; }
   HIP_TRY(hipMemcpyAsync(g.acc, (const char*)buf + sizeof m, ncell * sizeof(CellAcc), hipMemcpyHostToDevice, h->stream));
   {
     const int n_ring = (2 * g.W + 2 * g.H) * g.ngrid;
@@ -207,15 +199,7 @@ int32_t ndt3d_load_map(ndt3d_handle* h, const void* buf, size_t bytes) {
   g.W = m.width; g.H = m.height; g.D = m.depth; g.pad = 0;
   g.fix_scale = std::ldexp(1.0, kFixShift) / c;
   const size_t ncell = (size_t)m.n_cells;
-  if (ncell > h->cell_capacity) {
-    void* old[] = {g.rec, g.acc};
-    for (void* p : old) if (p) (void)hipFree(p);
-    g.rec = nullptr; g.acc = nullptr; h->cell_capacity = 0;
-    const size_t want = ncell + ncell / 8;
-    HIP_TRY(hipMalloc((void**)&g.rec, 4 * want * sizeof(float4)));
-    HIP_TRY(hipMalloc((void**)&g.acc, want * sizeof(CellAcc3)));
-    h->cell_capacity = want;
-  }
+  { const int32_t es = ensure_cells3(h, ncell); if (es != NDT_OK) return es; }
   HIP_TRY(hipMemcpyAsync(g.acc, (const char*)buf + sizeof m, ncell * sizeof(CellAcc3), hipMemcpyHostToDevice, h->stream));
   HIP_TRY(hipMemsetAsync(h->d_counters, 0, ndt::kCountInts * sizeof(int), h->stream));
   hipLaunchKernelGGL(k_finalise3, dim3((unsigned)((ncell + kBlock - 1) / kBlock)), dim3(kBlock), 0, h->stream, g,
