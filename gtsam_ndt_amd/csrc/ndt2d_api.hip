@@ -538,46 +538,56 @@ int32_t set_target_impl(ndt2d_handle* h, const float* d_x, const float* d_y, siz
 // Static part of the device context: grid + solver parameters.  Uploaded (synchronously)
 // whenever the target changes; the per-call part is written by k_begin from kernel arguments,
 // so no host buffer has to outlive an asynchronous call.
+// the solver's part of the device context (2D and 3D: ndt3d_params is ndt2d_params)
+void set_solve_params(SolveParams* p, const ndt2d_params& q) {
+  p->d1 = (float)q.d1;
+  p->d2 = (float)q.d2;
+  p->hessian_mode = q.hessian_mode;
+  p->max_iterations = q.max_iterations;
+  p->min_hits = q.min_hits;
+  p->line_search = q.line_search;
+  p->eps_trans = q.eps_trans;
+  p->eps_rot = q.eps_rot;
+  p->step_max_trans = q.step_max_trans;
+  p->step_max_rot = q.step_max_rot;
+  p->step_scale = q.step_scale > 0.0 ? q.step_scale : 1.0;
+}
+
 int32_t upload_static(ndt2d_handle* h) {
   // The copy is left in flight (everything that reads d_static is ordered behind it on the same
   // stream); the pinned source is only rewritten once the previous copy has left it.
   HIP_TRY(hipEventSynchronize(h->upload_ev));
   AlignStatic* c = h->h_static;
   c->grid = h->grid;
-  SolveParams& p = c->prm;
-  p.d1 = (float)h->prm.d1;
-  p.d2 = (float)h->prm.d2;
-  p.hessian_mode = h->prm.hessian_mode;
-  p.max_iterations = h->prm.max_iterations;
-  p.min_hits = h->prm.min_hits;
-  p.line_search = h->prm.line_search;
-  p.eps_trans = h->prm.eps_trans;
-  p.eps_rot = h->prm.eps_rot;
-  p.step_max_trans = h->prm.step_max_trans;
-  p.step_max_rot = h->prm.step_max_rot;
-  p.step_scale = h->prm.step_scale > 0.0 ? h->prm.step_scale : 1.0;
+  set_solve_params(&c->prm, h->prm);
   HIP_TRY(hipMemcpyAsync(h->d_static, c, sizeof(AlignStatic), hipMemcpyHostToDevice, h->stream));
   HIP_TRY(hipEventRecord(h->upload_ev, h->stream));
   h->static_on_device = true;
   return NDT_OK;
 }
 
+// The parameters every alignment kernel is instantiated for, as template arguments: returns f(MODE, NG), called with
+// std::integral_constant values of the Hessian (MODE 1: Newton) and the grid count (NG 4: overlapping grids).
+template <class F>
+auto with_mode(const ndt2d_params& p, F&& f) {
+  using Zero = std::integral_constant<int, 0>;
+  using One = std::integral_constant<int, 1>;
+  using Four = std::integral_constant<int, 4>;
+  if (p.hessian_mode == NDT_HESSIAN_NEWTON) return p.overlap_grids == 4 ? f(One{}, Four{}) : f(One{}, One{});
+  return p.overlap_grids == 4 ? f(Zero{}, Four{}) : f(Zero{}, One{});
+}
+
+// the k_iterate of this alignment, for graphs (ensure_graph) and plain launches (launch_iter)
+const void* iter_kernel(const ndt2d_handle* h) {
+  return with_mode(h->prm, [&](auto M, auto NG) {
+    return h->wide ? (const void*)&k_iterate<M, 0, kIterThreadsWide, NG> : (const void*)&k_iterate<M, 0, kIterThreads, NG>;
+  });
+}
+int iter_threads(const ndt2d_handle* h) { return h->wide ? kIterThreadsWide : kIterThreads; }
+
 void launch_iter(ndt2d_handle* h, int blocks, int k) {
-  const bool newton = h->prm.hessian_mode == NDT_HESSIAN_NEWTON, four = h->prm.overlap_grids == 4;
-#define NDT_LAUNCH_ITER(MODE, NG)                                                                                       \
-  do {                                                                                                                  \
-    if (h->wide)                                                                                                        \
-      hipLaunchKernelGGL((k_iterate<MODE, 0, kIterThreadsWide, NG>), dim3(blocks), dim3(kIterThreadsWide), 0, h->stream, \
-                         h->d_static, h->d_call, h->d_dyn, k & 1);                                                      \
-    else                                                                                                                \
-      hipLaunchKernelGGL((k_iterate<MODE, 0, kIterThreads, NG>), dim3(blocks), dim3(kIterThreads), 0, h->stream,        \
-                         h->d_static, h->d_call, h->d_dyn, k & 1);                                                      \
-  } while (0)
-  if (newton && four) NDT_LAUNCH_ITER(1, 4);
-  else if (newton) NDT_LAUNCH_ITER(1, 1);
-  else if (four) NDT_LAUNCH_ITER(0, 4);
-  else NDT_LAUNCH_ITER(0, 1);
-#undef NDT_LAUNCH_ITER
+  (void)launch_chain_kernel(iter_kernel(h), dim3(blocks), dim3(iter_threads(h)), h->d_static, h->d_call, h->d_dyn, k & 1,
+                            h->stream);
 }
 
 void drop_graph(ndt2d_handle* h) {
@@ -589,28 +599,13 @@ void drop_graph(ndt2d_handle* h) {
 // everything (grid, source pointers, n, parameters, state) from device memory, so one graph
 // serves every target and every source.
 int32_t ensure_graph(ndt2d_handle* h, int launches, int blocks) {
-  const bool newton = h->prm.hessian_mode == NDT_HESSIAN_NEWTON, four = h->prm.overlap_grids == 4;
-  const void* func;
-  if (h->wide)
-    func = newton ? (four ? (const void*)&k_iterate<1, 0, kIterThreadsWide, 4> : (const void*)&k_iterate<1, 0, kIterThreadsWide, 1>)
-                  : (four ? (const void*)&k_iterate<0, 0, kIterThreadsWide, 4> : (const void*)&k_iterate<0, 0, kIterThreadsWide, 1>);
-  else
-    func = newton ? (four ? (const void*)&k_iterate<1, 0, kIterThreads, 4> : (const void*)&k_iterate<1, 0, kIterThreads, 1>)
-                  : (four ? (const void*)&k_iterate<0, 0, kIterThreads, 4> : (const void*)&k_iterate<0, 0, kIterThreads, 1>);
-  HIP_TRY(h->graphs.get(func, dim3(blocks), dim3(h->wide ? kIterThreadsWide : kIterThreads), (void*)h->d_static, (void*)h->d_call,
+  HIP_TRY(h->graphs.get(iter_kernel(h), dim3(blocks), dim3(iter_threads(h)), (void*)h->d_static, (void*)h->d_call,
                         (void*)h->d_dyn, launches, h->prm.hessian_mode | (h->wide ? 16 : 0), h->stream, &h->graph_exec));
   return NDT_OK;
 }
 
-// Enqueue the Gauss-Newton loop.  check_every > 0: poll the done flag every that many
-// launches (synchronous early exit); 0: enqueue all launches, finished ones are no-ops.
 // Wait for a single-workgroup alignment: its last thread raises the flag in pinned host memory
 // after writing the state there, so the result is on the host the moment the spin ends.
-int32_t ensure_multi_buffers(ndt2d_handle* h) {
-  if (!h->h_state_multi) HIP_TRY(pinned_alloc(&h->h_state_multi, kMaxStarts * sizeof(IterState)));
-  return NDT_OK;
-}
-
 int32_t finish_small_run(ndt2d_handle* h) {
   if (!h->small_run) return NDT_OK;
   h->small_run = false;
@@ -635,6 +630,18 @@ int32_t finish_chunk_run(ndt2d_handle* h) {
   return NDT_OK;
 }
 
+// The result of an alignment against a grid with no valid cell (IterState or IterState3): the initial pose, NDT_TOO_FEW_CELLS
+template <class State>
+State no_cell_state(const double* pose) {
+  State s;
+  std::memset(&s, 0, sizeof(s));
+  for (size_t j = 0; j < sizeof(s.pose) / sizeof(s.pose[0]); ++j) s.pose[j] = pose[j];
+  s.status = NDT_TOO_FEW_CELLS;
+  return s;
+}
+
+// Enqueue the Gauss-Newton loop.  check_every > 0: poll the done flag every that many
+// launches (synchronous early exit); 0: enqueue all launches, finished ones are no-ops.
 int32_t run_align(ndt2d_handle* h, const float* d_sx, const float* d_sy, size_t n, const double pose[3],
                   int fixed_override, int check_every, bool wait = true, bool own_source = false) {
   TraceRange range("ndt2d_align: Gauss-Newton loop");
@@ -643,9 +650,7 @@ int32_t run_align(ndt2d_handle* h, const float* d_sx, const float* d_sy, size_t 
   if (n == 0 || n > kMaxSourcePoints || !pose) return NDT_ERR_INVALID_ARG;
   if (h->n_valid < 1) {
     h->pending = false;
-    std::memset(h->h_state, 0, sizeof(IterState));
-    h->h_state->pose[0] = pose[0]; h->h_state->pose[1] = pose[1]; h->h_state->pose[2] = pose[2];
-    h->h_state->status = NDT_TOO_FEW_CELLS;
+    *h->h_state = no_cell_state<IterState>(pose);
     h->h_state->done = 2;               // marks "result already on the host"
     return NDT_OK;
   }
@@ -654,26 +659,18 @@ int32_t run_align(ndt2d_handle* h, const float* d_sx, const float* d_sy, size_t 
   const int blocks = blocks_for(n);
   h->wide = h->use_wide && n >= h->wide_threshold;
   const bool chunked = h->use_graph && check_every > 0 && fixed == 0;
-  __atomic_store_n(&h->h_flag[0], 0, __ATOMIC_RELAXED);
-  __atomic_store_n(&h->h_flag[1], 0, __ATOMIC_RELAXED);
-  h->call_seq = h->call_seq == 0x7fffffff ? 1 : h->call_seq + 1;
+  next_seq(&h->call_seq, h->h_flag);
   if (h->use_small && h->use_graph && n <= (size_t)kSmallMaxPoints) {
     // short scan: the whole loop in one launch of one workgroup (ndt2d_small.hpp)
-    const bool newton = h->prm.hessian_mode == NDT_HESSIAN_NEWTON, four = h->prm.overlap_grids == 4;
-#define NDT_LAUNCH_SMALL(MODE, NG)                                                                                       \
-  do {                                                                                                                   \
-    if (n <= (size_t)kSmallLoPoints)                                                                                     \
-      hipLaunchKernelGGL((k_align_small<MODE, NG, kSmallThreadsLo>), dim3(1), dim3(kSmallThreadsLo), 0, h->stream,       \
-                         h->d_static, d_sx, d_sy, (int)n, pose[0], pose[1], pose[2], fixed, &h->d_dyn->state[0],         \
-                         h->h_state, h->h_flag);                                                                         \
-    else                                                                                                                 \
-      hipLaunchKernelGGL((k_align_small<MODE, NG, kSmallThreadsHi>), dim3(1), dim3(kSmallThreadsHi), 0, h->stream,       \
-                         h->d_static, d_sx, d_sy, (int)n, pose[0], pose[1], pose[2], fixed, &h->d_dyn->state[0],         \
-                         h->h_state, h->h_flag);                                                                         \
-  } while (0)
-    if (newton) { if (four) NDT_LAUNCH_SMALL(1, 4); else NDT_LAUNCH_SMALL(1, 1); }
-    else        { if (four) NDT_LAUNCH_SMALL(0, 4); else NDT_LAUNCH_SMALL(0, 1); }
-#undef NDT_LAUNCH_SMALL
+    const bool lo = n <= (size_t)kSmallLoPoints;
+    const void* func = with_mode(h->prm, [&](auto M, auto NG) {
+      return lo ? (const void*)&k_align_small<M, NG, kSmallThreadsLo> : (const void*)&k_align_small<M, NG, kSmallThreadsHi>;
+    });
+    int ni = (int)n;
+    IterState* dev_state = &h->d_dyn->state[0];
+    void* args[] = {&h->d_static, &d_sx, &d_sy, &ni, (void*)&pose[0], (void*)&pose[1], (void*)&pose[2], (void*)&fixed,
+                    &dev_state, &h->h_state, &h->h_flag};
+    (void)hipLaunchKernel(func, dim3(1), dim3(lo ? kSmallThreadsLo : kSmallThreadsHi), args, 0, h->stream);
     HIP_TRY(hipGetLastError());
     h->small_run = true;
     h->pending = false;
@@ -736,14 +733,37 @@ void sym6_to_9(const double* s, double* H) {
   H[6] = s[3]; H[7] = s[4]; H[8] = s[5];
 }
 
-void state_to_result(const IterState& s, ndt2d_result* out) {
+// IterState -> ndt2d_result, or -> ndt2d_eval (the fields it shares with the result)
+template <class Out>
+void state_to(const IterState& s, Out* out) {
   std::memset(out, 0, sizeof(*out));
-  for (int j = 0; j < 3; ++j) { out->pose[j] = s.pose[j]; out->g[j] = s.g[j]; }
   sym6_to_9(s.H, out->H);
+  for (int j = 0; j < 3; ++j) out->g[j] = s.g[j];
   out->score = s.score;
-  out->iterations = s.iter;
   out->n_hit = s.n_hit;
-  out->status = s.status;
+  if constexpr (std::is_same<Out, ndt2d_result>::value) {
+    for (int j = 0; j < 3; ++j) out->pose[j] = s.pose[j];
+    out->iterations = s.iter;
+    out->status = s.status;
+  }
+}
+
+// a host scan into the handle's staging arrays, behind the alignment in flight
+int32_t stage_source(ndt2d_handle* h, const float* sx, const float* sy, size_t n) {
+  { const int32_t fs = finish_chunk_run(h); if (fs != NDT_OK) return fs; }
+  HIP_TRY(grow({grow_buf(&h->d_sx), grow_buf(&h->d_sy)}, &h->scap, n, n + n / 4 + 1024));
+  HIP_TRY(hipMemcpyAsync(h->d_sx, sx, n * sizeof(float), hipMemcpyHostToDevice, h->stream));
+  HIP_TRY(hipMemcpyAsync(h->d_sy, sy, n * sizeof(float), hipMemcpyHostToDevice, h->stream));
+  return NDT_OK;
+}
+
+// the same for a host target cloud
+int32_t stage_target(ndt2d_handle* h, const float* x, const float* y, size_t n) {
+  { const int32_t fs = finish_chunk_run(h); if (fs != NDT_OK) return fs; }
+  HIP_TRY(grow({grow_buf(&h->d_tx), grow_buf(&h->d_ty)}, &h->tcap, n, n + n / 4 + 1024));
+  HIP_TRY(hipMemcpyAsync(h->d_tx, x, n * sizeof(float), hipMemcpyHostToDevice, h->stream));
+  HIP_TRY(hipMemcpyAsync(h->d_ty, y, n * sizeof(float), hipMemcpyHostToDevice, h->stream));
+  return NDT_OK;
 }
 
 }  // namespace
@@ -936,11 +956,8 @@ int32_t ndt2d_wait_stream(ndt2d_handle* h, void* producer_stream) {
 int32_t ndt2d_set_target(ndt2d_handle* h, const float* x, const float* y, size_t n) {
   if (!h || !x || !y || n == 0) return NDT_ERR_INVALID_ARG;
   HIP_TRY(hipSetDevice(h->device));
-  { const int32_t fs = finish_chunk_run(h); if (fs != NDT_OK) return fs; }
-  HIP_TRY(grow({grow_buf(&h->d_tx), grow_buf(&h->d_ty)}, &h->tcap, n, n + n / 4 + 1024));
-  HIP_TRY(hipMemcpyAsync(h->d_tx, x, n * sizeof(float), hipMemcpyHostToDevice, h->stream));
-  HIP_TRY(hipMemcpyAsync(h->d_ty, y, n * sizeof(float), hipMemcpyHostToDevice, h->stream));
-  return set_target_impl(h, h->d_tx, h->d_ty, n);
+  { const int32_t ss = stage_target(h, x, y, n); if (ss != NDT_OK) return ss; }
+  return ndt2d_set_target_dev(h, h->d_tx, h->d_ty, n, nullptr);
 }
 
 int32_t ndt2d_set_target_dev(ndt2d_handle* h, const float* d_x, const float* d_y, size_t n, void* stream) {
@@ -992,16 +1009,8 @@ int32_t ndt2d_add_target_points(ndt2d_handle* h, const float* x, const float* y,
   if (!h || !x || !y || n == 0) return NDT_ERR_INVALID_ARG;
   if (!h->has_target) return NDT_ERR_NO_TARGET;
   HIP_TRY(hipSetDevice(h->device));
-  { const int32_t fs = finish_chunk_run(h); if (fs != NDT_OK) return fs; }
-  HIP_TRY(grow({grow_buf(&h->d_tx), grow_buf(&h->d_ty)}, &h->tcap, n, n + n / 4 + 1024));
-  HIP_TRY(hipMemcpyAsync(h->d_tx, x, n * sizeof(float), hipMemcpyHostToDevice, h->stream));
-  HIP_TRY(hipMemcpyAsync(h->d_ty, y, n * sizeof(float), hipMemcpyHostToDevice, h->stream));
-  unsigned long long outside = 0;
-  const int32_t fs = accumulate_and_finalise(h, h->d_tx, h->d_ty, n, /*merge=*/true, &outside);
-  if (n_outside) *n_outside = (size_t)outside;
-  if (fs != NDT_OK) { h->has_target = false; return fs; }
-  h->n_points += n - (size_t)outside;
-  return NDT_OK;          // as above: nothing in the device context changes
+  { const int32_t ss = stage_target(h, x, y, n); if (ss != NDT_OK) return ss; }
+  return ndt2d_add_target_points_dev(h, h->d_tx, h->d_ty, n, nullptr, n_outside, nullptr);
 }
 
 int32_t ndt2d_get_grid_info(ndt2d_handle* h, ndt2d_grid_info* info) {
@@ -1050,19 +1059,8 @@ int32_t ndt2d_evaluate(ndt2d_handle* h, const float* sx, const float* sy, size_t
   if (!h || !sx || !sy || !pose || !out || n == 0) return NDT_ERR_INVALID_ARG;
   if (!h->has_target) return NDT_ERR_NO_TARGET;
   HIP_TRY(hipSetDevice(h->device));
-  HIP_TRY(grow({grow_buf(&h->d_sx), grow_buf(&h->d_sy)}, &h->scap, n, n + n / 4 + 1024));
-  HIP_TRY(hipMemcpyAsync(h->d_sx, sx, n * sizeof(float), hipMemcpyHostToDevice, h->stream));
-  HIP_TRY(hipMemcpyAsync(h->d_sy, sy, n * sizeof(float), hipMemcpyHostToDevice, h->stream));
-  int32_t st = run_align(h, h->d_sx, h->d_sy, n, pose, /*fixed_override=*/1, /*check_every=*/0);
-  if (st != NDT_OK) return st;
-  st = fetch_state(h);
-  if (st != NDT_OK) return st;
-  std::memset(out, 0, sizeof(*out));
-  sym6_to_9(h->h_state->H, out->H);
-  for (int j = 0; j < 3; ++j) out->g[j] = h->h_state->g[j];
-  out->score = h->h_state->score;
-  out->n_hit = h->h_state->n_hit;
-  return NDT_OK;
+  { const int32_t ss = stage_source(h, sx, sy, n); if (ss != NDT_OK) return ss; }
+  return ndt2d_evaluate_dev(h, h->d_sx, h->d_sy, n, pose, out);
 }
 
 // the same with the scan already on the device (order the handle behind its producer with ndt2d_wait_stream first)
@@ -1075,11 +1073,7 @@ int32_t ndt2d_evaluate_dev(ndt2d_handle* h, const float* d_sx, const float* d_sy
   if (st != NDT_OK) return st;
   st = fetch_state(h);
   if (st != NDT_OK) return st;
-  std::memset(out, 0, sizeof(*out));
-  sym6_to_9(h->h_state->H, out->H);
-  for (int j = 0; j < 3; ++j) out->g[j] = h->h_state->g[j];
-  out->score = h->h_state->score;
-  out->n_hit = h->h_state->n_hit;
+  state_to(*h->h_state, out);
   return NDT_OK;
 }
 
@@ -1093,20 +1087,16 @@ int32_t ndt2d_align_trace(ndt2d_handle* h, const float* sx, const float* sy, siz
   HIP_TRY(hipSetDevice(h->device));
   { const int32_t fs = finish_chunk_run(h); if (fs != NDT_OK) return fs; }
   if (h->n_valid < 1) {
-    std::memset(&rows[0], 0, sizeof(ndt2d_result));
-    for (int j = 0; j < 3; ++j) rows[0].pose[j] = init_pose[j];
-    rows[0].status = NDT_TOO_FEW_CELLS;
+    state_to(no_cell_state<IterState>(init_pose), &rows[0]);
     if (out) *out = rows[0];
     return NDT_OK;
   }
-  HIP_TRY(grow({grow_buf(&h->d_sx), grow_buf(&h->d_sy)}, &h->scap, n, n + n / 4 + 1024));
-  HIP_TRY(hipMemcpyAsync(h->d_sx, sx, n * sizeof(float), hipMemcpyHostToDevice, h->stream));
-  HIP_TRY(hipMemcpyAsync(h->d_sy, sy, n * sizeof(float), hipMemcpyHostToDevice, h->stream));
+  { const int32_t ss = stage_source(h, sx, sy, n); if (ss != NDT_OK) return ss; }
   // the launch-per-iteration kernels, one plain launch and one state fetch per iteration
   const int fixed = h->prm.fixed_iterations;
   const int K = fixed > 0 ? fixed : h->prm.max_iterations;
   h->wide = h->use_wide && n >= h->wide_threshold;
-  h->call_seq = h->call_seq == 0x7fffffff ? 1 : h->call_seq + 1;
+  next_seq(&h->call_seq);
   hipLaunchKernelGGL(k_begin, dim3(1), dim3(64), 0, h->stream, h->d_call, h->d_dyn, h->d_sx, h->d_sy, (int)n, init_pose[0],
                      init_pose[1], init_pose[2], fixed, (IterState*)nullptr, (int*)nullptr, h->call_seq);
   for (int k = 0; k <= K; ++k) {
@@ -1115,12 +1105,12 @@ int32_t ndt2d_align_trace(ndt2d_handle* h, const float* sx, const float* sy, siz
     if (k == 0) continue;                                  // launch 0 only evaluates
     HIP_TRY(hipMemcpyAsync(h->h_state, &h->d_dyn->state[k & 1], sizeof(IterState), hipMemcpyDeviceToHost, h->stream));
     HIP_TRY(hipStreamSynchronize(h->stream));
-    if (*n_rows < capacity) state_to_result(*h->h_state, &rows[(*n_rows)++]);
+    if (*n_rows < capacity) state_to(*h->h_state, &rows[(*n_rows)++]);
     if (h->h_state->done) break;
   }
   h->pending = false;
   h->h_state->done = 2;                                     // the final state is in h_state
-  if (out) state_to_result(*h->h_state, out);
+  if (out) state_to(*h->h_state, out);
   return NDT_OK;
 }
 
@@ -1129,14 +1119,7 @@ int32_t ndt2d_align_finish(ndt2d_handle* h, ndt2d_result* out) {
   HIP_TRY(hipSetDevice(h->device));
   const int32_t st = fetch_state(h);
   if (st != NDT_OK) return st;
-  const IterState& s = *h->h_state;
-  std::memset(out, 0, sizeof(*out));
-  for (int j = 0; j < 3; ++j) { out->pose[j] = s.pose[j]; out->g[j] = s.g[j]; }
-  sym6_to_9(s.H, out->H);
-  out->score = s.score;
-  out->iterations = s.iter;
-  out->n_hit = s.n_hit;
-  out->status = s.status;
+  state_to(*h->h_state, out);
   return NDT_OK;
 }
 
@@ -1162,9 +1145,7 @@ int32_t ndt2d_align(ndt2d_handle* h, const float* sx, const float* sy, size_t n,
   if (!h || !sx || !sy || !init_pose || !out || n == 0) return NDT_ERR_INVALID_ARG;
   if (!h->has_target) return NDT_ERR_NO_TARGET;
   HIP_TRY(hipSetDevice(h->device));
-  HIP_TRY(grow({grow_buf(&h->d_sx), grow_buf(&h->d_sy)}, &h->scap, n, n + n / 4 + 1024));
-  HIP_TRY(hipMemcpyAsync(h->d_sx, sx, n * sizeof(float), hipMemcpyHostToDevice, h->stream));
-  HIP_TRY(hipMemcpyAsync(h->d_sy, sy, n * sizeof(float), hipMemcpyHostToDevice, h->stream));
+  { const int32_t ss = stage_source(h, sx, sy, n); if (ss != NDT_OK) return ss; }
   const int32_t rs = run_align(h, h->d_sx, h->d_sy, n, init_pose, -1, h->check_every, /*wait=*/true, /*own_source=*/true);
   if (rs != NDT_OK) return rs;
   return ndt2d_align_finish(h, out);
@@ -1176,20 +1157,25 @@ int32_t ndt2d_align(ndt2d_handle* h, const float* sx, const float* sy, size_t n,
 // ---- multi-start alignment (ndt2d_multi_start.hpp) ---------------------------------------------
 namespace {
 
-template <int MODE, int THREADS, bool SHARED>
-const void* multi_kernel(int nh, bool four) {
-  if (four) return (const void*)&k_iterate_multi<MODE, 1, THREADS, SHARED, 4>;     // overlapping grids: one start per workgroup
-  if constexpr (THREADS <= 256) {           // a 1024-thread workgroup fills its CU with one start
+// The chain kernel of a multi-start call: the fused chain's k_iterate_multi (nh starts per workgroup), or split, the split
+// chain's k_multi_body (one start per workgroup; k_multi_solve is the chain's other kernel)
+template <int MODE, int NG, int THREADS, bool SHARED>
+const void* multi_kernel_of(bool split, int nh) {
+  if (split) return (const void*)&k_multi_body<MODE, 1, THREADS, SHARED, NG>;
+  // overlapping grids: one start per workgroup; a 1024-thread workgroup fills its CU with one start
+  if constexpr (NG == 1 && THREADS <= 256) {
     if (nh == 2) return (const void*)&k_iterate_multi<MODE, 2, THREADS, SHARED>;
     if (nh == 4) return (const void*)&k_iterate_multi<MODE, 4, THREADS, SHARED>;
   }
-  return (const void*)&k_iterate_multi<MODE, 1, THREADS, SHARED>;
+  return (const void*)&k_iterate_multi<MODE, 1, THREADS, SHARED, NG>;
 }
 
-template <int MODE, int THREADS, bool SHARED>
-const void* body_kernel(int, bool four) {   // the split chain evaluates one start per workgroup
-  if (four) return (const void*)&k_multi_body<MODE, 1, THREADS, SHARED, 4>;
-  return (const void*)&k_multi_body<MODE, 1, THREADS, SHARED>;
+const void* multi_kernel(const ndt2d_params& p, bool wide, bool shared, bool split, int nh) {
+  return with_mode(p, [&](auto M, auto NG) {
+    if (wide)
+      return shared ? multi_kernel_of<M, NG, kIterThreadsWide, true>(split, nh) : multi_kernel_of<M, NG, kIterThreadsWide, false>(split, nh);
+    return shared ? multi_kernel_of<M, NG, kIterThreads, true>(split, nh) : multi_kernel_of<M, NG, kIterThreads, false>(split, nh);
+  });
 }
 
 // m alignments against the cached grid in one launch chain: of one scan from m initial poses (shared), or
@@ -1201,21 +1187,12 @@ int32_t multi_align(ndt2d_handle* h, const float* const* sxs, const float* const
   HIP_TRY(hipSetDevice(h->device));
   { const int32_t fs = finish_chunk_run(h); if (fs != NDT_OK) return fs; }
   if (h->n_valid < 1) {
-    for (int32_t k = 0; k < m; ++k) {
-      std::memset(&results[k], 0, sizeof(ndt2d_result));
-      for (int j = 0; j < 3; ++j) results[k].pose[j] = init_poses[3 * k + j];
-      results[k].status = NDT_TOO_FEW_CELLS;
-    }
+    for (int32_t k = 0; k < m; ++k) state_to(no_cell_state<IterState>(&init_poses[3 * k]), &results[k]);
     return NDT_OK;
   }
-  { const int32_t st = ensure_multi_buffers(h); if (st != NDT_OK) return st; }
+  HIP_TRY(ensure_multi_chain(&h->h_state_multi, kMaxStarts, &h->d_dyn_multi, h->stream));
   size_t n_max = 0;
   for (int32_t k = 0; k < (shared ? 1 : m); ++k) n_max = ns[k] > n_max ? ns[k] : n_max;
-  if (!h->d_dyn_multi) {
-    HIP_TRY(hipMalloc((void**)&h->d_dyn_multi, sizeof(AlignDynMulti)));
-    HIP_TRY(hipMemsetAsync(h->d_dyn_multi, 0, sizeof(AlignDynMulti), h->stream));
-  }
-  const bool newton = h->prm.hessian_mode == NDT_HESSIAN_NEWTON;
   const bool wide = h->use_wide && n_max >= h->wide_threshold;
   const int fixed = h->prm.fixed_iterations;
   const int K = fixed > 0 ? fixed : h->prm.max_iterations;
@@ -1231,25 +1208,8 @@ int32_t multi_align(ndt2d_handle* h, const float* const* sxs, const float* const
   // From kSplitFrom starts on the chain alternates two kernels per iteration (one workgroup per start solves,
   // then everybody evaluates): the 256-fold redundant prologues of the fused kernel cost more than the
   // second kernel boundary there.
-  const void* func;
-  if (!split) {
-    if (shared)
-      func = wide ? (newton ? multi_kernel<1, kIterThreadsWide, true>(nh, four) : multi_kernel<0, kIterThreadsWide, true>(nh, four))
-                  : (newton ? multi_kernel<1, kIterThreads, true>(nh, four) : multi_kernel<0, kIterThreads, true>(nh, four));
-    else
-      func = wide ? (newton ? multi_kernel<1, kIterThreadsWide, false>(nh, four) : multi_kernel<0, kIterThreadsWide, false>(nh, four))
-                  : (newton ? multi_kernel<1, kIterThreads, false>(nh, four) : multi_kernel<0, kIterThreads, false>(nh, four));
-  } else {
-    if (shared)
-      func = wide ? (newton ? body_kernel<1, kIterThreadsWide, true>(nh, four) : body_kernel<0, kIterThreadsWide, true>(nh, four))
-                  : (newton ? body_kernel<1, kIterThreads, true>(nh, four) : body_kernel<0, kIterThreads, true>(nh, four));
-    else
-      func = wide ? (newton ? body_kernel<1, kIterThreadsWide, false>(nh, four) : body_kernel<0, kIterThreadsWide, false>(nh, four))
-                  : (newton ? body_kernel<1, kIterThreads, false>(nh, four) : body_kernel<0, kIterThreads, false>(nh, four));
-  }
-  __atomic_store_n(&h->h_flag[0], 0, __ATOMIC_RELAXED);
-  __atomic_store_n(&h->h_flag[1], 0, __ATOMIC_RELAXED);
-  h->call_seq = h->call_seq == 0x7fffffff ? 1 : h->call_seq + 1;
+  const void* func = multi_kernel(h->prm, wide, shared, split, nh);
+  next_seq(&h->call_seq, h->h_flag);
   StartPoses sp{};
   StartScans sc{};
   for (int k = 0; k < m; ++k) {
@@ -1276,18 +1236,11 @@ int32_t multi_align(ndt2d_handle* h, const float* const* sxs, const float* const
                            dim3(wide ? kIterThreadsWide : kIterThreads), (void*)h->d_static, (void*)h->d_call,
                            (void*)h->d_dyn_multi, launches, (key & ~(0xff << 8)) | (mg << 8) | (mg << 20), h->stream, &exec));
   }
-  if (converged_mode) {
-    bool seen = false;
-    HIP_TRY(run_chunks_until_flag(exec, h->stream, h->h_flag, launches, K + 1, h->call_seq, &seen));
-    HIP_TRY(hipGetLastError());
-    if (!seen) { set_error("the multi-start loop did not report its end"); return NDT_ERR_HIP; }
-  } else {
-    HIP_TRY(hipGraphLaunch(exec, h->stream));
-    HIP_TRY(hipMemcpyAsync(h->h_state_multi, h->d_dyn_multi->state[K & 1], kMaxStarts * sizeof(IterState),
-                           hipMemcpyDeviceToHost, h->stream));
-    HIP_TRY(hipStreamSynchronize(h->stream));
-  }
-  for (int k = 0; k < m; ++k) state_to_result(h->h_state_multi[k], &results[k]);
+  bool seen = true;
+  HIP_TRY(run_multi_chain(exec, h->stream, converged_mode ? h->h_flag : nullptr, launches, K + 1, h->call_seq, h->h_state_multi,
+                          h->d_dyn_multi->state[K & 1], kMaxStarts * sizeof(IterState), &seen));
+  if (!seen) { set_error("the multi-start loop did not report its end"); return NDT_ERR_HIP; }
+  for (int k = 0; k < m; ++k) state_to(h->h_state_multi[k], &results[k]);
   return NDT_OK;
 }
 

@@ -477,11 +477,8 @@ int32_t ndt2d_search(ndt2d_handle* h, const float* sx, const float* sy, size_t n
   { SearchLattice L; st = search_lattice(w, &L); if (st != NDT_OK) return st; }
   if (!h->has_target) return NDT_ERR_NO_TARGET;
   HIP_TRY(hipSetDevice(h->device));
-  { const int32_t fs = finish_chunk_run(h); if (fs != NDT_OK) return fs; }
-  HIP_TRY(grow({grow_buf(&h->d_sx), grow_buf(&h->d_sy)}, &h->scap, n, n + n / 4 + 1024));
-  HIP_TRY(hipMemcpyAsync(h->d_sx, sx, n * sizeof(float), hipMemcpyHostToDevice, h->stream));
-  HIP_TRY(hipMemcpyAsync(h->d_sy, sy, n * sizeof(float), hipMemcpyHostToDevice, h->stream));
-  return search_run(h, h->d_sx, h->d_sy, n, w, k, hits, n_hits, nullptr);
+  { const int32_t ss = stage_source(h, sx, sy, n); if (ss != NDT_OK) return ss; }
+  return ndt2d_search_dev(h, h->d_sx, h->d_sy, n, w, k, hits, n_hits);
 }
 
 int32_t ndt2d_search_scores_dev(ndt2d_handle* h, const float* d_sx, const float* d_sy, size_t n,

@@ -42,7 +42,6 @@ struct ndt3d_handle {
   int call_seq = 0;                   // alignments enqueued so far
   ndt::ChainGraphCache graphs;
   hipGraphExec_t graph_exec = nullptr;   // selected by ensure_graph3, owned by `graphs`
-  bool host_result = false;           // result already in h_state (no device work was enqueued)
   // an alignment in flight (ndt3d_align_dev_async ... ndt3d_align_finish): 0 none, 1 fixed-K chain with
   // the state copy enqueued behind it, 2 converged-mode chunk loop
   int in_flight = 0;
@@ -59,12 +58,7 @@ int32_t upload_static3(ndt3d_handle* h) {
   HIP_TRY(hipEventSynchronize(h->upload_ev));
   ndt::AlignStatic3* c = h->h_static;
   c->grid = h->grid;
-  ndt::SolveParams& p = c->prm;
-  p.d1 = (float)h->prm.d1; p.d2 = (float)h->prm.d2;
-  p.hessian_mode = h->prm.hessian_mode; p.max_iterations = h->prm.max_iterations; p.min_hits = h->prm.min_hits; p.line_search = h->prm.line_search;
-  p.eps_trans = h->prm.eps_trans; p.eps_rot = h->prm.eps_rot;
-  p.step_max_trans = h->prm.step_max_trans; p.step_max_rot = h->prm.step_max_rot;
-  p.step_scale = h->prm.step_scale > 0.0 ? h->prm.step_scale : 1.0;
+  set_solve_params(&c->prm, h->prm);
   HIP_TRY(hipMemcpyAsync(h->d_static, c, sizeof(ndt::AlignStatic3), hipMemcpyHostToDevice, h->stream));
   HIP_TRY(hipEventRecord(h->upload_ev, h->stream));
   return NDT_OK;
@@ -327,10 +321,14 @@ int32_t set_target3_impl(ndt3d_handle* h, const float* dx, const float* dy, cons
   return upload_static3(h);
 }
 
+// the k_iterate3 of the handle's Hessian, for graphs (ensure_graph3) and plain launches (ndt3d_align_trace)
+const void* iter3_kernel(const ndt3d_handle* h) {
+  return with_mode(h->prm, [](auto M, auto) { return (const void*)&ndt::k_iterate3<M>; });
+}
+
 int32_t ensure_graph3(ndt3d_handle* h, int launches) {
   using namespace ndt;
-  const bool newton = h->prm.hessian_mode == NDT_HESSIAN_NEWTON;
-  HIP_TRY(h->graphs.get(newton ? (const void*)&k_iterate3<1> : (const void*)&k_iterate3<0>, dim3(kMaxBlocks), dim3(kBlock),
+  HIP_TRY(h->graphs.get(iter3_kernel(h), dim3(kMaxBlocks), dim3(kBlock),
                         (void*)h->d_static, (void*)h->d_call, (void*)h->d_dyn, launches, h->prm.hessian_mode, h->stream,
                         &h->graph_exec));
   return NDT_OK;
@@ -363,15 +361,11 @@ int32_t begin_align3(ndt3d_handle* h, const float* dx, const float* dy, const fl
   if (h->in_flight == 2) { const int32_t fs = finish_align3(h); if (fs != NDT_OK) return fs; }
   if (n == 0 || n > kMaxSourcePoints) return NDT_ERR_INVALID_ARG;
   if (h->n_valid < 1) {
-    std::memset(h->h_state, 0, sizeof(IterState3));
-    for (int j = 0; j < 6; ++j) h->h_state->pose[j] = pose[j];
-    h->h_state->status = NDT_TOO_FEW_CELLS;
+    *h->h_state = no_cell_state<IterState3>(pose);
     return NDT_OK;
   }
   const int fixed = fixed_override >= 0 ? fixed_override : h->prm.fixed_iterations;
-  __atomic_store_n(&h->h_flag[0], 0, __ATOMIC_RELAXED);
-  __atomic_store_n(&h->h_flag[1], 0, __ATOMIC_RELAXED);
-  h->call_seq = h->call_seq == 0x7fffffff ? 1 : h->call_seq + 1;
+  next_seq(&h->call_seq, h->h_flag);
   hipLaunchKernelGGL(k_begin3, dim3(1), dim3(64), 0, h->stream, h->d_call, h->d_dyn, dx, dy, dz, (int)n, pose[0], pose[1],
                      pose[2], pose[3], pose[4], pose[5], fixed, fixed > 0 ? (IterState3*)nullptr : h->h_state,
                      fixed > 0 ? (int*)nullptr : h->h_flag, h->call_seq);
@@ -401,13 +395,44 @@ int32_t run_align3(ndt3d_handle* h, const float* dx, const float* dy, const floa
   return st != NDT_OK ? st : finish_align3(h);
 }
 
-void unpack_h21(const double* s, double* H);
+void unpack_h21(const double* s, double* H) {
+  H[0] = s[0]; H[1] = s[1]; H[2] = s[2]; H[7] = s[3]; H[8] = s[4]; H[14] = s[5];
+  for (int r = 0; r < 3; ++r) for (int k = 0; k < 3; ++k) H[6 * r + 3 + k] = s[6 + 3 * r + k];
+  H[21] = s[15]; H[22] = s[16]; H[23] = s[17]; H[28] = s[18]; H[29] = s[19]; H[35] = s[20];
+  for (int r = 0; r < 6; ++r) for (int c = 0; c < r; ++c) H[6 * r + c] = H[6 * c + r];
+}
 
-void state3_to_result(const ndt::IterState3& s, ndt3d_result* out) {
+// IterState3 -> ndt3d_result, or -> ndt3d_eval (the fields it shares with the result)
+template <class Out>
+void state3_to(const ndt::IterState3& s, Out* out) {
   std::memset(out, 0, sizeof(*out));
-  for (int j = 0; j < 6; ++j) { out->pose[j] = s.pose[j]; out->g[j] = s.g[j]; }
   unpack_h21(s.H, out->H);
-  out->score = s.score; out->iterations = s.iter; out->n_hit = s.n_hit; out->status = s.status;
+  for (int j = 0; j < 6; ++j) out->g[j] = s.g[j];
+  out->score = s.score;
+  out->n_hit = s.n_hit;
+  if constexpr (std::is_same<Out, ndt3d_result>::value) {
+    for (int j = 0; j < 6; ++j) out->pose[j] = s.pose[j];
+    out->iterations = s.iter;
+    out->status = s.status;
+  }
+}
+
+// a host scan into the handle's staging arrays, behind the alignment in flight
+int32_t stage_source3(ndt3d_handle* h, const float* sx, const float* sy, const float* sz, size_t n) {
+  { const int32_t fs = finish_align3(h); if (fs != NDT_OK) return fs; }
+  HIP_TRY(grow({grow_buf(&h->d_s[0]), grow_buf(&h->d_s[1]), grow_buf(&h->d_s[2])}, &h->scap, n, n + n / 4 + 1024));
+  const float* src[3] = {sx, sy, sz};
+  for (int a = 0; a < 3; ++a) HIP_TRY(hipMemcpyAsync(h->d_s[a], src[a], n * sizeof(float), hipMemcpyHostToDevice, h->stream));
+  return NDT_OK;
+}
+
+// the same for a host target cloud
+int32_t stage_target3(ndt3d_handle* h, const float* x, const float* y, const float* z, size_t n) {
+  { const int32_t fs = finish_align3(h); if (fs != NDT_OK) return fs; }
+  HIP_TRY(grow({grow_buf(&h->d_t[0]), grow_buf(&h->d_t[1]), grow_buf(&h->d_t[2])}, &h->tcap, n, n + n / 4 + 1024));
+  const float* src[3] = {x, y, z};
+  for (int a = 0; a < 3; ++a) HIP_TRY(hipMemcpyAsync(h->d_t[a], src[a], n * sizeof(float), hipMemcpyHostToDevice, h->stream));
+  return NDT_OK;
 }
 
 // m alignments against the cached voxel grid in one launch chain (ndt3d_multi.hpp)
@@ -419,25 +444,14 @@ int32_t multi_align3(ndt3d_handle* h, const float* const* sxs, const float* cons
   HIP_TRY(hipSetDevice(h->device));
   { const int32_t fs = finish_align3(h); if (fs != NDT_OK) return fs; }
   if (h->n_valid < 1) {
-    for (int32_t k = 0; k < m; ++k) {
-      std::memset(&results[k], 0, sizeof(ndt3d_result));
-      for (int j = 0; j < 6; ++j) results[k].pose[j] = init_poses[6 * k + j];
-      results[k].status = NDT_TOO_FEW_CELLS;
-    }
+    for (int32_t k = 0; k < m; ++k) state3_to(no_cell_state<IterState3>(&init_poses[6 * k]), &results[k]);
     return NDT_OK;
   }
-  if (!h->h_state_multi) HIP_TRY(pinned_alloc(&h->h_state_multi, kMaxStarts3 * sizeof(IterState3)));
-  if (!h->d_dyn_multi) {
-    HIP_TRY(hipMalloc((void**)&h->d_dyn_multi, sizeof(AlignDynMulti3)));
-    HIP_TRY(hipMemsetAsync(h->d_dyn_multi, 0, sizeof(AlignDynMulti3), h->stream));
-  }
-  const bool newton = h->prm.hessian_mode == NDT_HESSIAN_NEWTON;
+  HIP_TRY(ensure_multi_chain(&h->h_state_multi, kMaxStarts3, &h->d_dyn_multi, h->stream));
   const int fixed = h->prm.fixed_iterations;
   const int K = fixed > 0 ? fixed : h->prm.max_iterations;
   const bool converged_mode = fixed == 0;
-  __atomic_store_n(&h->h_flag[0], 0, __ATOMIC_RELAXED);
-  __atomic_store_n(&h->h_flag[1], 0, __ATOMIC_RELAXED);
-  h->call_seq = h->call_seq == 0x7fffffff ? 1 : h->call_seq + 1;
+  next_seq(&h->call_seq, h->h_flag);
   StartPoses3 sp{};
   StartScans3 sc{};
   for (int k = 0; k < m; ++k) {
@@ -453,34 +467,20 @@ int32_t multi_align3(ndt3d_handle* h, const float* const* sxs, const float* cons
   const int chunk = 8;
   const int steps = converged_mode ? chunk : K + 1;
   hipGraphExec_t exec = nullptr;
-  const void* fs = newton ? (const void*)&k_multi_solve3<1> : (const void*)&k_multi_solve3<0>;
-  const void* fb = newton ? (const void*)&k_multi_body3<1> : (const void*)&k_multi_body3<0>;
+  const void *fs = nullptr, *fb = nullptr;
+  with_mode(h->prm, [&](auto M, auto) { fs = (const void*)&k_multi_solve3<M>; fb = (const void*)&k_multi_body3<M>; });
   // launch shapes in powers of two (slots >= m are born finished: their workgroups return at once), so that a caller
   // whose m varies from call to call replays one of seven cached graphs instead of instantiating a new one each time
   int mg = 1;
   while (mg < m) mg <<= 1;
   HIP_TRY(h->graphs.get2(fs, dim3(mg), dim3(kBlock), fb, dim3(kMaxBlocks, mg), dim3(kBlock), (void*)h->d_static, (void*)h->d_call,
                          (void*)h->d_dyn_multi, steps, 0x100000 | (mg << 8) | h->prm.hessian_mode, h->stream, &exec));
-  if (converged_mode) {
-    bool seen = false;
-    HIP_TRY(run_chunks_until_flag(exec, h->stream, h->h_flag, steps, K + 1, h->call_seq, &seen));
-    HIP_TRY(hipGetLastError());
-    if (!seen) { set_error("the 3D multi-scan loop did not report its end"); return NDT_ERR_HIP; }
-  } else {
-    HIP_TRY(hipGraphLaunch(exec, h->stream));
-    HIP_TRY(hipMemcpyAsync(h->h_state_multi, h->d_dyn_multi->state[K & 1], kMaxStarts3 * sizeof(IterState3), hipMemcpyDeviceToHost,
-                           h->stream));
-    HIP_TRY(hipStreamSynchronize(h->stream));
-  }
-  for (int k = 0; k < m; ++k) state3_to_result(h->h_state_multi[k], &results[k]);
+  bool seen = true;
+  HIP_TRY(run_multi_chain(exec, h->stream, converged_mode ? h->h_flag : nullptr, steps, K + 1, h->call_seq, h->h_state_multi,
+                          h->d_dyn_multi->state[K & 1], kMaxStarts3 * sizeof(IterState3), &seen));
+  if (!seen) { set_error("the 3D multi-scan loop did not report its end"); return NDT_ERR_HIP; }
+  for (int k = 0; k < m; ++k) state3_to(h->h_state_multi[k], &results[k]);
   return NDT_OK;
-}
-
-void unpack_h21(const double* s, double* H) {
-  H[0] = s[0]; H[1] = s[1]; H[2] = s[2]; H[7] = s[3]; H[8] = s[4]; H[14] = s[5];
-  for (int r = 0; r < 3; ++r) for (int k = 0; k < 3; ++k) H[6 * r + 3 + k] = s[6 + 3 * r + k];
-  H[21] = s[15]; H[22] = s[16]; H[23] = s[17]; H[28] = s[18]; H[29] = s[19]; H[35] = s[20];
-  for (int r = 0; r < 6; ++r) for (int c = 0; c < r; ++c) H[6 * r + c] = H[6 * c + r];
 }
 
 }  // namespace
@@ -562,15 +562,8 @@ int32_t ndt3d_add_target_points(ndt3d_handle* h, const float* x, const float* y,
   if (!h || !x || !y || !z || n == 0) return NDT_ERR_INVALID_ARG;
   if (!h->has_target) return NDT_ERR_NO_TARGET;
   HIP_TRY(hipSetDevice(h->device));
-  { const int32_t fs = finish_align3(h); if (fs != NDT_OK) return fs; }
-  HIP_TRY(grow({grow_buf(&h->d_t[0]), grow_buf(&h->d_t[1]), grow_buf(&h->d_t[2])}, &h->tcap, n, n + n / 4 + 1024));
-  const float* src[3] = {x, y, z};
-  for (int a = 0; a < 3; ++a) HIP_TRY(hipMemcpyAsync(h->d_t[a], src[a], n * sizeof(float), hipMemcpyHostToDevice, h->stream));
-  unsigned long long outside = 0;
-  const int32_t fs = accumulate3(h, h->d_t[0], h->d_t[1], h->d_t[2], n, /*merge=*/true, &outside);
-  if (n_outside) *n_outside = (size_t)outside;
-  if (fs != NDT_OK) { h->has_target = false; return fs; }
-  return NDT_OK;          // geometry, storage and parameters are unchanged: the device context stays as it is
+  { const int32_t ss = stage_target3(h, x, y, z, n); if (ss != NDT_OK) return ss; }
+  return ndt3d_add_target_points_dev(h, h->d_t[0], h->d_t[1], h->d_t[2], n, nullptr, n_outside, nullptr);
 }
 
 int32_t ndt3d_range_image_to_points_dev(const float* d_ranges, int32_t n_elev, int32_t n_azim, const double* elevations,
@@ -632,7 +625,7 @@ int32_t ndt3d_add_target_points_dev(ndt3d_handle* h, const float* d_x, const flo
   const int32_t fs = accumulate3(h, p[0], p[1], p[2], n, /*merge=*/true, &outside, pose ? &T : nullptr);
   if (n_outside) *n_outside = (size_t)outside;
   if (fs != NDT_OK) { h->has_target = false; return fs; }
-  return NDT_OK;
+  return NDT_OK;          // geometry, storage and parameters are unchanged: the device context stays as it is
 }
 
 int32_t ndt3d_set_target_dev(ndt3d_handle* h, const float* d_x, const float* d_y, const float* d_z, size_t n, void* stream) {
@@ -646,11 +639,8 @@ int32_t ndt3d_set_target_dev(ndt3d_handle* h, const float* d_x, const float* d_y
 int32_t ndt3d_set_target(ndt3d_handle* h, const float* x, const float* y, const float* z, size_t n) {
   if (!h || !x || !y || !z || n == 0) return NDT_ERR_INVALID_ARG;
   HIP_TRY(hipSetDevice(h->device));
-  { const int32_t fs = finish_align3(h); if (fs != NDT_OK) return fs; }
-  HIP_TRY(grow({grow_buf(&h->d_t[0]), grow_buf(&h->d_t[1]), grow_buf(&h->d_t[2])}, &h->tcap, n, n + n / 4 + 1024));
-  const float* src[3] = {x, y, z};
-  for (int a = 0; a < 3; ++a) HIP_TRY(hipMemcpyAsync(h->d_t[a], src[a], n * sizeof(float), hipMemcpyHostToDevice, h->stream));
-  return set_target3_impl(h, h->d_t[0], h->d_t[1], h->d_t[2], n);
+  { const int32_t ss = stage_target3(h, x, y, z, n); if (ss != NDT_OK) return ss; }
+  return ndt3d_set_target_dev(h, h->d_t[0], h->d_t[1], h->d_t[2], n, nullptr);
 }
 
 int32_t ndt3d_get_grid_info(ndt3d_handle* h, ndt3d_grid_info* info) {
@@ -688,29 +678,13 @@ int32_t ndt3d_get_grid(ndt3d_handle* h, int32_t* count, float* mean_xyz, float* 
   return rc;
 }
 
-static int32_t upload_source3(ndt3d_handle* h, const float* sx, const float* sy, const float* sz, size_t n) {
-  { const int32_t fs = finish_align3(h); if (fs != NDT_OK) return fs; }
-  HIP_TRY(grow({grow_buf(&h->d_s[0]), grow_buf(&h->d_s[1]), grow_buf(&h->d_s[2])}, &h->scap, n, n + n / 4 + 1024));
-  const float* src[3] = {sx, sy, sz};
-  for (int a = 0; a < 3; ++a) HIP_TRY(hipMemcpyAsync(h->d_s[a], src[a], n * sizeof(float), hipMemcpyHostToDevice, h->stream));
-  return NDT_OK;
-}
-
 int32_t ndt3d_evaluate(ndt3d_handle* h, const float* sx, const float* sy, const float* sz, size_t n,
                        const double pose[6], ndt3d_eval* out) {
   if (!h || !sx || !sy || !sz || !pose || !out || n == 0) return NDT_ERR_INVALID_ARG;
   if (!h->has_target) return NDT_ERR_NO_TARGET;
   HIP_TRY(hipSetDevice(h->device));
-  int32_t st = upload_source3(h, sx, sy, sz, n);
-  if (st != NDT_OK) return st;
-  st = run_align3(h, h->d_s[0], h->d_s[1], h->d_s[2], n, pose, 1);
-  if (st != NDT_OK) return st;
-  std::memset(out, 0, sizeof(*out));
-  unpack_h21(h->h_state->H, out->H);
-  for (int j = 0; j < 6; ++j) out->g[j] = h->h_state->g[j];
-  out->score = h->h_state->score;
-  out->n_hit = h->h_state->n_hit;
-  return NDT_OK;
+  { const int32_t ss = stage_source3(h, sx, sy, sz, n); if (ss != NDT_OK) return ss; }
+  return ndt3d_evaluate_dev(h, h->d_s[0], h->d_s[1], h->d_s[2], n, pose, out);
 }
 
 int32_t ndt3d_evaluate_dev(ndt3d_handle* h, const float* d_sx, const float* d_sy, const float* d_sz, size_t n,
@@ -720,11 +694,7 @@ int32_t ndt3d_evaluate_dev(ndt3d_handle* h, const float* d_sx, const float* d_sy
   HIP_TRY(hipSetDevice(h->device));
   const int32_t st = run_align3(h, d_sx, d_sy, d_sz, n, pose, 1);
   if (st != NDT_OK) return st;
-  std::memset(out, 0, sizeof(*out));
-  unpack_h21(h->h_state->H, out->H);
-  for (int j = 0; j < 6; ++j) out->g[j] = h->h_state->g[j];
-  out->score = h->h_state->score;
-  out->n_hit = h->h_state->n_hit;
+  state3_to(*h->h_state, out);
   return NDT_OK;
 }
 
@@ -740,11 +710,7 @@ int32_t ndt3d_align_finish(ndt3d_handle* h, ndt3d_result* out) {
   HIP_TRY(hipSetDevice(h->device));
   const int32_t st = finish_align3(h);
   if (st != NDT_OK) return st;
-  const ndt::IterState3& s = *h->h_state;
-  std::memset(out, 0, sizeof(*out));
-  for (int j = 0; j < 6; ++j) { out->pose[j] = s.pose[j]; out->g[j] = s.g[j]; }
-  unpack_h21(s.H, out->H);
-  out->score = s.score; out->iterations = s.iter; out->n_hit = s.n_hit; out->status = s.status;
+  state3_to(*h->h_state, out);
   return NDT_OK;
 }
 
@@ -758,38 +724,29 @@ int32_t ndt3d_align_trace(ndt3d_handle* h, const float* sx, const float* sy, con
   if (!h->has_target) return NDT_ERR_NO_TARGET;
   TraceRange range("ndt3d_align_trace");
   HIP_TRY(hipSetDevice(h->device));
-  auto to_row = [](const IterState3& s, ndt3d_result* r) {
-    std::memset(r, 0, sizeof(*r));
-    for (int j = 0; j < 6; ++j) { r->pose[j] = s.pose[j]; r->g[j] = s.g[j]; }
-    unpack_h21(s.H, r->H);
-    r->score = s.score; r->iterations = s.iter; r->n_hit = s.n_hit; r->status = s.status;
-  };
   if (h->n_valid < 1) {
-    std::memset(&rows[0], 0, sizeof(ndt3d_result));
-    for (int j = 0; j < 6; ++j) rows[0].pose[j] = init_pose[j];
-    rows[0].status = NDT_TOO_FEW_CELLS;
+    state3_to(no_cell_state<IterState3>(init_pose), &rows[0]);
     if (out) *out = rows[0];
     return NDT_OK;
   }
-  { const int32_t us = upload_source3(h, sx, sy, sz, n); if (us != NDT_OK) return us; }
+  { const int32_t us = stage_source3(h, sx, sy, sz, n); if (us != NDT_OK) return us; }
   const int fixed = h->prm.fixed_iterations;
   const int K = fixed > 0 ? fixed : h->prm.max_iterations;
-  const bool newton = h->prm.hessian_mode == NDT_HESSIAN_NEWTON;
-  h->call_seq = h->call_seq == 0x7fffffff ? 1 : h->call_seq + 1;
+  next_seq(&h->call_seq);
   hipLaunchKernelGGL(k_begin3, dim3(1), dim3(64), 0, h->stream, h->d_call, h->d_dyn, h->d_s[0], h->d_s[1], h->d_s[2], (int)n,
                      init_pose[0], init_pose[1], init_pose[2], init_pose[3], init_pose[4], init_pose[5], fixed,
                      (IterState3*)nullptr, (int*)nullptr, h->call_seq);
+  const void* iterate = iter3_kernel(h);
   for (int k = 0; k <= K; ++k) {
-    if (newton) hipLaunchKernelGGL((k_iterate3<1>), dim3(kMaxBlocks), dim3(kBlock), 0, h->stream, h->d_static, h->d_call, h->d_dyn, k & 1);
-    else hipLaunchKernelGGL((k_iterate3<0>), dim3(kMaxBlocks), dim3(kBlock), 0, h->stream, h->d_static, h->d_call, h->d_dyn, k & 1);
+    (void)launch_chain_kernel(iterate, dim3(kMaxBlocks), dim3(kBlock), h->d_static, h->d_call, h->d_dyn, k & 1, h->stream);
     HIP_TRY(hipGetLastError());
     if (k == 0) continue;                                  // launch 0 only evaluates
     HIP_TRY(hipMemcpyAsync(h->h_state, &h->d_dyn->state[k & 1], sizeof(IterState3), hipMemcpyDeviceToHost, h->stream));
     HIP_TRY(hipStreamSynchronize(h->stream));
-    if (*n_rows < capacity) to_row(*h->h_state, &rows[(*n_rows)++]);
+    if (*n_rows < capacity) state3_to(*h->h_state, &rows[(*n_rows)++]);
     if (h->h_state->done) break;
   }
-  if (out) to_row(*h->h_state, out);
+  if (out) state3_to(*h->h_state, out);
   return NDT_OK;
 }
 
@@ -823,7 +780,7 @@ int32_t ndt3d_align(ndt3d_handle* h, const float* sx, const float* sy, const flo
   if (!h || !sx || !sy || !sz || !init_pose || !out || n == 0) return NDT_ERR_INVALID_ARG;
   if (!h->has_target) return NDT_ERR_NO_TARGET;
   HIP_TRY(hipSetDevice(h->device));
-  const int32_t st = upload_source3(h, sx, sy, sz, n);
+  const int32_t st = stage_source3(h, sx, sy, sz, n);
   if (st != NDT_OK) return st;
   return ndt3d_align_dev(h, h->d_s[0], h->d_s[1], h->d_s[2], n, init_pose, out);
 }

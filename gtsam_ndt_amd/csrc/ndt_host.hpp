@@ -131,6 +131,13 @@ inline hipError_t build_chain_graph(const void* func, dim3 grid, dim3 block, voi
   return hipSuccess;
 }
 
+// One plain launch of a kernel of such a chain, with the chain's arguments
+inline hipError_t launch_chain_kernel(const void* func, dim3 grid, dim3 block, void* a0, void* a1, void* a2, int parity,
+                                      hipStream_t stream) {
+  void* args[4] = {&a0, &a1, &a2, &parity};
+  return hipLaunchKernel(func, grid, block, args, 0, stream);
+}
+
 // The same for chains that alternate two kernels per step (A then B, both taking the step's parity).
 inline hipError_t build_chain_graph2(const void* fa, dim3 ga, dim3 ba, const void* fb, dim3 gb, dim3 bb, void* a0, void* a1,
                                      void* a2, int steps, hipGraph_t* graph_out, hipGraphExec_t* exec_out) {
@@ -326,6 +333,34 @@ inline hipError_t run_chunks_until_flag(hipGraphExec_t exec, hipStream_t stream,
   return chunk_run_finish(r, stream, flag, seen);
 }
 
+// The buffers of a handle's multi-start chains, allocated on first use: pinned room for `starts` final states and the
+// chains' device context (zeroed on `stream`).
+template <class State, class Dyn>
+inline hipError_t ensure_multi_chain(State** h_states, int starts, Dyn** d_dyn, hipStream_t stream) {
+  hipError_t e = *h_states ? hipSuccess : pinned_alloc(h_states, starts * sizeof(State));
+  if (e == hipSuccess && !*d_dyn) {
+    e = hipMalloc(reinterpret_cast<void**>(d_dyn), sizeof(Dyn));
+    if (e == hipSuccess) e = hipMemsetAsync(*d_dyn, 0, sizeof(Dyn), stream);
+  }
+  return e;
+}
+
+// Runs a multi-start chain whose first launch (k_begin_multi*) is enqueued, until its final states are in h_states.
+// Converged mode (flag != null): chunks of `launches` until the finishing launch, which writes the states there itself,
+// raises flag[0]; *seen = false: it did not.  Fixed mode: one replay of the whole chain, then a copy of `bytes` from d_states.
+inline hipError_t run_multi_chain(hipGraphExec_t exec, hipStream_t stream, int* flag, int launches, int max_launches, int seq,
+                                  void* h_states, const void* d_states, size_t bytes, bool* seen) {
+  *seen = true;
+  if (flag) {
+    const hipError_t e = run_chunks_until_flag(exec, stream, flag, launches, max_launches, seq, seen);
+    return e != hipSuccess ? e : hipGetLastError();
+  }
+  hipError_t e = hipGraphLaunch(exec, stream);
+  if (e == hipSuccess) e = hipMemcpyAsync(h_states, d_states, bytes, hipMemcpyDeviceToHost, stream);
+  if (e == hipSuccess) e = hipStreamSynchronize(stream);
+  return e;
+}
+
 // The pinned 256-byte block of a handle (h_small): counter shards at 0, the outside count at 128, the flag of a build's
 // read-back (publish_and_wait) at byte kSmallFlagByte.
 constexpr size_t kSmallBytes = 256, kSmallFlagByte = 192;
@@ -333,14 +368,24 @@ inline int* small_flag(void* h_small) { return reinterpret_cast<int*>(static_cas
 
 inline bool flag_raised(const int* flag, int seq) { return __atomic_load_n(flag, __ATOMIC_ACQUIRE) == seq; }
 
-// The read-back of a build through pinned memory: advances *seq (1 .. 2^31 - 1, never 0: pinned blocks start zeroed) and
-// calls launch(seq), which enqueues the publish kernel (k_build_publish, k_build_publish_clear3 or k_bounds3_publish): it
-// writes its words into pinned memory, then raises *flag to seq.  The host spins on the flag.  *seen = false: it did not
-// come (a stream error, or a second of silence) - the caller's fallback decides what that means.
+// Advances a sequence number the device echoes into pinned memory (1 .. 2^31 - 1, never 0: pinned blocks start zeroed) and
+// returns it: a build's read-back (publish_and_wait below) or an alignment call (ChunkRun::seq, the number k_begin* hands to
+// the chain).  flag: the converged-mode flags of an alignment call (ChunkRun), whose flag[0] and flag[1] are cleared first.
+inline int next_seq(int* seq, int* flag = nullptr) {
+  if (flag) {
+    __atomic_store_n(&flag[0], 0, __ATOMIC_RELAXED);
+    __atomic_store_n(&flag[1], 0, __ATOMIC_RELAXED);
+  }
+  return *seq = *seq == 0x7fffffff ? 1 : *seq + 1;
+}
+
+// The read-back of a build through pinned memory: advances *seq (next_seq) and calls launch(seq), which enqueues the publish
+// kernel (k_build_publish, k_build_publish_clear3 or k_bounds3_publish): it writes its words into pinned memory, then raises
+// *flag to seq.  The host spins on the flag.  *seen = false: it did not come (a stream error, or a second of silence) - the
+// caller's fallback decides what that means.
 template <class Launch>
 inline hipError_t publish_and_wait(hipStream_t stream, int* seq, const int* flag, Launch&& launch, bool* seen) {
-  *seq = *seq == 0x7fffffff ? 1 : *seq + 1;
-  const int want = *seq;
+  const int want = next_seq(seq);
   *seen = false;
   launch(want);
   const hipError_t e = hipGetLastError();
