@@ -108,6 +108,16 @@ class SearchHit2D(C.Structure):
     _fields_ = [("pose", C.c_double * 3), ("score", C.c_float), ("index", C.c_int32)]
 
 
+class SearchWindow3D(C.Structure):
+    """ndt3d_search_window: the (x, y, yaw) lattice of an exhaustive 3D pose search around a 6-vector centre."""
+    _fields_ = [("center", C.c_double * 6), ("half_extent", C.c_double * 3), ("step", C.c_double * 3),
+                ("min_sep_trans", C.c_double), ("min_sep_rot", C.c_double)]
+
+
+class SearchHit3D(C.Structure):
+    _fields_ = [("pose", C.c_double * 6), ("score", C.c_float), ("index", C.c_int32)]
+
+
 class Result3D(C.Structure):
     _fields_ = [("pose", C.c_double * 6), ("H", C.c_double * 36), ("g", C.c_double * 6), ("score", C.c_double),
                 ("iterations", C.c_int32), ("n_hit", C.c_int32), ("status", C.c_int32), ("reserved", C.c_int32)]
@@ -191,6 +201,14 @@ SIGNATURES = {
     "ndt2d_multi_align_dev": (C.c_int32, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "ndt2d_multi_plan": (C.c_int32, [C.c_int32, _vp, _vp, C.c_size_t, C.c_int32, _vp]),
     "ndt2d_multi_plan_hinted": (C.c_int32, [C.c_int32, _vp, _vp, C.c_size_t, C.c_int32, _vp, _vp]),
+    "ndt3d_search_lattice_size": (C.c_int32, [C.POINTER(SearchWindow3D), _vp]),
+    "ndt3d_search": (C.c_int32, [_vp, _vp, _vp, _vp, C.c_size_t, C.POINTER(SearchWindow3D), C.c_int32, _vp,
+                                 C.POINTER(C.c_int32)]),
+    "ndt3d_search_dev": (C.c_int32, [_vp, _vp, _vp, _vp, C.c_size_t, C.POINTER(SearchWindow3D), C.c_int32, _vp,
+                                     C.POINTER(C.c_int32)]),
+    "ndt3d_search_scores_dev": (C.c_int32, [_vp, _vp, _vp, _vp, C.c_size_t, C.POINTER(SearchWindow3D), _vp]),
+    "ndt3d_search_align_dev": (C.c_int32, [_vp, _vp, _vp, _vp, C.c_size_t, C.POINTER(SearchWindow3D), C.c_int32, _vp, _vp,
+                                           C.POINTER(C.c_int32)]),
     "ndt3d_default_params": (None, [C.POINTER(Params2D)]),
     "ndt3d_create": (C.c_int32, [C.POINTER(Params2D), C.c_int32, C.POINTER(_vp)]),
     "ndt3d_destroy": (C.c_int32, [_vp]),

@@ -17,12 +17,11 @@
 #include "ndt2d_build_sorted.hpp"
 #include "ndt2d_multi_start.hpp"
 #include "ndt_host.hpp"
+#include "ndt_search.hpp"
 
 #include <atomic>
 
 using namespace ndt;
-
-namespace ndt { struct SearchSel; }   // ndt2d_search.hpp
 
 struct ndt2d_handle {
   int device = 0;
@@ -89,13 +88,7 @@ struct ndt2d_handle {
   size_t wide_threshold = 300000;          // ... from this many source points
   bool use_graph = true;
   int check_every = 8;                     // converged mode: launches per chunk
-  // exhaustive pose search scratch (ndt2d_search.hpp), allocated on first use and grown on demand
-  float* d_srch_vol = nullptr; size_t srch_vol_cap = 0;                     // the score volume
-  unsigned long long* d_srch_keys = nullptr; size_t srch_keys_cap = 0;     // peak keys
-  unsigned char* d_srch_axes = nullptr; size_t srch_axes_cap = 0;          // the lattice's axes
-  ndt::SearchSel* d_srch_sel = nullptr;                                    // selection state and shortlist
-  unsigned char* h_srch_axes = nullptr; size_t h_srch_axes_cap = 0;        // pinned: the axes' upload
-  ndt::SearchSel* h_srch_sel = nullptr;                                    // pinned: the shortlist's read-back
+  SearchScratch srch;                      // exhaustive pose search scratch (ndt_search.hpp), allocated on first use
 };
 
 namespace {
@@ -915,10 +908,11 @@ int32_t ndt2d_destroy(ndt2d_handle* h) {
   drop_graph(h);
   if (h->h_state_multi) (void)hipHostFree(h->h_state_multi);
   void* dev[] = {h->d_acc2, h->d_split, h->d_bxy, h->d_table, h->d_parts, h->d_geom, h->d_dyn_multi, h->d_bounds, h->d_counters, h->d_outside, h->d_static, h->d_call, h->d_dyn, h->d_bx, h->d_by, h->d_tiles, h->d_tx, h->d_ty, h->d_sx, h->d_sy,
-                 h->grid.rec, h->grid.acc, h->d_srch_vol, h->d_srch_keys, h->d_srch_axes, h->d_srch_sel};
+                 h->grid.rec, h->grid.acc};
   for (void* p : dev) if (p) (void)hipFree(p);
-  void* host[] = {h->h_geom, h->h_static, h->h_state, h->h_small, h->h_flag, h->h_srch_axes, h->h_srch_sel};
+  void* host[] = {h->h_geom, h->h_static, h->h_state, h->h_small, h->h_flag};
   for (void* p : host) if (p) (void)hipHostFree(p);
+  h->srch.release();
   if (h->upload_ev) (void)hipEventDestroy(h->upload_ev);
   if (h->wait_ev) (void)hipEventDestroy(h->wait_ev);
   if (h->stream) (void)hipStreamDestroy(h->stream);
@@ -1268,3 +1262,4 @@ extern "C" int32_t ndt2d_align_multi_scan_dev(ndt2d_handle* h, const float* cons
 #include "ndt3d_multi_api.hpp"
 #include "ndt_map_io.hpp"
 #include "ndt2d_search.hpp"
+#include "ndt3d_search.hpp"

@@ -48,6 +48,7 @@ struct ndt3d_handle {
   ndt::ChunkRun chunk_run;
   ndt::AlignDynMulti3* d_dyn_multi = nullptr;   // multi-scan / multi-start chains (ndt3d_multi.hpp), on first use
   ndt::IterState3* h_state_multi = nullptr;     // pinned [kMaxStarts3]
+  ndt::SearchScratch srch;                      // exhaustive pose search scratch (ndt_search.hpp), allocated on first use
 };
 
 namespace {
@@ -539,6 +540,7 @@ int32_t ndt3d_destroy(ndt3d_handle* h) {
   for (void* p : dev) if (p) (void)hipFree(p);
   void* host[] = {h->h_static, h->h_state, h->h_small, h->h_flag, h->h_state_multi, h->h_pub3};
   for (void* p : host) if (p) (void)hipHostFree(p);
+  h->srch.release();
   if (h->upload_ev) (void)hipEventDestroy(h->upload_ev);
   if (h->stream) (void)hipStreamDestroy(h->stream);
   delete h;

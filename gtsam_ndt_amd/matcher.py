@@ -634,6 +634,7 @@ class NdtMatcher3D:
         h = C.c_void_p()
         L.check(self._lib.ndt3d_create(C.byref(self.params), int(device), C.byref(h)), "ndt3d_create")
         self._h = h
+        self._device = int(device)
         for k, v in (tuning or {}).items():
             L.check(self._lib.ndt3d_set_tuning(self._h, L.TUNING[k], int(v)), "ndt3d_set_tuning")
 
@@ -782,6 +783,74 @@ class NdtMatcher3D:
                                                       poses.ctypes.data_as(L._dp), m, C.cast(out, C.c_void_p)),
                 "ndt3d_align_multi_start_dev")
         return [self._result(out[k]) for k in range(m)]
+
+    # ---- exhaustive pose search over an (x, y, yaw) window (ndt3d_search_*; gtsam_ndt_amd/search.py restates it)
+    @staticmethod
+    def _window(center, half_extent, step, min_sep=(0.0, 0.0)) -> L.SearchWindow3D:
+        if len(center) != 6:
+            raise ValueError("center is a pose (tx, ty, tz, roll, pitch, yaw); x, y and yaw are searched")
+        w = L.SearchWindow3D()
+        for a in range(6):
+            w.center[a] = float(center[a])
+        for a in range(3):
+            w.half_extent[a], w.step[a] = float(half_extent[a]), float(step[a])
+        w.min_sep_trans, w.min_sep_rot = float(min_sep[0]), float(min_sep[1])
+        return w
+
+    def _on_device(self, sx, sy, sz):
+        """(sx, sy, sz) as CUDA tensors (numpy arrays are uploaded), after the handle's stream waits for torch's."""
+        import torch
+        if not _is_dev(sx):
+            sx, sy, sz = (torch.from_numpy(_host_f32(a)).to(f"cuda:{self._device}") for a in (sx, sy, sz))
+        L.check(self._lib.ndt3d_wait_stream(self._h, C.c_void_p(torch.cuda.current_stream().cuda_stream)), "ndt3d_wait_stream")
+        return sx, sy, sz
+
+    def search(self, sx, sy, sz, center, half_extent, step, k: int = 8, min_sep=(0.5, 0.1)):
+        """The best k (1..64) well-separated peaks of the NDT score over the (x, y, yaw) lattice of the window, with
+        z, roll and pitch pinned to the centre's (ndt3d_search / ndt3d_search_dev): a list of SearchHit whose poses
+        are 6-vectors, best first."""
+        w = self._window(center, half_extent, step, min_sep)
+        hits = (L.SearchHit3D * max(int(k), 1))()
+        nh = C.c_int32(0)
+        if _is_dev(sx):
+            sx, sy, sz = self._on_device(sx, sy, sz)
+            n = sx.numel()
+            st = self._lib.ndt3d_search_dev(self._h, _dev_ptr(sx, n), _dev_ptr(sy, n), _dev_ptr(sz, n), n, C.byref(w), int(k),
+                                            C.cast(hits, C.c_void_p), C.byref(nh))
+        else:
+            sx, sy, sz = _host_f32(sx), _host_f32(sy), _host_f32(sz)
+            st = self._lib.ndt3d_search(self._h, sx.ctypes.data, sy.ctypes.data, sz.ctypes.data, sx.size, C.byref(w), int(k),
+                                        C.cast(hits, C.c_void_p), C.byref(nh))
+        L.check(st, "ndt3d_search")
+        return [SearchHit(tuple(h.pose), float(h.score), int(h.index)) for h in hits[:nh.value]]
+
+    def search_scores(self, sx, sy, sz, center, half_extent, step):
+        """The score volume of the window's lattice (ndt3d_search_scores_dev): a float32 CUDA tensor [n_yaw, n_y, n_x]."""
+        import torch
+        w = self._window(center, half_extent, step)
+        dims = (C.c_int32 * 3)()
+        L.check(self._lib.ndt3d_search_lattice_size(C.byref(w), C.cast(dims, C.c_void_p)), "ndt3d_search_lattice_size")
+        sx, sy, sz = self._on_device(sx, sy, sz)
+        out = torch.empty(tuple(dims), dtype=torch.float32, device=sx.device)
+        n = sx.numel()
+        L.check(self._lib.ndt3d_search_scores_dev(self._h, _dev_ptr(sx, n), _dev_ptr(sy, n), _dev_ptr(sz, n), n, C.byref(w),
+                                                  C.c_void_p(out.data_ptr())), "ndt3d_search_scores_dev")
+        return out
+
+    def search_align(self, sx, sy, sz, center, half_extent, step, k: int = 8, min_sep=(0.5, 0.1)):
+        """search(), then align_multi_start() from the hits' poses (ndt3d_search_align_dev): a list of
+        (SearchHit, AlignResult3D), best lattice score first."""
+        w = self._window(center, half_extent, step, min_sep)
+        hits = (L.SearchHit3D * max(int(k), 1))()
+        res = (L.Result3D * max(int(k), 1))()
+        nh = C.c_int32(0)
+        sx, sy, sz = self._on_device(sx, sy, sz)
+        n = sx.numel()
+        L.check(self._lib.ndt3d_search_align_dev(self._h, _dev_ptr(sx, n), _dev_ptr(sy, n), _dev_ptr(sz, n), n, C.byref(w),
+                                                 int(k), C.cast(hits, C.c_void_p), C.cast(res, C.c_void_p), C.byref(nh)),
+                "ndt3d_search_align_dev")
+        return [(SearchHit(tuple(h.pose), float(h.score), int(h.index)), self._result(r))
+                for h, r in zip(hits[:nh.value], res[:nh.value])]
 
     def align_trace(self, sx, sy, sz, init_pose=(0.0,) * 6, capacity: int = 256):
         """Per-iteration trace (ndt3d_align_trace; host arrays): a list of AlignResult3D, entry j = the state

@@ -1,8 +1,10 @@
-"""Host restatement of the exhaustive 2D pose search (docs/ALGORITHM.md "Exhaustive pose search"), in the spirit of
-synth.scan_points: the lattice of a window and the peak / separation rules, in numpy.  It is the specification the
-tests hold ndt2d_search_* to; nothing on the GPU path calls it.
+"""Host restatement of the exhaustive pose searches (docs/ALGORITHM.md "Exhaustive pose search" and "Exhaustive 3D pose
+search"), in the spirit of synth.scan_points: the lattice of a window and the peak / separation rules, in numpy.  It is
+the specification the tests hold ndt2d_search_* and ndt3d_search_* to; nothing on the GPU path calls it.
 
-A window is (center, half_extent, step), each an (x, y, theta) triple; ``Window`` names the three.
+A window is (center, half_extent, step); ``Window`` names the three.  2D: each an (x, y, theta) triple.  3D: the
+centre is a 6-vector (tx, ty, tz, roll, pitch, yaw) whose indices 0, 1, 5 are searched (half_extent and step stay
+(x, y, yaw) triples) and whose tz, roll, pitch are pinned; the hits then carry 6-vector poses.
 """
 from __future__ import annotations
 
@@ -25,7 +27,7 @@ class Window(NamedTuple):
 
 @dataclass(frozen=True)
 class SearchHit:
-    pose: tuple        # (x, y, theta), theta wrapped to (-pi, pi]
+    pose: tuple        # (x, y, theta), theta wrapped to (-pi, pi]; a 3D window: (x, y, tz, roll, pitch, yaw)
     score: float       # the lattice score (a float32 value)
     index: int         # flat lattice index ((j * n_y) + iy) * n_x + ix
 
@@ -47,11 +49,13 @@ def wrap(t):
 
 def _check(window):
     c, h, s = (tuple(float(v) for v in a) for a in window)
-    if len(c) != 3 or len(h) != 3 or len(s) != 3:
-        raise ValueError("center, half_extent and step are (x, y, theta) triples")
+    if len(c) not in (3, 6) or len(h) != 3 or len(s) != 3:
+        raise ValueError("center is an (x, y, theta) triple or a 6-vector pose; half_extent and step are triples")
     for v in c + h + s:
         if not math.isfinite(v):
             raise ValueError("non-finite window value")
+    if len(c) == 6:
+        c = (c[0], c[1], c[5])             # the searched axes of a 3D window
     if any(not v >= 0.0 for v in h) or any(not v > 0.0 for v in s):
         raise ValueError("half extents must be >= 0 and steps > 0")
     return c, h, s
@@ -131,6 +135,7 @@ def select_hits(volume, window, k: int = 8, min_sep=(0.5, 0.1)):
     (nt, ny, nx), cyclic = dims(window)
     v = np.asarray(volume, dtype=np.float32).reshape(nt, ny, nx)
     xs, ys, th = lattice(window)
+    pinned = tuple(float(c) for c in window[0][2:5]) if len(window[0]) == 6 else None
     cand = np.flatnonzero(peaks(v, cyclic))
     sc = v.reshape(-1)[cand]
     order = np.lexsort((cand, -sc))[:SHORTLIST]
@@ -146,10 +151,10 @@ def select_hits(volume, window, k: int = 8, min_sep=(0.5, 0.1)):
         keep = True
         for hh in hits:
             dx, dy = p[0] - hh.pose[0], p[1] - hh.pose[1]
-            dt = abs(float(wrap(p[2] - hh.pose[2])))
+            dt = abs(float(wrap(p[2] - hh.pose[-1])))
             if dx * dx + dy * dy < st2 and dt < sr:
                 keep = False
                 break
         if keep:
-            hits.append(SearchHit(p, float(v.reshape(-1)[q]), q))
+            hits.append(SearchHit(p if pinned is None else (p[0], p[1], *pinned, p[2]), float(v.reshape(-1)[q]), q))
     return hits

@@ -552,6 +552,48 @@ int32_t ndt3d_align_multi_scan_dev(ndt3d_handle* h, const float* const* d_sx, co
                                    const size_t* n, const double* init_poses, int32_t m, ndt3d_result* results);
 int32_t ndt3d_align_multi_start_dev(ndt3d_handle* h, const float* d_sx, const float* d_sy, const float* d_sz, size_t n,
                                     const double* init_poses, int32_t m, ndt3d_result* results);
+/* Exhaustive 3D pose search (docs/ALGORITHM.md "Exhaustive 3D pose search"), the twin of ndt2d_search*: the NDT score of
+ * the scan at every pose of an (x, y, yaw) lattice against the cached voxel grid, then the best well-separated peaks - a
+ * ground vehicle's relocalisation or loop closure whose guess is metres and tens of degrees off.  z, roll and pitch are
+ * pinned to center[2], center[3], center[4] at every lattice pose (the refinement that follows frees all six).
+ * The window's axes are (x, y, yaw): half_extent[a] and step[a] go with center[0], center[1], center[5].  Validation,
+ * axis lengths, the cyclic yaw axis for half_extent[2] >= pi, wrapping to (-pi, pi], the flat index
+ * ((j n_y) + iy) n_x + ix, the 2^25-pose cap, peaks, the 4096-peak shortlist, the separation walk (dx, dy and wrapped
+ * yaw), k in 1..64 and bitwise determinism are those of ndt2d_search_window above; non-finite center[2..4] is
+ * NDT_ERR_INVALID_ARG too.  The score at a lattice pose is the score ndt3d_evaluate_dev reports at
+ * (x, y, center[2], center[3], center[4], yaw): the same float32 terms per point, summed in another order.  A window
+ * that misses the map returns NDT_OK with *n_hits = 0.  Any alignment in flight on the handle is finished first. */
+typedef struct ndt3d_search_window {
+  double center[6];       /* tx ty tz roll pitch yaw of the lattice's middle pose; tz, roll and pitch are pinned */
+  double half_extent[3];  /* x, y (metres), yaw (radians); >= 0, 0 pins the axis; yaw >= pi: a full turn */
+  double step[3];         /* lattice step per axis (x, y, yaw), > 0 */
+  double min_sep_trans;   /* hits closer than this in (x, y) ... */
+  double min_sep_rot;     /* ... AND in wrapped yaw than an accepted hit are dropped (both >= 0) */
+} ndt3d_search_window;
+
+typedef struct ndt3d_search_hit {
+  double pose[6];         /* lattice pose: x, y, center[2..4], yaw wrapped to (-pi, pi] */
+  float score;            /* the lattice score (float32, as in the volume) */
+  int32_t index;          /* flat lattice index */
+} ndt3d_search_hit;
+
+/* dims = n_yaw, n_y, n_x of the window's lattice (CPU only; the same validation as the searches) */
+int32_t ndt3d_search_lattice_size(const ndt3d_search_window* w, int32_t dims[3]);
+/* hits[0 .. *n_hits) (hits has room for k), best first.  Synchronous in the hits (host memory). */
+int32_t ndt3d_search_dev(ndt3d_handle* h, const float* d_sx, const float* d_sy, const float* d_sz, size_t n,
+                         const ndt3d_search_window* w, int32_t k, ndt3d_search_hit* hits, int32_t* n_hits);
+/* the same with a host scan */
+int32_t ndt3d_search(ndt3d_handle* h, const float* sx, const float* sy, const float* sz, size_t n,
+                     const ndt3d_search_window* w, int32_t k, ndt3d_search_hit* hits, int32_t* n_hits);
+/* the score volume itself into d_scores (device memory, n_yaw x n_y x n_x floats, flat index order); returns once it
+ * is written */
+int32_t ndt3d_search_scores_dev(ndt3d_handle* h, const float* d_sx, const float* d_sy, const float* d_sz, size_t n,
+                                const ndt3d_search_window* w, float* d_scores);
+/* ndt3d_search_dev, then ndt3d_align_multi_start_dev from the hits' poses: results[i] is bit for bit what
+ * ndt3d_align_multi_start_dev returns for those poses (results has room for k) */
+int32_t ndt3d_search_align_dev(ndt3d_handle* h, const float* d_sx, const float* d_sy, const float* d_sz, size_t n,
+                               const ndt3d_search_window* w, int32_t k, ndt3d_search_hit* hits,
+                               ndt3d_result* results, int32_t* n_hits);
 /* Per-iteration trace, as ndt2d_align_trace (debugging and stage-by-stage parity checks; never on a timed path):
  * rows[j], j < *n_rows <= capacity, is the state after j + 1 updates - the pose after them, H / g / score / n_hit
  * of the evaluation that produced the (j+1)-th update.  out (may be NULL): the final result.  Host arrays. */

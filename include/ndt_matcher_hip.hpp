@@ -596,6 +596,52 @@ class NdtMatcherHip3 {
     std::vector<DeviceScan3> scans(guesses.size(), DeviceScan3{d_sx, d_sy, d_sz, n});
     return alignMultiScanDev(scans, guesses);
   }
+  // Exhaustive pose search over an (x, y, yaw) window against the cached voxel grid (ndt3d_search_dev; lattice, peaks
+  // and separation: ndt_hip.h), as NdtMatcherHip::searchDev: the best k (1..64) well-separated lattice poses, best
+  // first; z, roll and pitch are the window centre's.  producer_stream: the stream that wrote the device arrays
+  // (complete = true: they are known to be complete, no ordering needed).
+  struct SearchHit {
+    Pose3 pose;            // the lattice pose, yaw wrapped to (-pi, pi]
+    float score = 0.f;     // the lattice score
+    int32_t index = 0;     // flat lattice index
+  };
+  struct SearchMatch {
+    SearchHit hit;
+    MatchResult3 result;   // alignMultiStartDev's result from hit.pose
+  };
+  std::vector<SearchHit> searchDev(const float* d_sx, const float* d_sy, const float* d_sz, size_t n,
+                                   const ndt3d_search_window& window, int k, void* producer_stream, bool complete = false) {
+    if (!complete) check(ndt3d_wait_stream(h_, producer_stream), "ndt3d_wait_stream");
+    std::vector<ndt3d_search_hit> hits(k > 0 ? (size_t)k : 1);
+    int32_t n_hits = 0;
+    check(ndt3d_search_dev(h_, d_sx, d_sy, d_sz, n, &window, (int32_t)k, hits.data(), &n_hits), "ndt3d_search_dev");
+    std::vector<SearchHit> out;
+    for (int32_t i = 0; i < n_hits; ++i) out.push_back(toSearchHit(hits[i]));
+    return out;
+  }
+  // searchDev, then one alignment from every hit in one launch chain (ndt3d_search_align_dev): result i is bit for bit
+  // what alignMultiStartDev returns from the hits' poses.  Search with a subsampled scan and refine with the full one
+  // when the lattice is large.
+  std::vector<SearchMatch> searchAlignDev(const float* d_sx, const float* d_sy, const float* d_sz, size_t n,
+                                          const ndt3d_search_window& window, int k, void* producer_stream,
+                                          bool complete = false) {
+    if (!complete) check(ndt3d_wait_stream(h_, producer_stream), "ndt3d_wait_stream");
+    std::vector<ndt3d_search_hit> hits(k > 0 ? (size_t)k : 1);
+    std::vector<ndt3d_result> r(hits.size());
+    int32_t n_hits = 0;
+    check(ndt3d_search_align_dev(h_, d_sx, d_sy, d_sz, n, &window, (int32_t)k, hits.data(), r.data(), &n_hits),
+          "ndt3d_search_align_dev");
+    std::vector<SearchMatch> out;
+    for (int32_t i = 0; i < n_hits; ++i) out.push_back(SearchMatch{toSearchHit(hits[i]), toMatchResult(r[i])});
+    return out;
+  }
+  static SearchHit toSearchHit(const ndt3d_search_hit& h) {
+    SearchHit s;
+    s.pose = {h.pose[0], h.pose[1], h.pose[2], h.pose[3], h.pose[4], h.pose[5]};
+    s.score = h.score;
+    s.index = h.index;
+    return s;
+  }
   ndt3d_grid_info gridInfo() const { ndt3d_grid_info g; check(ndt3d_get_grid_info(h_, &g), "ndt3d_get_grid_info"); return g; }
 
   MatchResult3 align(const float* sx, const float* sy, const float* sz, size_t n, const Pose3& guess = Pose3()) {
