@@ -175,6 +175,9 @@ SIGNATURES = {
     "ndt2d_search_scores_dev": (C.c_int32, [_vp, _vp, _vp, C.c_size_t, C.POINTER(SearchWindow2D), _vp]),
     "ndt2d_search_align_dev": (C.c_int32, [_vp, _vp, _vp, C.c_size_t, C.POINTER(SearchWindow2D), C.c_int32, _vp, _vp,
                                            C.POINTER(C.c_int32)]),
+    "ndt2d_evaluate_map": (C.c_int32, [_vp, _vp, _dp, C.POINTER(Eval2D)]),
+    "ndt2d_align_map": (C.c_int32, [_vp, _vp, _dp, C.POINTER(Result2D)]),
+    "ndt2d_get_components": (C.c_int32, [_vp, _vp, _vp, _vp, C.c_int32, C.POINTER(C.c_int32)]),
     "ndt2d_stream": (_vp, [_vp]),
     "ndt2d_set_tuning": (C.c_int32, [_vp, C.c_int32, C.c_int64]),
     "ndt2d_batch_set_tuning": (C.c_int32, [_vp, C.c_int32, C.c_int64]),

@@ -16,6 +16,7 @@
 #include "ndt2d_build.hpp"
 #include "ndt2d_build_sorted.hpp"
 #include "ndt2d_multi_start.hpp"
+#include "ndt2d_d2d.hpp"
 #include "ndt_host.hpp"
 #include "ndt_search.hpp"
 
@@ -89,6 +90,14 @@ struct ndt2d_handle {
   bool use_graph = true;
   int check_every = 8;                     // converged mode: launches per chunk
   SearchScratch srch;                      // exhaustive pose search scratch (ndt_search.hpp), allocated on first use
+  // map-to-map alignment (ndt2d_d2d_api.hpp), allocated on first use; both caches follow the grid (grid_changed)
+  float4* d_cov = nullptr; size_t cov_cap = 0;            // covariance records of the cached grid ([2 x cells], the layout of grid.rec)
+  unsigned int* d_blk = nullptr; size_t blk_cap = 0;      // valid cells per workgroup of k_cov_records | their exclusive scan | the total
+  float4* d_comp = nullptr; size_t comp_cap = 0;          // component list: this handle as the source of a map-to-map call
+  int n_comp = 0;
+  bool cov_valid = false, comp_valid = false;
+  MapCall* d_map_call = nullptr;                          // per-call context of k_iterate_d2d (this handle as the target)
+  hipEvent_t map_ev = nullptr;                            // orders a target handle's stream behind this handle's (order_after)
 };
 
 namespace {
@@ -135,6 +144,10 @@ int stream_blocks(size_t n) {   // streaming kernels: up to 8 blocks per CU
 }
 
 int32_t upload_static(ndt2d_handle* h);
+
+// The cached grid is about to change (a new target, merged points, a reserved extent, a loaded map): what map-to-map
+// alignment derived from it (ndt2d_d2d_api.hpp) is stale.
+void grid_changed(ndt2d_handle* h) { h->cov_valid = false; h->comp_valid = false; }
 
 int32_t finalise_grid(ndt2d_handle* h) {
   const size_t ncell = (size_t)h->grid.W * h->grid.H * h->grid.ngrid;
@@ -492,6 +505,7 @@ int32_t set_target_single_sync(ndt2d_handle* h, const float* d_x, const float* d
 int32_t set_target_impl(ndt2d_handle* h, const float* d_x, const float* d_y, size_t n) {
   TraceRange range("ndt2d_set_target: grid build");
   h->has_target = false;
+  grid_changed(h);
   if (n == 0) return NDT_ERR_INVALID_ARG;
   unsigned int fast_bounds[4];
   bool done = false, have_bounds = false;
@@ -908,13 +922,14 @@ int32_t ndt2d_destroy(ndt2d_handle* h) {
   drop_graph(h);
   if (h->h_state_multi) (void)hipHostFree(h->h_state_multi);
   void* dev[] = {h->d_acc2, h->d_split, h->d_bxy, h->d_table, h->d_parts, h->d_geom, h->d_dyn_multi, h->d_bounds, h->d_counters, h->d_outside, h->d_static, h->d_call, h->d_dyn, h->d_bx, h->d_by, h->d_tiles, h->d_tx, h->d_ty, h->d_sx, h->d_sy,
-                 h->grid.rec, h->grid.acc};
+                 h->grid.rec, h->grid.acc, h->d_cov, h->d_blk, h->d_comp, h->d_map_call};
   for (void* p : dev) if (p) (void)hipFree(p);
   void* host[] = {h->h_geom, h->h_static, h->h_state, h->h_small, h->h_flag};
   for (void* p : host) if (p) (void)hipHostFree(p);
   h->srch.release();
   if (h->upload_ev) (void)hipEventDestroy(h->upload_ev);
   if (h->wait_ev) (void)hipEventDestroy(h->wait_ev);
+  if (h->map_ev) (void)hipEventDestroy(h->map_ev);
   if (h->stream) (void)hipStreamDestroy(h->stream);
   delete h;
   return NDT_OK;
@@ -969,6 +984,7 @@ int32_t ndt2d_reserve_target(ndt2d_handle* h, double xmin, double ymin, double x
   HIP_TRY(hipSetDevice(h->device));
   { const int32_t fs = finish_chunk_run(h); if (fs != NDT_OK) return fs; }
   h->has_target = false;
+  grid_changed(h);
   const int32_t gs = setup_geometry(h, (float)xmin, (float)xmax, (float)ymin, (float)ymax);
   if (gs != NDT_OK) return gs;
   const size_t ncell = (size_t)h->grid.W * h->grid.H * h->grid.ngrid;
@@ -986,6 +1002,7 @@ int32_t ndt2d_add_target_points_dev(ndt2d_handle* h, const float* d_x, const flo
   if (!h->has_target) return NDT_ERR_NO_TARGET;
   HIP_TRY(hipSetDevice(h->device));
   { const int32_t fs = finish_chunk_run(h); if (fs != NDT_OK) return fs; }
+  grid_changed(h);
   // order after the caller's producer stream, as ndt2d_set_target_dev does
   if (stream) HIP_TRY(order_after(h->stream, (hipStream_t)stream));
   // the scan is moved into the map frame inside the build's first kernel (k_chunk_sort; k_transform_points on the other paths)
@@ -1263,3 +1280,4 @@ extern "C" int32_t ndt2d_align_multi_scan_dev(ndt2d_handle* h, const float* cons
 #include "ndt_map_io.hpp"
 #include "ndt2d_search.hpp"
 #include "ndt3d_search.hpp"
+#include "ndt2d_d2d_api.hpp"

@@ -190,22 +190,26 @@ __device__ __forceinline__ unsigned long long prod64(int a, int b) {
   return (unsigned long long)((long long)a * (long long)b);
 }
 
-// a3: exact sums -> Welford form (n, mean, M2) -> Sigma = M2/(n-1) -> eigenvalue clamp ->
-// Sigma^-1 record.  float64 scalar code in the order of oracle/ndt2d.py finalise_cell().
-// Returns false (record zeroed) when the cell is not usable.
-__device__ __forceinline__ bool finalise_sums(int n, long long sx, long long sy, long long sxx, long long sxy,
-                                              long long syy, double cx, double cy, double fix_scale,
-                                              int min_points, double eig_ratio, float4& ra, float4& rb) {
-  ra = make_float4(0.f, 0.f, 0.f, 0.f);
-  rb = make_float4(0.f, 0.f, 0.f, 0.f);
+// a3 (1/2): exact sums -> Welford form (n, mean, M2) -> Sigma = M2/(n-1) -> eigenvalues, clamp, unit eigenvector of
+// the large one.  float64 scalar code in the order of oracle/ndt2d.py finalise_cell().  Shared by the Sigma^-1
+// records (finalise_sums) and the covariance records of map-to-map alignment (ndt2d_d2d.hpp: cov_record).
+// Returns false when the cell is not usable.
+struct CellEig {
+  double mx, my;     // mean
+  double l1, l2c;    // large eigenvalue, clamped small one
+  double ex, ey;     // unit eigenvector of l1
+};
+__device__ __forceinline__ bool cell_eigen(int n, long long sx, long long sy, long long sxx, long long sxy, long long syy,
+                                           double cx, double cy, double fix_scale, int min_points, double eig_ratio,
+                                           CellEig& e) {
   if (n < min_points || n < 2) return false;
   // one reciprocal per cell: r = 1 / (n S); mean = centre + Su r; 1 / (n S^2) = r^2 n.  (A reciprocal of
   // fix_scale alone would be loop-invariant in every caller and cost a register pair held across the
   // whole build: the 1024-thread batch kernel spilled it.)
   const double dn = (double)n;
   const double r = 1.0 / (dn * fix_scale);
-  const double mx = fma((double)sx, r, cx);
-  const double my = fma((double)sy, r, cy);
+  e.mx = fma((double)sx, r, cx);
+  e.my = fma((double)sy, r, cy);
   // M2 = (n*Suu - Su*Su) / (n * S^2), numerator exact in 128-bit
   const double den = r * r * dn;
   const double m2xx = to_double(sub128(mul_s64(n, sxx), mul_s64(sx, sx))) * den;
@@ -215,18 +219,31 @@ __device__ __forceinline__ bool finalise_sums(int n, long long sx, long long sy,
   const double half_tr = 0.5 * (vxx + vyy);
   const double half_df = 0.5 * (vxx - vyy);
   const double disc = sqrt(fma(half_df, half_df, vxy * vxy));
-  const double l1 = half_tr + disc;
+  e.l1 = half_tr + disc;
   const double l2 = half_tr - disc;
-  if (!(l1 > 0.0)) return false;
-  const double l2c = fmax(l2, eig_ratio * l1);
+  if (!(e.l1 > 0.0)) return false;
+  e.l2c = fmax(l2, eig_ratio * e.l1);
   double ex, ey;
   if (half_df >= 0.0) { ex = half_df + disc; ey = vxy; }
   else                { ex = vxy; ey = disc - half_df; }
   const double nrm = sqrt(fma(ex, ex, ey * ey));
   if (nrm > 0.0) { ex /= nrm; ey /= nrm; } else { ex = 1.0; ey = 0.0; }
-  const double i1 = 1.0 / l1, i2 = 1.0 / l2c, d = i1 - i2;
+  e.ex = ex; e.ey = ey;
+  return true;
+}
+
+// a3 (2/2): -> Sigma^-1 record.  Returns false (record zeroed) when the cell is not usable.
+__device__ __forceinline__ bool finalise_sums(int n, long long sx, long long sy, long long sxx, long long sxy,
+                                              long long syy, double cx, double cy, double fix_scale,
+                                              int min_points, double eig_ratio, float4& ra, float4& rb) {
+  ra = make_float4(0.f, 0.f, 0.f, 0.f);
+  rb = make_float4(0.f, 0.f, 0.f, 0.f);
+  CellEig e;
+  if (!cell_eigen(n, sx, sy, sxx, sxy, syy, cx, cy, fix_scale, min_points, eig_ratio, e)) return false;
+  const double ex = e.ex, ey = e.ey;
+  const double i1 = 1.0 / e.l1, i2 = 1.0 / e.l2c, d = i1 - i2;
   const float b32 = (float)(d * ex * ey);
-  ra = make_float4((float)mx, (float)my, (float)fma(d * ex, ex, i2), b32);
+  ra = make_float4((float)e.mx, (float)e.my, (float)fma(d * ex, ex, i2), b32);
   rb = make_float4(b32, (float)fma(d * ey, ey, i2), (float)n, 0.f);
   return true;
 }

@@ -130,6 +130,7 @@ int32_t ndt2d_load_map(ndt2d_handle* h, const void* buf, size_t bytes) {
   HIP_TRY(hipSetDevice(h->device));
   { const int32_t fs = finish_chunk_run(h); if (fs != NDT_OK) return fs; }
   h->has_target = false;
+  grid_changed(h);
   GridDev& g = h->grid;
   const double c = h->prm.cell_size;
   g.cell = c; g.cell32 = (float)c; g.inv_c = (float)(1.0 / c);

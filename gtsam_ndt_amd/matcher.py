@@ -224,6 +224,36 @@ class NdtMatcher2D:
         L.check(st, "ndt2d_align")
         return _to_result(r)
 
+    # ---- map-to-map alignment (distribution-to-distribution NDT): no points, two cached grids
+    def align_map(self, source: "NdtMatcher2D", init_pose=(0.0, 0.0, 0.0)) -> AlignResult:
+        """Align `source`'s cached grid to this handle's (ndt2d_align_map): pose maps the source map's frame into
+        this map's frame.  This handle's parameters drive the solve; `source` may be this handle."""
+        p = (C.c_double * 3)(*[float(v) for v in init_pose])
+        r = L.Result2D()
+        L.check(self._lib.ndt2d_align_map(self._h, source._h, p, C.byref(r)), "ndt2d_align_map")
+        return _to_result(r)
+
+    def evaluate_map(self, source: "NdtMatcher2D", pose):
+        """(H, g, score, n_hit) of the map-to-map objective at `pose` (ndt2d_evaluate_map)."""
+        p = (C.c_double * 3)(*[float(v) for v in pose])
+        out = L.Eval2D()
+        L.check(self._lib.ndt2d_evaluate_map(self._h, source._h, p, C.byref(out)), "ndt2d_evaluate_map")
+        return (np.array(out.H, dtype=np.float64).reshape(3, 3), np.array(out.g, dtype=np.float64),
+                float(out.score), int(out.n_hit))
+
+    def components(self):
+        """(key int32 [n], mean float32 [n,2], cov float32 [n,3] = (Sxx, Sxy, Syy)) of the cached grid's valid cells,
+        in cell-key order: what this handle contributes as the source of align_map (ndt2d_get_components)."""
+        n = C.c_int32(0)
+        L.check(self._lib.ndt2d_get_components(self._h, None, None, None, 0, C.byref(n)), "ndt2d_get_components")
+        key = np.zeros(n.value, dtype=np.int32)
+        mean = np.zeros((n.value, 2), dtype=np.float32)
+        cov = np.zeros((n.value, 3), dtype=np.float32)
+        if n.value:
+            L.check(self._lib.ndt2d_get_components(self._h, mean.ctypes.data, cov.ctypes.data, key.ctypes.data, n.value,
+                                                   C.byref(n)), "ndt2d_get_components")
+        return key, mean, cov
+
     def align_trace(self, sx, sy, init_pose=(0.0, 0.0, 0.0), capacity: int = 256):
         """Per-iteration trace (ndt2d_align_trace; host arrays): a list of AlignResult, entry j = the state
         after j + 1 updates (H, g, score, n_hit of the evaluation behind that update)."""

@@ -19,7 +19,8 @@
  *     and are synchronous.  "_dev" entry points take device pointers (any allocator:
  *     hipMalloc, torch) and enqueue on the given hipStream_t (passed as void*); results
  *     written to device memory are valid after that stream is synchronised.
- *   - A handle is single-threaded; distinct handles may be used from distinct threads.
+ *   - A handle is single-threaded; distinct handles may be used from distinct threads.  A map-to-map call
+ *     (ndt2d_align_map / ndt2d_evaluate_map) uses BOTH its handles for its duration: no other thread may touch either.
  *   - Points are SoA float32 arrays (x[], y[]); poses are double (tx, ty, theta).
  *   - There is NO CPU fallback: every entry point that computes needs a gfx950 device.
  */
@@ -287,6 +288,35 @@ int32_t ndt2d_search_scores_dev(ndt2d_handle* h, const float* d_sx, const float*
 int32_t ndt2d_search_align_dev(ndt2d_handle* h, const float* d_sx, const float* d_sy, size_t n,
                                const ndt2d_search_window* w, int32_t k, ndt2d_search_hit* hits,
                                ndt2d_result* results, int32_t* n_hits);
+/* ---- map-to-map alignment (distribution-to-distribution NDT; docs/ALGORITHM.md section 2.13) ----------------
+ * Aligns the cached grid of `source` to the cached grid of `target` without any of the points either was built from:
+ * what a handle keeps after ndt2d_add_target_points_dev, and all that ndt2d_save_map / ndt2d_load_map persist, is
+ * enough.  The source is the list of its valid cells' Gaussians (mean, regularised covariance: its *components*, in
+ * cell-key order), each scored against the target Gaussian of the cell its transformed mean falls in, with the combined
+ * covariance R S_i R^T + S_j; every hit weighs the same.  pose = (tx, ty, theta) maps the source map's frame into the
+ * target map's frame.
+ *   - The TARGET handle's parameters drive the solve (d1, d2, hessian_mode, the limits and stops, step_scale,
+ *     line_search, its tuning knobs, its stream); the source handle's min_points / eig_ratio decide only its
+ *     components.  The cell sizes may differ.  step_scale: the Gauss-Newton Hessian of this objective is close to
+ *     the true one, so factors much above 1.5 over-relax and do not converge.
+ *   - target == source is legal (a map against itself: the identity is a fixed point).
+ *   - Both handles must live on the same device and neither may have overlap_grids = 4: NDT_ERR_INVALID_ARG.
+ *     No grid on either handle: NDT_ERR_NO_TARGET.  A non-finite pose: NDT_ERR_INVALID_ARG.  A source without a
+ *     component or a target without a valid cell: NDT_OK with status NDT_TOO_FEW_CELLS and the initial pose
+ *     (ndt2d_evaluate_map: all zeros).
+ *   - Both calls are synchronous; the target's stream is ordered behind the source's by the library.  The derived
+ *     per-handle data (covariance records, component list) is built on a handle's first such call and again after
+ *     anything that changes its grid.  Results are bit for bit reproducible from call to call.
+ *   - ndt2d_result / ndt2d_eval are those of ndt2d_align / ndt2d_evaluate (n_hit counts components that hit a valid
+ *     target cell).  ndt2d_calibrated_covariance accepts the H returned here, but its factors were calibrated for
+ *     the point-to-distribution objective: they are NOT calibrated for this one. */
+int32_t ndt2d_evaluate_map(ndt2d_handle* target, ndt2d_handle* source, const double pose[3], ndt2d_eval* out);
+int32_t ndt2d_align_map(ndt2d_handle* target, ndt2d_handle* source, const double init_pose[3], ndt2d_result* out);
+/* The components of a handle's cached grid, as host copies: mean_xy [2n], cov_abc [3n] = (Sxx, Sxy, Syy), key [n] =
+ * iy * width + ix, ascending.  Any pointer may be NULL; *n (if given) is the count, also when capacity is too small
+ * for the arrays asked for (NDT_ERR_CAPACITY). */
+int32_t ndt2d_get_components(ndt2d_handle* h, float* mean_xy, float* cov_abc, int32_t* key, int32_t capacity, int32_t* n);
+
 /* Execution-strategy knobs of a handle.  They choose between kernels that compute the same alignment
  * (results agree up to float32 summation order; the tests pin each pair of choices against each other
  * and against the oracle); the defaults are the measured best, nothing reads the environment.
@@ -355,6 +385,7 @@ int32_t ndt_magnusson_constants(double outlier_ratio, double cell_size, int32_t 
  * C_empirical C_calibrated^-1 in [0.4, 2.5]; the test asserts a factor 3) on scans with some 20 or more
  * points per occupied cell; the excess over H^-1 is discretisation noise and grows as the scans get
  * sparser (up to 5.5x off at 7 points per cell: inflate further there).  Needs no device.
+ * The factors are those of point-to-map alignment; for the H of ndt2d_align_map they are not calibrated.
  * Returns NDT_DEGENERATE_HESSIAN (cov zeroed) when H is not positive definite. */
 #define NDT_COV_SCALE_GN_TRANS 10.0
 #define NDT_COV_SCALE_GN_ROT 18.0

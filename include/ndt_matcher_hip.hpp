@@ -248,6 +248,23 @@ class NdtMatcherHip {
     check(ndt2d_evaluate(h_, sx, sy, n, p, &e), "ndt2d_evaluate");
     return e;
   }
+  // Map-to-map alignment (ndt2d_align_map): `source`'s cached grid against this matcher's, no points involved - the
+  // loop closure between two submaps, or between a reloaded map and the current one.  guess and the result map the
+  // source map's frame into this map's frame; this matcher's parameters drive the solve; source may be *this.
+  // The result's covariance carries the point-to-map calibration factors, which are NOT calibrated for this
+  // objective: build a noise model from result.information with factors of your own.
+  MatchResult alignMap(NdtMatcherHip& source, const Pose2& guess = Pose2()) {
+    const double init[3] = {guess.x, guess.y, guess.theta};
+    ndt2d_result r;
+    check(ndt2d_align_map(h_, source.h_, init, &r), "ndt2d_align_map");
+    return to_match_result(r, mode_);
+  }
+  ndt2d_eval evaluateMap(NdtMatcherHip& source, const Pose2& at) {
+    const double p[3] = {at.x, at.y, at.theta};
+    ndt2d_eval e;
+    check(ndt2d_evaluate_map(h_, source.h_, p, &e), "ndt2d_evaluate_map");
+    return e;
+  }
   ndt2d_handle* raw() { return h_; }
 
  private:

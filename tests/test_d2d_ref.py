@@ -1,0 +1,134 @@
+"""The float64 restatement of map-to-map alignment (tests/d2d_ref.py; docs/ALGORITHM.md section 2.13) is right by
+its own finite differences, a map against itself stays where it is, two scans of one scene a known transform apart
+are brought together, and the three entry points exist in the header, the library and the bindings."""
+import os
+import re
+
+import numpy as np
+import pytest
+
+import d2d_ref as R
+from gtsam_ndt_amd import synth
+from oracle import ndt2d as O
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+SCENES = {"room8": (1, {}), "room50": (2, dict(n_tgt=20_000, n_src=20_000))}
+NAMES = ("ndt2d_evaluate_map", "ndt2d_align_map", "ndt2d_get_components")
+
+
+def _maps(scene, prm):
+    cfg, kw = SCENES[scene]
+    d = synth.make_pair(cfg, **kw)
+    tgt, _ = R.build_map(d["tx"], d["ty"], prm)
+    _, comps = R.build_map(d["sx"], d["sy"], prm)
+    return d, tgt, comps
+
+
+def _poses(d, tgt, comps):
+    """Five poses: the start, the generating pose, the converged pose and two more off it."""
+    conv = R.align(tgt, comps, d["init"], O.NdtParams())["pose"]
+    i = d["init"]
+    return [i, d["pose"], conv, (i[0] + 0.2, i[1] - 0.15, i[2] + 0.02), (i[0] - 0.1, i[1] + 0.25, i[2] - 0.03)]
+
+
+@pytest.mark.parametrize("scene", sorted(SCENES))
+def test_gradient_and_newton_hessian_match_central_differences(scene):
+    """Steps: 1e-6 m in x and y, 1e-6 m of arc at the farthest component in theta, so every image moves at most
+    1e-6 m, 2e-4 of the narrowest Gaussian a default cell can hold (sqrt(eig_ratio) x a cell's 0.15 m spread):
+    the truncation term of a central difference is (2e-4)^2 / 6 < 1e-8 of the differentiated quantity's scale and
+    the float64 rounding term eps x (sum of magnitudes) / step is smaller still.  Asserted at 1e-6 of the scales
+    sqrt(H_aa score) for g and sqrt(H_aa H_bb) for H (H_aa of the Gauss-Newton form)."""
+    prm = O.NdtParams(hessian_mode=O.HESSIAN_NEWTON)
+    d, tgt, comps = _maps(scene, prm)
+    arm = float(np.hypot(comps.mean[:, 0], comps.mean[:, 1]).max())
+    step = (1e-6, 1e-6, 1e-6 / arm)
+    for pose in _poses(d, tgt, comps):
+        pairs = []
+        H, g, sc, n_hit = R.evaluate(tgt, comps, pose, prm, pairs=pairs)
+        Hgn = R.evaluate(tgt, comps, pose, O.NdtParams())[0]
+        assert n_hit >= 0.5 * comps.n
+        gf, Hf = np.zeros(3), np.zeros((3, 3))
+        for a in range(3):
+            pp, pm = list(pose), list(pose)
+            pp[a] += step[a]
+            pm[a] -= step[a]
+            ep, em = R.evaluate(tgt, comps, pp, prm, pairs=pairs), R.evaluate(tgt, comps, pm, prm, pairs=pairs)
+            gf[a] = -(ep[2] - em[2]) / (2 * step[a])            # f = -score
+            Hf[:, a] = (ep[1] - em[1]) / (2 * step[a])
+        for other in pairs[1:]:
+            assert np.array_equal(pairs[0], other), "a component changed its target cell inside the difference stencil"
+        dg = np.sqrt(np.diag(Hgn))
+        eg = np.abs(gf - g) / (dg * np.sqrt(sc))
+        eh = np.abs(Hf - H) / np.outer(dg, dg)
+        print(f"{scene} pose {np.round(pose, 4)}: n_hit {n_hit}, |g_fd - g| {eg.max():.2e}, |H_fd - H| {eh.max():.2e} (scaled)")
+        assert eg.max() < 1e-6 and eh.max() < 1e-6
+        assert np.abs(H - H.T).max() == 0.0
+
+
+@pytest.mark.parametrize("scene", sorted(SCENES))
+def test_gauss_newton_hessian_is_symmetric_positive_semidefinite(scene):
+    prm = O.NdtParams()
+    d, tgt, comps = _maps(scene, prm)
+    for pose in _poses(d, tgt, comps):
+        H = R.evaluate(tgt, comps, pose, prm)[0]
+        assert np.array_equal(H, H.T)
+        ev = np.linalg.eigvalsh(H)
+        assert ev.min() >= -1e-12 * ev.max(), ev
+
+
+@pytest.mark.parametrize("mode", [O.HESSIAN_GN, O.HESSIAN_NEWTON])
+@pytest.mark.parametrize("scene", sorted(SCENES))
+def test_a_map_against_itself_stays_at_the_identity(scene, mode):
+    prm = O.NdtParams(hessian_mode=mode)
+    cfg, kw = SCENES[scene]
+    d = synth.make_pair(cfg, **kw)
+    tgt, comps = R.build_map(d["tx"], d["ty"], prm)
+    H, g, sc, n_hit = R.evaluate(tgt, comps, (0.0, 0.0, 0.0), prm)
+    assert n_hit == comps.n and sc == pytest.approx(prm.d1 * comps.n, rel=1e-12)      # every mean sits on its own cell's mean
+    assert np.abs(g).max() <= 1e-12 * np.sqrt(np.abs(np.diag(H)).max() * sc)
+    r = R.align(tgt, comps, (0.0, 0.0, 0.0), prm)
+    assert r["status"] == O.NDT_OK and r["iterations"] == 1
+    assert np.abs(np.array(r["pose"])).max() < 1e-12
+
+
+@pytest.mark.parametrize("opts", [dict(), dict(step_scale=1.5), dict(line_search=4)], ids=["plain", "relaxed1.5", "linesearch4"])
+@pytest.mark.parametrize("mode", [O.HESSIAN_GN, O.HESSIAN_NEWTON])
+@pytest.mark.parametrize("scene", sorted(SCENES))
+def test_two_scans_a_known_transform_apart_converge(scene, mode, opts):
+    """From the generator's initial guess (0.13 m, 0.01 rad off).  The maps are two independent samplings with 3 cm of
+    noise, summarised per 0.5 m cell: the optimum is asked to lie within a tenth of a cell and 0.01 rad of the
+    generating pose, not closer."""
+    prm = O.NdtParams(hessian_mode=mode, **opts)
+    d, tgt, comps = _maps(scene, prm)
+    r = R.align(tgt, comps, d["init"], prm)
+    err = np.abs(np.array(r["pose"]) - np.array(d["pose"]))
+    print(f"{scene} mode {mode} {opts}: {r['iterations']} iterations, status {r['status']}, |pose - truth| {err}")
+    assert r["status"] == O.NDT_OK
+    assert err[0] < 0.05 and err[1] < 0.05 and err[2] < 0.01
+    assert r["n_hit"] >= 0.5 * comps.n
+
+
+def test_float32_restatement_tracks_the_float64_one():
+    """What the GPU tests take their bound from: the per-component arithmetic in float32 against float64."""
+    prm = O.NdtParams(hessian_mode=O.HESSIAN_NEWTON)
+    for scene in sorted(SCENES):
+        d, tgt, comps = _maps(scene, prm)
+        for pose in _poses(d, tgt, comps)[:3]:
+            a, b = R.evaluate(tgt, comps, pose, prm, mirror32=True), R.evaluate(tgt, comps, pose, prm)
+            diffs = R.eval_diffs(a, b)
+            print(f"{scene} pose {np.round(pose, 4)}: float32 vs float64 (H, g, score) {diffs}")
+            assert a[3] == b[3] and max(diffs) < 1e-4
+
+
+def test_the_three_entry_points_are_declared_exported_and_bound(ndt_lib):
+    from gtsam_ndt_amd import _lib
+    src = re.sub(r"/\*.*?\*/", "", open(os.path.join(ROOT, "include", "ndt_hip.h")).read(), flags=re.S)
+    for n in NAMES:
+        assert re.search(r"\bint32_t\s+%s\s*\(" % n, src), f"{n} is not declared in ndt_hip.h"
+        assert hasattr(ndt_lib, n), f"{n} is not exported"
+        assert n in _lib.SIGNATURES, f"{n} is not bound"
+    from gtsam_ndt_amd.matcher import NdtMatcher2D
+    for m in ("align_map", "evaluate_map", "components"):
+        assert callable(getattr(NdtMatcher2D, m))
+    wrapper = open(os.path.join(ROOT, "include", "ndt_matcher_hip.hpp")).read()
+    assert "alignMap(NdtMatcherHip& source" in wrapper
