@@ -5,6 +5,7 @@
 #include "ndt3d_kernels.hpp"
 #include "ndt3d_build.hpp"
 #include "ndt3d_multi.hpp"
+#include "ndt3d_d2d.hpp"
 
 // h_pub3, the pinned read-back of a single-sync build: the accumulator block's first 64 words, then the flag
 constexpr int kPub3FlagWord = 64, kPub3Words = kPub3FlagWord + 16;
@@ -49,9 +50,20 @@ struct ndt3d_handle {
   ndt::AlignDynMulti3* d_dyn_multi = nullptr;   // multi-scan / multi-start chains (ndt3d_multi.hpp), on first use
   ndt::IterState3* h_state_multi = nullptr;     // pinned [kMaxStarts3]
   ndt::SearchScratch srch;                      // exhaustive pose search scratch (ndt_search.hpp), allocated on first use
+  // map-to-map alignment (ndt3d_d2d_api.hpp), allocated on first use; both caches follow the grid (grid_changed3)
+  float4* d_cov = nullptr; size_t cov_cap = 0;            // covariance records, 3 float4 per voxel (k_cov_records3)
+  unsigned int* d_blk = nullptr; size_t blk_cap = 0;      // per-workgroup valid counts | their exclusive scan | the total
+  float4* d_comp = nullptr; size_t comp_cap = 0;          // component list, 3 float4 per component (k_components3)
+  int n_comp = 0;
+  bool cov_valid = false, comp_valid = false;
+  ndt::MapCall3* d_map_call = nullptr;
+  hipEvent_t map_ev = nullptr;                            // orders a target handle's stream behind this handle's (order_after)
 };
 
 namespace {
+
+// everything that changes the voxel grid's sums or geometry drops what map-to-map alignment derived from them
+void grid_changed3(ndt3d_handle* h) { h->cov_valid = false; h->comp_valid = false; }
 
 int32_t upload_static3(ndt3d_handle* h) {
   // as upload_static in 2D: the copy is left in flight (whatever reads d_static is ordered behind it on the same
@@ -282,6 +294,7 @@ int32_t set_target3_impl(ndt3d_handle* h, const float* dx, const float* dy, cons
   using namespace ndt;
   TraceRange range("ndt3d_set_target: voxel grid build");
   h->has_target = false;
+  grid_changed3(h);
   unsigned int* hb = (unsigned int*)h->h_small;
   unsigned int fast_bounds[6];
   bool done = false, have_bounds = false;
@@ -536,12 +549,14 @@ int32_t ndt3d_destroy(ndt3d_handle* h) {
   if (h->stream) (void)hipStreamSynchronize(h->stream);
   h->graphs.clear();
   void* dev[] = {h->d_parts3, h->d_bounds, h->d_counters, h->d_outside, h->d_static, h->d_call, h->d_dyn, h->d_t[0], h->d_t[1], h->d_t[2],
-                 h->d_s[0], h->d_s[1], h->d_s[2], h->d_b[0], h->d_b[1], h->d_b[2], h->d_tiles, h->d_split3, h->grid.rec, h->grid.acc, h->d_dyn_multi};
+                 h->d_s[0], h->d_s[1], h->d_s[2], h->d_b[0], h->d_b[1], h->d_b[2], h->d_tiles, h->d_split3, h->grid.rec, h->grid.acc, h->d_dyn_multi,
+                 h->d_cov, h->d_blk, h->d_comp, h->d_map_call};
   for (void* p : dev) if (p) (void)hipFree(p);
   void* host[] = {h->h_static, h->h_state, h->h_small, h->h_flag, h->h_state_multi, h->h_pub3};
   for (void* p : host) if (p) (void)hipHostFree(p);
   h->srch.release();
   if (h->upload_ev) (void)hipEventDestroy(h->upload_ev);
+  if (h->map_ev) (void)hipEventDestroy(h->map_ev);
   if (h->stream) (void)hipStreamDestroy(h->stream);
   delete h;
   return NDT_OK;
@@ -596,6 +611,7 @@ int32_t ndt3d_reserve_target(ndt3d_handle* h, const double lo[3], const double h
   HIP_TRY(hipSetDevice(h->device));
   { const int32_t fs = finish_align3(h); if (fs != NDT_OK) return fs; }
   h->has_target = false;
+  grid_changed3(h);
   { const int32_t gs = setup_geometry3(h, l, u); if (gs != NDT_OK) return gs; }
   const size_t ncell = (size_t)h->grid.W * h->grid.H * h->grid.D;
   HIP_TRY(hipMemsetAsync(h->grid.acc, 0, ncell * sizeof(ndt::CellAcc3), h->stream));
@@ -624,6 +640,7 @@ int32_t ndt3d_add_target_points_dev(ndt3d_handle* h, const float* d_x, const flo
     for (int j = 0; j < 3; ++j) T.t[j] = (float)pose[j];
   }
   unsigned long long outside = 0;
+  grid_changed3(h);
   const int32_t fs = accumulate3(h, p[0], p[1], p[2], n, /*merge=*/true, &outside, pose ? &T : nullptr);
   if (n_outside) *n_outside = (size_t)outside;
   if (fs != NDT_OK) { h->has_target = false; return fs; }

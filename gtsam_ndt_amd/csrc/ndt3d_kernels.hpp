@@ -274,9 +274,13 @@ __device__ __forceinline__ void jacobi_rot(double& app, double& aqq, double& apq
   }
 }
 
-// sums -> (mean, n | Sigma^-1) for one voxel; false when the voxel is not usable
-__device__ __forceinline__ bool finalise_sums3(const CellAcc3& c, double cx, double cy, double cz, double fix_scale,
-                                               int min_points, double eig_ratio, float4& ra, float4& rb, float4& rc) {
+// The eigen step of a voxel's sums, shared by the two record forms (finalise_sums3 below: Sigma^-1; cov_record3 of
+// ndt3d_d2d.hpp: Sigma).  `record` receives the float64 mean, the three eigenvalues, their lower limit
+// eig_ratio x the largest, and the eigenvector columns, and forms the record; false when the voxel is not usable.
+// (A functor and not a struct handed back, so that each caller compiles to the single straight-line function it was.)
+template <class Record>
+__device__ __forceinline__ bool cell_eigen3(const CellAcc3& c, double cx, double cy, double cz, double fix_scale,
+                                            int min_points, double eig_ratio, Record&& record) {
   const int n = (int)c.n;
   if (n < min_points || n < 2) return false;
   const double inv_s = 1.0 / fix_scale, dn = (double)n;
@@ -299,6 +303,16 @@ __device__ __forceinline__ bool finalise_sums3(const CellAcc3& c, double cx, dou
   const double lmax = fmax(axx, fmax(ayy, azz));
   if (!(lmax > 0.0)) return false;
   const double lim = eig_ratio * lmax;
+  record(n, mx, my, mz, axx, ayy, azz, lim, v0, v1, v2);
+  return true;
+}
+
+// sums -> (mean, n | Sigma^-1) for one voxel; false when the voxel is not usable
+__device__ __forceinline__ bool finalise_sums3(const CellAcc3& c, double cx, double cy, double cz, double fix_scale,
+                                               int min_points, double eig_ratio, float4& ra, float4& rb, float4& rc) {
+  return cell_eigen3(c, cx, cy, cz, fix_scale, min_points, eig_ratio,
+                     [&](int n, double mx, double my, double mz, double axx, double ayy, double azz, double lim,
+                         const double* v0, const double* v1, const double* v2) {
   const double i0 = 1.0 / fmax(axx, lim), i1 = 1.0 / fmax(ayy, lim), i2 = 1.0 / fmax(azz, lim);
   const double cxx = i0 * v0[0] * v0[0] + i1 * v1[0] * v1[0] + i2 * v2[0] * v2[0];
   const double cxy = i0 * v0[0] * v0[1] + i1 * v1[0] * v1[1] + i2 * v2[0] * v2[1];
@@ -309,7 +323,7 @@ __device__ __forceinline__ bool finalise_sums3(const CellAcc3& c, double cx, dou
   ra = make_float4((float)mx, (float)my, (float)mz, (float)n);
   rb = make_float4((float)cxx, (float)cxy, (float)cxz, (float)cyy);
   rc = make_float4((float)cyz, (float)czz, 0.f, 0.f);
-  return true;
+  });
 }
 
 __global__ __launch_bounds__(kBlock) void k_finalise3(Grid3Dev g, int min_points, double eig_ratio,

@@ -193,6 +193,7 @@ int32_t ndt3d_load_map(ndt3d_handle* h, const void* buf, size_t bytes) {
   HIP_TRY(hipSetDevice(h->device));
   { const int32_t fs = finish_align3(h); if (fs != NDT_OK) return fs; }
   h->has_target = false;
+  grid_changed3(h);
   Grid3Dev& g = h->grid;
   const double c = h->prm.cell_size;
   g.cell = c; g.inv_c = (float)(1.0 / c);

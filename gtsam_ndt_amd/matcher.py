@@ -786,6 +786,36 @@ class NdtMatcher3D:
                              np.array(r.g, dtype=np.float64), float(r.score), int(r.iterations), int(r.n_hit),
                              int(r.status))
 
+    # ---- map-to-map alignment (distribution-to-distribution NDT): no points, two cached voxel grids
+    def align_map(self, source: "NdtMatcher3D", init_pose=(0.0,) * 6) -> AlignResult3D:
+        """Align `source`'s cached voxel grid to this handle's (ndt3d_align_map): pose maps the source map's frame into
+        this map's frame.  This handle's parameters drive the solve; `source` may be this handle."""
+        p = (C.c_double * 6)(*[float(v) for v in init_pose])
+        r = L.Result3D()
+        L.check(self._lib.ndt3d_align_map(self._h, source._h, p, C.byref(r)), "ndt3d_align_map")
+        return self._result(r)
+
+    def evaluate_map(self, source: "NdtMatcher3D", pose):
+        """(H, g, score, n_hit) of the map-to-map objective at `pose` (ndt3d_evaluate_map)."""
+        p = (C.c_double * 6)(*[float(v) for v in pose])
+        out = L.Eval3D()
+        L.check(self._lib.ndt3d_evaluate_map(self._h, source._h, p, C.byref(out)), "ndt3d_evaluate_map")
+        return (np.array(out.H, dtype=np.float64).reshape(6, 6), np.array(out.g, dtype=np.float64),
+                float(out.score), int(out.n_hit))
+
+    def components(self):
+        """(key int32 [n], mean float32 [n,3], cov float32 [n,6] = (xx xy xz yy yz zz)) of the cached grid's valid
+        voxels, in voxel-key order: what this handle contributes as the source of align_map (ndt3d_get_components)."""
+        n = C.c_int32(0)
+        L.check(self._lib.ndt3d_get_components(self._h, None, None, None, 0, C.byref(n)), "ndt3d_get_components")
+        key = np.zeros(n.value, dtype=np.int32)
+        mean = np.zeros((n.value, 3), dtype=np.float32)
+        cov = np.zeros((n.value, 6), dtype=np.float32)
+        if n.value:
+            L.check(self._lib.ndt3d_get_components(self._h, mean.ctypes.data, cov.ctypes.data, key.ctypes.data, n.value,
+                                                   C.byref(n)), "ndt3d_get_components")
+        return key, mean, cov
+
     def align_multi_scan(self, scans, init_poses):
         """Up to 64 different device scans [(x, y, z), ...] against the cached voxel grid, each from its own initial
         pose, in one launch chain (ndt3d_align_multi_scan_dev); scan k's result equals align(scan k, pose k) bit for bit."""

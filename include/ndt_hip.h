@@ -20,7 +20,8 @@
  *     hipMalloc, torch) and enqueue on the given hipStream_t (passed as void*); results
  *     written to device memory are valid after that stream is synchronised.
  *   - A handle is single-threaded; distinct handles may be used from distinct threads.  A map-to-map call
- *     (ndt2d_align_map / ndt2d_evaluate_map) uses BOTH its handles for its duration: no other thread may touch either.
+ *     (ndt2d_align_map / ndt2d_evaluate_map, ndt3d_align_map / ndt3d_evaluate_map) uses BOTH its handles for its
+ *     duration: no other thread may touch either.
  *   - Points are SoA float32 arrays (x[], y[]); poses are double (tx, ty, theta).
  *   - There is NO CPU fallback: every entry point that computes needs a gfx950 device.
  */
@@ -630,6 +631,36 @@ int32_t ndt3d_search_align_dev(ndt3d_handle* h, const float* d_sx, const float* 
  * of the evaluation that produced the (j+1)-th update.  out (may be NULL): the final result.  Host arrays. */
 int32_t ndt3d_align_trace(ndt3d_handle* h, const float* sx, const float* sy, const float* sz, size_t n,
                           const double init_pose[6], ndt3d_result* rows, int32_t capacity, int32_t* n_rows, ndt3d_result* out);
+/* ---- 3D map-to-map alignment (distribution-to-distribution NDT; docs/ALGORITHM.md section 2.14) ---------------
+ * The SE(3) twin of ndt2d_align_map: aligns the cached voxel grid of `source` to the cached voxel grid of `target` from the
+ * per-voxel sums alone - what a handle keeps after ndt3d_add_target_points_dev, and all that ndt3d_save_map /
+ * ndt3d_load_map persist, is enough; no point of either map is needed.  The source is the list of its valid voxels'
+ * Gaussians (mean, regularised covariance: its *components*, in voxel-key order), each scored against the target Gaussian
+ * of the one voxel its transformed mean falls in, with the combined covariance R S_i R^T + S_j; every hit weighs the same.
+ * pose = (tx, ty, tz, roll, pitch, yaw) maps the source map's frame into the target map's frame.
+ *   - The TARGET handle's parameters drive the solve (d1, d2, hessian_mode, the limits and stops, step_scale,
+ *     line_search, its stream); the source handle's min_points / eig_ratio decide only its components.  The cell sizes
+ *     may differ.  step_scale much above 1 over-relaxes this objective, as in 2D.
+ *   - target == source is legal (a map against itself: the identity is a fixed point).
+ *   - Both handles must live on the same device: NDT_ERR_INVALID_ARG.  No grid on either handle: NDT_ERR_NO_TARGET.
+ *     A non-finite pose: NDT_ERR_INVALID_ARG.  A source without a component or a target without a valid voxel: NDT_OK
+ *     with status NDT_TOO_FEW_CELLS and the initial pose (ndt3d_evaluate_map: all zeros).
+ *   - Both calls are synchronous and finish an alignment in flight on either handle first; the target's stream is ordered
+ *     behind the source's by the library.  The derived per-handle data (covariance records, component list) is built on
+ *     a handle's first such call and again after anything that changes its grid.  Results are bit for bit reproducible.
+ *   - Two maps of one scene on the same voxel lattice pull towards the identity (measured at 1 m voxels: an
+ *     offset of 0.10 m / 10 mrad is recovered from the zero guess, 0.30 m / 30 mrad ends in a local optimum): from a guess
+ *     more than about a tenth of a voxel off, align a coarse pair of handles first and the fine pair from its result
+ *     (DESIGN.md section 5.9).
+ *   - ndt3d_result / ndt3d_eval are those of ndt3d_align / ndt3d_evaluate (n_hit counts components that hit a valid
+ *     target voxel).  No covariance calibration exists for this objective.  Not offered: a batched form, pairing with
+ *     neighbouring voxels, a search over component lists. */
+int32_t ndt3d_evaluate_map(ndt3d_handle* target, ndt3d_handle* source, const double pose[6], ndt3d_eval* out);
+int32_t ndt3d_align_map(ndt3d_handle* target, ndt3d_handle* source, const double init_pose[6], ndt3d_result* out);
+/* The components of a handle's cached voxel grid, as host copies: mean_xyz [3n], cov6 [6n] = (xx xy xz yy yz zz) of the
+ * regularised covariance, key [n] = (iz * height + iy) * width + ix, ascending.  Any pointer may be NULL; *n (if given) is
+ * the count, also when capacity is too small for the arrays asked for (NDT_ERR_CAPACITY). */
+int32_t ndt3d_get_components(ndt3d_handle* h, float* mean_xyz, float* cov6, int32_t* key, int32_t capacity, int32_t* n);
 void* ndt3d_stream(ndt3d_handle* h);
 /* as ndt2d_wait_stream: order the handle's stream behind the producer of the device arrays */
 int32_t ndt3d_wait_stream(ndt3d_handle* h, void* producer_stream);

@@ -667,6 +667,21 @@ class NdtMatcherHip3 {
     check(ndt3d_align(h_, sx, sy, sz, n, init, &r), "ndt3d_align");
     return toMatchResult(r);
   }
+  // Map-to-map alignment (ndt3d_align_map): source's cached voxel grid against this matcher's, no points; the pose maps
+  // the source map's frame into this map's frame; this matcher's parameters drive the solve; source may be *this.
+  // result.covariance is the plain inverse of the map-to-map Hessian: no calibration exists for this objective.
+  MatchResult3 alignMap(NdtMatcherHip3& source, const Pose3& guess = Pose3()) {
+    const double init[6] = {guess.x, guess.y, guess.z, guess.roll, guess.pitch, guess.yaw};
+    ndt3d_result r;
+    check(ndt3d_align_map(h_, source.h_, init, &r), "ndt3d_align_map");
+    return toMatchResult(r);
+  }
+  ndt3d_eval evaluateMap(NdtMatcherHip3& source, const Pose3& at) {
+    const double p[6] = {at.x, at.y, at.z, at.roll, at.pitch, at.yaw};
+    ndt3d_eval e;
+    check(ndt3d_evaluate_map(h_, source.h_, p, &e), "ndt3d_evaluate_map");
+    return e;
+  }
   ndt3d_handle* raw() { return h_; }
   static MatchResult3 toMatchResult(const ndt3d_result& r) {
     MatchResult3 m;
