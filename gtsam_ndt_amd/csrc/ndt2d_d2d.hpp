@@ -7,7 +7,8 @@
 //   k_comp_offsets    source side: exclusive scan of the per-workgroup counts of valid cells ...
 //   k_components      ... and the compaction of the valid cells into a dense list, in cell-key order
 //   k_begin_d2d       per-call part of the context (the twin of k_begin)
-//   k_iterate_d2d     one launch per Gauss-Newton iteration: k_iterate's prologue and epilogue around a new body
+//   k_iterate_d2d     one launch per Gauss-Newton iteration: the chain's shared prologue pieces and k_iterate's epilogue
+//                     around a new body
 #pragma once
 #include "ndt2d_kernels.hpp"
 
@@ -189,7 +190,8 @@ __device__ __forceinline__ void accumulate_component(const PoseF& P, const RotF&
 }
 
 // Launch k (parity = k & 1) consumes state[parity^1] / partials[parity^1] of launch k-1 and produces state[parity] /
-// partials[parity]: k_iterate's chain, state, flags and reduction, with call->blocks workgroups of kBlock threads
+// partials[parity]: k_iterate's chain, state, flags and reduction (the shared pieces of ndt_chain.hpp and
+// ndt2d_kernels.hpp), with call->blocks workgroups of kBlock threads
 // (a component per lane; a few thousand components do not need a workgroup per CU).  Same two dependent memory
 // round trips: previous state + partial rows + first component in one batch, then the record gather.
 template <int MODE>
@@ -227,72 +229,26 @@ __global__ __launch_bounds__(kBlock) void k_iterate_d2d(const AlignStatic* __res
   if (i < n) { ca = comp[2 * (size_t)i]; cb = comp[2 * (size_t)i + 1]; }
 
   if (ps_done) {                         // uniform: a finished alignment just carries its state
-    if (writer) {
-      copy_state(cur, prev, -1);
-      // the finishing launch is complete and left n = 0 behind: nothing reads the component list any more
-      if (host_flag) __hip_atomic_store(host_flag + 2, call->seq, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-    }
+    if (writer) chain_carry_done(cur, prev, host_flag, call);     // nothing reads the component list any more
     return;
   }
   double pose[3] = {ps_pose0, ps_pose1, ps_pose2};
   int iter = ps_iter;
   if (ps_have) {
-    // ---- prologue (k_iterate's): fixed-order float64 fold of the kMaxBlocks partial rows, then the solve
+    // ---- prologue: fixed-order float64 fold of the kMaxBlocks partial columns (fold_rows12), then the solve
     double H[6], g[3], score = 0.0;
     int n_hit = 0, status = 0;
-    {
-      double* t = reinterpret_cast<double*>(s_t[wave]);
-#pragma unroll
-      for (int v = 0; v < 3; ++v)
-        t[v * 66 + lane] = (((double)pv[v].x + (double)pv[v].y) + (double)pv[v].z) + (double)pv[v].w;
-      __builtin_amdgcn_wave_barrier();
-      double a = 0.0;
-      if (lane < 48) {
-        const double* row = t + (lane >> 4) * 66 + (lane & 15);
-        a = (row[0] + row[16]) + (row[32] + row[48]);
-      }
-      a += dpp_mov<0xB1, 0xf>(a);
-      a += dpp_mov<0x4E, 0xf>(a);
-      a += dpp_mov<0x124, 0xf>(a);
-      a += dpp_mov<0x128, 0xf>(a);
-      if ((lane & 15) == 0 && lane < 48) s_red[wave * 3 + (lane >> 4)] = a;
-      __builtin_amdgcn_wave_barrier();
-    }
+    fold_rows12(pv, reinterpret_cast<double*>(s_t[wave]), lane, &s_red[wave * 3]);
     __syncthreads();
-#pragma unroll
-    for (int j = 0; j < 6; ++j) H[j] = s_red[j];
-#pragma unroll
-    for (int j = 0; j < 3; ++j) g[j] = s_red[6 + j];
-    score = s_red[9];
-    n_hit = (int)(s_red[10] + 0.5);
+    unpack_sums(s_red, H, g, score, n_hit);
     const bool done = gn_update(pose, H, g, n_hit, iter, status, prm, fixed_iterations, score, &dyn->ls[parity ^ 1],
                                 &dyn->ls[parity], writer);
     if (writer) {
-      IterState o;
-      o.pose[0] = pose[0]; o.pose[1] = pose[1]; o.pose[2] = pose[2];
-#pragma unroll
-      for (int j = 0; j < 6; ++j) o.H[j] = H[j];
-#pragma unroll
-      for (int j = 0; j < 3; ++j) o.g[j] = g[j];
-      o.score = score;
-      o.n_hit = n_hit;
-      o.iter = iter;
-      o.status = status;
-      o.done = done ? 1 : 0;
-      o.have_partials = 1;
-      o.pad = ps_launch + 1;
-      *cur = o;
-      if (host_flag) {
-        if (done) {                      // state and this launch's number first, then the flag
-          *host_state = o;
-          __hip_atomic_store(host_flag + 1, ps_launch + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-          const_cast<MapCall*>(call)->n = 0;       // the launches enqueued past the end load no component
-          __threadfence_system();
-          __hip_atomic_store(host_flag, 1, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
-        } else {
-          __hip_atomic_store(host_flag + 1, ps_launch + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-        }
-      }
+      auto store = [&](IterState* o) {
+        pack_state(o, pose, H, g, score, n_hit, iter, status, done ? 1 : 0, ps_launch + 1);
+      };
+      store(cur);
+      chain_announce(store, done, ps_launch + 1, host_state, host_flag, call);
     }
     if (done) return;                    // uniform
   } else if (writer) {
@@ -325,7 +281,7 @@ __global__ __launch_bounds__(kBlock) void k_iterate_d2d(const AlignStatic* __res
   acc_store(A, prm.d2, acc);
   acc[11] = 0.f;
 
-  // ---- epilogue (k_iterate's): wave tree -> LDS -> one partial row per workgroup
+  // ---- epilogue: wave tree -> LDS -> one partial column entry per sum
   {
     const float r = wave_reduce11_lds(acc, s_t[wave], lane);
     if ((lane & 3) == 0 && lane < 4 * (kNumAcc - 1)) s_wave[wave][lane >> 2] = r;

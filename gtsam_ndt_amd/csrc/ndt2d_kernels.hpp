@@ -13,6 +13,7 @@
 //                       epilogue  = wave DPP tree -> LDS -> one partial row per block
 #pragma once
 #include "ndt_device.hpp"
+#include "ndt_chain.hpp"
 
 namespace ndt {
 
@@ -629,6 +630,57 @@ __device__ __forceinline__ float wave_reduce11_lds(const float* acc, float* s_t,
   return v;
 }
 
+// Prologue of a chain launch, a wave's share: three partial rows of 256 block entries (pv[v]: this lane's four of row v)
+// -> their totals in out[0..2], in a fixed order.  Each lane folds its 4 blocks per row in float64 and parks the 3
+// values in LDS (t: 3 x 66 doubles, [row][lane]); lane 16v+q adds the 4 values of row v whose lane index is q mod 16,
+// four DPP steps fold the 16 lanes - instead of three 6-step float64 DPP trees on the critical path.  Four waves
+// (rows 3w .. 3w+2 into s_red + 3w) and a __syncthreads make the 12 sums of an alignment.
+__device__ __forceinline__ void fold_rows12(const float4* pv, double* t, int lane, double* out) {
+#pragma unroll
+  for (int v = 0; v < 3; ++v)
+    t[v * 66 + lane] = (((double)pv[v].x + (double)pv[v].y) + (double)pv[v].z) + (double)pv[v].w;
+  __builtin_amdgcn_wave_barrier();
+  double a = 0.0;
+  if (lane < 48) {
+    const double* row = t + (lane >> 4) * 66 + (lane & 15);
+    a = (row[0] + row[16]) + (row[32] + row[48]);
+  }
+  a += dpp_mov<0xB1, 0xf>(a);
+  a += dpp_mov<0x4E, 0xf>(a);
+  a += dpp_mov<0x124, 0xf>(a);
+  a += dpp_mov<0x128, 0xf>(a);                           // every lane of the 16-lane row holds its total
+  if ((lane & 15) == 0 && lane < 48) out[lane >> 4] = a;
+  __builtin_amdgcn_wave_barrier();                       // where t is the epilogue's buffer, this wave rewrites it
+}
+
+// the folded sums -> what gn_update takes
+__device__ __forceinline__ void unpack_sums(const double* s_red, double* H, double* g, double& score, int& n_hit) {
+#pragma unroll
+  for (int j = 0; j < 6; ++j) H[j] = s_red[j];
+#pragma unroll
+  for (int j = 0; j < 3; ++j) g[j] = s_red[6 + j];
+  score = s_red[9];
+  n_hit = (int)(s_red[10] + 0.5);
+}
+
+// The state a launch leaves behind, field by field into *o (no struct temporary: see copy_state); pad = this launch's
+// index.
+__device__ __forceinline__ void pack_state(IterState* o, const double* pose, const double* H, const double* g,
+                                           double score, int n_hit, int iter, int status, int done, int launch) {
+  o->pose[0] = pose[0]; o->pose[1] = pose[1]; o->pose[2] = pose[2];
+#pragma unroll
+  for (int j = 0; j < 6; ++j) o->H[j] = H[j];
+#pragma unroll
+  for (int j = 0; j < 3; ++j) o->g[j] = g[j];
+  o->score = score;
+  o->n_hit = n_hit;
+  o->iter = iter;
+  o->status = status;
+  o->done = done;
+  o->have_partials = 1;
+  o->pad = launch;
+}
+
 // ---------------------------------------------------------------- a4-a8 iterate kernel
 // Launch k (parity = k & 1) consumes state[parity^1] and partials[parity^1] written by
 // launch k-1 and produces state[parity], partials[parity].  Always kMaxBlocks workgroups
@@ -685,12 +737,7 @@ __global__ __launch_bounds__(THREADS) void k_iterate(const AlignStatic* __restri
   if (i + stride < n) { x1 = sx[i + stride]; y1 = sy[i + stride]; }
 
   if (ps_done) {                         // uniform: a finished alignment just carries its state
-    if (writer) {
-      copy_state(cur, prev, -1);
-      // the launch that finished the loop is complete (this one started after it) and left n = 0
-      // behind: nothing reads the source arrays any more - tell the host it may hand them back
-      if (host_flag) __hip_atomic_store(host_flag + 2, call->seq, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-    }
+    if (writer) chain_carry_done(cur, prev, host_flag, call);
     return;
   }
   double pose[3] = {ps_pose0, ps_pose1, ps_pose2};
@@ -700,35 +747,11 @@ __global__ __launch_bounds__(THREADS) void k_iterate(const AlignStatic* __restri
     int n_hit = 0, status = 0;
     bool done = false;
     if (!(EXP & 1)) {
-      // ---- prologue: fixed-order reduction (wave w owns sums 3w..3w+2), then the solve.
-      // Each lane folds its 4 blocks per row in float64 and parks the 3 values in LDS ([row][lane]);
-      // lane 16v+q adds the 4 values of row v whose lane index is q mod 16, four DPP steps fold the
-      // 16 lanes - instead of three 6-step float64 DPP trees on the critical path.
-      if (wave < 4) {
-        double* t = reinterpret_cast<double*>(s_t[wave]);     // 3 x 66 doubles fit in the epilogue's buffer
-#pragma unroll
-        for (int v = 0; v < 3; ++v)
-          t[v * 66 + lane] = (((double)pv[v].x + (double)pv[v].y) + (double)pv[v].z) + (double)pv[v].w;
-        __builtin_amdgcn_wave_barrier();
-        double a = 0.0;
-        if (lane < 48) {
-          const double* row = t + (lane >> 4) * 66 + (lane & 15);
-          a = (row[0] + row[16]) + (row[32] + row[48]);
-        }
-        a += dpp_mov<0xB1, 0xf>(a);
-        a += dpp_mov<0x4E, 0xf>(a);
-        a += dpp_mov<0x124, 0xf>(a);
-        a += dpp_mov<0x128, 0xf>(a);                           // every lane of the 16-lane row holds its total
-        if ((lane & 15) == 0 && lane < 48) s_red[wave * 3 + (lane >> 4)] = a;
-        __builtin_amdgcn_wave_barrier();
-      }
+      // ---- prologue: fixed-order reduction (wave w owns sums 3w..3w+2), then the solve
+      if (wave < 4)                                            // 3 x 66 doubles fit in the epilogue's buffer
+        fold_rows12(pv, reinterpret_cast<double*>(s_t[wave]), lane, &s_red[wave * 3]);
       __syncthreads();
-#pragma unroll
-      for (int j = 0; j < 6; ++j) H[j] = s_red[j];
-#pragma unroll
-      for (int j = 0; j < 3; ++j) g[j] = s_red[6 + j];
-      score = s_red[9];
-      n_hit = (int)(s_red[10] + 0.5);
+      unpack_sums(s_red, H, g, score, n_hit);
       done = gn_update(pose, H, g, n_hit, iter, status, prm, fixed_iterations, score, &dyn->ls[parity ^ 1],
                        &dyn->ls[parity], writer);
     } else {
@@ -739,31 +762,11 @@ __global__ __launch_bounds__(THREADS) void k_iterate(const AlignStatic* __restri
       done = iter >= fixed_iterations;
     }
     if (writer) {
-      IterState o;
-      o.pose[0] = pose[0]; o.pose[1] = pose[1]; o.pose[2] = pose[2];
-#pragma unroll
-      for (int j = 0; j < 6; ++j) o.H[j] = H[j];
-#pragma unroll
-      for (int j = 0; j < 3; ++j) o.g[j] = g[j];
-      o.score = score;
-      o.n_hit = n_hit;
-      o.iter = iter;
-      o.status = status;
-      o.done = done ? 1 : 0;
-      o.have_partials = 1;
-      o.pad = ps_launch + 1;
-      *cur = o;
-      if (host_flag) {                   // tell the host directly
-        if (done) {                      // state and this launch's number first, then the flag
-          *host_state = o;
-          __hip_atomic_store(host_flag + 1, ps_launch + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-          const_cast<AlignCall*>(call)->n = 0;     // the launches enqueued past the end load no points
-          __threadfence_system();
-          __hip_atomic_store(host_flag, 1, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
-        } else {                         // progress: which launch this is
-          __hip_atomic_store(host_flag + 1, ps_launch + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-        }
-      }
+      auto store = [&](IterState* o) {
+        pack_state(o, pose, H, g, score, n_hit, iter, status, done ? 1 : 0, ps_launch + 1);
+      };
+      store(cur);
+      chain_announce(store, done, ps_launch + 1, host_state, host_flag, call);
     }
     if (done) return;                    // uniform
   } else if (writer) {

@@ -188,35 +188,20 @@ __global__ __launch_bounds__(THREADS) void k_iterate_multi(const AlignStatic* __
 
   if (herald) {
     dyn->launch[parity] = launch;
-    // progress, while anything is still running.  Not from the launches past the end: they may execute
-    // after the host has reset the flags for its NEXT call, and a stale progress number there makes that
-    // call's feeding loop run ahead of its own chain (found by tools/soak_round2.py: one call in a few
-    // thousand hit the loop's launch cap).
-    if (host_flag && subsets_done != (int)gridDim.y)
-      __hip_atomic_store(host_flag + 1, launch, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+    if (host_flag && subsets_done != (int)gridDim.y) multi_announce(true, launch, armed, host_flag, call);
   }
   bool sub_prev_done = true;
 #pragma unroll
   for (int h = 0; h < NH; ++h) sub_prev_done = sub_prev_done && pdone[h];
   if (sub_prev_done) {                   // uniform: this subset has finished - carry its states
     if (block0 && tid < NH) copy_state(&cur[tid], &prev[tid], -1);
-    if (herald && host_flag && subsets_done == (int)gridDim.y) {
-      // Every start had finished (and written its final state to the host) before this launch began.
-      // First such launch: stop the launches behind it from loading points, then raise the flag.
-      // Second: the first one is complete, nothing reads the source arrays any more.
-      if (armed != 0) {
-        const_cast<AlignCall*>(call)->n = 0;
-        __threadfence_system();
-        __hip_atomic_store(host_flag, 1, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
-      } else {
-        __hip_atomic_store(host_flag + 2, call->seq, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-      }
-    }
+    // every start had finished (and written its final state to the host) before this launch began: the end of the call
+    if (herald && host_flag && subsets_done == (int)gridDim.y) multi_announce(false, launch, armed, host_flag, call);
     return;
   }
 
-  // ---- prologue (1/2): fixed-order float64 reduction of the partial rows, the tree of k_iterate
-  // row for row
+  // ---- prologue (1/2): fixed-order float64 reduction of the partial rows, the tree of fold_rows12 row for row (this
+  // kernel keeps its own text: as a call it came out one instruction longer in two instances)
 #pragma unroll
   for (int j = 0; j < kPerWave; ++j) {
     const int g = wave + j * kWaves;
@@ -250,30 +235,15 @@ __global__ __launch_bounds__(THREADS) void k_iterate_multi(const AlignStatic* __
     if (done) {
       if (writer) copy_state(&cur[h], &prev[h], -1);
     } else if (q_have) {
-      double H[6], g[3];
-#pragma unroll
-      for (int k = 0; k < 6; ++k) H[k] = s_red[h][k];
-#pragma unroll
-      for (int k = 0; k < 3; ++k) g[k] = s_red[h][6 + k];
-      const double score = s_red[h][9];
-      const int n_hit = (int)(s_red[h][10] + 0.5);
+      double H[6], g[3], score;
+      int n_hit;
+      unpack_sums(s_red[h], H, g, score, n_hit);
       int iter = q_iter, status = 0;
       done = gn_update(pose, H, g, n_hit, iter, status, prm, fixed_iterations, score, &dyn->ls[parity ^ 1][hb + h],
                        &dyn->ls[parity][hb + h], writer) ? 1 : 0;
       if (writer) {
         IterState o;
-        o.pose[0] = pose[0]; o.pose[1] = pose[1]; o.pose[2] = pose[2];
-#pragma unroll
-        for (int k = 0; k < 6; ++k) o.H[k] = H[k];
-#pragma unroll
-        for (int k = 0; k < 3; ++k) o.g[k] = g[k];
-        o.score = score;
-        o.n_hit = n_hit;
-        o.iter = iter;
-        o.status = status;
-        o.done = done;
-        o.have_partials = 1;
-        o.pad = launch;
+        pack_state(&o, pose, H, g, score, n_hit, iter, status, done, launch);
         cur[h] = o;
         if (host_flag && done) host_state[hb + h] = o;        // final states go to the host as they come
       }
@@ -409,7 +379,8 @@ __global__ __launch_bounds__(THREADS) void k_iterate_multi(const AlignStatic* __
 
 // ------------------------------------------------------------------------------------------------------
 // Split chain for many starts: per iteration one launch of k_multi_solve (one workgroup per start: the
-// reduction of that start's partial rows and its update - k_iterate's prologue, once instead of in every
+// reduction of that start's partial rows and its update - fold_rows12 / unpack_sums / gn_update, once instead of in
+// every
 // one of the 256 workgroups that evaluate the start) and one of k_multi_body (the evaluation).  In the
 // fused kernel above the redundant prologues cost as much as the evaluation from a few dozen starts on
 // (64 starts: 16384 solves per launch); here a second kernel boundary (1.7 us) buys them back.  Same
@@ -444,17 +415,7 @@ __global__ __launch_bounds__(kBlock) void k_multi_solve(const AlignStatic* __res
   }
   if (herald) {
     dyn->launch[parity] = launch;
-    if (host_flag) {
-      if (starts_done != m) {                           // progress, while anything is still running
-        __hip_atomic_store(host_flag + 1, launch, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-      } else if (armed != 0) {                          // every start had finished before this launch: end of the call
-        const_cast<AlignCall*>(call)->n = 0;            // the launches behind load no points
-        __threadfence_system();
-        __hip_atomic_store(host_flag, 1, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
-      } else {                                          // ... and that launch is complete: the sources are free
-        __hip_atomic_store(host_flag + 2, call->seq, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-      }
-    }
+    if (host_flag) multi_announce(starts_done != m, launch, armed, host_flag, call);
   }
   AlignDynMulti::BodyPose* bp = &dyn->posef[parity][h];
   if (ps_done) {                                        // uniform: a finished start carries its state
@@ -464,31 +425,12 @@ __global__ __launch_bounds__(kBlock) void k_multi_solve(const AlignStatic* __res
   double pose[3] = {ps_pose0, ps_pose1, ps_pose2};
   int done = 0;
   if (ps_have) {
-    // k_iterate's prologue: wave w owns rows 3w .. 3w+2
-    double* t = s_t[wave];
-#pragma unroll
-    for (int v = 0; v < 3; ++v)
-      t[v * 66 + lane] = (((double)pv[v].x + (double)pv[v].y) + (double)pv[v].z) + (double)pv[v].w;
-    __builtin_amdgcn_wave_barrier();
-    double a = 0.0;
-    if (lane < 48) {
-      const double* row = t + (lane >> 4) * 66 + (lane & 15);
-      a = (row[0] + row[16]) + (row[32] + row[48]);
-    }
-    a += dpp_mov<0xB1, 0xf>(a);
-    a += dpp_mov<0x4E, 0xf>(a);
-    a += dpp_mov<0x124, 0xf>(a);
-    a += dpp_mov<0x128, 0xf>(a);
-    if ((lane & 15) == 0 && lane < 48) s_red[wave * 3 + (lane >> 4)] = a;
+    fold_rows12(pv, s_t[wave], lane, &s_red[wave * 3]);       // wave w owns rows 3w .. 3w+2
     __syncthreads();
     if (wave == 0) {
-      double H[6], g[3];
-#pragma unroll
-      for (int j = 0; j < 6; ++j) H[j] = s_red[j];
-#pragma unroll
-      for (int j = 0; j < 3; ++j) g[j] = s_red[6 + j];
-      const double score = s_red[9];
-      const int n_hit = (int)(s_red[10] + 0.5);
+      double H[6], g[3], score;
+      int n_hit;
+      unpack_sums(s_red, H, g, score, n_hit);
       int iter = ps_iter, status = 0;
       done = gn_update(pose, H, g, n_hit, iter, status, prm, fixed_iterations, score, &dyn->ls[parity ^ 1][h], &dyn->ls[parity][h],
                        writer) ? 1 : 0;

@@ -280,8 +280,9 @@ __device__ __forceinline__ void accumulate_component3(const MapPose3& T, const f
 }
 
 // Launch k (parity = k & 1) consumes state[parity^1] / partials[parity^1] of launch k-1 and produces state[parity] /
-// partials[parity]: k_iterate3<0>'s chain, state, flags, fold and reduction restated (so that its code object stays as it
-// is), with call->blocks workgroups of kBlock threads, a component per lane.  Both Hessian modes carry the same 29 sums:
+// partials[parity]: k_iterate3<0>'s chain, state, flags, fold and reduction (the shared pieces of ndt_chain.hpp and
+// ndt3d_kernels.hpp), with call->blocks workgroups of kBlock threads, a component per lane.  Both Hessian modes carry
+// the same 29 sums:
 // in the map-frame form the second-derivative terms are per-component, there is no M to contract in the prologue.
 template <int MODE>
 __global__ __launch_bounds__(kBlock) void k_iterate_d2d3(const AlignStatic3* __restrict__ st, const MapCall3* __restrict__ call,
@@ -321,16 +322,13 @@ __global__ __launch_bounds__(kBlock) void k_iterate_d2d3(const AlignStatic3* __r
   if (i < n) { ca = comp[3 * (size_t)i]; cb = comp[3 * (size_t)i + 1]; cc = comp[3 * (size_t)i + 2]; }
 
   if (ps_done) {                         // uniform: a finished alignment just carries its state
-    if (writer) {
-      copy_state3(cur, prev, -1);
-      // the finishing launch is complete and left n = 0 behind: nothing reads the component list any more
-      if (host_flag) __hip_atomic_store(host_flag + 2, call->seq, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-    }
+    if (writer) chain_carry_done(cur, prev, host_flag, call);     // nothing reads the component list any more
     return;
   }
   int iter = ps_iter;
   if (ps_have) {
-    // ---- prologue (k_iterate3<0>'s): fixed-order float64 fold of the kMaxBlocks partial columns, then the solve
+    // ---- prologue: fixed-order float64 fold of the kMaxBlocks partial columns (k_iterate3<0>'s: one round of 8 rows),
+    // then the solve
     {
       double* t = reinterpret_cast<double*>(s_t[wave]);
 #pragma unroll
@@ -349,6 +347,7 @@ __global__ __launch_bounds__(kBlock) void k_iterate_d2d3(const AlignStatic3* __r
       __builtin_amdgcn_wave_barrier();
     }
     __syncthreads();
+    // 6x6 from the 21 packed sums: Htt(6) Htr(9) Hrr(6)
     double A[36], g[6];
     A[0] = s_red[0]; A[1] = s_red[1]; A[2] = s_red[2]; A[7] = s_red[3]; A[8] = s_red[4]; A[14] = s_red[5];
 #pragma unroll
@@ -368,31 +367,15 @@ __global__ __launch_bounds__(kBlock) void k_iterate_d2d3(const AlignStatic3* __r
     const bool done = gn_update3(pose, A, g, n_hit, iter, status, prm, fixed_iterations, score, &dyn->ls[parity ^ 1],
                                  &dyn->ls[parity], writer);
     if (writer) {
-      auto store = [&](IterState3* o) {
-#pragma unroll
-        for (int j = 0; j < 6; ++j) { o->pose[j] = pose[j]; o->g[j] = g[j]; }
-#pragma unroll
-        for (int j = 0; j < 21; ++j) o->H[j] = s_red[j];
-        o->score = score;
-        o->n_hit = n_hit; o->iter = iter; o->status = status;
-        o->done = done ? 1 : 0; o->have_partials = 1; o->pad = ps_launch + 1;   // index of this launch
+      auto store = [&](IterState3* o) {          // the Gauss-Newton form in both modes: s_red holds the whole Hessian
+        store_state3<0>(o, pose, g, s_red, A, score, n_hit, iter, status, done ? 1 : 0, ps_launch + 1);
       };
       store(cur);
-      if (host_flag) {
-        if (done) {                      // state and this launch's number first, then the flag
-          store(host_state);
-          __hip_atomic_store(host_flag + 1, ps_launch + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-          const_cast<MapCall3*>(call)->n = 0;      // the launches enqueued past the end load no component
-          __threadfence_system();
-          __hip_atomic_store(host_flag, 1, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
-        } else {
-          __hip_atomic_store(host_flag + 1, ps_launch + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-        }
-      }
+      chain_announce(store, done, ps_launch + 1, host_state, host_flag, call);
     }
     if (done) return;                    // uniform
   } else if (writer) {
-    copy_state3(cur, prev, 1);
+    copy_state(cur, prev, 1);
   }
 
   // ---- body: per-component terms at `pose`
@@ -423,30 +406,8 @@ __global__ __launch_bounds__(kBlock) void k_iterate_d2d3(const AlignStatic3* __r
     ca = na; cb = nb; cc = nc; i = i2;
   }
 
-  // ---- epilogue (evaluate_block3's): the wave's sums through LDS, one partial column entry per sum
-  {
-    float* t = s_t[wave];
-#pragma unroll
-    for (int j = 0; j < NA; ++j) t[j * kSum3RowStride + lane] = acc[j];
-    __builtin_amdgcn_wave_barrier();
-    {
-      const int j = lane >> 1;
-      float a = 0.f, b = 0.f;
-      if (j < NA) {
-        const float* row = t + j * kSum3RowStride + (lane & 1);
-#pragma unroll
-        for (int k = 0; k < 32; k += 2) { a += row[2 * k]; b += row[2 * k + 2]; }
-      }
-      float v = a + b;
-      v += dpp_mov<0xB1, 0xf>(v);
-      if ((lane & 1) == 0 && j < NA) s_wave[wave][j] = v;
-    }
-  }
-  __syncthreads();
-  if (tid < kRowsMap3) {
-    const float r = tid < NA ? ((s_wave[0][tid] + s_wave[1][tid]) + s_wave[2][tid]) + s_wave[3][tid] : 0.f;
-    dyn->partials[parity][tid][blockIdx.x] = r;
-  }
+  // ---- epilogue: the wave's sums through LDS, one partial column entry per sum
+  block_reduce3_store<NA, kRowsMap3>(acc, s_t[wave], s_wave, &dyn->partials[parity][0][blockIdx.x]);
 }
 
 }  // namespace ndt

@@ -606,6 +606,38 @@ __device__ __forceinline__ void accumulate_point3(const Rot3F& T, float x, float
   acc[28] += hit ? 1.f : 0.f;
 }
 
+// Epilogue of a 3D chain launch: the wave's NA sums through LDS instead of one DPP tree each (wave_reduce11_lds of the
+// 2D path): park [j][lane] (row stride 66 floats), lane 2j+q adds the 32 values of accumulator j whose lane index is
+// q mod 2 in two chains, one quad DPP step folds the pair; 32 accumulators per round.  Then the fixed-order sum of the
+// four waves: this workgroup's entry of the ROWS partial rows the next prologue folds (partial_col[row * kMaxBlocks];
+// rows >= NA are padding, written as zero).
+template <int NA, int ROWS, int WS>
+__device__ __forceinline__ void block_reduce3_store(const float* acc, float* t, float (*s_wave)[WS],
+                                                    float* __restrict__ partial_col) {
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+#pragma unroll
+  for (int j = 0; j < NA; ++j) t[j * kSum3RowStride + lane] = acc[j];
+  __builtin_amdgcn_wave_barrier();
+#pragma unroll
+  for (int base = 0; base < NA; base += 32) {
+    const int j = base + (lane >> 1);
+    float a = 0.f, b = 0.f;
+    if (j < NA) {
+      const float* row = t + j * kSum3RowStride + (lane & 1);
+#pragma unroll
+      for (int k = 0; k < 32; k += 2) { a += row[2 * k]; b += row[2 * k + 2]; }
+    }
+    float v = a + b;
+    v += dpp_mov<0xB1, 0xf>(v);
+    if ((lane & 1) == 0 && j < NA) s_wave[wave][j] = v;
+  }
+  __syncthreads();
+  if (tid < ROWS) {
+    const float r = tid < NA ? ((s_wave[0][tid] + s_wave[1][tid]) + s_wave[2][tid]) + s_wave[3][tid] : 0.f;
+    partial_col[(size_t)tid * kMaxBlocks] = r;
+  }
+}
+
 // a4-a7 of one launch for one alignment, shared by k_iterate3 and the multi-scan chain (k_multi_body3): this
 // workgroup's points (thread -> point assignment i, i + stride, ...; the first point already loaded) under `pose`,
 // per-thread sums, the wave's sums through LDS, one partial row entry per sum at partial_col[row * kMaxBlocks].
@@ -615,7 +647,6 @@ __device__ __forceinline__ void evaluate_block3(const Grid3Dev& G, const SolvePa
                                                 const float* __restrict__ sz, int n, int i, float x, float y, float z,
                                                 float (*s_wave)[kNumAcc3], float* s_t_wave, float* __restrict__ partial_col) {
   constexpr int NA = Acc3<MODE>::kUsed;
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int stride = kMaxBlocks * kBlock;
   Rot3F T;
   make_rot3(pose, T);
@@ -645,33 +676,7 @@ __device__ __forceinline__ void evaluate_block3(const Grid3Dev& G, const SolvePa
     x = xn; y = yn; z = zn; i = inext;
   }
 
-  // the wave's sums through LDS instead of one DPP tree each (wave_reduce11_lds of the 2D path):
-  // park [j][lane] (row stride 66 floats), lane 2j+q adds the 32 values of accumulator j whose
-  // lane index is q mod 2 in two chains, one quad DPP step folds the pair; 32 accumulators per round
-  {
-    float* t = s_t_wave;
-#pragma unroll
-    for (int j = 0; j < NA; ++j) t[j * kSum3RowStride + lane] = acc[j];
-    __builtin_amdgcn_wave_barrier();
-#pragma unroll
-    for (int base = 0; base < NA; base += 32) {
-      const int j = base + (lane >> 1);
-      float a = 0.f, b = 0.f;
-      if (j < NA) {
-        const float* row = t + j * kSum3RowStride + (lane & 1);
-#pragma unroll
-        for (int k = 0; k < 32; k += 2) { a += row[2 * k]; b += row[2 * k + 2]; }
-      }
-      float v = a + b;
-      v += dpp_mov<0xB1, 0xf>(v);
-      if ((lane & 1) == 0 && j < NA) s_wave[wave][j] = v;
-    }
-  }
-  __syncthreads();
-  if (tid < Acc3<MODE>::kRows) {
-    const float r = tid < NA ? ((s_wave[0][tid] + s_wave[1][tid]) + s_wave[2][tid]) + s_wave[3][tid] : 0.f;
-    partial_col[(size_t)tid * kMaxBlocks] = r;
-  }
+  block_reduce3_store<NA, Acc3<MODE>::kRows>(acc, s_t_wave, s_wave, partial_col);
 }
 
 // Per-call part of the context (k_begin of the 2D path).
@@ -695,12 +700,30 @@ __global__ void k_begin3(AlignCall3* __restrict__ call, AlignDyn3* __restrict__ 
   dyn->ls[1] = LineSearch3{};
 }
 
-__device__ __forceinline__ void copy_state3(IterState3* dst, const IterState3* src, int have_partials) {
+__device__ __forceinline__ void copy_state(IterState3* dst, const IterState3* src, int have_partials) {
   const unsigned long long* s8 = reinterpret_cast<const unsigned long long*>(src);
   unsigned long long* d8 = reinterpret_cast<unsigned long long*>(dst);
 #pragma unroll
   for (int j = 0; j < (int)(sizeof(IterState3) / 8); ++j) d8[j] = s8[j];
   if (have_partials >= 0) dst->have_partials = have_partials;
+}
+
+// The state a launch leaves behind, into *o; pad = this launch's index.  MODE 1: the stored rotation block is the full
+// one of A (s_red holds it without the second derivatives).
+template <int MODE>
+__device__ __forceinline__ void store_state3(IterState3* o, const double* pose, const double* g, const double* s_red,
+                                             const double* A, double score, int n_hit, int iter, int status, int done,
+                                             int launch) {
+#pragma unroll
+  for (int j = 0; j < 6; ++j) { o->pose[j] = pose[j]; o->g[j] = g[j]; }
+#pragma unroll
+  for (int j = 0; j < 21; ++j) o->H[j] = s_red[j];
+  if (MODE == 1) {
+    o->H[15] = A[21]; o->H[16] = A[22]; o->H[17] = A[23]; o->H[18] = A[28]; o->H[19] = A[29]; o->H[20] = A[35];
+  }
+  o->score = score;
+  o->n_hit = n_hit; o->iter = iter; o->status = status;
+  o->done = done; o->have_partials = 1; o->pad = launch;
 }
 
 // ---------------------------------------------------------------------------- iterate
@@ -750,10 +773,7 @@ __global__ __launch_bounds__(kBlock) void k_iterate3(const AlignStatic3* __restr
   if (i < n) { x = sx[i]; y = sy[i]; z = sz[i]; }
 
   if (ps_done) {
-    if (writer) {
-      copy_state3(cur, prev, -1);
-      if (host_flag) __hip_atomic_store(host_flag + 2, call->seq, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);   // as k_iterate
-    }
+    if (writer) chain_carry_done(cur, prev, host_flag, call);
     return;
   }
   int iter = ps_iter;
@@ -807,33 +827,14 @@ __global__ __launch_bounds__(kBlock) void k_iterate3(const AlignStatic3* __restr
                                  &dyn->ls[parity], writer);
     if (writer) {
       auto store = [&](IterState3* o) {
-#pragma unroll
-        for (int j = 0; j < 6; ++j) { o->pose[j] = pose[j]; o->g[j] = g[j]; }
-#pragma unroll
-        for (int j = 0; j < 21; ++j) o->H[j] = s_red[j];
-        if (MODE == 1) {                 // the stored rotation block is the full one (s_red holds it without the second derivatives)
-          o->H[15] = A[21]; o->H[16] = A[22]; o->H[17] = A[23]; o->H[18] = A[28]; o->H[19] = A[29]; o->H[20] = A[35];
-        }
-        o->score = score;
-        o->n_hit = n_hit; o->iter = iter; o->status = status;
-        o->done = done ? 1 : 0; o->have_partials = 1; o->pad = ps_launch + 1;   // index of this launch
+        store_state3<MODE>(o, pose, g, s_red, A, score, n_hit, iter, status, done ? 1 : 0, ps_launch + 1);
       };
       store(cur);
-      if (host_flag) {                   // tell the host directly
-        if (done) {                      // state and this launch's number first, then the flag
-          store(host_state);
-          __hip_atomic_store(host_flag + 1, ps_launch + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-          const_cast<AlignCall3*>(call)->n = 0;    // the launches enqueued past the end load no points
-          __threadfence_system();
-          __hip_atomic_store(host_flag, 1, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
-        } else {                         // progress: which launch this is
-          __hip_atomic_store(host_flag + 1, ps_launch + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-        }
-      }
+      chain_announce(store, done, ps_launch + 1, host_state, host_flag, call);
     }
     if (done) return;
   } else if (writer) {
-    copy_state3(cur, prev, 1);
+    copy_state(cur, prev, 1);
   }
 
   evaluate_block3<MODE>(G, prm, pose, sx, sy, sz, n, i, x, y, z, s_wave, s_t[wave], &dyn->partials[parity][0][blockIdx.x]);

@@ -114,21 +114,11 @@ __global__ __launch_bounds__(kBlock) void k_multi_solve3(const AlignStatic3* __r
   }
   if (herald) {
     dyn->launch[parity] = launch;
-    if (host_flag) {
-      if (starts_done != m) {                           // progress, while anything is still running
-        __hip_atomic_store(host_flag + 1, launch, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-      } else if (armed != 0) {                          // every start had finished before this launch: end of the call
-        const_cast<AlignCall3*>(call)->n = 0;           // the launches behind load no points
-        __threadfence_system();
-        __hip_atomic_store(host_flag, 1, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
-      } else {                                          // ... and that launch is complete: the sources are free
-        __hip_atomic_store(host_flag + 2, call->seq, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-      }
-    }
+    if (host_flag) multi_announce(starts_done != m, launch, armed, host_flag, call);
   }
   AlignDynMulti3::Body* bp = &dyn->body[parity][h];
   if (ps_done) {                                        // uniform: a finished start carries its state
-    if (writer) { copy_state3(cur, prev, -1); bp->done = 1; }
+    if (writer) { copy_state(cur, prev, -1); bp->done = 1; }
     return;
   }
   int done = 0;
@@ -156,6 +146,7 @@ __global__ __launch_bounds__(kBlock) void k_multi_solve3(const AlignStatic3* __r
     }
     __syncthreads();
     if (wave == 0) {
+      // 6x6 from the 21 packed sums: Htt(6) Htr(9) Hrr(6)
       double A[36], g[6];
       A[0] = s_red[0]; A[1] = s_red[1]; A[2] = s_red[2]; A[7] = s_red[3]; A[8] = s_red[4]; A[14] = s_red[5];
 #pragma unroll
@@ -177,16 +168,7 @@ __global__ __launch_bounds__(kBlock) void k_multi_solve3(const AlignStatic3* __r
                         writer) ? 1 : 0;
       if (writer) {
         auto store = [&](IterState3* o) {
-#pragma unroll
-          for (int j = 0; j < 6; ++j) { o->pose[j] = pose[j]; o->g[j] = g[j]; }
-#pragma unroll
-          for (int j = 0; j < 21; ++j) o->H[j] = s_red[j];
-          if (MODE == 1) {
-            o->H[15] = A[21]; o->H[16] = A[22]; o->H[17] = A[23]; o->H[18] = A[28]; o->H[19] = A[29]; o->H[20] = A[35];
-          }
-          o->score = score;
-          o->n_hit = n_hit; o->iter = iter; o->status = status;
-          o->done = done; o->have_partials = 1; o->pad = launch;
+          store_state3<MODE>(o, pose, g, s_red, A, score, n_hit, iter, status, done, launch);
         };
         store(cur);
         if (done) {
@@ -196,7 +178,7 @@ __global__ __launch_bounds__(kBlock) void k_multi_solve3(const AlignStatic3* __r
       }
     }
   } else if (writer) {
-    copy_state3(cur, prev, 1);
+    copy_state(cur, prev, 1);
   }
   if (writer) {
 #pragma unroll
