@@ -177,6 +177,10 @@ SIGNATURES = {
                                            C.POINTER(C.c_int32)]),
     "ndt2d_evaluate_map": (C.c_int32, [_vp, _vp, _dp, C.POINTER(Eval2D)]),
     "ndt2d_align_map": (C.c_int32, [_vp, _vp, _dp, C.POINTER(Result2D)]),
+    "ndt2d_search_map": (C.c_int32, [_vp, _vp, C.POINTER(SearchWindow2D), C.c_int32, _vp, C.POINTER(C.c_int32)]),
+    "ndt2d_search_map_scores": (C.c_int32, [_vp, _vp, C.POINTER(SearchWindow2D), _vp]),
+    "ndt2d_search_align_map": (C.c_int32, [_vp, _vp, C.POINTER(SearchWindow2D), C.c_int32, _vp, _vp,
+                                           C.POINTER(C.c_int32)]),
     "ndt2d_get_components": (C.c_int32, [_vp, _vp, _vp, _vp, C.c_int32, C.POINTER(C.c_int32)]),
     "ndt3d_evaluate_map": (C.c_int32, [_vp, _vp, _dp, C.POINTER(Eval3D)]),
     "ndt3d_align_map": (C.c_int32, [_vp, _vp, _dp, C.POINTER(Result3D)]),

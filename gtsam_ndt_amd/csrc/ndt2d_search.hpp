@@ -119,6 +119,17 @@ SearchWindow search_window(const ndt2d_search_window& w) {
   return v;
 }
 
+// the walk's peaks as the ABI's hits
+void search_hits_out(const SearchPeak* peaks, int32_t n, ndt2d_search_hit* hits) {
+  for (int32_t q = 0; q < n; ++q) {
+    ndt2d_search_hit& hh = hits[q];
+    std::memset(&hh, 0, sizeof(hh));
+    for (int a = 0; a < 3; ++a) hh.pose[a] = peaks[q].pose[a];
+    hh.score = peaks[q].score;
+    hh.index = peaks[q].index;
+  }
+}
+
 // The whole search on the handle's stream.  d_scores != null: only the volume, into the caller's buffer; else the hits.
 int32_t search_run(ndt2d_handle* h, const float* d_sx, const float* d_sy, size_t n, const ndt2d_search_window* w2,
                    int32_t k, ndt2d_search_hit* hits, int32_t* n_hits, float* d_scores) {
@@ -149,13 +160,7 @@ int32_t search_run(ndt2d_handle* h, const float* d_sx, const float* d_sy, size_t
   }
   SearchPeak peaks[kMaxStarts];
   { const int32_t ss = search_select(h->srch, h->stream, vol, plan, w, k, peaks, n_hits); if (ss != NDT_OK) return ss; }
-  for (int32_t q = 0; q < *n_hits; ++q) {
-    ndt2d_search_hit& hh = hits[q];
-    std::memset(&hh, 0, sizeof(hh));
-    for (int a = 0; a < 3; ++a) hh.pose[a] = peaks[q].pose[a];
-    hh.score = peaks[q].score;
-    hh.index = peaks[q].index;
-  }
+  search_hits_out(peaks, *n_hits, hits);
   return NDT_OK;
 }
 

@@ -313,6 +313,22 @@ int32_t ndt2d_search_align_dev(ndt2d_handle* h, const float* d_sx, const float* 
  *     the point-to-distribution objective: they are NOT calibrated for this one. */
 int32_t ndt2d_evaluate_map(ndt2d_handle* target, ndt2d_handle* source, const double pose[3], ndt2d_eval* out);
 int32_t ndt2d_align_map(ndt2d_handle* target, ndt2d_handle* source, const double init_pose[3], ndt2d_result* out);
+/* Exhaustive pose search for map-to-map alignment (docs/ALGORITHM.md section 2.15): the score ndt2d_evaluate_map
+ * reports (the same float32 terms per component, summed in another order) at every pose of the window's lattice, then
+ * the best well-separated peaks - a loop closure between two submaps whose relative pose is known to metres and not at
+ * all in heading.  Window, lattice, hits, k in 1..64, the window errors and bitwise determinism are those of
+ * ndt2d_search above; handles, devices, overlap_grids and target == source are as for ndt2d_align_map (d1, d2: the
+ * target handle's).  A source without a component or a target without a valid cell gives an all-zero volume and no
+ * hit.  All three are synchronous: they return once nothing reads the source's component list any more.
+ * ndt2d_search_map_scores writes the volume [n_theta][n_y][n_x] into device memory.  ndt2d_search_align_map refines
+ * every hit with one ndt2d_align_map run, in hit order: results[q] is bit for bit what
+ * ndt2d_align_map(target, source, hits[q].pose) returns (hits and results have room for k). */
+int32_t ndt2d_search_map(ndt2d_handle* target, ndt2d_handle* source, const ndt2d_search_window* w,
+                         int32_t k, ndt2d_search_hit* hits, int32_t* n_hits);
+int32_t ndt2d_search_map_scores(ndt2d_handle* target, ndt2d_handle* source, const ndt2d_search_window* w,
+                                float* d_scores);
+int32_t ndt2d_search_align_map(ndt2d_handle* target, ndt2d_handle* source, const ndt2d_search_window* w,
+                               int32_t k, ndt2d_search_hit* hits, ndt2d_result* results, int32_t* n_hits);
 /* The components of a handle's cached grid, as host copies: mean_xy [2n], cov_abc [3n] = (Sxx, Sxy, Syy), key [n] =
  * iy * width + ix, ascending.  Any pointer may be NULL; *n (if given) is the count, also when capacity is too small
  * for the arrays asked for (NDT_ERR_CAPACITY). */

@@ -265,6 +265,31 @@ class NdtMatcherHip {
     check(ndt2d_evaluate_map(h_, source.h_, p, &e), "ndt2d_evaluate_map");
     return e;
   }
+  // The exhaustive search for this objective (ndt2d_search_map / ndt2d_search_align_map): the map-to-map score at every
+  // pose of the window's lattice, the best k well-separated peaks, and one alignMap run from each - a submap-to-submap
+  // loop closure whose guess is metres off and has no heading.  Window, hits and k as in searchDev.
+  std::vector<SearchHit> searchMap(NdtMatcherHip& source, const ndt2d_search_window& window, int k) {
+    std::vector<ndt2d_search_hit> hits(k > 0 ? (size_t)k : 1);
+    int32_t n_hits = 0;
+    check(ndt2d_search_map(h_, source.h_, &window, (int32_t)k, hits.data(), &n_hits), "ndt2d_search_map");
+    std::vector<SearchHit> out;
+    for (int32_t i = 0; i < n_hits; ++i) out.push_back(to_search_hit(hits[i]));
+    return out;
+  }
+  // the score volume [n_theta][n_y][n_x] itself, into device memory (ndt2d_search_map_scores)
+  void searchMapScores(NdtMatcherHip& source, const ndt2d_search_window& window, float* d_scores) {
+    check(ndt2d_search_map_scores(h_, source.h_, &window, d_scores), "ndt2d_search_map_scores");
+  }
+  // result i is bit for bit what alignMap returns from hit i's pose
+  std::vector<SearchMatch> searchAlignMap(NdtMatcherHip& source, const ndt2d_search_window& window, int k) {
+    std::vector<ndt2d_search_hit> hits(k > 0 ? (size_t)k : 1);
+    std::vector<ndt2d_result> r(hits.size());
+    int32_t n_hits = 0;
+    check(ndt2d_search_align_map(h_, source.h_, &window, (int32_t)k, hits.data(), r.data(), &n_hits), "ndt2d_search_align_map");
+    std::vector<SearchMatch> out;
+    for (int32_t i = 0; i < n_hits; ++i) out.push_back(SearchMatch{to_search_hit(hits[i]), to_match_result(r[i], mode_)});
+    return out;
+  }
   ndt2d_handle* raw() { return h_; }
 
  private:
