@@ -219,6 +219,10 @@ SIGNATURES = {
     "ndt3d_search_scores_dev": (C.c_int32, [_vp, _vp, _vp, _vp, C.c_size_t, C.POINTER(SearchWindow3D), _vp]),
     "ndt3d_search_align_dev": (C.c_int32, [_vp, _vp, _vp, _vp, C.c_size_t, C.POINTER(SearchWindow3D), C.c_int32, _vp, _vp,
                                            C.POINTER(C.c_int32)]),
+    "ndt3d_search_map": (C.c_int32, [_vp, _vp, C.POINTER(SearchWindow3D), C.c_int32, _vp, C.POINTER(C.c_int32)]),
+    "ndt3d_search_map_scores": (C.c_int32, [_vp, _vp, C.POINTER(SearchWindow3D), _vp]),
+    "ndt3d_search_align_map": (C.c_int32, [_vp, _vp, C.POINTER(SearchWindow3D), C.c_int32, _vp, _vp,
+                                           C.POINTER(C.c_int32)]),
     "ndt3d_default_params": (None, [C.POINTER(Params2D)]),
     "ndt3d_create": (C.c_int32, [C.POINTER(Params2D), C.c_int32, C.POINTER(_vp)]),
     "ndt3d_destroy": (C.c_int32, [_vp]),

@@ -153,6 +153,18 @@ int32_t search_lattice3(const ndt3d_search_window* w3, SearchWindow* w, SearchLa
   return search_lattice(*w, L);
 }
 
+// the peaks as the ABI's hits: the searched (x, y, yaw) from the peak, the pinned coordinates from the window's centre
+void search_hits_out3(const SearchPeak* peaks, int32_t n, const ndt3d_search_window& w3, ndt3d_search_hit* hits) {
+  for (int32_t q = 0; q < n; ++q) {
+    ndt3d_search_hit& hh = hits[q];
+    std::memset(&hh, 0, sizeof(hh));
+    hh.pose[0] = peaks[q].pose[0]; hh.pose[1] = peaks[q].pose[1]; hh.pose[5] = peaks[q].pose[2];
+    for (int a = 2; a <= 4; ++a) hh.pose[a] = w3.center[a];
+    hh.score = peaks[q].score;
+    hh.index = peaks[q].index;
+  }
+}
+
 // The whole search on the handle's stream.  d_scores != null: only the volume, into the caller's buffer; else the hits.
 int32_t search_run3(ndt3d_handle* h, const float* d_sx, const float* d_sy, const float* d_sz, size_t n,
                     const ndt3d_search_window* w3, int32_t k, ndt3d_search_hit* hits, int32_t* n_hits, float* d_scores) {
@@ -180,14 +192,7 @@ int32_t search_run3(ndt3d_handle* h, const float* d_sx, const float* d_sy, const
   }
   SearchPeak peaks[kMaxStarts3];
   { const int32_t ss = search_select(h->srch, h->stream, vol, plan, w, k, peaks, n_hits); if (ss != NDT_OK) return ss; }
-  for (int32_t q = 0; q < *n_hits; ++q) {
-    ndt3d_search_hit& hh = hits[q];
-    std::memset(&hh, 0, sizeof(hh));
-    hh.pose[0] = peaks[q].pose[0]; hh.pose[1] = peaks[q].pose[1]; hh.pose[5] = peaks[q].pose[2];
-    for (int a = 2; a <= 4; ++a) hh.pose[a] = w3->center[a];
-    hh.score = peaks[q].score;
-    hh.index = peaks[q].index;
-  }
+  search_hits_out3(peaks, *n_hits, *w3, hits);
   return NDT_OK;
 }
 

@@ -947,6 +947,42 @@ class NdtMatcher3D:
         return [(SearchHit(tuple(h.pose), float(h.score), int(h.index)), self._result(r))
                 for h, r in zip(hits[:nh.value], res[:nh.value])]
 
+    # ---- the same search for map-to-map alignment: `source`'s component list instead of a scan (ndt3d_search_map*)
+    def search_map(self, source: "NdtMatcher3D", center, half_extent, step, k: int = 8, min_sep=(0.5, 0.1)):
+        """The best k (1..64) well-separated peaks of the map-to-map score (evaluate_map's) over the (x, y, yaw) lattice
+        of the window, z, roll and pitch pinned to the centre's (ndt3d_search_map): a list of SearchHit whose poses are
+        6-vectors, best first.  Neither handle needs a point."""
+        w = self._window(center, half_extent, step, min_sep)
+        hits = (L.SearchHit3D * max(int(k), 1))()
+        nh = C.c_int32(0)
+        L.check(self._lib.ndt3d_search_map(self._h, source._h, C.byref(w), int(k), C.cast(hits, C.c_void_p), C.byref(nh)),
+                "ndt3d_search_map")
+        return [SearchHit(tuple(h.pose), float(h.score), int(h.index)) for h in hits[:nh.value]]
+
+    def search_map_scores(self, source: "NdtMatcher3D", center, half_extent, step):
+        """The map-to-map score volume of the window's lattice (ndt3d_search_map_scores): a float32 CUDA tensor
+        [n_yaw, n_y, n_x]."""
+        import torch
+        w = self._window(center, half_extent, step)
+        dims = (C.c_int32 * 3)()
+        L.check(self._lib.ndt3d_search_lattice_size(C.byref(w), C.cast(dims, C.c_void_p)), "ndt3d_search_lattice_size")
+        out = torch.empty(tuple(dims), dtype=torch.float32, device=f"cuda:{self._device}")
+        L.check(self._lib.ndt3d_search_map_scores(self._h, source._h, C.byref(w), C.c_void_p(out.data_ptr())),
+                "ndt3d_search_map_scores")
+        return out
+
+    def search_align_map(self, source: "NdtMatcher3D", center, half_extent, step, k: int = 8, min_sep=(0.5, 0.1)):
+        """search_map(), then align_map() from every hit's pose (ndt3d_search_align_map): a list of
+        (SearchHit, AlignResult3D), best lattice score first."""
+        w = self._window(center, half_extent, step, min_sep)
+        hits = (L.SearchHit3D * max(int(k), 1))()
+        res = (L.Result3D * max(int(k), 1))()
+        nh = C.c_int32(0)
+        L.check(self._lib.ndt3d_search_align_map(self._h, source._h, C.byref(w), int(k), C.cast(hits, C.c_void_p),
+                                                 C.cast(res, C.c_void_p), C.byref(nh)), "ndt3d_search_align_map")
+        return [(SearchHit(tuple(h.pose), float(h.score), int(h.index)), self._result(r))
+                for h, r in zip(hits[:nh.value], res[:nh.value])]
+
     def align_trace(self, sx, sy, sz, init_pose=(0.0,) * 6, capacity: int = 256):
         """Per-iteration trace (ndt3d_align_trace; host arrays): a list of AlignResult3D, entry j = the state
         after j + 1 updates (H, g, score, n_hit of the evaluation behind that update)."""

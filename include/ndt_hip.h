@@ -670,9 +670,25 @@ int32_t ndt3d_align_trace(ndt3d_handle* h, const float* sx, const float* sy, con
  *     (DESIGN.md section 5.9).
  *   - ndt3d_result / ndt3d_eval are those of ndt3d_align / ndt3d_evaluate (n_hit counts components that hit a valid
  *     target voxel).  No covariance calibration exists for this objective.  Not offered: a batched form, pairing with
- *     neighbouring voxels, a search over component lists. */
+ *     neighbouring voxels. */
 int32_t ndt3d_evaluate_map(ndt3d_handle* target, ndt3d_handle* source, const double pose[6], ndt3d_eval* out);
 int32_t ndt3d_align_map(ndt3d_handle* target, ndt3d_handle* source, const double init_pose[6], ndt3d_result* out);
+/* Exhaustive pose search for 3D map-to-map alignment (docs/ALGORITHM.md section 2.16): the score ndt3d_evaluate_map
+ * reports (the same float32 terms per component, summed in another order) at every pose of the window's (x, y, yaw)
+ * lattice, z, roll and pitch pinned to center[2..4], then the best well-separated peaks - a loop closure between two
+ * 3D submaps whose relative pose is known to metres and not at all in heading.  Window, lattice, hits (6-vector
+ * poses), k in 1..64, the window errors and bitwise determinism are those of ndt3d_search above; handles, devices and
+ * target == source are as for ndt3d_align_map (d1, d2: the target handle's).  A source without a component or a target
+ * without a valid voxel gives an all-zero volume and no hit.  All three are synchronous: they return once nothing reads
+ * the source's component list any more.  ndt3d_search_map_scores writes the volume [n_yaw][n_y][n_x] into device
+ * memory.  ndt3d_search_align_map refines every hit with one ndt3d_align_map run, in hit order: results[q] is bit for
+ * bit what ndt3d_align_map(target, source, hits[q].pose) returns (hits and results have room for k). */
+int32_t ndt3d_search_map(ndt3d_handle* target, ndt3d_handle* source, const ndt3d_search_window* w,
+                         int32_t k, ndt3d_search_hit* hits, int32_t* n_hits);
+int32_t ndt3d_search_map_scores(ndt3d_handle* target, ndt3d_handle* source, const ndt3d_search_window* w,
+                                float* d_scores);
+int32_t ndt3d_search_align_map(ndt3d_handle* target, ndt3d_handle* source, const ndt3d_search_window* w,
+                               int32_t k, ndt3d_search_hit* hits, ndt3d_result* results, int32_t* n_hits);
 /* The components of a handle's cached voxel grid, as host copies: mean_xyz [3n], cov6 [6n] = (xx xy xz yy yz zz) of the
  * regularised covariance, key [n] = (iz * height + iy) * width + ix, ascending.  Any pointer may be NULL; *n (if given) is
  * the count, also when capacity is too small for the arrays asked for (NDT_ERR_CAPACITY). */

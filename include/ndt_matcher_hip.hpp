@@ -649,7 +649,7 @@ class NdtMatcherHip3 {
   };
   struct SearchMatch {
     SearchHit hit;
-    MatchResult3 result;   // alignMultiStartDev's result from hit.pose
+    MatchResult3 result;   // alignMultiStartDev's result from hit.pose (searchAlignMap: alignMap's)
   };
   std::vector<SearchHit> searchDev(const float* d_sx, const float* d_sy, const float* d_sz, size_t n,
                                    const ndt3d_search_window& window, int k, void* producer_stream, bool complete = false) {
@@ -706,6 +706,32 @@ class NdtMatcherHip3 {
     ndt3d_eval e;
     check(ndt3d_evaluate_map(h_, source.h_, p, &e), "ndt3d_evaluate_map");
     return e;
+  }
+  // The exhaustive search for this objective (ndt3d_search_map / ndt3d_search_align_map): the map-to-map score at every
+  // pose of the window's (x, y, yaw) lattice, z, roll and pitch the window centre's, the best k well-separated peaks,
+  // and one alignMap run from each - a loop closure between two 3D submaps whose guess is metres off and has no
+  // heading.  Window, hits and k as in searchDev.
+  std::vector<SearchHit> searchMap(NdtMatcherHip3& source, const ndt3d_search_window& window, int k) {
+    std::vector<ndt3d_search_hit> hits(k > 0 ? (size_t)k : 1);
+    int32_t n_hits = 0;
+    check(ndt3d_search_map(h_, source.h_, &window, (int32_t)k, hits.data(), &n_hits), "ndt3d_search_map");
+    std::vector<SearchHit> out;
+    for (int32_t i = 0; i < n_hits; ++i) out.push_back(toSearchHit(hits[i]));
+    return out;
+  }
+  // the score volume [n_yaw][n_y][n_x] itself, into device memory (ndt3d_search_map_scores)
+  void searchMapScores(NdtMatcherHip3& source, const ndt3d_search_window& window, float* d_scores) {
+    check(ndt3d_search_map_scores(h_, source.h_, &window, d_scores), "ndt3d_search_map_scores");
+  }
+  // result i is bit for bit what alignMap returns from hit i's pose
+  std::vector<SearchMatch> searchAlignMap(NdtMatcherHip3& source, const ndt3d_search_window& window, int k) {
+    std::vector<ndt3d_search_hit> hits(k > 0 ? (size_t)k : 1);
+    std::vector<ndt3d_result> r(hits.size());
+    int32_t n_hits = 0;
+    check(ndt3d_search_align_map(h_, source.h_, &window, (int32_t)k, hits.data(), r.data(), &n_hits), "ndt3d_search_align_map");
+    std::vector<SearchMatch> out;
+    for (int32_t i = 0; i < n_hits; ++i) out.push_back(SearchMatch{toSearchHit(hits[i]), toMatchResult(r[i])});
+    return out;
   }
   ndt3d_handle* raw() { return h_; }
   static MatchResult3 toMatchResult(const ndt3d_result& r) {
