@@ -52,6 +52,12 @@ struct ndt2d_handle {
   int* h_flag = nullptr;                   // pinned: [0] raised by the launch that ends a converged-mode loop, [1] progress
   int last_parity = 0;
   bool pending = false;
+  // the second launch chain of asynchronous fixed-iteration calls (ndt_host.hpp: AsyncLane); lane 0 is stream / d_call / d_dyn
+  AsyncLane lane1;
+  AlignCall* d_call1 = nullptr;
+  AlignDyn* d_dyn1 = nullptr;
+  LaneState lanes;
+  int last_lane = 0;                       // the lane whose d_dyn holds the pending state (last_parity)
   // binned grid build scratch (ndt2d_build.hpp)
   float* d_bx = nullptr; float* d_by = nullptr; size_t bcap = 0;
   unsigned int* d_tiles = nullptr; size_t tile_cap = 0;   // total[nt] | start[nt+1] | cursor[nt]
@@ -75,13 +81,12 @@ struct ndt2d_handle {
   int publish_seq = 0;                     // k_build_publish's flag value of the build in flight (small_flag(h_small))
   // hipGraph of the launch chain (launch-bound inner loop: one replay instead of K+1 launches)
   ChainGraphCache graphs;
-  hipGraphExec_t graph_exec = nullptr;     // the one ensure_graph selected last (owned by `graphs`)
+  hipGraphExec_t graph_exec = nullptr;     // the one a map-to-map call selected last (owned by `graphs`)
   AlignDynMulti* d_dyn_multi = nullptr;    // multi-start chains (ndt2d_multi_start.hpp), allocated on first use
   IterState* h_state_multi = nullptr;      // pinned [kMaxStarts]
   int split_from = 12;                     // multi-start / multi-scan calls of this many starts use the split chain (NDT_TUNE_SPLIT_FROM)
   ChunkRun chunk_run;                      // converged-mode loop begun by ndt2d_align_dev_async
   int call_seq = 0;                        // alignments enqueued so far (never 0 once one has run)
-  bool wide = false;                       // this alignment's k_iterate launches use 1024-thread workgroups
   bool small_run = false;                  // a k_align_small launch whose flag has not been waited for
   // execution strategy knobs (ndt2d_set_tuning; results do not depend on them beyond float32 summation order)
   bool use_small = true;                   // short scans run the whole loop in one workgroup (k_align_small)
@@ -584,16 +589,18 @@ auto with_mode(const ndt2d_params& p, F&& f) {
   return p.overlap_grids == 4 ? f(Zero{}, Four{}) : f(Zero{}, One{});
 }
 
-// the k_iterate of this alignment, for graphs (ensure_graph) and plain launches (launch_iter)
-const void* iter_kernel(const ndt2d_handle* h) {
+// the k_iterate of an alignment, for graphs (ensure_graph) and plain launches (launch_iter).  wide: 1024-thread
+// workgroups - a property of the call (its scan size), two calls in flight on the two lanes may differ in it
+const void* iter_kernel(const ndt2d_handle* h, bool wide) {
   return with_mode(h->prm, [&](auto M, auto NG) {
-    return h->wide ? (const void*)&k_iterate<M, 0, kIterThreadsWide, NG> : (const void*)&k_iterate<M, 0, kIterThreads, NG>;
+    return wide ? (const void*)&k_iterate<M, 0, kIterThreadsWide, NG> : (const void*)&k_iterate<M, 0, kIterThreads, NG>;
   });
 }
-int iter_threads(const ndt2d_handle* h) { return h->wide ? kIterThreadsWide : kIterThreads; }
+int iter_threads(bool wide) { return wide ? kIterThreadsWide : kIterThreads; }
+bool is_wide(const ndt2d_handle* h, size_t n) { return h->use_wide && n >= h->wide_threshold; }
 
-void launch_iter(ndt2d_handle* h, int blocks, int k) {
-  (void)launch_chain_kernel(iter_kernel(h), dim3(blocks), dim3(iter_threads(h)), h->d_static, h->d_call, h->d_dyn, k & 1,
+void launch_iter(ndt2d_handle* h, bool wide, int blocks, int k) {
+  (void)launch_chain_kernel(iter_kernel(h, wide), dim3(blocks), dim3(iter_threads(wide)), h->d_static, h->d_call, h->d_dyn, k & 1,
                             h->stream);
 }
 
@@ -604,10 +611,11 @@ void drop_graph(ndt2d_handle* h) {
 
 // Graph of `launches` consecutive k_iterate launches starting at parity 0.  The kernels read
 // everything (grid, source pointers, n, parameters, state) from device memory, so one graph
-// serves every target and every source.
-int32_t ensure_graph(ndt2d_handle* h, int launches, int blocks) {
-  HIP_TRY(h->graphs.get(iter_kernel(h), dim3(blocks), dim3(iter_threads(h)), (void*)h->d_static, (void*)h->d_call,
-                        (void*)h->d_dyn, launches, h->prm.hessian_mode | (h->wide ? 16 : 0), h->stream, &h->graph_exec));
+// serves every target and every source - of its lane: the per-call and dynamic contexts are baked into it.
+int32_t ensure_graph(ndt2d_handle* h, int launches, int blocks, bool wide, int lane, hipGraphExec_t* exec) {
+  HIP_TRY(h->graphs.get(iter_kernel(h, wide), dim3(blocks), dim3(iter_threads(wide)), (void*)h->d_static,
+                        (void*)(lane ? h->d_call1 : h->d_call), (void*)(lane ? h->d_dyn1 : h->d_dyn), launches,
+                        h->prm.hessian_mode | (wide ? 16 : 0), h->stream, exec, lane));
   return NDT_OK;
 }
 
@@ -626,7 +634,8 @@ int32_t finish_small_run(ndt2d_handle* h) {
   return NDT_OK;
 }
 
-int32_t finish_chunk_run(ndt2d_handle* h) {
+// Waits for what the host has to keep fed or listen for (a short-scan launch, a converged-mode loop); both run on lane 0.
+int32_t finish_host_fed(ndt2d_handle* h) {
   { const int32_t fs = finish_small_run(h); if (fs != NDT_OK) return fs; }
   if (!h->chunk_run.active) return NDT_OK;
   bool seen = false;
@@ -635,6 +644,14 @@ int32_t finish_chunk_run(ndt2d_handle* h) {
   if (!seen) { set_error("the Gauss-Newton loop did not report its end"); return NDT_ERR_HIP; }
   h->pending = false;                                  // the finishing launch wrote the result into h_state
   return NDT_OK;
+}
+
+// The head of every entry point that is about to use the handle's stream for something else than an alternating
+// asynchronous alignment.  Lane 1 needs no wait here: the handle's stream was ordered behind its chain when that was
+// enqueued (AsyncLane::leave).  The alternation starts over, so the next asynchronous call forks from a fresh event.
+int32_t finish_chunk_run(ndt2d_handle* h) {
+  (void)lane_step(h->lanes, LaneEvent::kOther);
+  return finish_host_fed(h);
 }
 
 // The result of an alignment against a grid with no valid cell (IterState or IterState3): the initial pose, NDT_TOO_FEW_CELLS
@@ -653,9 +670,10 @@ int32_t run_align(ndt2d_handle* h, const float* d_sx, const float* d_sy, size_t 
                   int fixed_override, int check_every, bool wait = true, bool own_source = false) {
   TraceRange range("ndt2d_align: Gauss-Newton loop");
   if (!h->has_target) return NDT_ERR_NO_TARGET;
-  { const int32_t fs = finish_chunk_run(h); if (fs != NDT_OK) return fs; }     // an unfinished asynchronous call
-  if (n == 0 || n > kMaxSourcePoints || !pose) return NDT_ERR_INVALID_ARG;
+  { const int32_t fs = finish_host_fed(h); if (fs != NDT_OK) return fs; }     // an unfinished asynchronous call
+  if (n == 0 || n > kMaxSourcePoints || !pose) { (void)lane_step(h->lanes, LaneEvent::kOther); return NDT_ERR_INVALID_ARG; }
   if (h->n_valid < 1) {
+    (void)lane_step(h->lanes, LaneEvent::kOther);
     h->pending = false;
     *h->h_state = no_cell_state<IterState>(pose);
     h->h_state->done = 2;               // marks "result already on the host"
@@ -664,10 +682,14 @@ int32_t run_align(ndt2d_handle* h, const float* d_sx, const float* d_sy, size_t 
   const int fixed = fixed_override >= 0 ? fixed_override : h->prm.fixed_iterations;
   const int K = fixed > 0 ? fixed : h->prm.max_iterations;
   const int blocks = blocks_for(n);
-  h->wide = h->use_wide && n >= h->wide_threshold;
+  const bool wide = is_wide(h, n);
   const bool chunked = h->use_graph && check_every > 0 && fixed == 0;
+  const bool small = h->use_small && h->use_graph && n <= (size_t)kSmallMaxPoints;
+  // Only a whole fixed-iteration chain that nobody waits for alternates between the lanes; everything else runs on
+  // lane 0 and starts the alternation over.
+  const LanePlan plan = lane_step(h->lanes, fixed > 0 && h->use_graph && !small && !wait ? LaneEvent::kAsyncFixed : LaneEvent::kOther);
   next_seq(&h->call_seq, h->h_flag);
-  if (h->use_small && h->use_graph && n <= (size_t)kSmallMaxPoints) {
+  if (small) {
     // short scan: the whole loop in one launch of one workgroup (ndt2d_small.hpp)
     const bool lo = n <= (size_t)kSmallLoPoints;
     const void* func = with_mode(h->prm, [&](auto M, auto NG) {
@@ -681,32 +703,39 @@ int32_t run_align(ndt2d_handle* h, const float* d_sx, const float* d_sy, size_t 
     HIP_TRY(hipGetLastError());
     h->small_run = true;
     h->pending = false;
+    h->last_lane = 0;
     return wait ? finish_small_run(h) : NDT_OK;
   }
-  hipLaunchKernelGGL(k_begin, dim3(1), dim3(64), 0, h->stream, h->d_call, h->d_dyn, d_sx, d_sy, (int)n, pose[0], pose[1],
-                     pose[2], fixed, chunked ? h->h_state : (IterState*)nullptr, chunked ? h->h_flag : (int*)nullptr,
-                     h->call_seq);
+  hipStream_t stream = h->stream;
+  if (plan.record_fork) HIP_TRY(h->lane1.mark_fork(h->stream));
+  if (plan.lane == 1) { HIP_TRY(h->lane1.enter()); stream = h->lane1.stream; }
+  hipLaunchKernelGGL(k_begin, dim3(1), dim3(64), 0, stream, plan.lane ? h->d_call1 : h->d_call, plan.lane ? h->d_dyn1 : h->d_dyn,
+                     d_sx, d_sy, (int)n, pose[0], pose[1], pose[2], fixed, chunked ? h->h_state : (IterState*)nullptr,
+                     chunked ? h->h_flag : (int*)nullptr, h->call_seq);
   int k = 0;
+  hipGraphExec_t exec = nullptr;
   if (h->use_graph) {
     if (chunked) {
       // converged mode: chunks of launches until the finishing launch raises the host flag
       const int chunk = check_every + (check_every & 1);
-      const int32_t gs = ensure_graph(h, chunk, blocks);
+      const int32_t gs = ensure_graph(h, chunk, blocks, wide, 0, &exec);
       if (gs != NDT_OK) return gs;
       h->chunk_run.drain = !own_source;                // the handle's own staging arrays outlive the call
       h->chunk_run.seq = h->call_seq;
-      HIP_TRY(chunk_run_begin(h->chunk_run, h->graph_exec, h->stream, chunk, K + 1));
+      HIP_TRY(chunk_run_begin(h->chunk_run, exec, h->stream, chunk, K + 1));
       h->pending = false;
       return wait ? finish_chunk_run(h) : NDT_OK;
     } else {
-      const int32_t gs = ensure_graph(h, K + 1, blocks);
+      // (a lane-1 call that fails here leaves lane 1 behind the fork event and nothing else: harmless)
+      const int32_t gs = ensure_graph(h, K + 1, blocks, wide, plan.lane, &exec);
       if (gs != NDT_OK) return gs;
-      HIP_TRY(hipGraphLaunch(h->graph_exec, h->stream));
+      HIP_TRY(hipGraphLaunch(exec, stream));
+      if (plan.lane == 1) HIP_TRY(h->lane1.leave(h->stream));
       k = K + 1;
     }
   } else {
     for (; k <= K; ++k) {
-      launch_iter(h, blocks, k);
+      launch_iter(h, wide, blocks, k);
       if (check_every > 0 && fixed == 0 && k < K && (k % check_every) == check_every - 1) {
         HIP_TRY(hipGetLastError());
         HIP_TRY(hipMemcpyAsync(h->h_state, &h->d_dyn->state[k & 1], sizeof(IterState), hipMemcpyDeviceToHost,
@@ -718,15 +747,19 @@ int32_t run_align(ndt2d_handle* h, const float* d_sx, const float* d_sy, size_t 
   }
   HIP_TRY(hipGetLastError());
   h->last_parity = (k - 1) & 1;
+  h->last_lane = plan.lane;
   h->h_state->done = 0;
   h->pending = true;
   return NDT_OK;
 }
 
+// The state of the last alignment, from the lane it ran on (the handle's stream is behind both lanes' chains)
 int32_t fetch_state(ndt2d_handle* h) {
-  { const int32_t fs = finish_chunk_run(h); if (fs != NDT_OK) return fs; }
+  { const int32_t fs = finish_host_fed(h); if (fs != NDT_OK) return fs; }
+  (void)lane_step(h->lanes, LaneEvent::kFinish);
   if (h->pending) {
-    HIP_TRY(hipMemcpyAsync(h->h_state, &h->d_dyn->state[h->last_parity], sizeof(IterState),
+    const AlignDyn* dyn = h->last_lane ? h->d_dyn1 : h->d_dyn;
+    HIP_TRY(hipMemcpyAsync(h->h_state, &dyn->state[h->last_parity], sizeof(IterState),
                            hipMemcpyDeviceToHost, h->stream));
     HIP_TRY(hipStreamSynchronize(h->stream));
     h->pending = false;
@@ -910,6 +943,12 @@ int32_t ndt2d_create(const ndt2d_params* p, int32_t device_id, ndt2d_handle** ou
   if (hipEventCreateWithFlags(&h->upload_ev, hipEventDisableTiming) != hipSuccess) return fail(NDT_ERR_HIP);
   if (pinned_alloc(&h->h_small, kSmallBytes) != hipSuccess) return fail(NDT_ERR_ALLOC);
   if (hipMemset(h->d_dyn, 0, sizeof(AlignDyn)) != hipSuccess) return fail(NDT_ERR_HIP);
+  // lane 1 of the asynchronous fixed-iteration calls: allocated here, never inside a call that may be timed
+  if (h->lane1.create() != hipSuccess) return fail(NDT_ERR_HIP);
+  if (hipMalloc((void**)&h->d_call1, sizeof(AlignCall)) != hipSuccess) return fail(NDT_ERR_ALLOC);
+  if (hipMalloc((void**)&h->d_dyn1, sizeof(AlignDyn)) != hipSuccess) return fail(NDT_ERR_ALLOC);
+  if (hipMemset(h->d_dyn1, 0, sizeof(AlignDyn)) != hipSuccess) return fail(NDT_ERR_HIP);
+  h->graphs.lane1 = h->lane1.stream;
   *out = h;
   return NDT_OK;
 }
@@ -919,9 +958,11 @@ int32_t ndt2d_destroy(ndt2d_handle* h) {
   (void)hipSetDevice(h->device);
   (void)finish_chunk_run(h);
   if (h->stream) (void)hipStreamSynchronize(h->stream);
+  h->graphs.lane1 = nullptr;
+  h->lane1.destroy();                       // joins lane 1 first
   drop_graph(h);
   if (h->h_state_multi) (void)hipHostFree(h->h_state_multi);
-  void* dev[] = {h->d_acc2, h->d_split, h->d_bxy, h->d_table, h->d_parts, h->d_geom, h->d_dyn_multi, h->d_bounds, h->d_counters, h->d_outside, h->d_static, h->d_call, h->d_dyn, h->d_bx, h->d_by, h->d_tiles, h->d_tx, h->d_ty, h->d_sx, h->d_sy,
+  void* dev[] = {h->d_acc2, h->d_split, h->d_bxy, h->d_table, h->d_parts, h->d_geom, h->d_dyn_multi, h->d_bounds, h->d_counters, h->d_outside, h->d_static, h->d_call, h->d_dyn, h->d_call1, h->d_dyn1, h->d_bx, h->d_by, h->d_tiles, h->d_tx, h->d_ty, h->d_sx, h->d_sy,
                  h->grid.rec, h->grid.acc, h->d_cov, h->d_blk, h->d_comp, h->d_map_call};
   for (void* p : dev) if (p) (void)hipFree(p);
   void* host[] = {h->h_geom, h->h_static, h->h_state, h->h_small, h->h_flag};
@@ -951,6 +992,7 @@ int32_t ndt2d_set_tuning(ndt2d_handle* h, int32_t knob, int64_t value) {
       h->use_binned_build = value != 0; if (value) h->build_variant = (int)value; return NDT_OK;
     case NDT_TUNE_SPLIT_FROM: if (value < 1 || value > 1000) return NDT_ERR_INVALID_ARG; h->split_from = (int)value; return NDT_OK;
     case NDT_TUNE_SINGLE_SYNC_BUILD: h->one_round_trip = value != 0; return NDT_OK;
+    case NDT_TUNE_ASYNC_LANES: if (value < 1 || value > 2) return NDT_ERR_INVALID_ARG; h->lanes.lanes = (int)value; return NDT_OK;
     default: return NDT_ERR_INVALID_ARG;
   }
 }
@@ -959,6 +1001,9 @@ int32_t ndt2d_wait_stream(ndt2d_handle* h, void* producer_stream) {
   if (!h) return NDT_ERR_INVALID_ARG;
   HIP_TRY(hipSetDevice(h->device));
   HIP_TRY(order_after(h->stream, (hipStream_t)producer_stream, &h->wait_ev));
+  // the next asynchronous call may run on lane 1, which forks from a point of the handle's stream before this wait
+  if (lane_step(h->lanes, LaneEvent::kWaitStream).both_wait && (hipStream_t)producer_stream != h->stream)
+    HIP_TRY(hipStreamWaitEvent(h->lane1.stream, h->wait_ev, 0));
   return NDT_OK;
 }
 
@@ -1106,12 +1151,12 @@ int32_t ndt2d_align_trace(ndt2d_handle* h, const float* sx, const float* sy, siz
   // the launch-per-iteration kernels, one plain launch and one state fetch per iteration
   const int fixed = h->prm.fixed_iterations;
   const int K = fixed > 0 ? fixed : h->prm.max_iterations;
-  h->wide = h->use_wide && n >= h->wide_threshold;
+  const bool wide = is_wide(h, n);
   next_seq(&h->call_seq);
   hipLaunchKernelGGL(k_begin, dim3(1), dim3(64), 0, h->stream, h->d_call, h->d_dyn, h->d_sx, h->d_sy, (int)n, init_pose[0],
                      init_pose[1], init_pose[2], fixed, (IterState*)nullptr, (int*)nullptr, h->call_seq);
   for (int k = 0; k <= K; ++k) {
-    launch_iter(h, blocks_for(n), k);
+    launch_iter(h, wide, blocks_for(n), k);
     HIP_TRY(hipGetLastError());
     if (k == 0) continue;                                  // launch 0 only evaluates
     HIP_TRY(hipMemcpyAsync(h->h_state, &h->d_dyn->state[k & 1], sizeof(IterState), hipMemcpyDeviceToHost, h->stream));

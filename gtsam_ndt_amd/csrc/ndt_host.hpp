@@ -1,7 +1,8 @@
 // Host-side helpers shared by the C-ABI translation units: per-thread error text, the HIP_TRY
 // macro that turns a hipError_t into NDT_ERR_HIP without throwing, buffer growth and pinned
-// allocation, launch-chain graphs and their cache, and the host half of the converged-mode and
-// build read-back protocols (flags in pinned host memory).
+// allocation, launch-chain graphs and their cache, the two launch chains ("lanes") of asynchronous
+// alignments, and the host half of the converged-mode and build read-back protocols (flags in
+// pinned host memory).
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -170,18 +171,20 @@ inline hipError_t build_chain_graph2(const void* fa, dim3 ga, dim3 ba, const voi
 // of rebuilding one on every change.
 struct ChainGraphCache {
   static constexpr int kSlots = 16;
-  struct Slot { int launches = 0, blocks = 0, mode = -1; hipGraph_t graph = nullptr; hipGraphExec_t exec = nullptr; unsigned long stamp = 0; };
+  struct Slot { int launches = 0, blocks = 0, mode = -1, lane = 0; hipGraph_t graph = nullptr; hipGraphExec_t exec = nullptr; unsigned long stamp = 0; };
   Slot slot[kSlots];
   unsigned long clock = 0;
+  hipStream_t lane1 = nullptr;   // the owner's second launch chain (AsyncLane below): replays of lane-1 graphs are queued there
 
-  hipGraphExec_t find(int launches, int blocks, int mode) {
+  // lane: a graph bakes the AlignCall / AlignDyn pointers of its launches, so each launch chain of a handle has its own
+  hipGraphExec_t find(int launches, int blocks, int mode, int lane = 0) {
     for (Slot& s : slot)
-      if (s.exec && s.launches == launches && s.blocks == blocks && s.mode == mode) { s.stamp = ++clock; return s.exec; }
+      if (s.exec && s.launches == launches && s.blocks == blocks && s.mode == mode && s.lane == lane) { s.stamp = ++clock; return s.exec; }
     return nullptr;
   }
   // the slot to build into: an empty one, else the least recently used (destroyed first).  Replays
   // of the evicted exec may still be queued (a converged-mode loop leaves up to two chunks of no-op
-  // launches behind): the owner's stream is drained before the exec is destroyed.
+  // launches behind): the owner's stream (and its second lane) is drained before the exec is destroyed.
   Slot* victim(hipStream_t stream) {
     Slot* v = &slot[0];
     for (Slot& s : slot) {
@@ -189,6 +192,7 @@ struct ChainGraphCache {
       if (s.stamp < v->stamp) v = &s;
     }
     if (v->exec) (void)hipStreamSynchronize(stream);
+    if (v->exec && lane1) (void)hipStreamSynchronize(lane1);
     release(*v);
     return v;
   }
@@ -199,12 +203,12 @@ struct ChainGraphCache {
   }
   void clear() { for (Slot& s : slot) release(s); }
   hipError_t get(const void* func, dim3 grid, dim3 block, void* a0, void* a1, void* a2, int launches, int mode,
-                 hipStream_t stream, hipGraphExec_t* out) {
-    if (hipGraphExec_t e = find(launches, (int)grid.x, mode)) { *out = e; return hipSuccess; }
+                 hipStream_t stream, hipGraphExec_t* out, int lane = 0) {
+    if (hipGraphExec_t e = find(launches, (int)grid.x, mode, lane)) { *out = e; return hipSuccess; }
     Slot* s = victim(stream);
     const hipError_t err = build_chain_graph(func, grid, block, a0, a1, a2, launches, &s->graph, &s->exec);
     if (err != hipSuccess) { *s = Slot{}; return err; }
-    s->launches = launches; s->blocks = (int)grid.x; s->mode = mode; s->stamp = ++clock;
+    s->launches = launches; s->blocks = (int)grid.x; s->mode = mode; s->lane = lane; s->stamp = ++clock;
     *out = s->exec;
     return hipSuccess;
   }
@@ -218,6 +222,85 @@ struct ChainGraphCache {
     s->launches = steps; s->blocks = (int)ga.x; s->mode = mode; s->stamp = ++clock;
     *out = s->exec;
     return hipSuccess;
+  }
+};
+
+// ---- two launch chains per handle --------------------------------------------------------------------------------
+// Successive asynchronous fixed-iteration alignments on a handle are independent of one another (own scan, own initial
+// pose, the same read-only grid), and one launch chain leaves the chip idle for most of every launch.  So
+// such calls alternate between two "lanes": lane 0 is the handle's stream and device context, lane 1 a second stream
+// with a context of its own.  Calls overlap in pairs; the handle's stream stays ordered behind all of them:
+//   lane-0 call  record `fork` on the handle's stream, then enqueue the chain there
+//   lane-1 call  lane 1 waits for `fork` (everything before the lane-0 call, not its chain), enqueue the chain on
+//                lane 1, record `done` there, the handle's stream waits for `done`
+// Anything else that happens on the handle in between (another kind of call, a new target, a tuning change, finish)
+// starts the alternation over at lane 0, so a lane-1 call only ever follows its lane-0 partner directly and `fork` is
+// never stale.  ndt*_wait_stream is the exception: it orders both lanes behind the producer and keeps the pairing.
+
+enum class LaneEvent {
+  kAsyncFixed,   // an asynchronous call on the fixed-iteration graph path: the kind that alternates
+  kWaitStream,   // ndt*_wait_stream
+  kOther,        // any other entry point that uses the handle's stream (synchronous calls, converged mode, builds, tuning)
+  kFinish        // ndt*_align_finish: both lanes idle afterwards
+};
+
+struct LaneState {
+  int lanes = 2;        // NDT_TUNE_ASYNC_LANES: 1 = everything on lane 0, as a handle without lanes
+  int next = 0;         // the lane of the next alternating call
+};
+
+struct LanePlan {
+  int lane = 0;              // where this call's chain goes
+  bool record_fork = false;  // lane-0 call that may get a partner: record the fork event at its head
+  bool both_wait = false;    // kWaitStream: lane 1 waits for the producer too
+};
+
+// What an event on the handle does, and the state after it.  Pure: the only place the pairing rule lives.
+inline LanePlan lane_step(LaneState& s, LaneEvent ev) {
+  LanePlan p;
+  if (s.lanes < 2) { s.next = 0; return p; }
+  switch (ev) {
+    case LaneEvent::kAsyncFixed:
+      p.lane = s.next;
+      p.record_fork = s.next == 0;
+      s.next ^= 1;
+      break;
+    case LaneEvent::kWaitStream:
+      p.both_wait = true;
+      break;
+    case LaneEvent::kOther:
+    case LaneEvent::kFinish:
+      s.next = 0;
+      break;
+  }
+  return p;
+}
+
+// The stream and events of lane 1 (created with the handle, never inside a call that may be timed)
+struct AsyncLane {
+  hipStream_t stream = nullptr;
+  hipEvent_t fork = nullptr, done = nullptr;
+  hipError_t create() {
+    hipError_t e = hipStreamCreateWithFlags(&stream, hipStreamNonBlocking);
+    if (e == hipSuccess) e = hipEventCreateWithFlags(&fork, hipEventDisableTiming);
+    if (e == hipSuccess) e = hipEventCreateWithFlags(&done, hipEventDisableTiming);
+    return e;
+  }
+  void destroy() {
+    if (stream) (void)hipStreamSynchronize(stream);
+    if (fork) (void)hipEventDestroy(fork);
+    if (done) (void)hipEventDestroy(done);
+    if (stream) (void)hipStreamDestroy(stream);
+    *this = AsyncLane{};
+  }
+  // head of a lane-0 call
+  hipError_t mark_fork(hipStream_t main) { return hipEventRecord(fork, main); }
+  // head of a lane-1 call: behind everything that preceded its lane-0 partner
+  hipError_t enter() { return hipStreamWaitEvent(stream, fork, 0); }
+  // tail of a lane-1 call: the handle's stream is ordered behind this chain
+  hipError_t leave(hipStream_t main) {
+    const hipError_t e = hipEventRecord(done, stream);
+    return e == hipSuccess ? hipStreamWaitEvent(main, done, 0) : e;
   }
 };
 

@@ -213,7 +213,14 @@ int32_t ndt2d_align_dev(ndt2d_handle* h, const float* d_sx, const float* d_sy, s
  * handle's stream; ndt2d_align_finish() waits and fetches.  With fixed_iterations > 0 the whole
  * loop is enqueued here; in converged mode the first launches are enqueued here and
  * ndt2d_align_finish() keeps the loop fed until it converges, so the d_sx / d_sy buffers must
- * stay valid until it returns (any other call on the handle finishes a loop in flight first). */
+ * stay valid until it returns (any other call on the handle finishes a loop in flight first).
+ * Pipelining: consecutive fixed-iteration calls (scans above the short-scan limit, launch graphs on) may run
+ * concurrently, two at a time: the handle alternates them between two launch chains, so that the second call of a
+ * pair fills the launch gaps of the first (NDT_TUNE_ASYNC_LANES; 1 = one chain, calls run one after the other).
+ * Each alignment stays what it is - own scan, own initial pose, bit-identical result; ndt2d_align_finish returns
+ * the last call's result.  Every call's source arrays must stay valid until ndt2d_align_finish returns.
+ * Stream contract: when this function returns, ndt2d_stream(h) is ordered behind this alignment and all earlier
+ * ones, so an event recorded there afterwards covers them. */
 int32_t ndt2d_align_dev_async(ndt2d_handle* h, const float* d_sx, const float* d_sy, size_t n,
                               const double init_pose[3]);
 int32_t ndt2d_align_finish(ndt2d_handle* h, ndt2d_result* out);
@@ -350,6 +357,10 @@ int32_t ndt2d_get_components(ndt2d_handle* h, float* mean_xy, float* cov_abc, in
  *                               geometry on the device and enqueues the whole build at once (one host round trip;
  *                               it falls back by itself when the new grid does not fit the cached storage).
  *                               0: bounding box to the host first, then the build (two round trips)
+ *   NDT_TUNE_ASYNC_LANES        2 (default): consecutive fixed-iteration ndt2d_align_dev_async calls overlap in pairs on
+ *                               two streams of the handle; 1: one stream, one call after the other (for a caller that
+ *                               shares the GPU and wants one queue).  Other values: NDT_ERR_INVALID_ARG.  Results are
+ *                               bit-identical either way
  *   NDT_TUNE_BATCH_SMALL_VARIANT (batch contexts) 1 (default): lidar-sized pairs run on the 256-thread
  *                               variant of the batch kernel first; 0: every pair on the 1024-thread one
  *   NDT_TUNE_BATCH_GLOBAL_WORKGROUPS (batch contexts, 2D and 3D) workgroups of the global-table variant, each with its own
@@ -369,7 +380,8 @@ enum {
   /* 7: was the one-XCD team kernel of round 2 (measured slower than the default, moved to tools/experiments) */
   NDT_TUNE_SPLIT_FROM = 8,
   NDT_TUNE_SINGLE_SYNC_BUILD = 9,
-  NDT_TUNE_BATCH_GLOBAL_WORKGROUPS = 10
+  NDT_TUNE_BATCH_GLOBAL_WORKGROUPS = 10,
+  NDT_TUNE_ASYNC_LANES = 11
 };
 int32_t ndt2d_set_tuning(ndt2d_handle* h, int32_t knob, int64_t value);
 /* hipStream_t the handle enqueues on (as void*), for event timing by the caller */
