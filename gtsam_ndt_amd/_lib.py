@@ -29,7 +29,7 @@ NDT_ERR_RCCL = -7
 # ndt2d_set_tuning / ndt2d_batch_set_tuning knobs
 TUNING = {"launch_graphs": 1, "wide_threshold": 2, "short_scan_kernel": 3, "chunk_launches": 4, "binned_build": 5,
           "batch_small_variant": 6, "split_from": 8, "single_sync_build": 9,
-          "batch_global_workgroups": 10, "async_lanes": 11}
+          "batch_global_workgroups": 10, "async_lanes": 11, "map_multi_from": 12}
 
 HESSIAN_GAUSS_NEWTON = 0
 HESSIAN_NEWTON = 1
@@ -177,6 +177,7 @@ SIGNATURES = {
                                            C.POINTER(C.c_int32)]),
     "ndt2d_evaluate_map": (C.c_int32, [_vp, _vp, _dp, C.POINTER(Eval2D)]),
     "ndt2d_align_map": (C.c_int32, [_vp, _vp, _dp, C.POINTER(Result2D)]),
+    "ndt2d_align_map_multi": (C.c_int32, [_vp, _vp, _vp, C.c_int32, _vp]),
     "ndt2d_search_map": (C.c_int32, [_vp, _vp, C.POINTER(SearchWindow2D), C.c_int32, _vp, C.POINTER(C.c_int32)]),
     "ndt2d_search_map_scores": (C.c_int32, [_vp, _vp, C.POINTER(SearchWindow2D), _vp]),
     "ndt2d_search_align_map": (C.c_int32, [_vp, _vp, C.POINTER(SearchWindow2D), C.c_int32, _vp, _vp,

@@ -17,6 +17,7 @@
 #include "ndt2d_build_sorted.hpp"
 #include "ndt2d_multi_start.hpp"
 #include "ndt2d_d2d.hpp"
+#include "ndt2d_d2d_multi.hpp"
 #include "ndt_host.hpp"
 #include "ndt_search.hpp"
 
@@ -103,6 +104,7 @@ struct ndt2d_handle {
   bool cov_valid = false, comp_valid = false;
   MapCall* d_map_call = nullptr;                          // per-call context of k_iterate_d2d (this handle as the target)
   hipEvent_t map_ev = nullptr;                            // orders a target handle's stream behind this handle's (order_after)
+  int map_multi_from = 2;                                 // ndt2d_align_map_multi calls of this many starts use one chain (NDT_TUNE_MAP_MULTI_FROM)
 };
 
 namespace {
@@ -993,6 +995,7 @@ int32_t ndt2d_set_tuning(ndt2d_handle* h, int32_t knob, int64_t value) {
     case NDT_TUNE_SPLIT_FROM: if (value < 1 || value > 1000) return NDT_ERR_INVALID_ARG; h->split_from = (int)value; return NDT_OK;
     case NDT_TUNE_SINGLE_SYNC_BUILD: h->one_round_trip = value != 0; return NDT_OK;
     case NDT_TUNE_ASYNC_LANES: if (value < 1 || value > 2) return NDT_ERR_INVALID_ARG; h->lanes.lanes = (int)value; return NDT_OK;
+    case NDT_TUNE_MAP_MULTI_FROM: if (value < 1 || value > kMaxStarts + 1) return NDT_ERR_INVALID_ARG; h->map_multi_from = (int)value; return NDT_OK;
     default: return NDT_ERR_INVALID_ARG;
   }
 }

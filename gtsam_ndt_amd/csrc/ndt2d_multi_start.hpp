@@ -37,6 +37,10 @@ struct AlignDynMulti {
   struct BodyPose { float cs, sn, tx, ty; int done; int pad[3]; } posef[2][kMaxStarts];
   int starts_done;
   int pad2[3];
+  // map-to-map chains (ndt2d_d2d_multi.hpp): every start has its own component list; `blocks` = the workgroups its single
+  // alignment launches (the rows of its partial table in use); one array of covariance records, the target handle's
+  struct MapStart { const float4* comp; int n; int blocks; } map[kMaxStarts];
+  const float4* map_cov;
 };
 
 struct StartPoses {

@@ -444,6 +444,35 @@ inline hipError_t run_multi_chain(hipGraphExec_t exec, hipStream_t stream, int* 
   return e;
 }
 
+// ---- the plan of a call that carries several map-to-map alignments (ndt2d_align_map_multi) --------------------------
+// Pure host functions: tests/cpp/d2d_multi_host_test.cpp walks them without a device.
+
+// Workgroups of `threads` threads for n items, at most `cap` (a map-to-map launch: one component per lane, kMaxBlocks rows)
+inline int capped_blocks(long long n, int threads, int cap) {
+  const long long b = (n + threads - 1) / threads;
+  return (int)(b < cap ? b : cap);
+}
+
+// The smallest power of two >= v (v >= 1): launch shapes in powers of two keep the number of cached graphs small
+inline int pow2_at_least(int v) {
+  int p = 1;
+  while (p < v) p <<= 1;
+  return p;
+}
+
+// The distinct pointers of in[0 .. m), in the order of their first occurrence, into out (room for m); returns their number.
+// A caller's list of source handles may name one handle many times (a multi-start): its derived data is prepared once.
+template <class T>
+inline int distinct_pointers(T* const* in, int m, T** out) {
+  int n = 0;
+  for (int k = 0; k < m; ++k) {
+    bool seen = false;
+    for (int j = 0; j < n && !seen; ++j) seen = out[j] == in[k];
+    if (!seen) out[n++] = in[k];
+  }
+  return n;
+}
+
 // The pinned 256-byte block of a handle (h_small): counter shards at 0, the outside count at 128, the flag of a build's
 // read-back (publish_and_wait) at byte kSmallFlagByte.
 constexpr size_t kSmallBytes = 256, kSmallFlagByte = 192;

@@ -233,6 +233,22 @@ class NdtMatcher2D:
         L.check(self._lib.ndt2d_align_map(self._h, source._h, p, C.byref(r)), "ndt2d_align_map")
         return _to_result(r)
 
+    def align_map_multi(self, sources, init_poses):
+        """Up to 64 map-to-map alignments against this handle's grid in one launch chain (ndt2d_align_map_multi).
+        sources: one matcher (a multi-start: every pose starts that matcher's map) or a sequence of matchers, one per
+        pose; a matcher may repeat and may be this one.  Returns a list of AlignResult, entry k bit for bit what
+        align_map(sources[k], init_poses[k]) returns."""
+        poses = np.ascontiguousarray(init_poses, dtype=np.float64).reshape(-1, 3)
+        m = poses.shape[0]
+        srcs = [sources] * m if isinstance(sources, NdtMatcher2D) else list(sources)
+        if len(srcs) != m:
+            raise ValueError(f"{len(srcs)} sources for {m} initial poses")
+        hs = (C.c_void_p * max(m, 1))(*[s._h.value for s in srcs])
+        out = (L.Result2D * max(m, 1))()
+        L.check(self._lib.ndt2d_align_map_multi(self._h, hs, poses.ctypes.data, m, C.cast(out, C.c_void_p)),
+                "ndt2d_align_map_multi")
+        return [_to_result(r) for r in out[:m]]
+
     def evaluate_map(self, source: "NdtMatcher2D", pose):
         """(H, g, score, n_hit) of the map-to-map objective at `pose` (ndt2d_evaluate_map)."""
         p = (C.c_double * 3)(*[float(v) for v in pose])

@@ -320,6 +320,22 @@ int32_t ndt2d_search_align_dev(ndt2d_handle* h, const float* d_sx, const float* 
  *     the point-to-distribution objective: they are NOT calibrated for this one. */
 int32_t ndt2d_evaluate_map(ndt2d_handle* target, ndt2d_handle* source, const double pose[3], ndt2d_eval* out);
 int32_t ndt2d_align_map(ndt2d_handle* target, ndt2d_handle* source, const double init_pose[3], ndt2d_result* out);
+/* m (1..64) map-to-map alignments against ONE target in one launch chain: start k aligns sources[k] from
+ * init_poses[3k .. 3k+2].  The same handle m times is a multi-start (a loop closure with a poor guess); different
+ * handles are several submaps relocalised against one older submap; sources[k] may be `target`.
+ *   - results[k] is bit for bit what ndt2d_align_map(target, sources[k], &init_poses[3k], ...) returns, whatever
+ *     hessian_mode, fixed or converged mode, max_iterations, step_scale, line_search and the tuning knobs are; a start
+ *     that has finished is frozen while the others go on.
+ *   - The target handle's parameters, stream and tuning drive the call, as for ndt2d_align_map.  Synchronous: it
+ *     returns once nothing reads any source's component list any more.
+ *   - Errors of the whole call, found before anything is enqueued (the handles stay usable): a null pointer, a null
+ *     entry of sources, m outside 1..64 (these three before any device call), a non-finite pose, overlap_grids = 4 on
+ *     any handle, handles on different devices: NDT_ERR_INVALID_ARG; a handle without a grid: NDT_ERR_NO_TARGET.
+ *   - Inside an NDT_OK call: a source without a component gives ITS start status NDT_TOO_FEW_CELLS and its initial
+ *     pose while the others run; a target without a valid cell gives that to every start.
+ * Pairs with different targets are not covered (one call per target), and there is no 3D twin. */
+int32_t ndt2d_align_map_multi(ndt2d_handle* target, ndt2d_handle* const* sources, const double* init_poses /* [m][3] */,
+                              int32_t m, ndt2d_result* results /* [m] */);
 /* Exhaustive pose search for map-to-map alignment (docs/ALGORITHM.md section 2.15): the score ndt2d_evaluate_map
  * reports (the same float32 terms per component, summed in another order) at every pose of the window's lattice, then
  * the best well-separated peaks - a loop closure between two submaps whose relative pose is known to metres and not at
@@ -328,7 +344,7 @@ int32_t ndt2d_align_map(ndt2d_handle* target, ndt2d_handle* source, const double
  * target handle's).  A source without a component or a target without a valid cell gives an all-zero volume and no
  * hit.  All three are synchronous: they return once nothing reads the source's component list any more.
  * ndt2d_search_map_scores writes the volume [n_theta][n_y][n_x] into device memory.  ndt2d_search_align_map refines
- * every hit with one ndt2d_align_map run, in hit order: results[q] is bit for bit what
+ * all hits in one ndt2d_align_map_multi call (nothing is launched for zero hits): results[q] is bit for bit what
  * ndt2d_align_map(target, source, hits[q].pose) returns (hits and results have room for k). */
 int32_t ndt2d_search_map(ndt2d_handle* target, ndt2d_handle* source, const ndt2d_search_window* w,
                          int32_t k, ndt2d_search_hit* hits, int32_t* n_hits);
@@ -361,6 +377,9 @@ int32_t ndt2d_get_components(ndt2d_handle* h, float* mean_xy, float* cov_abc, in
  *                               two streams of the handle; 1: one stream, one call after the other (for a caller that
  *                               shares the GPU and wants one queue).  Other values: NDT_ERR_INVALID_ARG.  Results are
  *                               bit-identical either way
+ *   NDT_TUNE_MAP_MULTI_FROM     ndt2d_align_map_multi calls of at least this many starts run one launch chain for all
+ *                               starts; smaller calls run one ndt2d_align_map chain per start (default 2; 1..65, 65:
+ *                               never the shared chain).  Results are bit-identical either way
  *   NDT_TUNE_BATCH_SMALL_VARIANT (batch contexts) 1 (default): lidar-sized pairs run on the 256-thread
  *                               variant of the batch kernel first; 0: every pair on the 1024-thread one
  *   NDT_TUNE_BATCH_GLOBAL_WORKGROUPS (batch contexts, 2D and 3D) workgroups of the global-table variant, each with its own
@@ -381,7 +400,8 @@ enum {
   NDT_TUNE_SPLIT_FROM = 8,
   NDT_TUNE_SINGLE_SYNC_BUILD = 9,
   NDT_TUNE_BATCH_GLOBAL_WORKGROUPS = 10,
-  NDT_TUNE_ASYNC_LANES = 11
+  NDT_TUNE_ASYNC_LANES = 11,
+  NDT_TUNE_MAP_MULTI_FROM = 12
 };
 int32_t ndt2d_set_tuning(ndt2d_handle* h, int32_t knob, int64_t value);
 /* hipStream_t the handle enqueues on (as void*), for event timing by the caller */

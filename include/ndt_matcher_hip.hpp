@@ -259,6 +259,23 @@ class NdtMatcherHip {
     check(ndt2d_align_map(h_, source.h_, init, &r), "ndt2d_align_map");
     return to_match_result(r, mode_);
   }
+  // Up to 64 map-to-map alignments against this matcher's grid in one launch chain (ndt2d_align_map_multi): start k
+  // aligns *sources[k] from guesses[k].  The same matcher in every entry is a multi-start; an entry may be this matcher.
+  // Result k is bit for bit what alignMap(*sources[k], guesses[k]) returns.
+  std::vector<MatchResult> alignMapMulti(const std::vector<NdtMatcherHip*>& sources, const std::vector<Pose2>& guesses) {
+    if (sources.size() != guesses.size()) throw NdtError(NDT_ERR_INVALID_ARG, "alignMapMulti: one guess per source");
+    std::vector<ndt2d_handle*> hs;
+    std::vector<double> init;
+    for (size_t k = 0; k < sources.size(); ++k) {
+      hs.push_back(sources[k] ? sources[k]->h_ : nullptr);
+      init.insert(init.end(), {guesses[k].x, guesses[k].y, guesses[k].theta});
+    }
+    std::vector<ndt2d_result> r(hs.size());
+    check(ndt2d_align_map_multi(h_, hs.data(), init.data(), (int32_t)hs.size(), r.data()), "ndt2d_align_map_multi");
+    std::vector<MatchResult> out;
+    for (const ndt2d_result& x : r) out.push_back(to_match_result(x, mode_));
+    return out;
+  }
   ndt2d_eval evaluateMap(NdtMatcherHip& source, const Pose2& at) {
     const double p[3] = {at.x, at.y, at.theta};
     ndt2d_eval e;
