@@ -185,6 +185,7 @@ SIGNATURES = {
     "ndt2d_get_components": (C.c_int32, [_vp, _vp, _vp, _vp, C.c_int32, C.POINTER(C.c_int32)]),
     "ndt3d_evaluate_map": (C.c_int32, [_vp, _vp, _dp, C.POINTER(Eval3D)]),
     "ndt3d_align_map": (C.c_int32, [_vp, _vp, _dp, C.POINTER(Result3D)]),
+    "ndt3d_align_map_multi": (C.c_int32, [_vp, _vp, _vp, C.c_int32, _vp]),
     "ndt3d_get_components": (C.c_int32, [_vp, _vp, _vp, _vp, C.c_int32, C.POINTER(C.c_int32)]),
     "ndt2d_stream": (_vp, [_vp]),
     "ndt2d_set_tuning": (C.c_int32, [_vp, C.c_int32, C.c_int64]),

@@ -6,6 +6,7 @@
 #include "ndt3d_build.hpp"
 #include "ndt3d_multi.hpp"
 #include "ndt3d_d2d.hpp"
+#include "ndt3d_d2d_multi.hpp"
 
 // h_pub3, the pinned read-back of a single-sync build: the accumulator block's first 64 words, then the flag
 constexpr int kPub3FlagWord = 64, kPub3Words = kPub3FlagWord + 16;
@@ -57,6 +58,7 @@ struct ndt3d_handle {
   int n_comp = 0;
   bool cov_valid = false, comp_valid = false;
   ndt::MapCall3* d_map_call = nullptr;
+  int map_multi_from = 2;                                 // ndt3d_align_map_multi calls of this many starts use one chain (NDT_TUNE_MAP_MULTI_FROM)
   hipEvent_t map_ev = nullptr;                            // orders a target handle's stream behind this handle's (order_after)
 };
 
@@ -563,9 +565,12 @@ int32_t ndt3d_destroy(ndt3d_handle* h) {
 }
 
 int32_t ndt3d_set_tuning(ndt3d_handle* h, int32_t knob, int64_t value) {
-  if (!h || knob != NDT_TUNE_SINGLE_SYNC_BUILD) return NDT_ERR_INVALID_ARG;
-  h->one_round_trip = value != 0;
-  return NDT_OK;
+  if (!h) return NDT_ERR_INVALID_ARG;
+  switch (knob) {
+    case NDT_TUNE_SINGLE_SYNC_BUILD: h->one_round_trip = value != 0; return NDT_OK;
+    case NDT_TUNE_MAP_MULTI_FROM: if (value < 1 || value > ndt::kMaxStarts3 + 1) return NDT_ERR_INVALID_ARG; h->map_multi_from = (int)value; return NDT_OK;
+    default: return NDT_ERR_INVALID_ARG;
+  }
 }
 
 int32_t ndt3d_wait_stream(ndt3d_handle* h, void* producer_stream) {

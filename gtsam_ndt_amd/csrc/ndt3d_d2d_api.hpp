@@ -8,6 +8,9 @@
 namespace {
 
 constexpr int kMapGraphKey3 = 0x2000000;     // ChainGraphCache key of the k_iterate_d2d3 chains (| hessian_mode)
+// ... and of the k_multi_solve3<0> + k_multi_body_d2d3 chains (| the body's grid width << 8 | hessian_mode; the solve's
+// grid is the `blocks` of the key).  Bit 27: multi_align3's keys are 0x100000 | up to 64 << 8
+constexpr int kMapMultiGraphKey3 = 0x8000000;
 
 int32_t ensure_cov_records3(ndt3d_handle* h) {
   using namespace ndt;
@@ -106,9 +109,91 @@ int32_t run_align_map3(ndt3d_handle* t, ndt3d_handle* s, const double pose[6], i
   return finish_align3(t);              // synchronous: nothing reads the source's list once this returns
 }
 
+// m map-to-map alignments against t's grid, start k from sources[k]'s component list and init_poses[6k] (no entry of
+// sources is null, 1 <= m <= kMaxStarts3): the split chain of multi_align3 with k_multi_body_d2d3 as its evaluation, on
+// t's stream, context and graph cache.  Everything is checked before anything is enqueued; returns once t's stream has
+// drained or the chain has said that nothing reads a component list any more.
+int32_t run_align_map_multi3(ndt3d_handle* t, ndt3d_handle* const* sources, const double* init_poses, int32_t m, ndt3d_result* results) {
+  using namespace ndt;
+  TraceRange range("ndt3d_align_map_multi");
+  ndt3d_handle* distinct[kMaxStarts3];
+  const int nd = distinct_pointers(sources, m, distinct);
+  if (!t->has_target) return NDT_ERR_NO_TARGET;
+  for (int j = 0; j < nd; ++j) if (!distinct[j]->has_target) return NDT_ERR_NO_TARGET;
+  for (int j = 0; j < nd; ++j)
+    if (distinct[j]->device != t->device) { set_error("map-to-map alignment: all handles must live on one device"); return NDT_ERR_INVALID_ARG; }
+  for (int k = 0; k < 6 * m; ++k) if (!std::isfinite(init_poses[k])) return NDT_ERR_INVALID_ARG;
+  if (m < t->map_multi_from) {             // few starts: one single chain after the other costs less than the launch pairs
+    for (int k = 0; k < m; ++k) {
+      const int32_t st = run_align_map3(t, sources[k], &init_poses[6 * k], -1);
+      if (st != NDT_OK) return st;
+      state3_to(*t->h_state, &results[k]);
+    }
+    return NDT_OK;
+  }
+  HIP_TRY(hipSetDevice(t->device));
+  { const int32_t fs = finish_align3(t); if (fs != NDT_OK) return fs; }
+  for (int j = 0; j < nd; ++j)
+    if (distinct[j] != t) { const int32_t fs = finish_align3(distinct[j]); if (fs != NDT_OK) return fs; }
+  for (int j = 0; j < nd; ++j) { const int32_t cs = ensure_components3(distinct[j]); if (cs != NDT_OK) return cs; }
+  { const int32_t cs = ensure_cov_records3(t); if (cs != NDT_OK) return cs; }
+  // starts whose source has no component (all of them, if the target has no valid voxel) are answered here
+  StartPoses3 sp{};
+  StartMaps3 sm{};
+  int live = 0, max_blocks = 1;
+  for (int k = 0; k < m; ++k) {
+    for (int j = 0; j < 6; ++j) sp.p[k][j] = init_poses[6 * k + j];
+    const int n = t->n_valid < 1 ? 0 : sources[k]->n_comp;
+    if (n < 1) { state3_to(no_cell_state<IterState3>(&init_poses[6 * k]), &results[k]); continue; }
+    sm.comp[k] = sources[k]->d_comp;
+    sm.n[k] = n;
+    sm.blocks[k] = capped_blocks(n, kBlock, kMaxBlocks);
+    max_blocks = sm.blocks[k] > max_blocks ? sm.blocks[k] : max_blocks;
+    ++live;
+  }
+  if (live == 0) return NDT_OK;
+  for (int j = 0; j < nd; ++j)             // a list may still be in flight on its handle's stream
+    if (distinct[j] != t) HIP_TRY(order_after(t->stream, distinct[j]->stream, &distinct[j]->map_ev));
+  HIP_TRY(ensure_multi_chain(&t->h_state_multi, kMaxStarts3, &t->d_dyn_multi, t->stream));
+  const int fixed = t->prm.fixed_iterations;
+  const int K = fixed > 0 ? fixed : t->prm.max_iterations;
+  const bool converged_mode = fixed == 0;
+  next_seq(&t->call_seq, t->h_flag);
+  hipLaunchKernelGGL(k_begin_d2d_multi3_maps, dim3(kMaxStarts3), dim3(kBlock), 0, t->stream, t->d_dyn_multi, sm, (int)m);
+  hipLaunchKernelGGL(k_begin_d2d_multi3, dim3(1), dim3(64), 0, t->stream, t->d_call, t->d_dyn_multi, (const float4*)t->d_cov, sp,
+                     (int)m, fixed, converged_mode ? t->h_state_multi : (IterState3*)nullptr,
+                     converged_mode ? t->h_flag : (int*)nullptr, t->call_seq);
+  HIP_TRY(hipGetLastError());
+  // launch shapes in powers of two (multi_align3's reason): slots past m and workgroups past a start's blocks return at
+  // once.  The solve is k_multi_solve3<0> in both Hessian modes: the body writes the 29 sums of the Gauss-Newton layout
+  const int chunk = 8;
+  const int steps = converged_mode ? chunk : K + 1;
+  const dim3 gs(pow2_at_least(m)), gb(pow2_at_least(max_blocks), gs.x);
+  const void* solve = (const void*)&k_multi_solve3<0>;
+  const void* body = with_mode(t->prm, [](auto M, auto) { return (const void*)&k_multi_body_d2d3<M>; });
+  hipGraphExec_t exec = nullptr;
+  HIP_TRY(t->graphs.get2(solve, gs, dim3(kBlock), body, gb, dim3(kBlock), (void*)t->d_static, (void*)t->d_call, (void*)t->d_dyn_multi,
+                         steps, kMapMultiGraphKey3 | ((int)gb.x << 8) | t->prm.hessian_mode, t->stream, &exec));
+  bool seen = true;
+  HIP_TRY(run_multi_chain(exec, t->stream, converged_mode ? t->h_flag : nullptr, steps, K + 1, t->call_seq, t->h_state_multi,
+                          t->d_dyn_multi->state[K & 1], kMaxStarts3 * sizeof(IterState3), &seen));
+  if (!seen) { set_error("the 3D map-to-map multi-start loop did not report its end"); return NDT_ERR_HIP; }
+  for (int k = 0; k < m; ++k)
+    if (sm.n[k] > 0) state3_to(t->h_state_multi[k], &results[k]);
+  return NDT_OK;
+}
+
 }  // namespace
 
 extern "C" {
+
+int32_t ndt3d_align_map_multi(ndt3d_handle* target, ndt3d_handle* const* sources, const double* init_poses, int32_t m,
+                              ndt3d_result* results) {
+  if (!target || !sources || !init_poses || !results) return NDT_ERR_INVALID_ARG;
+  if (m < 1 || m > ndt::kMaxStarts3) return NDT_ERR_INVALID_ARG;
+  for (int32_t k = 0; k < m; ++k) if (!sources[k]) return NDT_ERR_INVALID_ARG;
+  return run_align_map_multi3(target, sources, init_poses, m, results);
+}
 
 int32_t ndt3d_evaluate_map(ndt3d_handle* target, ndt3d_handle* source, const double pose[6], ndt3d_eval* out) {
   if (!target || !source || !pose || !out) return NDT_ERR_INVALID_ARG;

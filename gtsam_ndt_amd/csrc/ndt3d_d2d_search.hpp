@@ -243,10 +243,16 @@ int32_t ndt3d_search_map_scores(ndt3d_handle* target, ndt3d_handle* source, cons
 int32_t ndt3d_search_align_map(ndt3d_handle* target, ndt3d_handle* source, const ndt3d_search_window* w, int32_t k,
                                ndt3d_search_hit* hits, ndt3d_result* results, int32_t* n_hits) {
   if (!results) return NDT_ERR_INVALID_ARG;
-  int32_t st = ndt3d_search_map(target, source, w, k, hits, n_hits);
-  // no multi-start chain exists for this objective: one map-to-map loop per hit, in hit order
-  for (int32_t q = 0; st == NDT_OK && q < *n_hits; ++q) st = ndt3d_align_map(target, source, hits[q].pose, &results[q]);
-  return st;
+  const int32_t st = ndt3d_search_map(target, source, w, k, hits, n_hits);
+  if (st != NDT_OK || *n_hits < 1) return st;
+  // every hit is a start of one map-to-map chain (ndt3d_align_map_multi: bit for bit ndt3d_align_map from each pose)
+  ndt3d_handle* sources[ndt::kMaxStarts3];
+  double poses[ndt::kMaxStarts3][6];
+  for (int32_t q = 0; q < *n_hits; ++q) {
+    sources[q] = source;
+    for (int j = 0; j < 6; ++j) poses[q][j] = hits[q].pose[j];
+  }
+  return ndt3d_align_map_multi(target, sources, &poses[0][0], *n_hits, results);
 }
 
 }  // extern "C"

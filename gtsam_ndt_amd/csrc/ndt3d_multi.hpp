@@ -20,6 +20,8 @@ namespace ndt {
 
 constexpr int kMaxStarts3 = 64;
 
+struct MapStart3 { const float4* comp; int n; int blocks; };       // n = 0: the start takes no part
+
 struct AlignDynMulti3 {
   IterState3 state[2][kMaxStarts3];
   float partials[2][kMaxStarts3][kNumAcc3][kMaxBlocks];
@@ -32,6 +34,10 @@ struct AlignDynMulti3 {
   const float* sz[kMaxStarts3];
   int n[kMaxStarts3];
   struct Body { double pose[6]; int done; int pad; } body[2][kMaxStarts3];   // what each start's evaluation uses
+  // map-to-map chains (ndt3d_d2d_multi.hpp): each start's source component list and the workgroups of its single call,
+  // and the target's covariance records.  Behind everything the point-to-map chain reads: nothing of it moves
+  MapStart3 map[kMaxStarts3];
+  const float4* map_cov;
 };
 
 struct StartPoses3 { double p[kMaxStarts3][6]; };                 // 3 KB of kernel arguments

@@ -709,7 +709,8 @@ class NdtMatcher3D:
     """3D SE(3) variant (BASELINE config 5); mirrors ndt3d_* of include/ndt_hip.h."""
 
     def __init__(self, device: int = 0, tuning: dict | None = None, **overrides):
-        """tuning: execution-strategy knobs by name (L.TUNING; 3D handles know "single_sync_build")."""
+        """tuning: execution-strategy knobs by name (L.TUNING; 3D handles know "single_sync_build" and
+        "map_multi_from")."""
         self._lib = L.load()
         self.params = default_params3d(**overrides)
         h = C.c_void_p()
@@ -717,7 +718,10 @@ class NdtMatcher3D:
         self._h = h
         self._device = int(device)
         for k, v in (tuning or {}).items():
-            L.check(self._lib.ndt3d_set_tuning(self._h, L.TUNING[k], int(v)), "ndt3d_set_tuning")
+            self.set_tuning(k, v)
+
+    def set_tuning(self, knob: str, value: int):
+        L.check(self._lib.ndt3d_set_tuning(self._h, L.TUNING[knob], int(value)), "ndt3d_set_tuning")
 
     def close(self):
         if getattr(self, "_h", None):
@@ -845,6 +849,22 @@ class NdtMatcher3D:
         r = L.Result3D()
         L.check(self._lib.ndt3d_align_map(self._h, source._h, p, C.byref(r)), "ndt3d_align_map")
         return self._result(r)
+
+    def align_map_multi(self, sources, init_poses):
+        """Up to 64 map-to-map alignments against this handle's voxel grid in one launch chain (ndt3d_align_map_multi).
+        sources: one matcher (a multi-start: every pose starts that matcher's map) or a sequence of matchers, one per
+        pose; a matcher may repeat and may be this one.  Returns a list of AlignResult3D, entry k bit for bit what
+        align_map(sources[k], init_poses[k]) returns."""
+        poses = np.ascontiguousarray(init_poses, dtype=np.float64).reshape(-1, 6)
+        m = poses.shape[0]
+        srcs = [sources] * m if isinstance(sources, NdtMatcher3D) else list(sources)
+        if len(srcs) != m:
+            raise ValueError(f"{len(srcs)} sources for {m} initial poses")
+        hs = (C.c_void_p * max(m, 1))(*[s._h.value for s in srcs])
+        out = (L.Result3D * max(m, 1))()
+        L.check(self._lib.ndt3d_align_map_multi(self._h, hs, poses.ctypes.data, m, C.cast(out, C.c_void_p)),
+                "ndt3d_align_map_multi")
+        return [self._result(r) for r in out[:m]]
 
     def evaluate_map(self, source: "NdtMatcher3D", pose):
         """(H, g, score, n_hit) of the map-to-map objective at `pose` (ndt3d_evaluate_map)."""

@@ -333,7 +333,7 @@ int32_t ndt2d_align_map(ndt2d_handle* target, ndt2d_handle* source, const double
  *     any handle, handles on different devices: NDT_ERR_INVALID_ARG; a handle without a grid: NDT_ERR_NO_TARGET.
  *   - Inside an NDT_OK call: a source without a component gives ITS start status NDT_TOO_FEW_CELLS and its initial
  *     pose while the others run; a target without a valid cell gives that to every start.
- * Pairs with different targets are not covered (one call per target), and there is no 3D twin. */
+ * Pairs with different targets are not covered (one call per target).  The 3D twin is ndt3d_align_map_multi. */
 int32_t ndt2d_align_map_multi(ndt2d_handle* target, ndt2d_handle* const* sources, const double* init_poses /* [m][3] */,
                               int32_t m, ndt2d_result* results /* [m] */);
 /* Exhaustive pose search for map-to-map alignment (docs/ALGORITHM.md section 2.15): the score ndt2d_evaluate_map
@@ -379,7 +379,8 @@ int32_t ndt2d_get_components(ndt2d_handle* h, float* mean_xy, float* cov_abc, in
  *                               bit-identical either way
  *   NDT_TUNE_MAP_MULTI_FROM     ndt2d_align_map_multi calls of at least this many starts run one launch chain for all
  *                               starts; smaller calls run one ndt2d_align_map chain per start (default 2; 1..65, 65:
- *                               never the shared chain).  Results are bit-identical either way
+ *                               never the shared chain).  Results are bit-identical either way.  The same knob, range
+ *                               and default on ndt3d_set_tuning for ndt3d_align_map_multi
  *   NDT_TUNE_BATCH_SMALL_VARIANT (batch contexts) 1 (default): lidar-sized pairs run on the 256-thread
  *                               variant of the batch kernel first; 0: every pair on the 1024-thread one
  *   NDT_TUNE_BATCH_GLOBAL_WORKGROUPS (batch contexts, 2D and 3D) workgroups of the global-table variant, each with its own
@@ -701,10 +702,28 @@ int32_t ndt3d_align_trace(ndt3d_handle* h, const float* sx, const float* sy, con
  *     more than about a tenth of a voxel off, align a coarse pair of handles first and the fine pair from its result
  *     (DESIGN.md section 5.9).
  *   - ndt3d_result / ndt3d_eval are those of ndt3d_align / ndt3d_evaluate (n_hit counts components that hit a valid
- *     target voxel).  No covariance calibration exists for this objective.  Not offered: a batched form, pairing with
- *     neighbouring voxels. */
+ *     target voxel).  No covariance calibration exists for this objective.  Not offered: pairing with neighbouring
+ *     voxels.  Several alignments against one target: ndt3d_align_map_multi below. */
 int32_t ndt3d_evaluate_map(ndt3d_handle* target, ndt3d_handle* source, const double pose[6], ndt3d_eval* out);
 int32_t ndt3d_align_map(ndt3d_handle* target, ndt3d_handle* source, const double init_pose[6], ndt3d_result* out);
+/* m (1..64) 3D map-to-map alignments against ONE target in one launch chain (the twin of ndt2d_align_map_multi): start
+ * k aligns sources[k] from init_poses[6k .. 6k+5].  The same handle m times is a multi-start (the peaks of
+ * ndt3d_search_map); different handles are several submaps relocalised against one older submap; sources[k] may be
+ * `target`.
+ *   - results[k] is bit for bit what ndt3d_align_map(target, sources[k], &init_poses[6k], ...) returns, whatever
+ *     hessian_mode, fixed or converged mode, max_iterations, step_scale, line_search and NDT_TUNE_MAP_MULTI_FROM are; a
+ *     start that has finished is frozen while the others go on.
+ *   - The target handle's parameters, stream and graph cache drive the call, as for ndt3d_align_map.  Synchronous: it
+ *     returns once nothing reads any source's component list any more.
+ *   - Errors of the whole call, found before anything is enqueued (the handles stay usable): a null pointer, a null
+ *     entry of sources, m outside 1..64 (these three before any device call), a non-finite pose, handles on different
+ *     devices: NDT_ERR_INVALID_ARG; a handle without a grid: NDT_ERR_NO_TARGET.
+ *   - Inside an NDT_OK call: a source without a component gives ITS start status NDT_TOO_FEW_CELLS and its initial
+ *     pose while the others run; a target without a valid voxel gives that to every start; nothing is launched if no
+ *     start is live.
+ * Pairs with different targets are not covered (one call per target). */
+int32_t ndt3d_align_map_multi(ndt3d_handle* target, ndt3d_handle* const* sources, const double* init_poses /* [m][6] */,
+                              int32_t m, ndt3d_result* results /* [m] */);
 /* Exhaustive pose search for 3D map-to-map alignment (docs/ALGORITHM.md section 2.16): the score ndt3d_evaluate_map
  * reports (the same float32 terms per component, summed in another order) at every pose of the window's (x, y, yaw)
  * lattice, z, roll and pitch pinned to center[2..4], then the best well-separated peaks - a loop closure between two
@@ -713,8 +732,9 @@ int32_t ndt3d_align_map(ndt3d_handle* target, ndt3d_handle* source, const double
  * target == source are as for ndt3d_align_map (d1, d2: the target handle's).  A source without a component or a target
  * without a valid voxel gives an all-zero volume and no hit.  All three are synchronous: they return once nothing reads
  * the source's component list any more.  ndt3d_search_map_scores writes the volume [n_yaw][n_y][n_x] into device
- * memory.  ndt3d_search_align_map refines every hit with one ndt3d_align_map run, in hit order: results[q] is bit for
- * bit what ndt3d_align_map(target, source, hits[q].pose) returns (hits and results have room for k). */
+ * memory.  ndt3d_search_align_map refines all hits in one ndt3d_align_map_multi call (nothing is launched for zero
+ * hits): results[q] is bit for bit what ndt3d_align_map(target, source, hits[q].pose) returns (hits and results have
+ * room for k). */
 int32_t ndt3d_search_map(ndt3d_handle* target, ndt3d_handle* source, const ndt3d_search_window* w,
                          int32_t k, ndt3d_search_hit* hits, int32_t* n_hits);
 int32_t ndt3d_search_map_scores(ndt3d_handle* target, ndt3d_handle* source, const ndt3d_search_window* w,
@@ -731,7 +751,12 @@ int32_t ndt3d_wait_stream(ndt3d_handle* h, void* producer_stream);
 /* Execution-strategy knobs of a 3D handle (as ndt2d_set_tuning: they choose between code paths that build the same grid).
  *   NDT_TUNE_SINGLE_SYNC_BUILD  1 (default): ndt3d_set_target on a handle that already holds a grid decides the new grid's
  *                               geometry on the device and pays one host round trip; 0: the bounding box comes to the host
- *                               first (two round trips).  Other knobs: NDT_ERR_INVALID_ARG. */
+ *                               first (two round trips)
+ *   NDT_TUNE_MAP_MULTI_FROM     ndt3d_align_map_multi calls of at least this many starts run one launch chain for all
+ *                               starts; smaller calls run one ndt3d_align_map chain per start (default 2; 1..65, 65:
+ *                               never the shared chain; other values NDT_ERR_INVALID_ARG).  Results are bit-identical
+ *                               either way.
+ * Other knobs: NDT_ERR_INVALID_ARG. */
 int32_t ndt3d_set_tuning(ndt3d_handle* h, int32_t knob, int64_t value);
 
 /* ---- 3D loop-closure candidate batch ------------------------------------------------------------ */

@@ -718,6 +718,23 @@ class NdtMatcherHip3 {
     check(ndt3d_align_map(h_, source.h_, init, &r), "ndt3d_align_map");
     return toMatchResult(r);
   }
+  // Up to 64 map-to-map alignments against this matcher's voxel grid in one launch chain (ndt3d_align_map_multi): start
+  // k aligns *sources[k] from guesses[k].  The same matcher in every entry is a multi-start; an entry may be this
+  // matcher.  Result k is bit for bit what alignMap(*sources[k], guesses[k]) returns.
+  std::vector<MatchResult3> alignMapMulti(const std::vector<NdtMatcherHip3*>& sources, const std::vector<Pose3>& guesses) {
+    if (sources.size() != guesses.size()) throw NdtError(NDT_ERR_INVALID_ARG, "alignMapMulti: one guess per source");
+    std::vector<ndt3d_handle*> hs;
+    std::vector<double> init;
+    for (size_t k = 0; k < sources.size(); ++k) {
+      hs.push_back(sources[k] ? sources[k]->h_ : nullptr);
+      init.insert(init.end(), {guesses[k].x, guesses[k].y, guesses[k].z, guesses[k].roll, guesses[k].pitch, guesses[k].yaw});
+    }
+    std::vector<ndt3d_result> r(hs.size());
+    check(ndt3d_align_map_multi(h_, hs.data(), init.data(), (int32_t)hs.size(), r.data()), "ndt3d_align_map_multi");
+    std::vector<MatchResult3> out;
+    for (const ndt3d_result& x : r) out.push_back(toMatchResult(x));
+    return out;
+  }
   ndt3d_eval evaluateMap(NdtMatcherHip3& source, const Pose3& at) {
     const double p[6] = {at.x, at.y, at.z, at.roll, at.pitch, at.yaw};
     ndt3d_eval e;
