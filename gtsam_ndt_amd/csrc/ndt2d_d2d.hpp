@@ -205,6 +205,7 @@ __global__ __launch_bounds__(kBlock) void k_iterate_d2d(const AlignStatic* __res
   IterState* cur = &dyn->state[parity];
   const bool writer = (blockIdx.x == 0) && (tid == 0);
 
+  __builtin_amdgcn_sched_barrier(0);     // the four arguments stay one s_load batch above everything else
   // ---- batch 1 of loads: previous state (scalar), partial rows (vector), first component
   const double ps_pose0 = prev->pose[0], ps_pose1 = prev->pose[1], ps_pose2 = prev->pose[2];
   const int ps_iter = prev->iter, ps_done = prev->done, ps_have = prev->have_partials, ps_launch = prev->pad;

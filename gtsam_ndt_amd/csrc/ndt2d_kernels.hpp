@@ -477,6 +477,7 @@ __global__ void k_begin(AlignCall* __restrict__ call, AlignDyn* __restrict__ dyn
 // (x,y) math on register pairs for v_pk_*_f32 was measured: no gain, gfx950 issues packed f32
 // at half rate.)
 typedef float v2f __attribute__((ext_vector_type(2)));
+typedef float v4f __attribute__((ext_vector_type(4)));
 
 struct PoseF {
   float cs, sn, tx, ty, ox, oy, inv_c;
@@ -687,9 +688,10 @@ __device__ __forceinline__ void pack_state(IterState* o, const double* pose, con
 // (one per CU); a workgroup without points contributes a zero partial row.
 //
 // The iteration is a serial dependence chain (reduce -> solve -> transform -> gather ->
-// reduce), so the kernel is written to keep the number of dependent memory round trips at
-// two: everything the prologue needs (previous state, partial rows, first source point) is
-// requested up front in one batch, then the cell-record gather.
+// reduce), so the kernel is written to keep the number of dependent memory round trips behind
+// the argument load at two: the partial rows, then the previous state with the read-only
+// scalars in one s_load batch, then the first source points are all requested before anything
+// waits for the rows; the cell-record gather is the second.
 // EXP is an ablation mask for tools/exp_iter.hip only (1: no reduce/solve, 2: no body,
 // 4: no epilogue tree, 8: empty); the library instantiates EXP = 0.
 template <int MODE, int EXP = 0, int THREADS = kBlock, int NG = 1>
@@ -705,10 +707,25 @@ __global__ __launch_bounds__(THREADS) void k_iterate(const AlignStatic* __restri
   IterState* cur = &dyn->state[parity];
   const bool writer = (blockIdx.x == 0) && (tid == 0);
 
-  // ---- batch 1 of loads: previous state (scalar), partial rows (vector), first point
+  // ---- batch 1 of loads.  The partial rows go first: the previous launch wrote them from every XCD, so they come
+  // from beyond this XCD's L2 and are the only thing the fold waits for.  They are requested before ps_done and
+  // ps_have are known - the table always exists, so the loads are harmless on every path - but pv[] holds nothing
+  // meaningful when ps_done is set or ps_have is clear and must not be used there.
+  __builtin_amdgcn_sched_barrier(0);     // the four arguments stay one s_load batch above everything else
+  float4 pv[3];
+  if (!(EXP & 1)) {
+    // Waves 0..3 own the 12 partial rows.  No exec branch around the loads: hipcc puts the phi copies of the join, and
+    // with them a wait for the rows, at the end of such a branch.  Where there are more than four waves the others read
+    // the first 16 bytes of rows 0..2 instead (one cache line per load and wave) and never look at them.
+    const float* part = &dyn->partials[parity ^ 1][0][0];
+    const int off = (THREADS / 64 <= 4 || wave < 4) ? wave * 3 * kMaxBlocks + lane * 4 : 0;
+#pragma unroll
+    for (int v = 0; v < 3; ++v) pv[v] = *reinterpret_cast<const float4*>(part + off + v * kMaxBlocks);
+  }
+  // previous state, static and call part: scalar loads, all in ONE batch behind the row loads, one scalar wait
   const double ps_pose0 = prev->pose[0], ps_pose1 = prev->pose[1], ps_pose2 = prev->pose[2];
   const int ps_iter = prev->iter, ps_done = prev->done, ps_have = prev->have_partials, ps_launch = prev->pad;
-  const SolveParams prm = st->prm;       // read-only: scalar loads, all in this first batch
+  const SolveParams prm = st->prm;
   const GridDev G = st->grid;
   const int n = call->n;
   const int fixed_iterations = call->fixed_iterations;
@@ -716,20 +733,13 @@ __global__ __launch_bounds__(THREADS) void k_iterate(const AlignStatic* __restri
   const float* __restrict__ sy = call->sy;
   IterState* const host_state = call->host_state;
   int* const host_flag = call->host_flag;
-  float4 pv[3];
-  if (!(EXP & 1) && wave < 4) {          // waves 0..3 own the 12 partial rows
-    const float* part = &dyn->partials[parity ^ 1][0][0];
-#pragma unroll
-    for (int v = 0; v < 3; ++v)
-      pv[v] = *reinterpret_cast<const float4*>(part + (wave * 3 + v) * kMaxBlocks + lane * 4);
-  }
   // Pin the read-only scalars here: without this hipcc sinks their s_loads below the
   // `done` branch and they become a third dependent round trip.
   asm volatile("" ::"s"(G.ox), "s"(G.oy), "s"(G.inv_c), "s"(G.W), "s"(G.H), "s"(G.rec),
-               "s"(prm.d1), "s"(prm.d2), "s"(prm.min_hits), "s"(prm.max_iterations), "s"(prm.eps_trans),
-               "s"(prm.eps_rot), "s"(prm.step_max_trans), "s"(prm.step_max_rot), "s"(prm.step_scale), "s"(ps_pose0), "s"(ps_pose1),
-               "s"(ps_pose2), "s"(ps_iter), "s"(ps_done), "s"(ps_have), "s"(ps_launch), "s"(fixed_iterations), "s"(host_state),
-               "s"(host_flag));
+               "s"(prm.d1), "s"(prm.d2), "s"(prm.hessian_mode), "s"(prm.min_hits), "s"(prm.max_iterations), "s"(prm.eps_trans),
+               "s"(prm.eps_rot), "s"(prm.step_max_trans), "s"(prm.step_max_rot), "s"(prm.step_scale), "s"(prm.line_search), "s"(ps_pose0),
+               "s"(ps_pose1), "s"(ps_pose2), "s"(ps_iter), "s"(ps_done), "s"(ps_have), "s"(ps_launch), "s"(fixed_iterations),
+               "s"(host_state), "s"(host_flag));
   const int stride = kMaxBlocks * THREADS;
   int i = blockIdx.x * THREADS + tid;
   float x = 0.f, y = 0.f, x1 = 0.f, y1 = 0.f;
@@ -748,8 +758,17 @@ __global__ __launch_bounds__(THREADS) void k_iterate(const AlignStatic* __restri
     bool done = false;
     if (!(EXP & 1)) {
       // ---- prologue: fixed-order reduction (wave w owns sums 3w..3w+2), then the solve
-      if (wave < 4)                                            // 3 x 66 doubles fit in the epilogue's buffer
+      if (wave < 4) {                                          // 3 x 66 doubles fit in the epilogue's buffer
+        // Keep the rows opaque until here: hipcc otherwise hoists the fold's float64 conversions, and with them the
+        // wait for the rows, up to the row loads - in front of the scalar batch and the point loads.
+#pragma unroll
+        for (int v = 0; v < 3; ++v) {
+          v4f r = {pv[v].x, pv[v].y, pv[v].z, pv[v].w};
+          asm volatile("" : "+v"(r));
+          pv[v] = make_float4(r.x, r.y, r.z, r.w);
+        }
         fold_rows12(pv, reinterpret_cast<double*>(s_t[wave]), lane, &s_red[wave * 3]);
+      }
       __syncthreads();
       unpack_sums(s_red, H, g, score, n_hit);
       done = gn_update(pose, H, g, n_hit, iter, status, prm, fixed_iterations, score, &dyn->ls[parity ^ 1],

@@ -744,6 +744,7 @@ __global__ __launch_bounds__(kBlock) void k_iterate3(const AlignStatic3* __restr
   IterState3* cur = &dyn->state[parity];
   const bool writer = (blockIdx.x == 0) && (tid == 0);
 
+  __builtin_amdgcn_sched_barrier(0);     // the four arguments stay one s_load batch above everything else
   double pose[6];
 #pragma unroll
   for (int j = 0; j < 6; ++j) pose[j] = prev->pose[j];

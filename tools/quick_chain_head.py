@@ -1,0 +1,35 @@
+"""The time per k_iterate launch of a chain on the headline pair (config 3: 1M-point target, 100k-point scan, 30 fixed
+iterations = 31 launches per alignment), with one launch chain (NDT_TUNE_ASYNC_LANES = 1: what a change to the head of
+the kernel moves) and with two (the throughput bench.py's headline reports).  100 back-to-back asynchronous alignments
+per sample, REPEATS samples each, lanes alternating so that drift hits both alike.  Host clock around the 100 calls and
+the finish, divided by the launches: the figure is launch + boundary and carries the host's share of enqueueing 100
+k_begin + graph launches (the device is the slower side here, so it is small, but it is in there) - a chain's time per
+launch, good for comparing two builds, not the bare latency of a launch.
+NDT_HIP_LIB selects the library, to compare two builds in one session."""
+import os, sys, time
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+import numpy as np, torch
+from gtsam_ndt_amd import synth
+from gtsam_ndt_amd.matcher import NdtMatcher2D
+REPEATS, CALLS, K = 7, 100, 30
+d = synth.make_pair(3)
+tx, ty = torch.from_numpy(d["tx"]).cuda(), torch.from_numpy(d["ty"]).cuda()
+sx, sy = torch.from_numpy(d["sx"]).cuda(), torch.from_numpy(d["sy"]).cuda()
+torch.cuda.synchronize()
+us = {1: [], 2: []}
+with NdtMatcher2D(fixed_iterations=K) as m:
+    m.set_target(tx, ty)
+    for rep in range(REPEATS + 1):              # sample 0 is the warm-up
+        for lanes in (1, 2):
+            m.set_tuning("async_lanes", lanes)
+            t0 = time.perf_counter()
+            for _ in range(CALLS):
+                m.align_async(sx, sy, d["init"], producer_complete=True)
+            r = m.finish()
+            el = time.perf_counter() - t0
+            if rep:
+                us[lanes].append(1e6 * el / (CALLS * (K + 1)))
+for lanes in (1, 2):
+    a = np.array(us[lanes])
+    print(f"lanes {lanes}: {np.median(a):.3f} us per launch (min {a.min():.3f}, max {a.max():.3f}, {REPEATS} samples of "
+          f"{CALLS} alignments) = {K / (K + 1) / np.median(a) * 1e3:.1f}k iterations/s; pose {r.pose}")
