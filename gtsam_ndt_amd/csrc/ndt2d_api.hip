@@ -95,6 +95,7 @@ struct ndt2d_handle {
   size_t wide_threshold = 300000;          // ... from this many source points
   bool use_graph = true;
   int check_every = 8;                     // converged mode: launches per chunk
+  bool fused_begin = true;                 // NDT_TUNE_FUSED_BEGIN: launch 0 of a single-scan chain is k_iterate_first (no k_begin)
   SearchScratch srch;                      // exhaustive pose search scratch (ndt_search.hpp), allocated on first use
   // map-to-map alignment (ndt2d_d2d_api.hpp), allocated on first use; both caches follow the grid (grid_changed)
   float4* d_cov = nullptr; size_t cov_cap = 0;            // covariance records of the cached grid ([2 x cells], the layout of grid.rec)
@@ -550,8 +551,8 @@ int32_t set_target_impl(ndt2d_handle* h, const float* d_x, const float* d_y, siz
 }
 
 // Static part of the device context: grid + solver parameters.  Uploaded (synchronously)
-// whenever the target changes; the per-call part is written by k_begin from kernel arguments,
-// so no host buffer has to outlive an asynchronous call.
+// whenever the target changes; the per-call part is written by the chain's first launch (k_iterate_first; k_begin under
+// the old protocol) from kernel arguments, so no host buffer has to outlive an asynchronous call.
 // the solver's part of the device context (2D and 3D: ndt3d_params is ndt2d_params)
 void set_solve_params(SolveParams* p, const ndt2d_params& q) {
   p->d1 = (float)q.d1;
@@ -598,6 +599,12 @@ const void* iter_kernel(const ndt2d_handle* h, bool wide) {
     return wide ? (const void*)&k_iterate<M, 0, kIterThreadsWide, NG> : (const void*)&k_iterate<M, 0, kIterThreads, NG>;
   });
 }
+// launch 0 of a chain with k_begin folded in: the same instances
+const void* first_kernel(const ndt2d_handle* h, bool wide) {
+  return with_mode(h->prm, [&](auto M, auto NG) {
+    return wide ? (const void*)&k_iterate_first<M, kIterThreadsWide, NG> : (const void*)&k_iterate_first<M, kIterThreads, NG>;
+  });
+}
 int iter_threads(bool wide) { return wide ? kIterThreadsWide : kIterThreads; }
 bool is_wide(const ndt2d_handle* h, size_t n) { return h->use_wide && n >= h->wide_threshold; }
 
@@ -611,13 +618,14 @@ void drop_graph(ndt2d_handle* h) {
   h->graph_exec = nullptr;
 }
 
-// Graph of `launches` consecutive k_iterate launches starting at parity 0.  The kernels read
+// Graph of `launches` consecutive k_iterate launches starting at parity `first_parity` (1: launch 0 is a k_iterate_first
+// in front of the graph; 0: the old protocol behind k_begin - the cache keeps the two apart).  The kernels read
 // everything (grid, source pointers, n, parameters, state) from device memory, so one graph
 // serves every target and every source - of its lane: the per-call and dynamic contexts are baked into it.
-int32_t ensure_graph(ndt2d_handle* h, int launches, int blocks, bool wide, int lane, hipGraphExec_t* exec) {
+int32_t ensure_graph(ndt2d_handle* h, int launches, int blocks, bool wide, int lane, hipGraphExec_t* exec, int first_parity) {
   HIP_TRY(h->graphs.get(iter_kernel(h, wide), dim3(blocks), dim3(iter_threads(wide)), (void*)h->d_static,
                         (void*)(lane ? h->d_call1 : h->d_call), (void*)(lane ? h->d_dyn1 : h->d_dyn), launches,
-                        h->prm.hessian_mode | (wide ? 16 : 0), h->stream, exec, lane));
+                        h->prm.hessian_mode | (wide ? 16 : 0), h->stream, exec, lane, first_parity));
   return NDT_OK;
 }
 
@@ -711,25 +719,38 @@ int32_t run_align(ndt2d_handle* h, const float* d_sx, const float* d_sy, size_t 
   hipStream_t stream = h->stream;
   if (plan.record_fork) HIP_TRY(h->lane1.mark_fork(h->stream));
   if (plan.lane == 1) { HIP_TRY(h->lane1.enter()); stream = h->lane1.stream; }
-  hipLaunchKernelGGL(k_begin, dim3(1), dim3(64), 0, stream, plan.lane ? h->d_call1 : h->d_call, plan.lane ? h->d_dyn1 : h->d_dyn,
-                     d_sx, d_sy, (int)n, pose[0], pose[1], pose[2], fixed, chunked ? h->h_state : (IterState*)nullptr,
-                     chunked ? h->h_flag : (int*)nullptr, h->call_seq);
-  int k = 0;
+  // Launch 0.  Fused (the default): k_iterate_first, a plain launch that evaluates at the initial pose and writes the
+  // per-call context from its arguments; launches 1 .. K follow.  Old protocol: k_begin, then launches 0 .. K.
+  const int first = h->fused_begin ? 1 : 0;
+  AlignCall* const d_call = plan.lane ? h->d_call1 : h->d_call;
+  AlignDyn* const d_dyn = plan.lane ? h->d_dyn1 : h->d_dyn;
+  IterState* const host_state = chunked ? h->h_state : (IterState*)nullptr;
+  int* const host_flag = chunked ? h->h_flag : (int*)nullptr;
+  if (first) {
+    int ni = (int)n, fi = fixed;
+    void* args[] = {&h->d_static, (void*)&d_call, (void*)&d_dyn, &d_sx, &d_sy, &ni, (void*)&pose[0], (void*)&pose[1],
+                    (void*)&pose[2], &fi, (void*)&host_state, (void*)&host_flag, &h->call_seq};
+    (void)hipLaunchKernel(first_kernel(h, wide), dim3(blocks), dim3(iter_threads(wide)), args, 0, stream);
+  } else {
+    hipLaunchKernelGGL(k_begin, dim3(1), dim3(64), 0, stream, d_call, d_dyn, d_sx, d_sy, (int)n, pose[0], pose[1], pose[2], fixed,
+                       host_state, host_flag, h->call_seq);
+  }
+  int k = first;
   hipGraphExec_t exec = nullptr;
   if (h->use_graph) {
     if (chunked) {
       // converged mode: chunks of launches until the finishing launch raises the host flag
       const int chunk = check_every + (check_every & 1);
-      const int32_t gs = ensure_graph(h, chunk, blocks, wide, 0, &exec);
+      const int32_t gs = ensure_graph(h, chunk, blocks, wide, 0, &exec, first);
       if (gs != NDT_OK) return gs;
       h->chunk_run.drain = !own_source;                // the handle's own staging arrays outlive the call
       h->chunk_run.seq = h->call_seq;
-      HIP_TRY(chunk_run_begin(h->chunk_run, exec, h->stream, chunk, K + 1));
+      HIP_TRY(chunk_run_begin(h->chunk_run, exec, h->stream, chunk, K + 1, first));
       h->pending = false;
       return wait ? finish_chunk_run(h) : NDT_OK;
     } else {
       // (a lane-1 call that fails here leaves lane 1 behind the fork event and nothing else: harmless)
-      const int32_t gs = ensure_graph(h, K + 1, blocks, wide, plan.lane, &exec);
+      const int32_t gs = ensure_graph(h, K + 1 - first, blocks, wide, plan.lane, &exec, first);
       if (gs != NDT_OK) return gs;
       HIP_TRY(hipGraphLaunch(exec, stream));
       if (plan.lane == 1) HIP_TRY(h->lane1.leave(h->stream));
@@ -996,6 +1017,8 @@ int32_t ndt2d_set_tuning(ndt2d_handle* h, int32_t knob, int64_t value) {
     case NDT_TUNE_SINGLE_SYNC_BUILD: h->one_round_trip = value != 0; return NDT_OK;
     case NDT_TUNE_ASYNC_LANES: if (value < 1 || value > 2) return NDT_ERR_INVALID_ARG; h->lanes.lanes = (int)value; return NDT_OK;
     case NDT_TUNE_MAP_MULTI_FROM: if (value < 1 || value > kMaxStarts + 1) return NDT_ERR_INVALID_ARG; h->map_multi_from = (int)value; return NDT_OK;
+    // (the graphs of the two protocols have different first parities in the cache's key and never alias: nothing to drop)
+    case NDT_TUNE_FUSED_BEGIN: if (value != 0 && value != 1) return NDT_ERR_INVALID_ARG; h->fused_begin = value != 0; return NDT_OK;
     default: return NDT_ERR_INVALID_ARG;
   }
 }

@@ -84,8 +84,9 @@ struct IterState {
 // Device context, split by who writes it so that the read-only parts can be fetched with
 // scalar loads in one batch at kernel entry:
 //   AlignStatic  grid + solver parameters; uploaded by the host when the target changes
-//   AlignCall    per-alignment arguments; written by k_begin
-//   AlignDyn     iteration state and block partials; written by k_iterate
+//   AlignCall    per-alignment arguments; written by the first launch of a single-scan chain (k_iterate_first, from its
+//                kernel arguments) or, under the old protocol (NDT_TUNE_FUSED_BEGIN = 0, ndt2d_align_trace), by k_begin
+//   AlignDyn     iteration state and block partials; written by k_iterate_first / k_begin and k_iterate
 struct AlignStatic {
   GridDev grid;
   SolveParams prm;
@@ -682,6 +683,56 @@ __device__ __forceinline__ void pack_state(IterState* o, const double* pose, con
   o->pad = launch;
 }
 
+// The per-call arguments of a chain, as its first launch takes them (k_begin's)
+struct BeginArgs {
+  const float* sx;
+  const float* sy;
+  int n;
+  double p0, p1, p2;
+  int fixed_iterations;
+  IterState* host_state;
+  int* host_flag;
+  int seq;
+};
+
+// What the one writing thread of k_iterate_first leaves for launch 1, field by field (no struct temporary: see
+// copy_state): AlignCall as k_begin writes it; state[0] as the old launch 0 left it (the initial state with
+// have_partials = 1, pad = launch 0); state[1] as k_begin left it (have_partials = 0); both line-search slots cleared.
+// pose: the initial pose with its angle wrapped.
+__device__ __forceinline__ void begin_state(IterState* o, const double* pose, int have_partials) {
+  o->pose[0] = pose[0]; o->pose[1] = pose[1]; o->pose[2] = pose[2];
+#pragma unroll
+  for (int j = 0; j < 6; ++j) o->H[j] = 0.0;
+#pragma unroll
+  for (int j = 0; j < 3; ++j) o->g[j] = 0.0;
+  o->score = 0.0;
+  o->n_hit = 0;
+  o->iter = 0;
+  o->status = 0;
+  o->done = 0;
+  o->have_partials = have_partials;
+  o->pad = 0;
+}
+__device__ __forceinline__ void clear_line_search(LineSearch* o) {
+#pragma unroll
+  for (int j = 0; j < 3; ++j) { o->base[j] = 0.0; o->step[j] = 0.0; }
+  o->score = 0.0; o->alpha = 0.0; o->trials = 0; o->valid = 0;
+}
+__device__ __forceinline__ void begin_chain(AlignCall* call, AlignDyn* dyn, const BeginArgs& b, const double* pose) {
+  call->seq = b.seq;
+  call->pad = 0;
+  call->sx = b.sx;
+  call->sy = b.sy;
+  call->n = b.n;
+  call->fixed_iterations = b.fixed_iterations;
+  call->host_state = b.host_state;
+  call->host_flag = b.host_flag;
+  begin_state(&dyn->state[0], pose, 1);
+  begin_state(&dyn->state[1], pose, 0);
+  clear_line_search(&dyn->ls[0]);
+  clear_line_search(&dyn->ls[1]);
+}
+
 // ---------------------------------------------------------------- a4-a8 iterate kernel
 // Launch k (parity = k & 1) consumes state[parity^1] and partials[parity^1] written by
 // launch k-1 and produces state[parity], partials[parity].  Always kMaxBlocks workgroups
@@ -694,165 +745,28 @@ __device__ __forceinline__ void pack_state(IterState* o, const double* pose, con
 // waits for the rows; the cell-record gather is the second.
 // EXP is an ablation mask for tools/exp_iter.hip only (1: no reduce/solve, 2: no body,
 // 4: no epilogue tree, 8: empty); the library instantiates EXP = 0.
+//
+// The text of the launch is ndt2d_iterate_text.hpp, shared with k_iterate_first (launch 0 of a chain, FIRST = 1).
 template <int MODE, int EXP = 0, int THREADS = kBlock, int NG = 1>
 __global__ __launch_bounds__(THREADS) void k_iterate(const AlignStatic* __restrict__ st,
                                                     const AlignCall* __restrict__ call,
                                                     AlignDyn* __restrict__ dyn, int parity) {
-  __shared__ double s_red[kNumAcc];
-  __shared__ float s_wave[THREADS / 64][kNumAcc];
-  __shared__ float s_t[THREADS / 64][(kNumAcc - 1) * kSumRowStride];
-  if (EXP & 8) return;
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const IterState* prev = &dyn->state[parity ^ 1];
-  IterState* cur = &dyn->state[parity];
-  const bool writer = (blockIdx.x == 0) && (tid == 0);
+  constexpr int FIRST = 0;
+  const BeginArgs b{};
+#include "ndt2d_iterate_text.hpp"
+}
 
-  // ---- batch 1 of loads.  The partial rows go first: the previous launch wrote them from every XCD, so they come
-  // from beyond this XCD's L2 and are the only thing the fold waits for.  They are requested before ps_done and
-  // ps_have are known - the table always exists, so the loads are harmless on every path - but pv[] holds nothing
-  // meaningful when ps_done is set or ps_have is clear and must not be used there.
-  __builtin_amdgcn_sched_barrier(0);     // the four arguments stay one s_load batch above everything else
-  float4 pv[3];
-  if (!(EXP & 1)) {
-    // Waves 0..3 own the 12 partial rows.  No exec branch around the loads: hipcc puts the phi copies of the join, and
-    // with them a wait for the rows, at the end of such a branch.  Where there are more than four waves the others read
-    // the first 16 bytes of rows 0..2 instead (one cache line per load and wave) and never look at them.
-    const float* part = &dyn->partials[parity ^ 1][0][0];
-    const int off = (THREADS / 64 <= 4 || wave < 4) ? wave * 3 * kMaxBlocks + lane * 4 : 0;
-#pragma unroll
-    for (int v = 0; v < 3; ++v) pv[v] = *reinterpret_cast<const float4*>(part + off + v * kMaxBlocks);
-  }
-  // previous state, static and call part: scalar loads, all in ONE batch behind the row loads, one scalar wait
-  const double ps_pose0 = prev->pose[0], ps_pose1 = prev->pose[1], ps_pose2 = prev->pose[2];
-  const int ps_iter = prev->iter, ps_done = prev->done, ps_have = prev->have_partials, ps_launch = prev->pad;
-  const SolveParams prm = st->prm;
-  const GridDev G = st->grid;
-  const int n = call->n;
-  const int fixed_iterations = call->fixed_iterations;
-  const float* __restrict__ sx = call->sx;
-  const float* __restrict__ sy = call->sy;
-  IterState* const host_state = call->host_state;
-  int* const host_flag = call->host_flag;
-  // Pin the read-only scalars here: without this hipcc sinks their s_loads below the
-  // `done` branch and they become a third dependent round trip.
-  asm volatile("" ::"s"(G.ox), "s"(G.oy), "s"(G.inv_c), "s"(G.W), "s"(G.H), "s"(G.rec),
-               "s"(prm.d1), "s"(prm.d2), "s"(prm.hessian_mode), "s"(prm.min_hits), "s"(prm.max_iterations), "s"(prm.eps_trans),
-               "s"(prm.eps_rot), "s"(prm.step_max_trans), "s"(prm.step_max_rot), "s"(prm.step_scale), "s"(prm.line_search), "s"(ps_pose0),
-               "s"(ps_pose1), "s"(ps_pose2), "s"(ps_iter), "s"(ps_done), "s"(ps_have), "s"(ps_launch), "s"(fixed_iterations),
-               "s"(host_state), "s"(host_flag));
-  const int stride = kMaxBlocks * THREADS;
-  int i = blockIdx.x * THREADS + tid;
-  float x = 0.f, y = 0.f, x1 = 0.f, y1 = 0.f;
-  if (i < n) { x = sx[i]; y = sy[i]; }
-  if (i + stride < n) { x1 = sx[i + stride]; y1 = sy[i + stride]; }
-
-  if (ps_done) {                         // uniform: a finished alignment just carries its state
-    if (writer) chain_carry_done(cur, prev, host_flag, call);
-    return;
-  }
-  double pose[3] = {ps_pose0, ps_pose1, ps_pose2};
-  int iter = ps_iter;
-  if (ps_have) {
-    double H[6], g[3], score = 0.0;
-    int n_hit = 0, status = 0;
-    bool done = false;
-    if (!(EXP & 1)) {
-      // ---- prologue: fixed-order reduction (wave w owns sums 3w..3w+2), then the solve
-      if (wave < 4) {                                          // 3 x 66 doubles fit in the epilogue's buffer
-        // Keep the rows opaque until here: hipcc otherwise hoists the fold's float64 conversions, and with them the
-        // wait for the rows, up to the row loads - in front of the scalar batch and the point loads.
-#pragma unroll
-        for (int v = 0; v < 3; ++v) {
-          v4f r = {pv[v].x, pv[v].y, pv[v].z, pv[v].w};
-          asm volatile("" : "+v"(r));
-          pv[v] = make_float4(r.x, r.y, r.z, r.w);
-        }
-        fold_rows12(pv, reinterpret_cast<double*>(s_t[wave]), lane, &s_red[wave * 3]);
-      }
-      __syncthreads();
-      unpack_sums(s_red, H, g, score, n_hit);
-      done = gn_update(pose, H, g, n_hit, iter, status, prm, fixed_iterations, score, &dyn->ls[parity ^ 1],
-                       &dyn->ls[parity], writer);
-    } else {
-#pragma unroll
-      for (int j = 0; j < 6; ++j) H[j] = 0.0;
-      g[0] = g[1] = g[2] = 0.0;
-      iter += 1;
-      done = iter >= fixed_iterations;
-    }
-    if (writer) {
-      auto store = [&](IterState* o) {
-        pack_state(o, pose, H, g, score, n_hit, iter, status, done ? 1 : 0, ps_launch + 1);
-      };
-      store(cur);
-      chain_announce(store, done, ps_launch + 1, host_state, host_flag, call);
-    }
-    if (done) return;                    // uniform
-  } else if (writer) {
-    copy_state(cur, prev, 1);
-  }
-
-  // ---- body: per-point terms at `pose`
-  double sn_d, cs_d;
-  sincos_wrapped(pose[2], &sn_d, &cs_d);
-  const float4* __restrict__ rec = G.rec;
-  const PoseF P = make_pose((float)cs_d, (float)sn_d, (float)pose[0], (float)pose[1], G.ox, G.oy, G.inv_c, G.W,
-                            G.H, prm.d1, prm.d2);
-  Acc2D A;
-  acc_zero(A);
-
-  // two points in flight per thread: both gathers are issued before either is consumed
-  while (!(EXP & 2) && i < n) {
-    const int i2 = i + 2 * stride;
-    float xn0 = 0.f, yn0 = 0.f, xn1 = 0.f, yn1 = 0.f;
-    if (i2 < n) { xn0 = sx[i2]; yn0 = sy[i2]; }
-    if (i2 + stride < n) { xn1 = sx[i2 + stride]; yn1 = sy[i2 + stride]; }
-    PointRec r0, r1;
-    const bool two = (i + stride) < n;
-    if (NG == 1) {
-      lookup_point(P, rec, x, y, true, r0);
-      lookup_point(P, rec, x1, y1, two, r1);
-      accumulate_point<MODE>(P, r0, A);
-      accumulate_point<MODE>(P, r1, A);
-    } else {
-      // overlapping grids (Biber): the same image point scores against every grid
-      image_point(P, x, y, r0);
-      image_point(P, x1, y1, r1);
-      const int ncell = G.W * G.H;
-#pragma unroll
-      for (int q = 0; q < NG; ++q) {
-        const int k0 = q * ncell + image_key(P, G.gx[q], G.gy[q], r0, true);
-        const int k1 = q * ncell + image_key(P, G.gx[q], G.gy[q], r1, two);
-        r0.A = rec[2 * k0]; r0.B = rec[2 * k0 + 1];
-        r1.A = rec[2 * k1]; r1.B = rec[2 * k1 + 1];
-        accumulate_point<MODE>(P, r0, A);
-        accumulate_point<MODE>(P, r1, A);
-      }
-    }
-    x = xn0; y = yn0; x1 = xn1; y1 = yn1; i = i2;
-  }
-  float acc[kNumAcc];
-  acc_store(A, prm.d2, acc);
-  acc[11] = 0.f;
-
-  // ---- epilogue: wave tree -> LDS -> one partial row per block
-  if (EXP & 4) {
-    if (tid < kNumAcc) dyn->partials[parity][tid][blockIdx.x] = acc[tid & 1];
-    return;
-  }
-  {
-    const float r = wave_reduce11_lds(acc, s_t[wave], lane);
-    if ((lane & 3) == 0 && lane < 4 * (kNumAcc - 1)) s_wave[wave][lane >> 2] = r;
-  }
-  __syncthreads();
-  if (tid < kNumAcc) {
-    float r = 0.f;
-    if (tid < kNumAcc - 1) {
-#pragma unroll
-      for (int w = 0; w < THREADS / 64; ++w) r += s_wave[w][tid];     // fixed order
-    }
-    dyn->partials[parity][tid][blockIdx.x] = r;
-  }
+// Launch 0 of a single-scan chain with k_begin folded in: evaluates at the initial pose (partials[0]) straight from its
+// arguments, and its workgroup 0 writes the per-call context and both state slots for launch 1 (parity 1) to find
+// across the kernel boundary.  No workgroup of this launch reads any of them.  The same text as k_iterate.
+template <int MODE, int THREADS = kBlock, int NG = 1>
+__global__ __launch_bounds__(THREADS) void k_iterate_first(const AlignStatic* __restrict__ st, AlignCall* __restrict__ call,
+                                                          AlignDyn* __restrict__ dyn, const float* sx0, const float* sy0, int n0,
+                                                          double p0, double p1, double p2, int fixed0, IterState* host_state0,
+                                                          int* host_flag0, int seq) {
+  constexpr int FIRST = 1, EXP = 0, parity = 0;
+  const BeginArgs b{sx0, sy0, n0, p0, p1, p2, fixed0, host_state0, host_flag0, seq};
+#include "ndt2d_iterate_text.hpp"
 }
 
 // ------------------------------------------------------------- scan format (section 8f rank 4)

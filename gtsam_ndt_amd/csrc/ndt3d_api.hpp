@@ -59,6 +59,7 @@ struct ndt3d_handle {
   bool cov_valid = false, comp_valid = false;
   ndt::MapCall3* d_map_call = nullptr;
   int map_multi_from = 2;                                 // ndt3d_align_map_multi calls of this many starts use one chain (NDT_TUNE_MAP_MULTI_FROM)
+  bool fused_begin = true;                                // NDT_TUNE_FUSED_BEGIN: launch 0 of a chain is k_iterate3_first (no k_begin3)
   hipEvent_t map_ev = nullptr;                            // orders a target handle's stream behind this handle's (order_after)
 };
 
@@ -342,11 +343,12 @@ const void* iter3_kernel(const ndt3d_handle* h) {
   return with_mode(h->prm, [](auto M, auto) { return (const void*)&ndt::k_iterate3<M>; });
 }
 
-int32_t ensure_graph3(ndt3d_handle* h, int launches) {
+// first_parity 1: the graph follows a k_iterate3_first and starts at launch 1 (the cache keeps the two kinds apart)
+int32_t ensure_graph3(ndt3d_handle* h, int launches, int first_parity) {
   using namespace ndt;
   HIP_TRY(h->graphs.get(iter3_kernel(h), dim3(kMaxBlocks), dim3(kBlock),
                         (void*)h->d_static, (void*)h->d_call, (void*)h->d_dyn, launches, h->prm.hessian_mode, h->stream,
-                        &h->graph_exec));
+                        &h->graph_exec, 0, first_parity));
   return NDT_OK;
 }
 
@@ -382,12 +384,25 @@ int32_t begin_align3(ndt3d_handle* h, const float* dx, const float* dy, const fl
   }
   const int fixed = fixed_override >= 0 ? fixed_override : h->prm.fixed_iterations;
   next_seq(&h->call_seq, h->h_flag);
-  hipLaunchKernelGGL(k_begin3, dim3(1), dim3(64), 0, h->stream, h->d_call, h->d_dyn, dx, dy, dz, (int)n, pose[0], pose[1],
-                     pose[2], pose[3], pose[4], pose[5], fixed, fixed > 0 ? (IterState3*)nullptr : h->h_state,
-                     fixed > 0 ? (int*)nullptr : h->h_flag, h->call_seq);
+  // Launch 0.  Fused (the default): k_iterate3_first evaluates at the initial pose and writes the per-call context from
+  // its arguments; launches 1 .. K follow.  Old protocol: k_begin3, then launches 0 .. K.
+  const int first = h->fused_begin ? 1 : 0;
+  IterState3* const host_state = fixed > 0 ? (IterState3*)nullptr : h->h_state;
+  int* const host_flag = fixed > 0 ? (int*)nullptr : h->h_flag;
+  if (first) {
+    with_mode(h->prm, [&](auto M, auto) {
+      hipLaunchKernelGGL((k_iterate3_first<M>), dim3(kMaxBlocks), dim3(kBlock), 0, h->stream, (const AlignStatic3*)h->d_static,
+                         h->d_call, h->d_dyn, dx, dy, dz, (int)n, pose[0], pose[1], pose[2], pose[3], pose[4], pose[5], fixed,
+                         host_state, host_flag, h->call_seq);
+      return 0;
+    });
+  } else {
+    hipLaunchKernelGGL(k_begin3, dim3(1), dim3(64), 0, h->stream, h->d_call, h->d_dyn, dx, dy, dz, (int)n, pose[0], pose[1],
+                       pose[2], pose[3], pose[4], pose[5], fixed, host_state, host_flag, h->call_seq);
+  }
   const int K = fixed > 0 ? fixed : h->prm.max_iterations;
   if (fixed > 0) {
-    const int32_t gs = ensure_graph3(h, K + 1);
+    const int32_t gs = ensure_graph3(h, K + 1 - first, first);
     if (gs != NDT_OK) return gs;
     HIP_TRY(hipGraphLaunch(h->graph_exec, h->stream));
     HIP_TRY(hipGetLastError());
@@ -395,11 +410,11 @@ int32_t begin_align3(ndt3d_handle* h, const float* dx, const float* dy, const fl
     h->in_flight = 1;
   } else {
     const int chunk = 8;
-    const int32_t gs = ensure_graph3(h, chunk);
+    const int32_t gs = ensure_graph3(h, chunk, first);
     if (gs != NDT_OK) return gs;
     h->chunk_run.drain = true;
     h->chunk_run.seq = h->call_seq;
-    HIP_TRY(chunk_run_begin(h->chunk_run, h->graph_exec, h->stream, chunk, K + 1));
+    HIP_TRY(chunk_run_begin(h->chunk_run, h->graph_exec, h->stream, chunk, K + 1, first));
     h->in_flight = 2;
   }
   return NDT_OK;
@@ -569,6 +584,8 @@ int32_t ndt3d_set_tuning(ndt3d_handle* h, int32_t knob, int64_t value) {
   switch (knob) {
     case NDT_TUNE_SINGLE_SYNC_BUILD: h->one_round_trip = value != 0; return NDT_OK;
     case NDT_TUNE_MAP_MULTI_FROM: if (value < 1 || value > ndt::kMaxStarts3 + 1) return NDT_ERR_INVALID_ARG; h->map_multi_from = (int)value; return NDT_OK;
+    // takes effect with the next alignment; an alignment in flight keeps the protocol it began with
+    case NDT_TUNE_FUSED_BEGIN: if (value != 0 && value != 1) return NDT_ERR_INVALID_ARG; h->fused_begin = value != 0; return NDT_OK;
     default: return NDT_ERR_INVALID_ARG;
   }
 }

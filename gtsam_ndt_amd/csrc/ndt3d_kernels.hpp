@@ -841,4 +841,58 @@ __global__ __launch_bounds__(kBlock) void k_iterate3(const AlignStatic3* __restr
   evaluate_block3<MODE>(G, prm, pose, sx, sy, sz, n, i, x, y, z, s_wave, s_t[wave], &dyn->partials[parity][0][blockIdx.x]);
 }
 
+// Launch 0 of a 3D chain with k_begin3 folded in (k_iterate_first of the 2D path): the evaluation at the initial pose
+// straight from the kernel arguments into partials[0] - nothing in its head waits for `dyn` or `call` - and, from workgroup
+// 0's thread 0, what k_begin3 and the old launch 0 left behind between them: AlignCall3; state[0] = the initial state with
+// have_partials = 1 and pad = 0; state[1] = the same with have_partials = 0; both line-search slots cleared.  No workgroup
+// of this launch reads any of them; launch 1 (parity 1) finds them across the kernel boundary.  k_iterate3 is untouched.
+__device__ __forceinline__ void begin_state3(IterState3* o, const double* pose, int have_partials) {
+#pragma unroll
+  for (int j = 0; j < 6; ++j) { o->pose[j] = pose[j]; o->g[j] = 0.0; }
+#pragma unroll
+  for (int j = 0; j < 21; ++j) o->H[j] = 0.0;
+  o->score = 0.0;
+  o->n_hit = 0; o->iter = 0; o->status = 0;
+  o->done = 0; o->have_partials = have_partials; o->pad = 0;
+}
+__device__ __forceinline__ void clear_line_search3(LineSearch3* o) {
+#pragma unroll
+  for (int j = 0; j < 6; ++j) { o->base[j] = 0.0; o->step[j] = 0.0; }
+  o->score = 0.0; o->alpha = 0.0; o->trials = 0; o->valid = 0;
+}
+
+template <int MODE>
+__global__ __launch_bounds__(kBlock) void k_iterate3_first(const AlignStatic3* __restrict__ st, AlignCall3* __restrict__ call,
+                                                            AlignDyn3* __restrict__ dyn, const float* sx, const float* sy,
+                                                            const float* sz, int n, double p0, double p1, double p2, double p3,
+                                                            double p4, double p5, int fixed_iterations, IterState3* host_state,
+                                                            int* host_flag, int seq) {
+  constexpr int NA = Acc3<MODE>::kUsed;
+  __shared__ float s_wave[kBlock / 64][kNumAcc3];
+  __shared__ float s_t[kBlock / 64][NA * kSum3RowStride];
+  const int tid = threadIdx.x, wave = tid >> 6;
+  const SolveParams prm = st->prm;
+  const Grid3Dev G = st->grid;
+  asm volatile("" ::"s"(G.ox), "s"(G.oy), "s"(G.oz), "s"(G.inv_c), "s"(G.W), "s"(G.H), "s"(G.D), "s"(G.rec),
+               "s"(prm.d1), "s"(prm.d2));
+  const int i = blockIdx.x * kBlock + tid;
+  float x = 0.f, y = 0.f, z = 0.f;
+  if (i < n) { x = sx[i]; y = sy[i]; z = sz[i]; }
+  const double pose[6] = {p0, p1, p2, wrap_angle(p3), wrap_angle(p4), wrap_angle(p5)};
+  if (blockIdx.x == 0 && tid == 0) {
+    call->seq = seq;
+    call->pad = 0;
+    call->sx = sx; call->sy = sy; call->sz = sz;
+    call->n = n;
+    call->fixed_iterations = fixed_iterations;
+    call->host_state = host_state;
+    call->host_flag = host_flag;
+    begin_state3(&dyn->state[0], pose, 1);
+    begin_state3(&dyn->state[1], pose, 0);
+    clear_line_search3(&dyn->ls[0]);
+    clear_line_search3(&dyn->ls[1]);
+  }
+  evaluate_block3<MODE>(G, prm, pose, sx, sy, sz, n, i, x, y, z, s_wave, s_t[wave], &dyn->partials[0][0][blockIdx.x]);
+}
+
 }  // namespace ndt

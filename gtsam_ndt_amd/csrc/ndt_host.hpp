@@ -106,14 +106,16 @@ inline hipError_t order_after(hipStream_t consumer, hipStream_t producer, hipEve
 // A linear chain of `launches` launches of one kernel whose last argument is the launch parity
 // (k & 1), built with explicit graph nodes.  No stream capture: capture state is process-wide
 // in the HIP runtime and this library's handles may be driven from several threads at once.
+// first_parity: the parity of the graph's first launch - 1 where launch 0 of the chain is enqueued outside the graph
+// (a first launch that carries the per-call arguments, k_iterate_first).
 inline hipError_t build_chain_graph(const void* func, dim3 grid, dim3 block, void* a0, void* a1, void* a2,
-                                    int launches, hipGraph_t* graph_out, hipGraphExec_t* exec_out) {
+                                    int launches, hipGraph_t* graph_out, hipGraphExec_t* exec_out, int first_parity = 0) {
   hipGraph_t g = nullptr;
   hipError_t e = hipGraphCreate(&g, 0);
   if (e != hipSuccess) return e;
   hipGraphNode_t prev = nullptr;
   for (int k = 0; k < launches && e == hipSuccess; ++k) {
-    int parity = k & 1;
+    int parity = (k + first_parity) & 1;
     void* args[4] = {&a0, &a1, &a2, &parity};
     hipKernelNodeParams p{};
     p.func = const_cast<void*>(func);
@@ -171,15 +173,17 @@ inline hipError_t build_chain_graph2(const void* fa, dim3 ga, dim3 ba, const voi
 // of rebuilding one on every change.
 struct ChainGraphCache {
   static constexpr int kSlots = 16;
-  struct Slot { int launches = 0, blocks = 0, mode = -1, lane = 0; hipGraph_t graph = nullptr; hipGraphExec_t exec = nullptr; unsigned long stamp = 0; };
+  struct Slot { int launches = 0, blocks = 0, mode = -1, lane = 0, first_parity = 0; hipGraph_t graph = nullptr; hipGraphExec_t exec = nullptr; unsigned long stamp = 0; };
   Slot slot[kSlots];
   unsigned long clock = 0;
   hipStream_t lane1 = nullptr;   // the owner's second launch chain (AsyncLane below): replays of lane-1 graphs are queued there
 
-  // lane: a graph bakes the AlignCall / AlignDyn pointers of its launches, so each launch chain of a handle has its own
-  hipGraphExec_t find(int launches, int blocks, int mode, int lane = 0) {
+  // lane: a graph bakes the AlignCall / AlignDyn pointers of its launches, so each launch chain of a handle has its own.
+  // first_parity: and the parities of its launches, so a chain that starts at launch 1 never gets one that starts at launch 0
+  hipGraphExec_t find(int launches, int blocks, int mode, int lane = 0, int first_parity = 0) {
     for (Slot& s : slot)
-      if (s.exec && s.launches == launches && s.blocks == blocks && s.mode == mode && s.lane == lane) { s.stamp = ++clock; return s.exec; }
+      if (s.exec && s.launches == launches && s.blocks == blocks && s.mode == mode && s.lane == lane &&
+          s.first_parity == first_parity) { s.stamp = ++clock; return s.exec; }
     return nullptr;
   }
   // the slot to build into: an empty one, else the least recently used (destroyed first).  Replays
@@ -203,12 +207,13 @@ struct ChainGraphCache {
   }
   void clear() { for (Slot& s : slot) release(s); }
   hipError_t get(const void* func, dim3 grid, dim3 block, void* a0, void* a1, void* a2, int launches, int mode,
-                 hipStream_t stream, hipGraphExec_t* out, int lane = 0) {
-    if (hipGraphExec_t e = find(launches, (int)grid.x, mode, lane)) { *out = e; return hipSuccess; }
+                 hipStream_t stream, hipGraphExec_t* out, int lane = 0, int first_parity = 0) {
+    if (hipGraphExec_t e = find(launches, (int)grid.x, mode, lane, first_parity)) { *out = e; return hipSuccess; }
     Slot* s = victim(stream);
-    const hipError_t err = build_chain_graph(func, grid, block, a0, a1, a2, launches, &s->graph, &s->exec);
+    const hipError_t err = build_chain_graph(func, grid, block, a0, a1, a2, launches, &s->graph, &s->exec, first_parity);
     if (err != hipSuccess) { *s = Slot{}; return err; }
-    s->launches = launches; s->blocks = (int)grid.x; s->mode = mode; s->lane = lane; s->stamp = ++clock;
+    s->launches = launches; s->blocks = (int)grid.x; s->mode = mode; s->lane = lane; s->first_parity = first_parity;
+    s->stamp = ++clock;
     *out = s->exec;
     return hipSuccess;
   }
@@ -312,9 +317,13 @@ struct AsyncLane {
 //   flag[0]  raised by the finishing launch
 //   flag[1]  index of the last launch that ran its prologue (the host's view of progress)
 //   flag[2]  call number, written by the first launch past the end: the source arrays are free
+// Launch indices count from the chain's launch 0.  Where that launch was enqueued in front of the chunks (a first launch
+// that carries the per-call arguments), chunk w holds launches first + w * chunk .. first + (w + 1) * chunk - 1 with
+// first = 1, and its graph starts at parity 1; chunks have even length, so replays keep alternating.
 struct ChunkRun {          // a converged-mode loop in flight (begin ... finish)
   hipGraphExec_t exec = nullptr;
   int chunk = 0, max_launches = 0, launched = 0;
+  int first = 0;           // index of the first launch of chunk 0: the launches enqueued in front of the chunks
   bool active = false;
   int seq = 0;             // number of this call: flag[2] == seq means "nothing reads the sources any more"
   bool drain = true;       // before returning, wait until nothing reads the source arrays any more (the
@@ -322,8 +331,9 @@ struct ChunkRun {          // a converged-mode loop in flight (begin ... finish)
 };
 
 // Enqueue the first two chunks and return: the asynchronous half.
-inline hipError_t chunk_run_begin(ChunkRun& r, hipGraphExec_t exec, hipStream_t stream, int chunk, int max_launches) {
-  r.exec = exec; r.chunk = chunk; r.max_launches = max_launches; r.launched = 0; r.active = true;
+inline hipError_t chunk_run_begin(ChunkRun& r, hipGraphExec_t exec, hipStream_t stream, int chunk, int max_launches,
+                                  int first = 0) {
+  r.exec = exec; r.chunk = chunk; r.max_launches = max_launches; r.launched = 0; r.first = first; r.active = true;
   hipError_t e = hipGraphLaunch(exec, stream);
   ++r.launched;
   if (e == hipSuccess) { e = hipGraphLaunch(exec, stream); ++r.launched; }
@@ -374,14 +384,14 @@ inline hipError_t chunk_run_finish(ChunkRun& r, hipStream_t stream, int* flag, b
   hipError_t e = hipSuccess;
   *seen = false;
   while (e == hipSuccess) {
-    const int need = (waited + 1) * r.chunk - 1;         // chunk `waited` is through when progress reaches this
+    const int need = r.first + (waited + 1) * r.chunk - 1;   // chunk `waited` is through when progress reaches this
     bool ok = false;
     e = spin_until(stream, [&]() { return raised() || __atomic_load_n(&flag[1], __ATOMIC_ACQUIRE) >= need; }, &ok);
     if (e != hipSuccess || raised()) break;
     // ok == false: the stream is idle and the progress counter did not move - feed it anyway; the
     // launch cap below ends a loop that can never finish
     ++waited;
-    if ((r.launched - 1) * r.chunk > r.max_launches + 2 * r.chunk) { e = hipErrorLaunchFailure; break; }
+    if (r.first + (r.launched - 1) * r.chunk > r.max_launches + 2 * r.chunk) { e = hipErrorLaunchFailure; break; }
     e = hipGraphLaunch(r.exec, stream);
     ++r.launched;
   }
@@ -394,7 +404,7 @@ inline hipError_t chunk_run_finish(ChunkRun& r, hipStream_t stream, int* flag, b
     // flag[1] now holds the finishing launch's index: if it was the last launch enqueued there is
     // nothing behind it to raise flag[2], and the stream's end is what to wait for.
     const int last = __atomic_load_n(&flag[1], __ATOMIC_ACQUIRE);
-    if (r.launched * r.chunk - 1 > last) {
+    if (r.first + r.launched * r.chunk - 1 > last) {
       bool ok = false;
       e = spin_until(stream, [&]() { return __atomic_load_n(&flag[2], __ATOMIC_ACQUIRE) == r.seq; }, &ok);
       if (e == hipSuccess && !ok) e = hipStreamSynchronize(stream);

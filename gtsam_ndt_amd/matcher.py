@@ -709,8 +709,8 @@ class NdtMatcher3D:
     """3D SE(3) variant (BASELINE config 5); mirrors ndt3d_* of include/ndt_hip.h."""
 
     def __init__(self, device: int = 0, tuning: dict | None = None, **overrides):
-        """tuning: execution-strategy knobs by name (L.TUNING; 3D handles know "single_sync_build" and
-        "map_multi_from")."""
+        """tuning: execution-strategy knobs by name (L.TUNING; 3D handles know "single_sync_build",
+        "map_multi_from" and "fused_begin")."""
         self._lib = L.load()
         self.params = default_params3d(**overrides)
         h = C.c_void_p()

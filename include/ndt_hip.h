@@ -381,6 +381,11 @@ int32_t ndt2d_get_components(ndt2d_handle* h, float* mean_xy, float* cov_abc, in
  *                               starts; smaller calls run one ndt2d_align_map chain per start (default 2; 1..65, 65:
  *                               never the shared chain).  Results are bit-identical either way.  The same knob, range
  *                               and default on ndt3d_set_tuning for ndt3d_align_map_multi
+ *   NDT_TUNE_FUSED_BEGIN        1 (default): the first launch of a single-scan alignment takes the call's arguments and
+ *                               evaluates at the initial pose itself (K + 1 launches for K iterations); 0: a small
+ *                               kernel writes the arguments into the device context first (K + 2 launches, the protocol
+ *                               ndt2d_align_trace always runs).  Other values: NDT_ERR_INVALID_ARG.  Results are
+ *                               bit-identical either way.  The same knob on ndt3d_set_tuning
  *   NDT_TUNE_BATCH_SMALL_VARIANT (batch contexts) 1 (default): lidar-sized pairs run on the 256-thread
  *                               variant of the batch kernel first; 0: every pair on the 1024-thread one
  *   NDT_TUNE_BATCH_GLOBAL_WORKGROUPS (batch contexts, 2D and 3D) workgroups of the global-table variant, each with its own
@@ -402,7 +407,8 @@ enum {
   NDT_TUNE_SINGLE_SYNC_BUILD = 9,
   NDT_TUNE_BATCH_GLOBAL_WORKGROUPS = 10,
   NDT_TUNE_ASYNC_LANES = 11,
-  NDT_TUNE_MAP_MULTI_FROM = 12
+  NDT_TUNE_MAP_MULTI_FROM = 12,
+  NDT_TUNE_FUSED_BEGIN = 13
 };
 int32_t ndt2d_set_tuning(ndt2d_handle* h, int32_t knob, int64_t value);
 /* hipStream_t the handle enqueues on (as void*), for event timing by the caller */
@@ -756,6 +762,7 @@ int32_t ndt3d_wait_stream(ndt3d_handle* h, void* producer_stream);
  *                               starts; smaller calls run one ndt3d_align_map chain per start (default 2; 1..65, 65:
  *                               never the shared chain; other values NDT_ERR_INVALID_ARG).  Results are bit-identical
  *                               either way.
+ *   NDT_TUNE_FUSED_BEGIN        as on ndt2d_set_tuning, for ndt3d_align* (k_iterate3_first against k_begin3; default 1)
  * Other knobs: NDT_ERR_INVALID_ARG. */
 int32_t ndt3d_set_tuning(ndt3d_handle* h, int32_t knob, int64_t value);
 

@@ -5,13 +5,17 @@ per sample, REPEATS samples each, lanes alternating so that drift hits both alik
 the finish, divided by the launches: the figure is launch + boundary and carries the host's share of enqueueing 100
 k_begin + graph launches (the device is the slower side here, so it is small, but it is in there) - a chain's time per
 launch, good for comparing two builds, not the bare latency of a launch.
-NDT_HIP_LIB selects the library, to compare two builds in one session."""
+NDT_HIP_LIB selects the library, to compare two builds in one session.
+--fused 0 | 1: set NDT_TUNE_FUSED_BEGIN (a library that has the knob): 0 = k_begin + K + 1 launches, 1 = the first launch
+carries the call's arguments (K + 1 kernels in all).  Either way the time is divided by K + 1 launches, so that the
+figures of the two protocols compare as time per alignment / (K + 1); the time per alignment is printed as well."""
 import os, sys, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np, torch
 from gtsam_ndt_amd import synth
 from gtsam_ndt_amd.matcher import NdtMatcher2D
 REPEATS, CALLS, K = 7, 100, 30
+FUSED = int(sys.argv[sys.argv.index("--fused") + 1]) if "--fused" in sys.argv else None
 d = synth.make_pair(3)
 tx, ty = torch.from_numpy(d["tx"]).cuda(), torch.from_numpy(d["ty"]).cuda()
 sx, sy = torch.from_numpy(d["sx"]).cuda(), torch.from_numpy(d["sy"]).cuda()
@@ -19,6 +23,8 @@ torch.cuda.synchronize()
 us = {1: [], 2: []}
 with NdtMatcher2D(fixed_iterations=K) as m:
     m.set_target(tx, ty)
+    if FUSED is not None:
+        m.set_tuning("fused_begin", FUSED)
     for rep in range(REPEATS + 1):              # sample 0 is the warm-up
         for lanes in (1, 2):
             m.set_tuning("async_lanes", lanes)
@@ -32,4 +38,6 @@ with NdtMatcher2D(fixed_iterations=K) as m:
 for lanes in (1, 2):
     a = np.array(us[lanes])
     print(f"lanes {lanes}: {np.median(a):.3f} us per launch (min {a.min():.3f}, max {a.max():.3f}, {REPEATS} samples of "
-          f"{CALLS} alignments) = {K / (K + 1) / np.median(a) * 1e3:.1f}k iterations/s; pose {r.pose}")
+          f"{CALLS} alignments; time / {K + 1} launches) = {np.median(a) * (K + 1):.1f} us per alignment = "
+          f"{K / (K + 1) / np.median(a) * 1e3:.1f}k iterations/s; fused_begin {'default' if FUSED is None else FUSED}; "
+          f"{os.environ.get('NDT_HIP_LIB', 'product library')}; pose {r.pose}")
