@@ -36,7 +36,7 @@ struct ndt2d_handle {
   int n_valid = 0;
   size_t n_points = 0;
   unsigned int* d_bounds = nullptr;        // [4]
-  int* d_counters = nullptr;               // [2] valid cells, overflowed cells
+  int* d_counters = nullptr;               // [kCountWords] shards of valid / overflowed cells, the cells a removal broke
   unsigned long long* d_outside = nullptr; // [1]
   void* h_small = nullptr;                 // pinned scratch (kSmallBytes: counter shards at 0, the outside count at 128, a flag)
   // staging for host-pointer entry points
@@ -74,8 +74,9 @@ struct ndt2d_handle {
   float4* d_parts = nullptr;               // [kBoundsParts]: per-workgroup partial bounding boxes
   unsigned char* d_split = nullptr; size_t split_cap = 0;  // tickets | cursor | touched | parts | pool of the shared tiles (SplitBufs)
   unsigned int build_seq = 0;              // sorted builds so far on this handle (SplitBufs::seq; never 0 in a launch)
-  // accumulators of the sorted build, ping-pong: half p = 256 bytes: int counters[kCountInts] | u64 outside at 128.  A build
-  // adds to half acc_parity and clears the other one for the next build (k_tile_gather), so no fill launch precedes it.
+  // accumulators of the sorted build, ping-pong: half p = 256 bytes: int counters[kCountInts] | u64 outside at 128 | the cells
+  // a removal broke (word kCountUnder).  A build adds to half acc_parity and clears the other one for the next build
+  // (k_tile_gather), so no fill launch precedes it.
   unsigned char* d_acc2 = nullptr;
   int acc_parity = 0;
   bool acc_clean = false;                  // both halves known to be zero where the next build needs it
@@ -157,18 +158,33 @@ int32_t upload_static(ndt2d_handle* h);
 // alignment derived from it (ndt2d_d2d_api.hpp) is stale.
 void grid_changed(ndt2d_handle* h) { h->cov_valid = false; h->comp_valid = false; }
 
-int32_t finalise_grid(ndt2d_handle* h) {
+// The words a removal adds to a failed call: what the kernels counted in kCountUnder means that points were removed that
+// are not in the map.
+int32_t check_removal(const int* hc) {
+  if (hc[ndt::kCountUnder] > 0) {
+    set_error("removed points are not in the target: a cell's count fell below zero, or reached zero with sums left");
+    return NDT_ERR_INVALID_ARG;
+  }
+  return NDT_OK;
+}
+
+// sign = -1: the finalise behind a removal (accumulate_and_finalise), which also looks for the cells it broke
+int32_t finalise_grid(ndt2d_handle* h, int sign = 1) {
   const size_t ncell = (size_t)h->grid.W * h->grid.H * h->grid.ngrid;
-  HIP_TRY(hipMemsetAsync(h->d_counters, 0, ndt::kCountInts * sizeof(int), h->stream));
-  hipLaunchKernelGGL(k_finalise, dim3((unsigned)((ncell + kBlock - 1) / kBlock)), dim3(kBlock), 0,
-                     h->stream, h->grid, h->prm.min_points, h->prm.eig_ratio, h->d_counters);
+  HIP_TRY(hipMemsetAsync(h->d_counters, 0, ndt::kCountWords * sizeof(int), h->stream));
+  const dim3 blocks((unsigned)((ncell + kBlock - 1) / kBlock));
+  if (sign < 0) hipLaunchKernelGGL((k_finalise<-1>), blocks, dim3(kBlock), 0, h->stream, h->grid, h->prm.min_points, h->prm.eig_ratio, h->d_counters);
+  else hipLaunchKernelGGL((k_finalise<1>), blocks, dim3(kBlock), 0, h->stream, h->grid, h->prm.min_points, h->prm.eig_ratio, h->d_counters);
   HIP_TRY(hipGetLastError());
   int* hc = (int*)h->h_small;
   HIP_TRY(hipMemcpyAsync(hc, h->d_counters, ndt::kCountInts * sizeof(int), hipMemcpyDeviceToHost, h->stream));
+  // (on its own: the caller's outside count may be on its way into the two words between)
+  HIP_TRY(hipMemcpyAsync(hc + ndt::kCountUnder, h->d_counters + ndt::kCountUnder, sizeof(int), hipMemcpyDeviceToHost, h->stream));
   HIP_TRY(hipStreamSynchronize(h->stream));
   int n_valid_sum = 0, n_over_sum = 0;
   sum_count_shards(hc, &n_valid_sum, &n_over_sum);
   h->n_valid = n_valid_sum;
+  if (sign < 0) { const int32_t rs = check_removal(hc); if (rs != NDT_OK) return rs; }
   if (n_over_sum > 0) { set_error("a target cell holds more than 2^20 points"); return NDT_ERR_CAPACITY; }
   return NDT_OK;
 }
@@ -271,11 +287,11 @@ int32_t read_back(ndt2d_handle* h, const void* d_src, void* h_dst, int nwords) {
 // They add the counter shards and the outside count into d_cnt and d_out.
 
 // Chunk-sorted build (ndt2d_build_sorted.hpp): sort every chunk of the cloud by tile, then one workgroup per tile gathers
-// its runs.  Host geometry: ga = {} (merge = add to the cached sums; the last grid's gather clears `clear_next`, the
-// accumulator half of the next build).  Device geometry: ga, whose chunk sort prologue decides it into ga.out.
+// its runs.  Host geometry: ga = {} (merge = add to the cached sums, or with sign = -1 take the cloud out of them; the
+// last grid's gather clears `clear_next`, the accumulator half of the next build).  Device geometry: ga, whose chunk sort prologue decides it into ga.out.
 int32_t enqueue_sorted_build(ndt2d_handle* h, const float* d_x, const float* d_y, size_t n, const SortPlan& sp, const SplitBufs& sb,
                              int tiles, bool merge, const MoveArgs& mv, const GeomArgs& ga, int* d_cnt, unsigned long long* d_out,
-                             unsigned int* clear_next) {
+                             unsigned int* clear_next, int sign = 1) {
   const GridDev& g = h->grid;
   const GeomDev* dg = ga.out;
   const int ngrid = dg ? 1 : g.ngrid;
@@ -284,7 +300,8 @@ int32_t enqueue_sorted_build(ndt2d_handle* h, const float* d_x, const float* d_y
   for (int q = 0; q < ngrid; ++q) {
     const BinGeom bg = dg ? BinGeom{} : BinGeom{g.gx[q], g.gy[q], g.inv_c, g.W, g.H, ntx, tiles};
     launch_chunk_sort(h, sp, d_x, d_y, n, bg, tiles, mv, q == 0 ? d_out : (unsigned long long*)nullptr, ga, sb);
-    hipLaunchKernelGGL(k_tile_gather, dim3(tiles, split), dim3(kGatherThreads), 0, h->stream, (const float2*)h->d_bxy,
+    const auto gather = sign < 0 ? &k_tile_gather<-1> : &k_tile_gather<1>;
+    hipLaunchKernelGGL(gather, dim3(tiles, split), dim3(kGatherThreads), 0, h->stream, (const float2*)h->d_bxy,
                        (const unsigned int*)h->d_table, sp.nchunks, sp.chunk, g, q, ntx, merge ? 1 : 0, h->prm.min_points,
                        h->prm.eig_ratio, d_cnt, dg, (const GridDev*)ga.grid, sb, q == ngrid - 1 ? clear_next : (unsigned int*)nullptr);
     HIP_TRY(hipGetLastError());
@@ -304,7 +321,7 @@ int32_t ensure_binned_buffers(ndt2d_handle* h, size_t n, int tiles) {
 // add to the cached sums).  Device geometry: dg and dgrid, decided by k_geometry behind the caller's k_build_init, which
 // cleared the tile totals.
 int32_t enqueue_binned_build(ndt2d_handle* h, const float* d_x, const float* d_y, size_t n, int tiles, bool merge, const GeomDev* dg,
-                             const GridDev* dgrid, int* d_cnt, unsigned long long* d_out) {
+                             const GridDev* dgrid, int* d_cnt, unsigned long long* d_out, int sign = 1) {
   const GridDev& g = h->grid;
   const int ngrid = dg ? 1 : g.ngrid;
   const int ntx = dg ? 0 : (g.W + kTile - 1) >> kTileShift;
@@ -323,7 +340,8 @@ int32_t enqueue_binned_build(ndt2d_handle* h, const float* d_x, const float* d_y
     hipLaunchKernelGGL(k_tile_scan, dim3(1), dim3(1024), 0, h->stream, d_total, d_start, d_cursor, dg ? 0 : tiles, dg);
     hipLaunchKernelGGL(k_tile_scatter, dim3((unsigned)nb), dim3(kBinThreads), 2 * tiles * sizeof(unsigned int),
                        h->stream, d_x, d_y, n, bg, d_cursor, h->d_bx, h->d_by, dg);
-    hipLaunchKernelGGL(k_tile_accumulate, dim3(tiles), dim3(kBinThreads), 0, h->stream, h->d_bx, h->d_by, d_start, g, q,
+    const auto tile_kernel = sign < 0 ? &k_tile_accumulate<-1> : &k_tile_accumulate<1>;
+    hipLaunchKernelGGL(tile_kernel, dim3(tiles), dim3(kBinThreads), 0, h->stream, h->d_bx, h->d_by, d_start, g, q,
                        ntx, merge ? 1 : 0, h->prm.min_points, h->prm.eig_ratio, d_cnt, dg, dgrid);
     HIP_TRY(hipGetLastError());
   }
@@ -332,9 +350,11 @@ int32_t enqueue_binned_build(ndt2d_handle* h, const float* d_x, const float* d_y
 
 // a2 + a3 for n points: binned LDS build when the tile histogram fits in LDS (always, below
 // ~2.9 km x 2.9 km at 0.5 m cells), else scattered global atomics + k_finalise.  merge = add to
-// the cached sums (incremental submap update) instead of starting from zero.
+// the cached sums (incremental submap update) instead of starting from zero; sign = -1 (with merge): take the points
+// out of the cached sums again - the same kernels on every path, with the sign (NDT_ERR_INVALID_ARG when the points are
+// not in the map: check_removal).
 int32_t accumulate_and_finalise(ndt2d_handle* h, const float* d_x, const float* d_y, size_t n, bool merge,
-                                unsigned long long* h_outside, const MoveArgs* move = nullptr) {
+                                unsigned long long* h_outside, const MoveArgs* move = nullptr, int sign = 1) {
   TraceRange range(merge ? "ndt2d: submap update (moments + finalise)" : "ndt2d: moments + finalise");
   GridDev& g = h->grid;
   const size_t ncell1 = (size_t)g.W * g.H, ncell = ncell1 * g.ngrid;
@@ -352,13 +372,13 @@ int32_t accumulate_and_finalise(ndt2d_handle* h, const float* d_x, const float* 
     const MoveArgs none{1.f, 0.f, 0.f, 0.f, 0};
     { const int32_t bs = enqueue_sorted_build(h, d_x, d_y, n, sp, sb, ntile, merge, move ? *move : none, GeomArgs{},
                                               reinterpret_cast<int*>(cur), reinterpret_cast<unsigned long long*>(cur + 128),
-                                              reinterpret_cast<unsigned int*>(nxt));
+                                              reinterpret_cast<unsigned int*>(nxt), sign);
       if (bs != NDT_OK) return bs; }
     h->last_ntile = ntile;
     int* hc = (int*)h->h_small;
     unsigned long long* ho = (unsigned long long*)((char*)h->h_small + 128);
     static_assert(ndt::kCountInts * sizeof(int) == 128, "the accumulator halves mirror h_small: counters at 0, outside at 128");
-    { const int32_t ps = read_back(h, cur, hc, 34); if (ps != NDT_OK) return ps; }   // counter shards + outside count
+    { const int32_t ps = read_back(h, cur, hc, ndt::kCountWords); if (ps != NDT_OK) return ps; }   // counter shards, outside count, broken cells
     h->acc_parity ^= 1;
     h->acc_clean = true;
     int n_valid_sum = 0, n_over_sum = 0;
@@ -366,7 +386,7 @@ int32_t accumulate_and_finalise(ndt2d_handle* h, const float* d_x, const float* 
     h->n_valid = merge ? h->n_valid + n_valid_sum : n_valid_sum;       // merge: the gather kernel counts the change, tile by touched tile
     if (h_outside) *h_outside = *ho;
     if (n_over_sum > 0) { set_error("a target cell holds more than 2^20 points"); return NDT_ERR_CAPACITY; }
-    return NDT_OK;
+    return sign < 0 ? check_removal(hc) : NDT_OK;
   }
   // the other paths take the points as they are: move them into the map frame first
   if (move && move->use) {
@@ -380,29 +400,30 @@ int32_t accumulate_and_finalise(ndt2d_handle* h, const float* d_x, const float* 
   if (h->use_binned_build && ntile_ll <= kBinMaxTiles && n <= 0xFFFFFFFFull) {
     const int ntile = (int)ntile_ll;
     { const int32_t es = ensure_binned_buffers(h, n, ntile); if (es != NDT_OK) return es; }
-    HIP_TRY(hipMemsetAsync(h->d_counters, 0, ndt::kCountInts * sizeof(int), h->stream));
-    { const int32_t bs = enqueue_binned_build(h, d_x, d_y, n, ntile, merge, nullptr, nullptr, h->d_counters, h->d_outside);
+    HIP_TRY(hipMemsetAsync(h->d_counters, 0, ndt::kCountWords * sizeof(int), h->stream));
+    { const int32_t bs = enqueue_binned_build(h, d_x, d_y, n, ntile, merge, nullptr, nullptr, h->d_counters, h->d_outside, sign);
       if (bs != NDT_OK) return bs; }
     h->last_ntile = ntile;
     int* hc = (int*)h->h_small;
     unsigned long long* ho = (unsigned long long*)((char*)h->h_small + 128);
-    HIP_TRY(hipMemcpyAsync(hc, h->d_counters, ndt::kCountInts * sizeof(int), hipMemcpyDeviceToHost, h->stream));
-    HIP_TRY(hipMemcpyAsync(ho, h->d_outside, sizeof(unsigned long long), hipMemcpyDeviceToHost, h->stream));
+    HIP_TRY(hipMemcpyAsync(hc, h->d_counters, ndt::kCountWords * sizeof(int), hipMemcpyDeviceToHost, h->stream));
+    HIP_TRY(hipMemcpyAsync(ho, h->d_outside, sizeof(unsigned long long), hipMemcpyDeviceToHost, h->stream));   // (over the two spare words)
     HIP_TRY(hipStreamSynchronize(h->stream));
     int n_valid_sum = 0, n_over_sum = 0;
     sum_count_shards(hc, &n_valid_sum, &n_over_sum);
     h->n_valid = n_valid_sum;
     if (h_outside) *h_outside = *ho;
     if (n_over_sum > 0) { set_error("a target cell holds more than 2^20 points"); return NDT_ERR_CAPACITY; }
-    return NDT_OK;
+    return sign < 0 ? check_removal(hc) : NDT_OK;
   }
   // fallback: scattered global atomics
   if (!merge) HIP_TRY(hipMemsetAsync(g.acc, 0, ncell * sizeof(CellAcc), h->stream));
-  hipLaunchKernelGGL(k_accumulate, dim3(stream_blocks(n)), dim3(kBlock), 0, h->stream, d_x, d_y, n, g, h->d_outside);
+  if (sign < 0) hipLaunchKernelGGL((k_accumulate<-1>), dim3(stream_blocks(n)), dim3(kBlock), 0, h->stream, d_x, d_y, n, g, h->d_outside);
+  else hipLaunchKernelGGL((k_accumulate<1>), dim3(stream_blocks(n)), dim3(kBlock), 0, h->stream, d_x, d_y, n, g, h->d_outside);
   HIP_TRY(hipGetLastError());
   unsigned long long* ho = (unsigned long long*)((char*)h->h_small + 128);
   HIP_TRY(hipMemcpyAsync(ho, h->d_outside, sizeof(unsigned long long), hipMemcpyDeviceToHost, h->stream));
-  const int32_t st = finalise_grid(h);
+  const int32_t st = finalise_grid(h, sign);
   if (h_outside) *h_outside = *ho;
   return st;
 }
@@ -946,7 +967,7 @@ int32_t ndt2d_create(const ndt2d_params* p, int32_t device_id, ndt2d_handle** ou
   if (hipSetDevice(device_id) != hipSuccess) return fail(NDT_ERR_HIP);
   if (hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking) != hipSuccess) return fail(NDT_ERR_HIP);
   if (hipMalloc((void**)&h->d_bounds, 4 * sizeof(unsigned int)) != hipSuccess) return fail(NDT_ERR_ALLOC);
-  if (hipMalloc((void**)&h->d_counters, ndt::kCountInts * sizeof(int)) != hipSuccess) return fail(NDT_ERR_ALLOC);
+  if (hipMalloc((void**)&h->d_counters, ndt::kCountWords * sizeof(int)) != hipSuccess) return fail(NDT_ERR_ALLOC);
   if (hipMalloc((void**)&h->d_parts, kBoundsParts * sizeof(float4)) != hipSuccess) return fail(NDT_ERR_ALLOC);
   if (hipMalloc((void**)&h->d_acc2, 512) != hipSuccess) return fail(NDT_ERR_ALLOC);
   {   // k_chunk_sort: 32 KB of points + up to 32 KB of tile histogram, just over the 64 KB a kernel gets without asking
@@ -1067,10 +1088,15 @@ int32_t ndt2d_reserve_target(ndt2d_handle* h, double xmin, double ymin, double x
   return upload_static(h);
 }
 
-int32_t ndt2d_add_target_points_dev(ndt2d_handle* h, const float* d_x, const float* d_y, size_t n,
-                                    const double pose[3], size_t* n_outside, void* stream) {
+namespace {
+
+// ndt2d_add_target_points_dev (sign = 1) and ndt2d_remove_target_points_dev (sign = -1): one submap update, with a sign
+int32_t update_target_points_dev(ndt2d_handle* h, const float* d_x, const float* d_y, size_t n, const double pose[3],
+                                 size_t* n_outside, void* stream, int sign) {
   if (!h || !d_x || !d_y || n == 0) return NDT_ERR_INVALID_ARG;
   if (!h->has_target) return NDT_ERR_NO_TARGET;
+  // (a wrapped count is told from a full cell by its size: removed_cell_broken, ndt2d_kernels.hpp)
+  if (sign < 0 && n >= 0xFFF00000ull) { set_error("more points to remove than a call can take (2^32 - 2^20)"); return NDT_ERR_INVALID_ARG; }
   HIP_TRY(hipSetDevice(h->device));
   { const int32_t fs = finish_chunk_run(h); if (fs != NDT_OK) return fs; }
   grid_changed(h);
@@ -1080,11 +1106,32 @@ int32_t ndt2d_add_target_points_dev(ndt2d_handle* h, const float* d_x, const flo
   MoveArgs mv{1.f, 0.f, 0.f, 0.f, 0};
   if (pose) { mv.cs = (float)std::cos(pose[2]); mv.sn = (float)std::sin(pose[2]); mv.tx = (float)pose[0]; mv.ty = (float)pose[1]; mv.use = 1; }
   unsigned long long outside = 0;
-  const int32_t fs = accumulate_and_finalise(h, d_x, d_y, n, /*merge=*/true, &outside, &mv);
+  const int32_t fs = accumulate_and_finalise(h, d_x, d_y, n, /*merge=*/true, &outside, &mv, sign);
   if (n_outside) *n_outside = (size_t)outside;
   if (fs != NDT_OK) { h->has_target = false; return fs; }
-  h->n_points += n - (size_t)outside;
+  if (sign < 0) h->n_points -= n - (size_t)outside;
+  else h->n_points += n - (size_t)outside;
   return NDT_OK;          // geometry, storage and parameters are unchanged: the device context stays as it is
+}
+
+}  // namespace
+
+int32_t ndt2d_add_target_points_dev(ndt2d_handle* h, const float* d_x, const float* d_y, size_t n,
+                                    const double pose[3], size_t* n_outside, void* stream) {
+  return update_target_points_dev(h, d_x, d_y, n, pose, n_outside, stream, 1);
+}
+
+int32_t ndt2d_remove_target_points_dev(ndt2d_handle* h, const float* d_x, const float* d_y, size_t n,
+                                       const double pose[3], size_t* n_outside, void* stream) {
+  return update_target_points_dev(h, d_x, d_y, n, pose, n_outside, stream, -1);
+}
+
+int32_t ndt2d_remove_target_points(ndt2d_handle* h, const float* x, const float* y, size_t n, size_t* n_outside) {
+  if (!h || !x || !y || n == 0) return NDT_ERR_INVALID_ARG;
+  if (!h->has_target) return NDT_ERR_NO_TARGET;
+  HIP_TRY(hipSetDevice(h->device));
+  { const int32_t ss = stage_target(h, x, y, n); if (ss != NDT_OK) return ss; }
+  return ndt2d_remove_target_points_dev(h, h->d_tx, h->d_ty, n, nullptr, n_outside, nullptr);
 }
 
 int32_t ndt2d_add_target_points(ndt2d_handle* h, const float* x, const float* y, size_t n, size_t* n_outside) {

@@ -205,7 +205,9 @@ __global__ __launch_bounds__(kBinThreads) void k_tile_scatter(const float* __res
 }
 
 // P3: one workgroup per tile.  LDS sums (+ the existing global sums when adding to a cached
-// grid), finalise, coalesced write-back of sums and records.
+// grid), finalise, coalesced write-back of sums and records.  SIGN = -1 (with merge): the points are taken out of the
+// cached sums; a cell that breaks (removed_cell_broken) is counted in counters[kCountUnder].
+template <int SIGN>
 __global__ __launch_bounds__(kBinThreads) void k_tile_accumulate(const float* __restrict__ bx, const float* __restrict__ by,
                                                                   const unsigned int* __restrict__ tile_start, GridDev g,
                                                                   int q, int ntx, int merge, int min_points,
@@ -254,17 +256,17 @@ __global__ __launch_bounds__(kBinThreads) void k_tile_accumulate(const float* __
         const int ux = fix_coord(px[u], cell_centre(ox, ix, g.cell), g.fix_scale);
         const int uy = fix_coord(py[u], cell_centre(oy, iy, g.cell), g.fix_scale);
         const int c = ((iy - ty0) << kTileShift) + (ix - tx0);
-        atomicAdd(&s_n[c], 1u);
-        atomicAdd(&s_sum[0][c], (unsigned long long)(long long)ux);
-        atomicAdd(&s_sum[1][c], (unsigned long long)(long long)uy);
-        atomicAdd(&s_sum[2][c], prod64(ux, ux));
-        atomicAdd(&s_sum[3][c], prod64(ux, uy));
-        atomicAdd(&s_sum[4][c], prod64(uy, uy));
+        atomicAdd(&s_n[c], signed_one<SIGN>());
+        atomicAdd(&s_sum[0][c], signed_term<SIGN>((unsigned long long)(long long)ux));
+        atomicAdd(&s_sum[1][c], signed_term<SIGN>((unsigned long long)(long long)uy));
+        atomicAdd(&s_sum[2][c], signed_term<SIGN>(prod64(ux, ux)));
+        atomicAdd(&s_sum[3][c], signed_term<SIGN>(prod64(ux, uy)));
+        atomicAdd(&s_sum[4][c], signed_term<SIGN>(prod64(uy, uy)));
       }
     }
   }
   __syncthreads();
-  int nvalid = 0, nover = 0;
+  int nvalid = 0, nover = 0, nunder = 0;
   for (int c = threadIdx.x; c < kTileCells; c += kBinThreads) {
     const int ix = tx0 + (c & (kTile - 1)), iy = ty0 + (c >> kTileShift);
     if (ix < g.W && iy < g.H) {
@@ -274,7 +276,8 @@ __global__ __launch_bounds__(kBinThreads) void k_tile_accumulate(const float* __
       a.sx = (long long)s_sum[0][c]; a.sy = (long long)s_sum[1][c]; a.sxx = (long long)s_sum[2][c];
       a.sxy = (long long)s_sum[3][c]; a.syy = (long long)s_sum[4][c]; a.n = n; a.pad = 0u;
       float4 ra = make_float4(0.f, 0.f, 0.f, 0.f), rb = make_float4(0.f, 0.f, 0.f, 0.f);
-      if (n > kMaxCellCount) nover++;
+      if (SIGN < 0 && removed_cell_broken(n, (unsigned long long)(a.sx | a.sy | a.sxx | a.sxy | a.syy))) nunder++;
+      else if (n > kMaxCellCount) nover++;
       else if ((int)n >= min_points &&
                finalise_sums((int)n, a.sx, a.sy, a.sxx, a.sxy, a.syy, cell_centre(ox, ix, g.cell),
                              cell_centre(oy, iy, g.cell), g.fix_scale, min_points, eig_ratio, ra, rb))
@@ -285,6 +288,7 @@ __global__ __launch_bounds__(kBinThreads) void k_tile_accumulate(const float* __
     }
   }
   block_count_add(counters, nvalid, nover);       // one add per workgroup, sharded (ndt_device.hpp)
+  if (SIGN < 0 && nunder) atomicAdd(&counters[kCountUnder], nunder);      // (a removal of points that are not in the map)
 }
 
 }  // namespace ndt

@@ -321,6 +321,13 @@ __device__ unsigned long long g_gather_wave_end[1024][16];   // ... and the end 
 
 // ---- gather + accumulate + finalise: one workgroup per tile ------------------------------------------------------
 // counters (sharded, ndt_device.hpp) += valid cells (merge: the CHANGE in valid cells of this tile), overflowed cells.
+// SIGN = -1 (with merge): the cloud is taken out of the cached sums - its points enter the LDS sums negated, everything
+// else runs as it stands.  A workgroup's share of a shared tile then holds counts of -k mod 2^32, which are non-zero
+// exactly where k is (k < 2^32), so the list hand-off's "non-empty" test picks the same cells, and the finishing
+// workgroup's adds are the same wrapping adds.  The tiles a removal skips are the tiles an update skips: the sort decides
+// that, and it counts points.  The change in valid cells may be negative; a cell the removal breaks
+// (removed_cell_broken) is counted in counters[kCountUnder].
+template <int SIGN>
 __global__ __launch_bounds__(kGatherThreads) void k_tile_gather(const float2* __restrict__ binned, const unsigned int* __restrict__ table,
                                                                  int nchunks, int chunk_points, GridDev g, int q, int ntx, int merge,
                                                                  int min_points, double eig_ratio, int* __restrict__ counters,
@@ -354,7 +361,7 @@ __global__ __launch_bounds__(kGatherThreads) void k_tile_gather(const float2* __
   const int sub = blockIdx.y;
   // the NEXT build's accumulators (counter shards + outside count: the other half of a ping-pong pair, which nothing adds
   // to in this call) are cleared here instead of by two fill launches in front of every build
-  if (zero_next && tile == 0 && sub == 0 && threadIdx.x < kCountInts + 2) zero_next[threadIdx.x] = 0u;
+  if (zero_next && tile == 0 && sub == 0 && threadIdx.x < kCountWords) zero_next[threadIdx.x] = 0u;
   if (__builtin_amdgcn_readfirstlane(sb.touched[tile]) != sb.seq && (sub > 0 || merge)) return;    // nothing arrived (uniform)
   if (threadIdx.x == 0) { s_total = 0u; s_list = 0u; }
   __syncthreads();
@@ -397,12 +404,12 @@ __global__ __launch_bounds__(kGatherThreads) void k_tile_gather(const float2* __
     const int ux = fix_coord(p.x, cell_centre(ox, cx, cell_size), fix_scale);
     const int uy = fix_coord(p.y, cell_centre(oy, cy, cell_size), fix_scale);
     const int c = (cy - ty0) * kTileStride + (cx - tx0);
-    atomicAdd(&s_n[c], 1u);
-    atomicAdd(&s_sum[0][c], (unsigned long long)(long long)ux);
-    atomicAdd(&s_sum[1][c], (unsigned long long)(long long)uy);
-    atomicAdd(&s_sum[2][c], prod64(ux, ux));
-    atomicAdd(&s_sum[3][c], prod64(ux, uy));
-    atomicAdd(&s_sum[4][c], prod64(uy, uy));
+    atomicAdd(&s_n[c], signed_one<SIGN>());
+    atomicAdd(&s_sum[0][c], signed_term<SIGN>((unsigned long long)(long long)ux));
+    atomicAdd(&s_sum[1][c], signed_term<SIGN>((unsigned long long)(long long)uy));
+    atomicAdd(&s_sum[2][c], signed_term<SIGN>(prod64(ux, ux)));
+    atomicAdd(&s_sum[3][c], signed_term<SIGN>(prod64(ux, uy)));
+    atomicAdd(&s_sum[4][c], signed_term<SIGN>(prod64(uy, uy)));
   };
   // A wave per run, four runs in flight: wave w takes the runs w, w + 16, ... of this tile.  The loads of four runs
   // are issued before any point is summed - one load per lane and run covers a run of up to 64 points, which is
@@ -512,14 +519,15 @@ __global__ __launch_bounds__(kGatherThreads) void k_tile_gather(const float2* __
     __syncthreads();                                           // the write-back below reads other threads' slots
   }
   NDT_STAMP(3);
-  int nvalid = 0, nover = 0;
+  int nvalid = 0, nover = 0, nunder = 0;
   float4 ra = make_float4(0.f, 0.f, 0.f, 0.f), rb = make_float4(0.f, 0.f, 0.f, 0.f);
   if (in_grid) {
     const unsigned int n = s_n[slot];
     const long long sx = (long long)s_sum[0][slot], sy = (long long)s_sum[1][slot], sxx = (long long)s_sum[2][slot],
                     sxy = (long long)s_sum[3][slot], syy = (long long)s_sum[4][slot];
     if (merge) nvalid -= rec[2 * cell + 1].z > 0.f ? 1 : 0;       // a valid record carries its point count there
-    if (n > kMaxCellCount) nover++;
+    if (SIGN < 0 && removed_cell_broken(n, (unsigned long long)(sx | sy | sxx | sxy | syy))) nunder++;
+    else if (n > kMaxCellCount) nover++;
     else if ((int)n >= min_points &&
              finalise_sums((int)n, sx, sy, sxx, sxy, syy, cell_centre(ox, ix, cell_size), cell_centre(oy, iy, cell_size),
                            fix_scale, min_points, eig_ratio, ra, rb))
@@ -559,6 +567,7 @@ __global__ __launch_bounds__(kGatherThreads) void k_tile_gather(const float2* __
   }
   NDT_STAMP(5);
   block_count_add(counters, nvalid, nover);       // one add per workgroup, sharded (ndt_device.hpp)
+  if (SIGN < 0 && nunder) atomicAdd(&counters[kCountUnder], nunder);      // (a removal of points that are not in the map)
 #if defined(NDT_BUILD_PHASE_CLOCKS)
   if (lane == 0) g_gather_wave_end[blockIdx.x & 1023][wave] = __builtin_amdgcn_s_memrealtime();
 #endif

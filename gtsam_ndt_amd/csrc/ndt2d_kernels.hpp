@@ -250,12 +250,22 @@ __device__ __forceinline__ bool finalise_sums(int n, long long sx, long long sy,
   return true;
 }
 
+// What a removal (SIGN = -1 of the build kernels) must not leave in a cell: a count that went below zero - it wrapped, and
+// a cell of a usable grid never holds more than kMaxCellCount points, so anything above that is a wrap as long as the
+// removed cloud has fewer than 2^32 - 2^20 points (the entry points see to that) - or a count of zero with a sum left.
+// Either shows that points were removed that are not in the map.  any_sum = the cell's sums or-ed together.
+__device__ __forceinline__ bool removed_cell_broken(unsigned int n, unsigned long long any_sum) {
+  return n > kMaxCellCount || (n == 0u && any_sum != 0ull);
+}
+
 // ------------------------------------------------------------------ a1+a2 accumulate
 // Exact, order-independent per-cell sufficient statistics: cell-centred coordinates
 // quantised to c*2^-22 and summed with 64-bit integer atomics.  Integer addition is
 // associative, so the sums (and everything derived from them) are bitwise identical from
 // run to run and under any point order; merging two clouds' sums is the exact form of the
 // Chan/Welford pairwise update.
+// SIGN = -1: the points' contributions are taken out of the sums (ndt_device.hpp, "a build with a sign").
+template <int SIGN>
 __global__ __launch_bounds__(kBlock) void k_accumulate(const float* __restrict__ x,
                                                         const float* __restrict__ y, size_t n,
                                                         GridDev g,
@@ -276,12 +286,12 @@ __global__ __launch_bounds__(kBlock) void k_accumulate(const float* __restrict__
         const int ux = fix_coord(px, cell_centre(ox, ix, g.cell), g.fix_scale);
         const int uy = fix_coord(py, cell_centre(oy, iy, g.cell), g.fix_scale);
         CellAcc* c = g.acc + (q * ncell + (size_t)iy * g.W + ix);
-        atomicAdd(&c->n, 1u);
-        atomicAdd((unsigned long long*)&c->sx, (unsigned long long)(long long)ux);
-        atomicAdd((unsigned long long*)&c->sy, (unsigned long long)(long long)uy);
-        atomicAdd((unsigned long long*)&c->sxx, prod64(ux, ux));
-        atomicAdd((unsigned long long*)&c->sxy, prod64(ux, uy));
-        atomicAdd((unsigned long long*)&c->syy, prod64(uy, uy));
+        atomicAdd(&c->n, signed_one<SIGN>());
+        atomicAdd((unsigned long long*)&c->sx, signed_term<SIGN>((unsigned long long)(long long)ux));
+        atomicAdd((unsigned long long*)&c->sy, signed_term<SIGN>((unsigned long long)(long long)uy));
+        atomicAdd((unsigned long long*)&c->sxx, signed_term<SIGN>(prod64(ux, ux)));
+        atomicAdd((unsigned long long*)&c->sxy, signed_term<SIGN>(prod64(ux, uy)));
+        atomicAdd((unsigned long long*)&c->syy, signed_term<SIGN>(prod64(uy, uy)));
       }
     }
     if (!any) outside++;
@@ -290,9 +300,11 @@ __global__ __launch_bounds__(kBlock) void k_accumulate(const float* __restrict__
 }
 
 // ------------------------------------------------------------------------- a3 finalise
-// One thread per cell.
+// One thread per cell.  SIGN = -1 (behind a removal): a cell the removal broke is counted in counters[kCountUnder].
+template <int SIGN>
 __global__ __launch_bounds__(kBlock) void k_finalise(GridDev g, int min_points, double eig_ratio,
                                                       int* __restrict__ counters /*[kCountShards][2]: valid, overflow*/) {
+  int* const under = counters + kCountUnder;
   counters = count_shard(counters);
   const size_t ncell = (size_t)g.W * g.H;
   const size_t k = (size_t)blockIdx.x * kBlock + threadIdx.x;
@@ -300,7 +312,11 @@ __global__ __launch_bounds__(kBlock) void k_finalise(GridDev g, int min_points, 
   const CellAcc c = g.acc[k];
   float4 ra, rb;
   bool ok = false;
-  if (c.n > kMaxCellCount) {
+  if (SIGN < 0 && removed_cell_broken(c.n, (unsigned long long)(c.sx | c.sy | c.sxx | c.sxy | c.syy))) {
+    atomicAdd(under, 1);                           // (only a removal of points that are not in the map comes here)
+    ra = make_float4(0.f, 0.f, 0.f, 0.f);
+    rb = make_float4(0.f, 0.f, 0.f, 0.f);
+  } else if (c.n > kMaxCellCount) {
     atomicAdd(&counters[1], 1);
     ra = make_float4(0.f, 0.f, 0.f, 0.f);
     rb = make_float4(0.f, 0.f, 0.f, 0.f);

@@ -82,8 +82,8 @@ int32_t upload_static3(ndt3d_handle* h) {
 
 // The device words and buffers of a binned build of n points over at most `ntile` tiles.
 // One block of device words carries everything a build adds into, so that ONE fill clears it (round 2: four) and one
-// publish brings the results back:  counter shards [32] | outside count (u64) | pad to 64 (the arrival count of k_tile_count3's
-// workgroups at word 41, a device-decided geometry from word kGeom3Word) | tile totals [ntile] | tickets of the shared tiles [ntile] |
+// publish brings the results back:  counter shards [32] | outside count (u64) | pad to 64 (the voxels a removal broke at word
+// kCountUnder = 34, the arrival count of k_tile_count3's workgroups at word 41, a device-decided geometry from word kGeom3Word) | tile totals [ntile] | tickets of the shared tiles [ntile] |
 // tile starts [ntile + 1] | scatter cursors [ntile] | number of (tile, share) workgroups [1] | their list [wg_bound]
 struct Build3Bufs {
   int* d_cnt; unsigned long long* d_out;
@@ -123,7 +123,7 @@ int32_t ensure_build3_bufs(ndt3d_handle* h, size_t n, int ntile, bool binned, Bu
 // scatter -> tile kernel, for a geometry the host knows (ga = {}: the grid of h->grid; merge = add to the cached sums, mv =
 // the motion applied on the way in) or for one the count kernel's prologue decides into ga.out (set_target3_single_sync).
 int32_t enqueue_binned_build3(ndt3d_handle* h, const float* dx, const float* dy, const float* dz, size_t n, int tiles,
-                              const Build3Bufs& B, bool merge, const ndt::Move3Args& mv, const ndt::Geom3Args& ga) {
+                              const Build3Bufs& B, bool merge, const ndt::Move3Args& mv, const ndt::Geom3Args& ga, int sign = 1) {
   using namespace ndt;
   const Grid3Dev& g = h->grid;
   const GeomDev3* dg = ga.out;
@@ -136,7 +136,8 @@ int32_t enqueue_binned_build3(ndt3d_handle* h, const float* dx, const float* dy,
   hipLaunchKernelGGL(k_tile_scatter3, dim3((unsigned)nb), dim3(kBinThreads), 2 * tiles * sizeof(unsigned int), h->stream, dx, dy, dz,
                      n, bg, B.d_cursor, h->d_b[0], h->d_b[1], h->d_b[2], dg, mv);
   // (no fill of the grid's sums: the workgroup that finishes a tile writes every voxel's sums, empty ones included)
-  hipLaunchKernelGGL(k_tile_accumulate3, dim3((unsigned)B.wg_bound), dim3(kBinThreads), 0, h->stream, h->d_b[0], h->d_b[1], h->d_b[2],
+  const auto tile_kernel = sign < 0 ? &k_tile_accumulate3<-1> : &k_tile_accumulate3<1>;       // sign = -1 (with merge): a removal
+  hipLaunchKernelGGL(tile_kernel, dim3((unsigned)B.wg_bound), dim3(kBinThreads), 0, h->stream, h->d_b[0], h->d_b[1], h->d_b[2],
                      B.d_start, g, ntx, nty, merge ? 1 : 0, h->prm.min_points, h->prm.eig_ratio, B.d_cnt, B.d_ticket, B.sb,
                      (const unsigned int*)B.d_wgtotal, (const unsigned int*)B.d_wgmap, dg, (const Grid3Dev*)ga.grid);
   HIP_TRY(hipGetLastError());
@@ -161,9 +162,10 @@ int32_t read_back3(ndt3d_handle* h, unsigned int* h_dst, int nwords, int* flag, 
 
 // a2 + a3 for n points into the grid whose geometry and storage are set: binned LDS build, or
 // scattered global atomics for maps beyond the tile histogram.  merge = add to the cached sums
-// (incremental submap update) instead of starting from zero.
+// (incremental submap update) instead of starting from zero; sign = -1 (with merge): take the points out of the cached
+// sums again - the same kernels with the sign (NDT_ERR_INVALID_ARG when the points are not in the map).
 int32_t accumulate3(ndt3d_handle* h, const float* dx, const float* dy, const float* dz, size_t n, bool merge,
-                    unsigned long long* h_outside, const ndt::Rigid3F* move = nullptr) {
+                    unsigned long long* h_outside, const ndt::Rigid3F* move = nullptr, int sign = 1) {
   using namespace ndt;
   Grid3Dev& g = h->grid;
   const size_t ncell = (size_t)g.W * g.H * g.D;
@@ -180,7 +182,7 @@ int32_t accumulate3(ndt3d_handle* h, const float* dx, const float* dy, const flo
   if (binned) {
     Move3Args mv{};
     if (move) { mv.T = *move; mv.use = 1; }
-    { const int32_t bs = enqueue_binned_build3(h, dx, dy, dz, n, ntile, B, merge, mv, Geom3Args{}); if (bs != NDT_OK) return bs; }
+    { const int32_t bs = enqueue_binned_build3(h, dx, dy, dz, n, ntile, B, merge, mv, Geom3Args{}, sign); if (bs != NDT_OK) return bs; }
     h->last_ntile = ntile;
   } else {
     if (move) {                                      // this path takes the points as they are: move them first
@@ -191,21 +193,27 @@ int32_t accumulate3(ndt3d_handle* h, const float* dx, const float* dy, const flo
       dx = h->d_t[0]; dy = h->d_t[1]; dz = h->d_t[2];
     }
     if (!merge) HIP_TRY(hipMemsetAsync(g.acc, 0, ncell * sizeof(CellAcc3), h->stream));
-    hipLaunchKernelGGL(k_accumulate3, dim3(stream_blocks(n)), dim3(kBlock), 0, h->stream, dx, dy, dz, n, g, B.d_out);
+    const auto accumulate = sign < 0 ? &k_accumulate3<-1> : &k_accumulate3<1>;
+    const auto finalise = sign < 0 ? &k_finalise3<-1> : &k_finalise3<1>;
+    hipLaunchKernelGGL(accumulate, dim3(stream_blocks(n)), dim3(kBlock), 0, h->stream, dx, dy, dz, n, g, B.d_out);
     HIP_TRY(hipGetLastError());
-    hipLaunchKernelGGL(k_finalise3, dim3((unsigned)((ncell + kBlock - 1) / kBlock)), dim3(kBlock), 0, h->stream, g,
+    hipLaunchKernelGGL(finalise, dim3((unsigned)((ncell + kBlock - 1) / kBlock)), dim3(kBlock), 0, h->stream, g,
                        h->prm.min_points, h->prm.eig_ratio, B.d_cnt);
     HIP_TRY(hipGetLastError());
   }
   // counter shards and outside count to the host through pinned memory and a flag (as the 2D build)
   int* hc = (int*)h->h_small;
   unsigned long long* ho = (unsigned long long*)((char*)h->h_small + 128);
-  { const int32_t rs = read_back3(h, (unsigned int*)hc, 34, small_flag(h->h_small), B.zero_words); if (rs != NDT_OK) return rs; }
+  { const int32_t rs = read_back3(h, (unsigned int*)hc, kCountWords, small_flag(h->h_small), B.zero_words); if (rs != NDT_OK) return rs; }
   if (h_outside) *h_outside = *ho;
   int n_valid_sum = 0, n_over_sum = 0;
   sum_count_shards(hc, &n_valid_sum, &n_over_sum);
   h->n_valid = n_valid_sum;
   if (n_over_sum > 0) { set_error("a target cell holds more than 2^20 points"); return NDT_ERR_CAPACITY; }
+  if (sign < 0 && hc[kCountUnder] > 0) {
+    set_error("removed points are not in the target: a voxel's count fell below zero, or reached zero with sums left");
+    return NDT_ERR_INVALID_ARG;
+  }
   return NDT_OK;
 }
 
@@ -643,10 +651,13 @@ int32_t ndt3d_reserve_target(ndt3d_handle* h, const double lo[3], const double h
   return upload_static3(h);
 }
 
-int32_t ndt3d_add_target_points_dev(ndt3d_handle* h, const float* d_x, const float* d_y, const float* d_z, size_t n,
-                                    const double pose[6], size_t* n_outside, void* stream) {
+// ndt3d_add_target_points_dev (sign = 1) and ndt3d_remove_target_points_dev (sign = -1): one submap update, with a sign
+static int32_t update_target_points3_dev(ndt3d_handle* h, const float* d_x, const float* d_y, const float* d_z, size_t n,
+                                         const double pose[6], size_t* n_outside, void* stream, int sign) {
   if (!h || !d_x || !d_y || !d_z || n == 0) return NDT_ERR_INVALID_ARG;
   if (!h->has_target) return NDT_ERR_NO_TARGET;
+  // (a wrapped count is told from a full voxel by its size: removed_cell_broken, ndt2d_kernels.hpp)
+  if (sign < 0 && n >= 0xFFF00000ull) { set_error("more points to remove than a call can take (2^32 - 2^20)"); return NDT_ERR_INVALID_ARG; }
   HIP_TRY(hipSetDevice(h->device));
   { const int32_t fs = finish_align3(h); if (fs != NDT_OK) return fs; }
   if (stream) HIP_TRY(ndt::order_after(h->stream, (hipStream_t)stream));
@@ -663,10 +674,28 @@ int32_t ndt3d_add_target_points_dev(ndt3d_handle* h, const float* d_x, const flo
   }
   unsigned long long outside = 0;
   grid_changed3(h);
-  const int32_t fs = accumulate3(h, p[0], p[1], p[2], n, /*merge=*/true, &outside, pose ? &T : nullptr);
+  const int32_t fs = accumulate3(h, p[0], p[1], p[2], n, /*merge=*/true, &outside, pose ? &T : nullptr, sign);
   if (n_outside) *n_outside = (size_t)outside;
   if (fs != NDT_OK) { h->has_target = false; return fs; }
   return NDT_OK;          // geometry, storage and parameters are unchanged: the device context stays as it is
+}
+
+int32_t ndt3d_add_target_points_dev(ndt3d_handle* h, const float* d_x, const float* d_y, const float* d_z, size_t n,
+                                    const double pose[6], size_t* n_outside, void* stream) {
+  return update_target_points3_dev(h, d_x, d_y, d_z, n, pose, n_outside, stream, 1);
+}
+
+int32_t ndt3d_remove_target_points_dev(ndt3d_handle* h, const float* d_x, const float* d_y, const float* d_z, size_t n,
+                                       const double pose[6], size_t* n_outside, void* stream) {
+  return update_target_points3_dev(h, d_x, d_y, d_z, n, pose, n_outside, stream, -1);
+}
+
+int32_t ndt3d_remove_target_points(ndt3d_handle* h, const float* x, const float* y, const float* z, size_t n, size_t* n_outside) {
+  if (!h || !x || !y || !z || n == 0) return NDT_ERR_INVALID_ARG;
+  if (!h->has_target) return NDT_ERR_NO_TARGET;
+  HIP_TRY(hipSetDevice(h->device));
+  { const int32_t ss = stage_target3(h, x, y, z, n); if (ss != NDT_OK) return ss; }
+  return ndt3d_remove_target_points_dev(h, h->d_t[0], h->d_t[1], h->d_t[2], n, nullptr, n_outside, nullptr);
 }
 
 int32_t ndt3d_set_target_dev(ndt3d_handle* h, const float* d_x, const float* d_y, const float* d_z, size_t n, void* stream) {

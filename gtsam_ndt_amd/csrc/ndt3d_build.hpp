@@ -307,6 +307,10 @@ __device__ unsigned long long g_tile3_stamps[4096][8];       // tools-only: 100 
 __device__ __forceinline__ bool finalise_sums3(const CellAcc3& c, double cx, double cy, double cz, double fix_scale,
                                                int min_points, double eig_ratio, float4& ra, float4& rb, float4& rc);
 
+// SIGN = -1 (with merge): the cloud is taken out of the cached sums.  The point loop is the same; the private copies fold
+// into the tile's sums with the sign, so a share's slab holds the negated sums and the finishing workgroup adds slabs and
+// cached sums up as before.  A voxel the removal breaks (removed_cell_broken) is counted in counters[kCountUnder].
+template <int SIGN>
 __global__ __launch_bounds__(kBinThreads) void k_tile_accumulate3(const float* __restrict__ bx, const float* __restrict__ by,
                                                                    const float* __restrict__ bz,
                                                                    const unsigned int* __restrict__ tile_start, Grid3Dev g,
@@ -404,13 +408,13 @@ __global__ __launch_bounds__(kBinThreads) void k_tile_accumulate3(const float* _
     unsigned long long tot = 0ull;
 #pragma unroll
     for (int k = 0; k < kCopies3; ++k) tot += s_part[e * kCopies3 + ((k + threadIdx.x) & (kCopies3 - 1))];   // (rotated: no two lanes on a bank)
-    (&s_sum[0][0])[e] += tot;
+    (&s_sum[0][0])[e] += signed_term<SIGN>(tot);
   }
   if (threadIdx.x < kTile3Cells) {
     unsigned int tot = 0u;
 #pragma unroll
     for (int k = 0; k < kCopies3; ++k) tot += s_npart[threadIdx.x * kCopies3 + ((k + threadIdx.x) & (kCopies3 - 1))];
-    s_n[threadIdx.x] += tot;
+    s_n[threadIdx.x] += SIGN > 0 ? tot : 0u - tot;
   }
   __syncthreads();
   NDT_STAMP3(2);
@@ -485,7 +489,7 @@ __global__ __launch_bounds__(kBinThreads) void k_tile_accumulate3(const float* _
     }
   }
   NDT_STAMP3(3);
-  int nvalid = 0;
+  int nvalid = 0, nunder = 0;
   for (int c = threadIdx.x; c < kTile3Cells; c += kBinThreads) {
     const int ix = tx0 + (c & ((1 << kT3x) - 1)), iy = ty0 + ((c >> kT3x) & ((1 << kT3y) - 1)), iz = tz0 + (c >> (kT3x + kT3y));
     if (ix < g.W && iy < g.H && iz < g.D) {
@@ -497,7 +501,8 @@ __global__ __launch_bounds__(kBinThreads) void k_tile_accumulate3(const float* _
       for (int j = 0; j < 6; ++j) a.ss[j] = (long long)s_sum[3 + j][c];
       a.n = s_n[c]; a.pad = 0u;
       float4 ra = make_float4(0.f, 0.f, 0.f, 0.f), rb = ra, rc = ra;
-      if (a.n > kMaxCellCount) nover++;
+      if (SIGN < 0 && removed_cell_broken(a.n, any_sum3(a))) nunder++;
+      else if (a.n > kMaxCellCount) nover++;
       else if (finalise_sums3(a, cell_centre(g.ox, ix, g.cell), cell_centre(g.oy, iy, g.cell), cell_centre(g.oz, iz, g.cell),
                               g.fix_scale, min_points, eig_ratio, ra, rb, rc))
         nvalid++;
@@ -507,6 +512,7 @@ __global__ __launch_bounds__(kBinThreads) void k_tile_accumulate3(const float* _
   }
   NDT_STAMP3(4);
   block_count_add(counters, nvalid, nover);       // one add per workgroup, sharded (ndt_device.hpp)
+  if (SIGN < 0 && nunder) atomicAdd(&counters[kCountUnder], nunder);      // (a removal of points that are not in the map)
   NDT_STAMP3(5);
 }
 

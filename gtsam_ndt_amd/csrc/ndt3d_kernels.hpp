@@ -223,6 +223,13 @@ __global__ __launch_bounds__(64) void k_bounds3_publish(const float* __restrict_
 }
 
 // ---------------------------------------------------------------------------- accumulate
+// a voxel's nine sums or-ed together: non-zero when any of them is (removed_cell_broken, ndt2d_kernels.hpp)
+__device__ __forceinline__ unsigned long long any_sum3(const CellAcc3& c) {
+  return (unsigned long long)(c.s[0] | c.s[1] | c.s[2] | c.ss[0] | c.ss[1] | c.ss[2] | c.ss[3] | c.ss[4] | c.ss[5]);
+}
+
+// SIGN = -1: the points' contributions are taken out of the sums (ndt_device.hpp, "a build with a sign").
+template <int SIGN>
 __global__ __launch_bounds__(kBlock) void k_accumulate3(const float* __restrict__ x, const float* __restrict__ y,
                                                          const float* __restrict__ z, size_t n, Grid3Dev g,
                                                          unsigned long long* __restrict__ n_outside) {
@@ -237,16 +244,16 @@ __global__ __launch_bounds__(kBlock) void k_accumulate3(const float* __restrict_
       const int uy = fix_coord(py, cell_centre(g.oy, iy, g.cell), g.fix_scale);
       const int uz = fix_coord(pz, cell_centre(g.oz, iz, g.cell), g.fix_scale);
       CellAcc3* c = g.acc + (((size_t)iz * g.H + iy) * g.W + ix);
-      atomicAdd(&c->n, 1u);
-      atomicAdd((unsigned long long*)&c->s[0], (unsigned long long)(long long)ux);
-      atomicAdd((unsigned long long*)&c->s[1], (unsigned long long)(long long)uy);
-      atomicAdd((unsigned long long*)&c->s[2], (unsigned long long)(long long)uz);
-      atomicAdd((unsigned long long*)&c->ss[0], prod64(ux, ux));
-      atomicAdd((unsigned long long*)&c->ss[1], prod64(ux, uy));
-      atomicAdd((unsigned long long*)&c->ss[2], prod64(ux, uz));
-      atomicAdd((unsigned long long*)&c->ss[3], prod64(uy, uy));
-      atomicAdd((unsigned long long*)&c->ss[4], prod64(uy, uz));
-      atomicAdd((unsigned long long*)&c->ss[5], prod64(uz, uz));
+      atomicAdd(&c->n, signed_one<SIGN>());
+      atomicAdd((unsigned long long*)&c->s[0], signed_term<SIGN>((unsigned long long)(long long)ux));
+      atomicAdd((unsigned long long*)&c->s[1], signed_term<SIGN>((unsigned long long)(long long)uy));
+      atomicAdd((unsigned long long*)&c->s[2], signed_term<SIGN>((unsigned long long)(long long)uz));
+      atomicAdd((unsigned long long*)&c->ss[0], signed_term<SIGN>(prod64(ux, ux)));
+      atomicAdd((unsigned long long*)&c->ss[1], signed_term<SIGN>(prod64(ux, uy)));
+      atomicAdd((unsigned long long*)&c->ss[2], signed_term<SIGN>(prod64(ux, uz)));
+      atomicAdd((unsigned long long*)&c->ss[3], signed_term<SIGN>(prod64(uy, uy)));
+      atomicAdd((unsigned long long*)&c->ss[4], signed_term<SIGN>(prod64(uy, uz)));
+      atomicAdd((unsigned long long*)&c->ss[5], signed_term<SIGN>(prod64(uz, uz)));
     }
   }
 }
@@ -326,8 +333,11 @@ __device__ __forceinline__ bool finalise_sums3(const CellAcc3& c, double cx, dou
   });
 }
 
+// SIGN = -1 (behind a removal): a voxel the removal broke is counted in counters[kCountUnder]
+template <int SIGN>
 __global__ __launch_bounds__(kBlock) void k_finalise3(Grid3Dev g, int min_points, double eig_ratio,
                                                        int* __restrict__ counters /*[kCountShards][2]*/) {
+  int* const under = counters + kCountUnder;
   counters = count_shard(counters);
   const size_t ncell = (size_t)g.W * g.H * g.D;
   const size_t k = (size_t)blockIdx.x * kBlock + threadIdx.x;
@@ -335,7 +345,9 @@ __global__ __launch_bounds__(kBlock) void k_finalise3(Grid3Dev g, int min_points
   const CellAcc3 c = g.acc[k];
   float4 ra = make_float4(0.f, 0.f, 0.f, 0.f), rb = ra, rc = ra;
   bool ok = false;
-  if (c.n > kMaxCellCount) {
+  if (SIGN < 0 && removed_cell_broken(c.n, any_sum3(c))) {
+    atomicAdd(under, 1);                           // (only a removal of points that are not in the map comes here)
+  } else if (c.n > kMaxCellCount) {
     atomicAdd(&counters[1], 1);
   } else if ((int)c.n >= min_points) {
     const unsigned int k32 = (unsigned int)k, w32 = (unsigned int)g.W, h32 = (unsigned int)g.H;

@@ -76,7 +76,15 @@ __device__ __forceinline__ float wave_max(float v) {
 // blockIdx.x % kCountShards - and the host adds the pairs up.
 constexpr int kCountShards = 16;
 constexpr int kCountInts = 2 * kCountShards;
+// Behind the shards, in every block of build counts (the accumulator halves of the 2D sorted build, the 3D build's block,
+// d_counters): words kCountInts, kCountInts + 1 = the outside count where the block carries it, word kCountUnder = the
+// cells a REMOVAL found inconsistent (count below zero, or zero with sums left: removed_cell_broken in
+// ndt2d_kernels.hpp).  One word, not sharded: it is added to only when a removal names points that are not in the map,
+// which ends the call with an error.
+constexpr int kCountUnder = kCountInts + 2;
+constexpr int kCountWords = kCountInts + 4;
 __device__ __forceinline__ int* count_shard(int* counters) { return counters + 2 * (blockIdx.x & (kCountShards - 1)); }
+
 // one add per WORKGROUP: every thread of the workgroup must call it (it has barriers); a, b = this thread's counts
 __device__ __forceinline__ void block_count_add(int* counters, int a, int b) {
   __shared__ int s_cnt[2];
@@ -94,6 +102,15 @@ __device__ __forceinline__ void block_count_add(int* counters, int a, int b) {
     if (s_cnt[1]) atomicAdd(&c[1], s_cnt[1]);
   }
 }
+
+// ---------------------------------------------------------------- a build with a sign
+// The build kernels that take part in a submap update are templates over SIGN: +1 adds a cloud's contributions to the
+// cells' exact sums, -1 takes them out again.  The sums are integers mod 2^64 (counts mod 2^32), so subtracting is the
+// exact inverse of adding under any order and any split across workgroups.
+template <int SIGN>
+__device__ __forceinline__ unsigned long long signed_term(unsigned long long v) { return SIGN > 0 ? v : 0ull - v; }
+template <int SIGN>
+__device__ __forceinline__ unsigned int signed_one() { return SIGN > 0 ? 1u : 0xFFFFFFFFu; }
 
 // ---------------------------------------------------------------- ordered float <-> uint
 __device__ __forceinline__ unsigned int float_to_ordered(float f) {

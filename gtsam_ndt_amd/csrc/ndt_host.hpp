@@ -483,8 +483,8 @@ inline int distinct_pointers(T* const* in, int m, T** out) {
   return n;
 }
 
-// The pinned 256-byte block of a handle (h_small): counter shards at 0, the outside count at 128, the flag of a build's
-// read-back (publish_and_wait) at byte kSmallFlagByte.
+// The pinned 256-byte block of a handle (h_small): counter shards at 0, the outside count at 128, the cells a removal broke
+// behind it (word kCountUnder of ndt_device.hpp), the flag of a build's read-back (publish_and_wait) at byte kSmallFlagByte.
 constexpr size_t kSmallBytes = 256, kSmallFlagByte = 192;
 inline int* small_flag(void* h_small) { return reinterpret_cast<int*>(static_cast<char*>(h_small) + kSmallFlagByte); }
 

@@ -204,7 +204,7 @@ int32_t ndt3d_load_map(ndt3d_handle* h, const void* buf, size_t bytes) {
   { const int32_t es = ensure_cells3(h, ncell); if (es != NDT_OK) return es; }
   HIP_TRY(hipMemcpyAsync(g.acc, (const char*)buf + sizeof m, ncell * sizeof(CellAcc3), hipMemcpyHostToDevice, h->stream));
   HIP_TRY(hipMemsetAsync(h->d_counters, 0, ndt::kCountInts * sizeof(int), h->stream));
-  hipLaunchKernelGGL(k_finalise3, dim3((unsigned)((ncell + kBlock - 1) / kBlock)), dim3(kBlock), 0, h->stream, g,
+  hipLaunchKernelGGL((k_finalise3<1>), dim3((unsigned)((ncell + kBlock - 1) / kBlock)), dim3(kBlock), 0, h->stream, g,
                      h->prm.min_points, h->prm.eig_ratio, h->d_counters);
   HIP_TRY(hipGetLastError());
   int* hc = (int*)h->h_small;

@@ -158,6 +158,26 @@ class NdtMatcher2D:
                 "ndt2d_add_target_points")
         return int(out.value)
 
+    def remove_target_points(self, x, y, pose=None) -> int:
+        """Take points out of the cached grid again - the exact inverse of add_target_points() for points (and a pose)
+        that were added before; returns how many fell outside its extent.  Points that are not in the map raise
+        NdtError (NDT_ERR_INVALID_ARG) and leave the matcher without a target."""
+        out = C.c_size_t(0)
+        if _is_dev(x):
+            import torch
+            n = x.numel()
+            p = (C.c_double * 3)(*[float(v) for v in pose]) if pose is not None else None
+            L.check(self._lib.ndt2d_remove_target_points_dev(self._h, _dev_ptr(x, n), _dev_ptr(y, n), n, p, C.byref(out),
+                                                             C.c_void_p(torch.cuda.current_stream().cuda_stream)),
+                    "ndt2d_remove_target_points_dev")
+            return int(out.value)
+        if pose is not None:
+            raise ValueError("pose is applied on the device: pass device tensors")
+        x, y = _host_f32(x), _host_f32(y)
+        L.check(self._lib.ndt2d_remove_target_points(self._h, x.ctypes.data, y.ctypes.data, x.size, C.byref(out)),
+                "ndt2d_remove_target_points")
+        return int(out.value)
+
     def grid_info(self) -> L.GridInfo2D:
         info = L.GridInfo2D()
         L.check(self._lib.ndt2d_get_grid_info(self._h, C.byref(info)), "ndt2d_get_grid_info")
@@ -777,6 +797,26 @@ class NdtMatcher3D:
         x, y, z = _host_f32(x), _host_f32(y), _host_f32(z)
         L.check(self._lib.ndt3d_add_target_points(self._h, x.ctypes.data, y.ctypes.data, z.ctypes.data, x.size,
                                                   C.byref(out)), "ndt3d_add_target_points")
+        return int(out.value)
+
+    def remove_target_points(self, x, y, z, pose=None) -> int:
+        """Take points out of the cached voxel grid again - the exact inverse of add_target_points() for points (and a
+        pose) that were added before; returns how many fell outside its extent.  Points that are not in the map raise
+        NdtError (NDT_ERR_INVALID_ARG) and leave the matcher without a target."""
+        out = C.c_size_t(0)
+        if _is_dev(x):
+            import torch
+            n = x.numel()
+            p = (C.c_double * 6)(*[float(v) for v in pose]) if pose is not None else None
+            L.check(self._lib.ndt3d_remove_target_points_dev(self._h, _dev_ptr(x, n), _dev_ptr(y, n), _dev_ptr(z, n), n, p,
+                                                             C.byref(out), C.c_void_p(torch.cuda.current_stream().cuda_stream)),
+                    "ndt3d_remove_target_points_dev")
+            return int(out.value)
+        if pose is not None:
+            raise ValueError("pose is applied on the device: pass device tensors")
+        x, y, z = _host_f32(x), _host_f32(y), _host_f32(z)
+        L.check(self._lib.ndt3d_remove_target_points(self._h, x.ctypes.data, y.ctypes.data, z.ctypes.data, x.size,
+                                                     C.byref(out)), "ndt3d_remove_target_points")
         return int(out.value)
 
     def grid_info(self) -> L.GridInfo3D:

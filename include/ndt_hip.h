@@ -163,6 +163,24 @@ int32_t ndt2d_add_target_points(ndt2d_handle* h, const float* x, const float* y,
  * d_x/d_y (NULL: already complete); the call returns when the grid is updated. */
 int32_t ndt2d_add_target_points_dev(ndt2d_handle* h, const float* d_x, const float* d_y, size_t n,
                                     const double pose[3], size_t* n_outside, void* stream);
+/* The exact inverse of ndt2d_add_target_points: takes n points out of the cached grid's per-cell sums and
+ * re-finalises the cells they lie in.  The points are binned by the float32 operations of the add (outside and
+ * ring points are counted in *n_outside and nothing is subtracted for them; with overlap_grids = 4 a point leaves
+ * all four grids), and the sums are exact integers, so if the points are - as float32 values - points that were
+ * added before, the grid is bit for bit the one the handle would hold had they never been added, whatever was
+ * added or removed in between: sums (ndt2d_save_map), records, n_valid, n_points and every alignment.  A cell that
+ * falls below min_points becomes invalid (zero record); geometry and storage never change, and a grid with
+ * everything removed equals a fresh ndt2d_reserve_target of its extent.
+ * Points that are not in the map are detected where the integers show it - a cell's count would go below zero, or
+ * reaches zero while one of its sums does not: NDT_ERR_INVALID_ARG (ndt_last_error() says so), and the handle has
+ * no target afterwards, as after a failed add.  One call takes fewer than 2^32 - 2^20 points. */
+int32_t ndt2d_remove_target_points(ndt2d_handle* h, const float* x, const float* y, size_t n,
+                                   size_t* n_outside);
+/* The same with the points on the device: pose, NaN points, `stream` and the return are those of
+ * ndt2d_add_target_points_dev.  Removing a scan with the pose it was added with and adding it again with another
+ * re-anchors it in the submap (a loop closure moved it) at the cost of two scans, not of the submap. */
+int32_t ndt2d_remove_target_points_dev(ndt2d_handle* h, const float* d_x, const float* d_y, size_t n,
+                                       const double pose[3], size_t* n_outside, void* stream);
 /* ---- submap persistence -------------------------------------------------------------------
  * The cached grid as a flat buffer: this header, then n_cells per-cell blocks of the EXACT fixed-point sums the
  * build keeps (2D, 48 B: int64 sx, sy, sxx, sxy, syy; uint32 n, pad.  3D, 80 B: int64 s[3], ss[6] (xx xy xz yy yz
@@ -602,6 +620,14 @@ int32_t ndt3d_reserve_target(ndt3d_handle* h, const double lo[3], const double h
  * produced the arrays (NULL: already complete); the call returns when the grid is updated. */
 int32_t ndt3d_add_target_points_dev(ndt3d_handle* h, const float* d_x, const float* d_y, const float* d_z, size_t n,
                                     const double pose[6], size_t* n_outside, void* stream);
+/* The exact inverse of ndt3d_add_target_points(_dev), as ndt2d_remove_target_points(_dev): the points leave the voxels'
+ * exact sums, binned (and moved, with a pose) by the float32 operations of the add; removing points that were added
+ * leaves bit for bit the grid without them; points that are not in the map (a voxel's count below zero, or zero with
+ * a sum left) give NDT_ERR_INVALID_ARG and a handle without a target. */
+int32_t ndt3d_remove_target_points(ndt3d_handle* h, const float* x, const float* y, const float* z, size_t n,
+                                   size_t* n_outside);
+int32_t ndt3d_remove_target_points_dev(ndt3d_handle* h, const float* d_x, const float* d_y, const float* d_z, size_t n,
+                                       const double pose[6], size_t* n_outside, void* stream);
 /* device arrays; `stream` = the stream that produced them (NULL: already complete) */
 int32_t ndt3d_set_target_dev(ndt3d_handle* h, const float* d_x, const float* d_y, const float* d_z, size_t n,
                              void* stream);

@@ -128,6 +128,21 @@ class NdtMatcherHip {
           "ndt2d_add_target_points_dev");
     return outside;
   }
+  // the exact inverse of addTargetPoints(Dev): the points leave the cached grid's sums (throws when they are not in the
+  // map); removing a scan at its old pose and adding it at a new one re-anchors it after a loop closure
+  size_t removeTargetPoints(const float* x, const float* y, size_t n) {
+    size_t outside = 0;
+    check(ndt2d_remove_target_points(h_, x, y, n, &outside), "ndt2d_remove_target_points");
+    return outside;
+  }
+  size_t removeTargetPointsDev(const float* d_x, const float* d_y, size_t n, const Pose2* pose = nullptr,
+                               void* producer_stream = nullptr) {
+    size_t outside = 0;
+    const double p[3] = {pose ? pose->x : 0.0, pose ? pose->y : 0.0, pose ? pose->theta : 0.0};
+    check(ndt2d_remove_target_points_dev(h_, d_x, d_y, n, pose ? p : nullptr, &outside, producer_stream),
+          "ndt2d_remove_target_points_dev");
+    return outside;
+  }
   ndt2d_grid_info gridInfo() const { ndt2d_grid_info g; check(ndt2d_get_grid_info(h_, &g), "ndt2d_get_grid_info"); return g; }
   // submap persistence: the cached grid as a flat buffer (ndt_map_header + exact per-cell sums), and back - bit for
   // bit the same grid when the loading matcher has the saving one's parameters; it goes on taking points
@@ -618,6 +633,20 @@ class NdtMatcherHip3 {
     double p[6] = {0, 0, 0, 0, 0, 0};
     if (pose) { p[0] = pose->x; p[1] = pose->y; p[2] = pose->z; p[3] = pose->roll; p[4] = pose->pitch; p[5] = pose->yaw; }
     check(ndt3d_add_target_points_dev(h_, d_x, d_y, d_z, n, pose ? p : nullptr, &outside, producer_stream), "ndt3d_add_target_points_dev");
+    return outside;
+  }
+  // the exact inverse of addTargetPoints(Dev), as NdtMatcherHip::removeTargetPoints(Dev)
+  size_t removeTargetPoints(const float* x, const float* y, const float* z, size_t n) {
+    size_t outside = 0;
+    check(ndt3d_remove_target_points(h_, x, y, z, n, &outside), "ndt3d_remove_target_points");
+    return outside;
+  }
+  size_t removeTargetPointsDev(const float* d_x, const float* d_y, const float* d_z, size_t n, const Pose3* pose = nullptr,
+                               void* producer_stream = nullptr) {
+    size_t outside = 0;
+    double p[6] = {0, 0, 0, 0, 0, 0};
+    if (pose) { p[0] = pose->x; p[1] = pose->y; p[2] = pose->z; p[3] = pose->roll; p[4] = pose->pitch; p[5] = pose->yaw; }
+    check(ndt3d_remove_target_points_dev(h_, d_x, d_y, d_z, n, pose ? p : nullptr, &outside, producer_stream), "ndt3d_remove_target_points_dev");
     return outside;
   }
   MatchResult3 alignDev(const float* d_sx, const float* d_sy, const float* d_sz, size_t n, const Pose3& guess = Pose3()) {

@@ -70,8 +70,8 @@ int main(int argc, char** argv) {
   CK(hipMemset(g.acc, 0, nc * sizeof(CellAcc)));
   int* d_cnt; CK(hipMalloc(&d_cnt, 8)); CK(hipMemset(d_cnt, 0, 8));
   hipStream_t st; CK(hipStreamCreate(&st));
-  hipLaunchKernelGGL(k_accumulate, dim3(2048), dim3(kBlock), 0, st, dtx, dty, (size_t)n_t, g, (unsigned long long*)nullptr);
-  hipLaunchKernelGGL(k_finalise, dim3((unsigned)((nc + kBlock - 1) / kBlock)), dim3(kBlock), 0, st, g, 3, 1e-3, d_cnt);
+  hipLaunchKernelGGL((k_accumulate<1>), dim3(2048), dim3(kBlock), 0, st, dtx, dty, (size_t)n_t, g, (unsigned long long*)nullptr);
+  hipLaunchKernelGGL((k_finalise<1>), dim3((unsigned)((nc + kBlock - 1) / kBlock)), dim3(kBlock), 0, st, g, 3, 1e-3, d_cnt);
   int cnt[2]; CK(hipMemcpyAsync(cnt, d_cnt, 8, hipMemcpyDeviceToHost, st)); CK(hipStreamSynchronize(st));
   printf("valid cells %d\n", cnt[0]);
   AlignStatic* d_st; AlignCall* d_call; AlignDyn* d_dyn;
