@@ -1396,6 +1396,7 @@ extern "C" int32_t ndt2d_align_multi_scan_dev(ndt2d_handle* h, const float* cons
 #include "ndt3d_batch_api.hpp"
 #include "ndt3d_multi_api.hpp"
 #include "ndt_map_io.hpp"
+#include "ndt_coarsen.hpp"
 #include "ndt2d_search.hpp"
 #include "ndt3d_search.hpp"
 #include "ndt2d_d2d_api.hpp"

@@ -87,6 +87,26 @@ int32_t check_map_cells3(const void* cells, size_t n_cells) {
   return NDT_OK;
 }
 
+// The 3D counterpart of finalise_grid for sums that are already in the grid (a loaded or a coarsened map): every voxel's
+// record from its sums, n_valid and the over-count back.  Synchronises the handle's stream.
+int32_t finalise_grid3(ndt3d_handle* h) {
+  using namespace ndt;
+  const Grid3Dev& g = h->grid;
+  const size_t ncell = (size_t)g.W * g.H * g.D;
+  HIP_TRY(hipMemsetAsync(h->d_counters, 0, kCountInts * sizeof(int), h->stream));
+  hipLaunchKernelGGL((k_finalise3<1>), dim3((unsigned)((ncell + kBlock - 1) / kBlock)), dim3(kBlock), 0, h->stream, g,
+                     h->prm.min_points, h->prm.eig_ratio, h->d_counters);
+  HIP_TRY(hipGetLastError());
+  int* hc = (int*)h->h_small;
+  HIP_TRY(hipMemcpyAsync(hc, h->d_counters, kCountInts * sizeof(int), hipMemcpyDeviceToHost, h->stream));
+  HIP_TRY(hipStreamSynchronize(h->stream));
+  int n_valid_sum = 0, n_over_sum = 0;
+  sum_count_shards(hc, &n_valid_sum, &n_over_sum);
+  h->n_valid = n_valid_sum;
+  if (n_over_sum > 0) { set_error("a target cell holds more than 2^20 points"); return NDT_ERR_CAPACITY; }
+  return NDT_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -203,17 +223,7 @@ int32_t ndt3d_load_map(ndt3d_handle* h, const void* buf, size_t bytes) {
   const size_t ncell = (size_t)m.n_cells;
   { const int32_t es = ensure_cells3(h, ncell); if (es != NDT_OK) return es; }
   HIP_TRY(hipMemcpyAsync(g.acc, (const char*)buf + sizeof m, ncell * sizeof(CellAcc3), hipMemcpyHostToDevice, h->stream));
-  HIP_TRY(hipMemsetAsync(h->d_counters, 0, ndt::kCountInts * sizeof(int), h->stream));
-  hipLaunchKernelGGL((k_finalise3<1>), dim3((unsigned)((ncell + kBlock - 1) / kBlock)), dim3(kBlock), 0, h->stream, g,
-                     h->prm.min_points, h->prm.eig_ratio, h->d_counters);
-  HIP_TRY(hipGetLastError());
-  int* hc = (int*)h->h_small;
-  HIP_TRY(hipMemcpyAsync(hc, h->d_counters, ndt::kCountInts * sizeof(int), hipMemcpyDeviceToHost, h->stream));
-  HIP_TRY(hipStreamSynchronize(h->stream));      // buf is free on return
-  int n_valid_sum = 0, n_over_sum = 0;
-  sum_count_shards(hc, &n_valid_sum, &n_over_sum);
-  h->n_valid = n_valid_sum;
-  if (n_over_sum > 0) { set_error("a target cell holds more than 2^20 points"); return NDT_ERR_CAPACITY; }
+  { const int32_t fs = finalise_grid3(h); if (fs != NDT_OK) return fs; }     // synchronises: buf is free on return
   h->has_target = true;
   return upload_static3(h);
 }

@@ -207,6 +207,13 @@ class NdtMatcher2D:
         buf = np.ascontiguousarray(np.frombuffer(buf, dtype=np.uint8) if not isinstance(buf, np.ndarray) else buf.view(np.uint8))
         L.check(self._lib.ndt2d_load_map(self._h, buf.ctypes.data, buf.size), "ndt2d_load_map")
 
+    def coarsen_into(self, dst: "NdtMatcher2D") -> int:
+        """Give `dst` - a matcher whose cell_size is exactly 2 or 4 times this one's - the grid whose cells are unions of
+        this grid's cells, from the exact per-cell sums alone (ndt2d_coarsen_map: no points, on the device, deterministic
+        to the bit), finalised with dst's min_points / eig_ratio.  Returns dst's valid-cell count."""
+        L.check(self._lib.ndt2d_coarsen_map(self._h, dst._h), "ndt2d_coarsen_map")
+        return int(dst.grid_info().n_valid)
+
     # ---- (ii)+(iii) one evaluation
     def evaluate(self, sx, sy, pose):
         p = (C.c_double * 3)(*[float(v) for v in pose])
@@ -844,6 +851,12 @@ class NdtMatcher3D:
         buf = np.ascontiguousarray(np.frombuffer(buf, dtype=np.uint8) if not isinstance(buf, np.ndarray) else buf.view(np.uint8))
         L.check(self._lib.ndt3d_load_map(self._h, buf.ctypes.data, buf.size), "ndt3d_load_map")
 
+    def coarsen_into(self, dst: "NdtMatcher3D") -> int:
+        """The 3D coarsen_into of NdtMatcher2D (ndt3d_coarsen_map): dst's voxels are unions of 2^3 or 4^3 of this grid's.
+        Returns dst's valid-voxel count."""
+        L.check(self._lib.ndt3d_coarsen_map(self._h, dst._h), "ndt3d_coarsen_map")
+        return int(dst.grid_info().n_valid)
+
     def evaluate(self, sx, sy, sz, pose):
         p = (C.c_double * 6)(*[float(v) for v in pose])
         out = L.Eval3D()
@@ -1402,3 +1415,92 @@ class NdtPyramid3D:
             pose = r.pose
         r.iterations = total
         return r
+
+
+def map_level_params(fine, level):
+    """Keyword parameters of one coarse level of a map pyramid: the fine matcher's, with the level's cell size and - for
+    a (multiplier, eig_ratio) level - the eigenvalue floor and loose stops of NdtPyramid2D / NdtPyramid3D; a
+    (multiplier, dict) level takes the dict's parameters and nothing else."""
+    mult, spec = level
+    kw = {k: getattr(fine, k) for k, _ in L.Params2D._fields_ if not k.startswith("reserved")}
+    kw["cell_size"] = fine.cell_size * mult
+    if isinstance(spec, dict):
+        kw.update(spec)
+    else:
+        kw.update(eig_ratio=spec, eps_trans=1e-3, eps_rot=1e-4, max_iterations=30, fixed_iterations=0,
+                  step_max_trans=fine.step_max_trans * mult)
+    return kw
+
+
+class _NdtMapPyramid:
+    """Coarse-to-fine map-to-map alignment between submaps that hold no points: the coarse levels are derived from the
+    fine matcher's exact per-cell sums (coarsen_into), so a submap that came back from load_map gets the same escape
+    from the fine lattice's local optimum that NdtPyramid2D / NdtPyramid3D give scans."""
+    _Matcher = None
+    _zero = None
+
+    def __init__(self, fine, levels=PYRAMID_LEVELS, _owns_fine: bool = False):
+        """fine: a matcher that holds a target (it stays the caller's, and is the last level).  levels: (cell
+        multiplier, eig_ratio) or (cell multiplier, dict of parameters), multipliers 2 or 4, coarse to fine."""
+        self._fine, self._owns_fine = fine, _owns_fine
+        self.levels = []
+        try:
+            for level in levels:
+                m = self._Matcher(fine._device, **map_level_params(fine.params, level))
+                self.levels.append(m)
+                fine.coarsen_into(m)
+        except Exception:
+            self.close()
+            raise
+        self.levels.append(fine)
+
+    @classmethod
+    def from_blob(cls, blob, device: int = 0, levels=PYRAMID_LEVELS, **params):
+        """The pyramid of a saved submap (save_map's buffer): a fresh fine matcher with `params` (cell_size defaults to
+        the blob's) loads it, and the coarse levels follow from it.  close() frees all of them."""
+        head = L.MapHeader.from_buffer_copy(bytes(memoryview(np.ascontiguousarray(blob).view(np.uint8))[:C.sizeof(L.MapHeader)]))
+        params.setdefault("cell_size", head.cell_size)
+        fine = cls._Matcher(device, **params)
+        try:
+            fine.load_map(blob)
+            return cls(fine, levels, _owns_fine=True)
+        except Exception:
+            fine.close()
+            raise
+
+    def close(self):
+        for m in self.levels:
+            if m is not self._fine or self._owns_fine:
+                m.close()
+        self.levels = []
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def align_map(self, source, init_pose=None):
+        """level.align_map(source.level, pose) coarse to fine, each level from the one before; returns the last level's
+        result with the iterations of all levels summed (as NdtPyramid2D.align)."""
+        if len(source.levels) != len(self.levels):
+            raise ValueError("both pyramids need the same levels")
+        pose, total, r = tuple(init_pose) if init_pose is not None else self._zero, 0, None
+        for m, sm in zip(self.levels, source.levels):
+            r = m.align_map(sm, pose)
+            total += r.iterations
+            if r.status not in (L.NDT_OK, L.NDT_NOT_CONVERGED):
+                break
+            pose = r.pose
+        r.iterations = total
+        return r
+
+
+class NdtMapPyramid2D(_NdtMapPyramid):
+    _Matcher = NdtMatcher2D
+    _zero = (0.0,) * 3
+
+
+class NdtMapPyramid3D(_NdtMapPyramid):
+    _Matcher = NdtMatcher3D
+    _zero = (0.0,) * 6

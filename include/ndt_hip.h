@@ -207,6 +207,34 @@ size_t ndt2d_map_size(const ndt2d_handle* h);
 /* *written (may be NULL) = the bytes needed, also when capacity is too small (NDT_ERR_CAPACITY) */
 int32_t ndt2d_save_map(ndt2d_handle* h, void* buf, size_t capacity, size_t* written);
 int32_t ndt2d_load_map(ndt2d_handle* h, const void* buf, size_t bytes);
+/* ---- a coarser submap from a submap's sums ------------------------------------------------
+ * dst receives a target grid whose cells are unions of f x f cells of src's cached grid, f = dst's cell_size / src's,
+ * which must be exactly 2 or 4 (tested as dst_cell == f * src_cell in double).  No points are needed: the exact
+ * per-cell sums of the children give the parent's by integer arithmetic alone (docs/ALGORITHM.md section 2.17), on the
+ * device, deterministic to the bit.  This is what a pyramid level of a submap needs that came back from
+ * ndt2d_load_map and never saw a point.
+ * Lattice, per axis: with k0 = rint(origin / c) the fine origin in fine cells, the coarse cells are those of the
+ * lattice of multiples of f c; the coarse origin is (float)(K0 c) with K0 = f floor((k0 + 1 - f) / f), fine cell ix
+ * lies in coarse cell (k0 + ix - K0) / f, and the coarse extent is (k0 + W - 2 - K0) / f + 2.  For a src that
+ * ndt2d_set_target built from a cloud these are the origin and extents ndt2d_set_target derives from the same cloud
+ * at cell f c; the outermost ring of dst is empty, as the 2D contract asks.  The float32 rounding of the coarse origin
+ * shifts the lattice by less than an ulp of the origin, as the fine origin's own rounding does; it is zero where
+ * K0 c is a float32 value (dyadic cell sizes at ordinary coordinates).
+ * Sums: a child at position k of f along an axis has its centre (2k - f + 1) 2^21 fine units from the parent's; the
+ * children's sums are moved there and added exactly (up to 67 bits), then brought to the parent's unit (f fine
+ * units) by S' = floor((N + f/2) / f) and SS' = floor((NN + f^2/2) / f^2) - the only roundings.  Where they leave
+ * n' SS'_aa < S'_a^2 (a nearly degenerate cell), SS'_aa is raised to ceil(S'_a^2 / n'), so that every coarse map
+ * passes ndt2d_load_map.  n_points carries over.
+ * The coarse sums are finalised with DST's min_points / eig_ratio, as ndt2d_load_map does, and dst then is what a handle
+ * is after ndt2d_load_map: it aligns, serves ndt2d_align_map* / ndt2d_search_*map* on either side, takes
+ * ndt2d_add_target_points* / ndt2d_remove_target_points*, and saves.  src is unchanged.  Pending asynchronous
+ * alignments of both handles are finished first; the call returns when dst is ready.
+ * NDT_ERR_INVALID_ARG: a null handle, src == dst, handles on different devices, a ratio that is not 2 or 4, or
+ * overlap_grids = 4 on either side (out of scope: four fine grids shifted by half a FINE cell do not coarsen into
+ * grids shifted by half a COARSE cell).  NDT_ERR_NO_TARGET: src holds no grid.  NDT_ERR_CAPACITY: the coarse grid
+ * exceeds 2^27 cells, or a coarse cell would hold more than 2^20 points; dst has no target afterwards, as after a
+ * failed load.  ndt_last_error() says which. */
+int32_t ndt2d_coarsen_map(ndt2d_handle* src, ndt2d_handle* dst);
 
 int32_t ndt2d_get_grid_info(ndt2d_handle* h, ndt2d_grid_info* info);
 /* Copies the finalised cell records to host arrays of width*height entries each
@@ -354,7 +382,7 @@ int32_t ndt2d_align_map(ndt2d_handle* target, ndt2d_handle* source, const double
  * Pairs with different targets are not covered (one call per target).  The 3D twin is ndt3d_align_map_multi. */
 int32_t ndt2d_align_map_multi(ndt2d_handle* target, ndt2d_handle* const* sources, const double* init_poses /* [m][3] */,
                               int32_t m, ndt2d_result* results /* [m] */);
-/* Exhaustive pose search for map-to-map alignment (docs/ALGORITHM.md section 2.15): the score ndt2d_evaluate_map
+/* Exhaustive pose search for map-to-map alignment (docs/ALGORITHM.md section 2.17): the score ndt2d_evaluate_map
  * reports (the same float32 terms per component, summed in another order) at every pose of the window's lattice, then
  * the best well-separated peaks - a loop closure between two submaps whose relative pose is known to metres and not at
  * all in heading.  Window, lattice, hits, k in 1..64, the window errors and bitwise determinism are those of
@@ -635,6 +663,11 @@ int32_t ndt3d_set_target_dev(ndt3d_handle* h, const float* d_x, const float* d_y
 size_t ndt3d_map_size(const ndt3d_handle* h);
 int32_t ndt3d_save_map(ndt3d_handle* h, void* buf, size_t capacity, size_t* written);
 int32_t ndt3d_load_map(ndt3d_handle* h, const void* buf, size_t bytes);
+/* ndt2d_coarsen_map for voxel grids: dst's voxels are unions of f x f x f voxels of src's, f = 2 or 4; lattice, sums,
+ * roundings, finalisation with dst's parameters and return values as there (no overlap_grids in 3D).  A 3D grid has
+ * no empty-ring contract - ndt3d_add_target_points* bins a point into a ring voxel of a reserved extent like into any
+ * other - so sums found in src's ring are kept: they go to the coarse voxel their place on the lattice names. */
+int32_t ndt3d_coarsen_map(ndt3d_handle* src, ndt3d_handle* dst);
 int32_t ndt3d_get_grid_info(ndt3d_handle* h, ndt3d_grid_info* info);
 /* count [cells], mean [cells][3], icov [cells][6] (xx xy xz yy yz zz); any pointer may be NULL */
 int32_t ndt3d_get_grid(ndt3d_handle* h, int32_t* count, float* mean_xyz, float* icov6);

@@ -152,6 +152,9 @@ class NdtMatcherHip {
     return buf;
   }
   void loadMap(const std::vector<unsigned char>& buf) { check(ndt2d_load_map(h_, buf.data(), buf.size()), "ndt2d_load_map"); }
+  // dst (cell_size exactly 2 or 4 times this matcher's) receives the grid whose cells are unions of this grid's, from the
+  // exact per-cell sums alone (ndt2d_coarsen_map): a pyramid level for a submap that holds no points
+  void coarsenInto(NdtMatcherHip& dst) { check(ndt2d_coarsen_map(h_, dst.h_), "ndt2d_coarsen_map"); }
 
   // (ii)+(iii)+solve: full alignment from an initial guess
   MatchResult align(const float* sx, const float* sy, size_t n, const Pose2& guess = Pose2()) {
@@ -625,6 +628,8 @@ class NdtMatcherHip3 {
     return buf;
   }
   void loadMap(const std::vector<unsigned char>& buf) { check(ndt3d_load_map(h_, buf.data(), buf.size()), "ndt3d_load_map"); }
+  // as NdtMatcherHip::coarsenInto, for voxel grids (ndt3d_coarsen_map)
+  void coarsenInto(NdtMatcherHip3& dst) { check(ndt3d_coarsen_map(h_, dst.h_), "ndt3d_coarsen_map"); }
   // device points, optionally moved into the map frame by `pose` first (the pose an alignment returned);
   // producer_stream = the stream that wrote them (nullptr: complete)
   size_t addTargetPointsDev(const float* d_x, const float* d_y, const float* d_z, size_t n, const Pose3* pose = nullptr,
