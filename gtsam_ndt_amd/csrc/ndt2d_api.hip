@@ -58,6 +58,7 @@ struct ndt2d_handle {
   AlignCall* d_call1 = nullptr;
   AlignDyn* d_dyn1 = nullptr;
   LaneState lanes;
+  bool fork_every_pair = false;            // NDT_TUNE_LANE_FORK = 1: lane 1 forks from the handle's stream at every pair
   int last_lane = 0;                       // the lane whose d_dyn holds the pending state (last_parity)
   // binned grid build scratch (ndt2d_build.hpp)
   float* d_bx = nullptr; float* d_by = nullptr; size_t bcap = 0;
@@ -679,7 +680,8 @@ int32_t finish_host_fed(ndt2d_handle* h) {
 
 // The head of every entry point that is about to use the handle's stream for something else than an alternating
 // asynchronous alignment.  Lane 1 needs no wait here: the handle's stream was ordered behind its chain when that was
-// enqueued (AsyncLane::leave).  The alternation starts over, so the next asynchronous call forks from a fresh event.
+// enqueued (AsyncLane::leave).  The alternation starts over and lane 1 is stale from here on (lane_step: kOther): the
+// next asynchronous call records a fresh fork event behind this entry point's work, and its lane-1 partner waits for it.
 int32_t finish_chunk_run(ndt2d_handle* h) {
   (void)lane_step(h->lanes, LaneEvent::kOther);
   return finish_host_fed(h);
@@ -738,8 +740,21 @@ int32_t run_align(ndt2d_handle* h, const float* d_sx, const float* d_sy, size_t 
     return wait ? finish_small_run(h) : NDT_OK;
   }
   hipStream_t stream = h->stream;
-  if (plan.record_fork) HIP_TRY(h->lane1.mark_fork(h->stream));
-  if (plan.lane == 1) { HIP_TRY(h->lane1.enter()); stream = h->lane1.stream; }
+  // the fork: where non-chain work on the handle's stream may precede the pair (or at every pair, NDT_TUNE_LANE_FORK = 1)
+  // (a record that fails must not leave the state claiming a fork: the rule is kept across calls, so lane 1 stays stale)
+  if (h->fork_every_pair ? plan.record_fork : plan.mark) {
+    const hipError_t fe = h->lane1.mark_fork(h->stream);
+    if (fe != hipSuccess) (void)lane_step(h->lanes, LaneEvent::kOther);
+    HIP_TRY(fe);
+  }
+  if (plan.lane == 1) {
+    if (h->fork_every_pair || plan.wait) {
+      const hipError_t we = h->lane1.enter();
+      if (we != hipSuccess) (void)lane_step(h->lanes, LaneEvent::kOther);
+      HIP_TRY(we);
+    }
+    stream = h->lane1.stream;
+  }
   // Launch 0.  Fused (the default): k_iterate_first, a plain launch that evaluates at the initial pose and writes the
   // per-call context from its arguments; launches 1 .. K follow.  Old protocol: k_begin, then launches 0 .. K.
   const int first = h->fused_begin ? 1 : 0;
@@ -770,7 +785,7 @@ int32_t run_align(ndt2d_handle* h, const float* d_sx, const float* d_sy, size_t 
       h->pending = false;
       return wait ? finish_chunk_run(h) : NDT_OK;
     } else {
-      // (a lane-1 call that fails here leaves lane 1 behind the fork event and nothing else: harmless)
+      // (a lane-1 call that fails here leaves lane 1 behind the fork event at most and nothing else: harmless)
       const int32_t gs = ensure_graph(h, K + 1 - first, blocks, wide, plan.lane, &exec, first);
       if (gs != NDT_OK) return gs;
       HIP_TRY(hipGraphLaunch(exec, stream));
@@ -1040,6 +1055,8 @@ int32_t ndt2d_set_tuning(ndt2d_handle* h, int32_t knob, int64_t value) {
     case NDT_TUNE_MAP_MULTI_FROM: if (value < 1 || value > kMaxStarts + 1) return NDT_ERR_INVALID_ARG; h->map_multi_from = (int)value; return NDT_OK;
     // (the graphs of the two protocols have different first parities in the cache's key and never alias: nothing to drop)
     case NDT_TUNE_FUSED_BEGIN: if (value != 0 && value != 1) return NDT_ERR_INVALID_ARG; h->fused_begin = value != 0; return NDT_OK;
+    // (finish_chunk_run above has made lane 1 stale, so the first pair under either protocol forks)
+    case NDT_TUNE_LANE_FORK: if (value != 0 && value != 1) return NDT_ERR_INVALID_ARG; h->fork_every_pair = value != 0; return NDT_OK;
     default: return NDT_ERR_INVALID_ARG;
   }
 }
@@ -1047,10 +1064,18 @@ int32_t ndt2d_set_tuning(ndt2d_handle* h, int32_t knob, int64_t value) {
 int32_t ndt2d_wait_stream(ndt2d_handle* h, void* producer_stream) {
   if (!h) return NDT_ERR_INVALID_ARG;
   HIP_TRY(hipSetDevice(h->device));
-  HIP_TRY(order_after(h->stream, (hipStream_t)producer_stream, &h->wait_ev));
-  // the next asynchronous call may run on lane 1, which forks from a point of the handle's stream before this wait
-  if (lane_step(h->lanes, LaneEvent::kWaitStream).both_wait && (hipStream_t)producer_stream != h->stream)
+  const bool own = (hipStream_t)producer_stream == h->stream;
+  HIP_TRY(order_after(h->stream, (hipStream_t)producer_stream, &h->wait_ev));      // (nothing to do for the handle's own stream)
+  // The next asynchronous call may run on lane 1, which is behind the handle's stream only up to its last fork - taken
+  // before this wait, and in a run of asynchronous calls long ago.  So lane 1 waits for the producer too; where that is
+  // the handle's own stream (the caller's work on ndt2d_stream), for an event recorded there now.
+  if (lane_step(h->lanes, LaneEvent::kWaitStream).both_wait) {
+    if (own) {
+      if (!h->wait_ev) HIP_TRY(hipEventCreateWithFlags(&h->wait_ev, hipEventDisableTiming));
+      HIP_TRY(hipEventRecord(h->wait_ev, h->stream));
+    }
     HIP_TRY(hipStreamWaitEvent(h->lane1.stream, h->wait_ev, 0));
+  }
   return NDT_OK;
 }
 

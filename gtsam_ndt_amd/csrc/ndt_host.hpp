@@ -234,13 +234,24 @@ struct ChainGraphCache {
 // Successive asynchronous fixed-iteration alignments on a handle are independent of one another (own scan, own initial
 // pose, the same read-only grid), and one launch chain leaves the chip idle for most of every launch.  So
 // such calls alternate between two "lanes": lane 0 is the handle's stream and device context, lane 1 a second stream
-// with a context of its own.  Calls overlap in pairs; the handle's stream stays ordered behind all of them:
-//   lane-0 call  record `fork` on the handle's stream, then enqueue the chain there
-//   lane-1 call  lane 1 waits for `fork` (everything before the lane-0 call, not its chain), enqueue the chain on
-//                lane 1, record `done` there, the handle's stream waits for `done`
-// Anything else that happens on the handle in between (another kind of call, a new target, a tuning change, finish)
-// starts the alternation over at lane 0, so a lane-1 call only ever follows its lane-0 partner directly and `fork` is
-// never stale.  ndt*_wait_stream is the exception: it orders both lanes behind the producer and keeps the pairing.
+// with a context of its own.  The handle's stream stays ordered behind all of them:
+//   lane-0 call  enqueue the chain on the handle's stream
+//   lane-1 call  enqueue the chain on lane 1, record `done` there, the handle's stream waits for `done`
+// Lane 1 in turn has to be behind everything on the handle's stream that is NOT an alternating chain (a build, an
+// update, a synchronous or converged call, a tuning change: `kOther`) - and behind nothing else: its own previous chain
+// is ordered by its stream, and lane 0's chains share nothing writable with it (own AlignCall / AlignDyn / graphs,
+// read-only AlignStatic, grid and scans).  So the fork is taken only when such work may precede the pair:
+//   lane-0 call  if lane 1 is `stale` (a kOther since it last forked; a new handle): record `fork` on the handle's
+//                stream in front of the chain (`mark`)
+//   lane-1 call  if a fork was recorded since lane 1 last waited (`fork_live`): lane 1 waits for it (`wait`) -
+//                everything before its lane-0 partner, not the partner's chain
+// In a run of back-to-back asynchronous calls the first pair forks and lane 1 then runs its chains back to back: a
+// wait for a fork at every pair would put two cross-queue hops (lane 1 ends -> handle's stream records the fork ->
+// lane 1 starts) between a lane's chains for nothing.  NDT_TUNE_LANE_FORK = 1 forks at every pair all the same
+// (`record_fork`), to compare the two in one process.
+// Anything else that happens on the handle in between starts the alternation over at lane 0, so a lane-1 call only ever
+// follows a lane-0 call directly, and that call has recorded the fork if one is due.  ndt*_wait_stream is the
+// exception: it orders both lanes behind the producer and keeps the pairing.
 
 enum class LaneEvent {
   kAsyncFixed,   // an asynchronous call on the fixed-iteration graph path: the kind that alternates
@@ -250,30 +261,45 @@ enum class LaneEvent {
 };
 
 struct LaneState {
-  int lanes = 2;        // NDT_TUNE_ASYNC_LANES: 1 = everything on lane 0, as a handle without lanes
-  int next = 0;         // the lane of the next alternating call
+  int lanes = 2;           // NDT_TUNE_ASYNC_LANES: 1 = everything on lane 0, as a handle without lanes
+  int next = 0;            // the lane of the next alternating call
+  bool stale = true;       // lane 1 is not known to be behind the non-chain work on the handle's stream
+  bool fork_live = false;  // a fork has been recorded since lane 1 last waited
 };
 
 struct LanePlan {
   int lane = 0;              // where this call's chain goes
-  bool record_fork = false;  // lane-0 call that may get a partner: record the fork event at its head
+  bool record_fork = false;  // lane-0 call that may get a partner (where every pair forks: NDT_TUNE_LANE_FORK = 1)
   bool both_wait = false;    // kWaitStream: lane 1 waits for the producer too
+  bool mark = false;         // lane-0 call: record the fork event at its head, lane 1 is stale
+  bool wait = false;         // lane-1 call: wait for the fork event, one was recorded since the last wait
 };
 
 // What an event on the handle does, and the state after it.  Pure: the only place the pairing rule lives.
 inline LanePlan lane_step(LaneState& s, LaneEvent ev) {
   LanePlan p;
-  if (s.lanes < 2) { s.next = 0; return p; }
+  if (s.lanes < 2) { s.next = 0; s.stale = true; s.fork_live = false; return p; }
   switch (ev) {
     case LaneEvent::kAsyncFixed:
       p.lane = s.next;
       p.record_fork = s.next == 0;
+      if (s.next == 0) {
+        p.mark = s.stale;
+        if (s.stale) { s.fork_live = true; s.stale = false; }
+      } else {
+        p.wait = s.fork_live;
+        s.fork_live = false;
+      }
       s.next ^= 1;
       break;
     case LaneEvent::kWaitStream:
       p.both_wait = true;
       break;
     case LaneEvent::kOther:
+      s.stale = true;
+      s.fork_live = false;
+      s.next = 0;
+      break;
     case LaneEvent::kFinish:
       s.next = 0;
       break;
@@ -298,9 +324,9 @@ struct AsyncLane {
     if (stream) (void)hipStreamDestroy(stream);
     *this = AsyncLane{};
   }
-  // head of a lane-0 call
+  // head of a lane-0 call (LanePlan::mark)
   hipError_t mark_fork(hipStream_t main) { return hipEventRecord(fork, main); }
-  // head of a lane-1 call: behind everything that preceded its lane-0 partner
+  // head of a lane-1 call (LanePlan::wait): behind everything that preceded the lane-0 call that recorded the fork
   hipError_t enter() { return hipStreamWaitEvent(stream, fork, 0); }
   // tail of a lane-1 call: the handle's stream is ordered behind this chain
   hipError_t leave(hipStream_t main) {

@@ -432,6 +432,11 @@ int32_t ndt2d_get_components(ndt2d_handle* h, float* mean_xy, float* cov_abc, in
  *                               kernel writes the arguments into the device context first (K + 2 launches, the protocol
  *                               ndt2d_align_trace always runs).  Other values: NDT_ERR_INVALID_ARG.  Results are
  *                               bit-identical either way.  The same knob on ndt3d_set_tuning
+ *   NDT_TUNE_LANE_FORK          0 (default): the second stream of NDT_TUNE_ASYNC_LANES = 2 waits for the handle's stream
+ *                               only where something other than such an alignment (a build, an update, a synchronous or
+ *                               converged call, a tuning change) precedes a pair of them, and runs its alignments back
+ *                               to back otherwise; 1: it waits for the head of its partner at every pair.  Other values:
+ *                               NDT_ERR_INVALID_ARG.  Results are bit-identical either way.  ndt2d_set_tuning only
  *   NDT_TUNE_BATCH_SMALL_VARIANT (batch contexts) 1 (default): lidar-sized pairs run on the 256-thread
  *                               variant of the batch kernel first; 0: every pair on the 1024-thread one
  *   NDT_TUNE_BATCH_GLOBAL_WORKGROUPS (batch contexts, 2D and 3D) workgroups of the global-table variant, each with its own
@@ -454,7 +459,8 @@ enum {
   NDT_TUNE_BATCH_GLOBAL_WORKGROUPS = 10,
   NDT_TUNE_ASYNC_LANES = 11,
   NDT_TUNE_MAP_MULTI_FROM = 12,
-  NDT_TUNE_FUSED_BEGIN = 13
+  NDT_TUNE_FUSED_BEGIN = 13,
+  NDT_TUNE_LANE_FORK = 14
 };
 int32_t ndt2d_set_tuning(ndt2d_handle* h, int32_t knob, int64_t value);
 /* hipStream_t the handle enqueues on (as void*), for event timing by the caller */
@@ -465,7 +471,10 @@ void* ndt2d_stream(ndt2d_handle* h);
  * ndt2d_wait_stream orders everything the handle enqueues after this call behind the work that is
  * in producer_stream now (event record + stream wait: the host does not block; NULL = the legacy
  * default stream).  Call it before ndt2d_align_dev / ndt2d_align_dev_async whenever the source
- * arrays were written on another stream and that stream has not been synchronised.
+ * arrays were written on a stream that has not been synchronised - ANY stream, the handle's own
+ * (ndt2d_stream) included: an asynchronous fixed-iteration alignment may run on the handle's second
+ * stream (NDT_TUNE_ASYNC_LANES), which is ordered behind the caller's work on ndt2d_stream only by
+ * ndt2d_wait_stream(h, ndt2d_stream(h)).
  * (ndt2d_set_target_dev and ndt2d_add_target_points_dev take the producer stream themselves.) */
 int32_t ndt2d_wait_stream(ndt2d_handle* h, void* producer_stream);
 

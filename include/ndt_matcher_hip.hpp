@@ -169,7 +169,8 @@ class NdtMatcherHip {
   // Source scan already on the device (e.g. from ndt2d_polar_to_points_dev).  producer_stream is
   // the stream that wrote d_sx / d_sy: the handle's own stream is ordered behind it first
   // (ndt2d_wait_stream; nullptr = the legacy default stream); complete = true when those arrays are
-  // known to be complete (the producer was synchronised), which skips the ordering.
+  // known to be complete (the producer was synchronised), which skips the ordering.  The same holds for arrays
+  // written on the handle's own stream (ndt2d_stream): pass that stream as producer_stream, it is not implied.
   MatchResult alignDev(const float* d_sx, const float* d_sy, size_t n, const Pose2& guess, void* producer_stream,
                        bool complete = false) {
     if (!complete) check(ndt2d_wait_stream(h_, producer_stream), "ndt2d_wait_stream");

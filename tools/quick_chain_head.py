@@ -8,7 +8,9 @@ launch, good for comparing two builds, not the bare latency of a launch.
 NDT_HIP_LIB selects the library, to compare two builds in one session.
 --fused 0 | 1: set NDT_TUNE_FUSED_BEGIN (a library that has the knob): 0 = k_begin + K + 1 launches, 1 = the first launch
 carries the call's arguments (K + 1 kernels in all).  Either way the time is divided by K + 1 launches, so that the
-figures of the two protocols compare as time per alignment / (K + 1); the time per alignment is printed as well."""
+figures of the two protocols compare as time per alignment / (K + 1); the time per alignment is printed as well.
+--lane-fork 0 | 1: set NDT_TUNE_LANE_FORK (a library that has the knob): 0 = lane 1 forks from the handle's stream only
+behind non-chain work, 1 = at every pair.  It moves the two-lane figure; the one-lane figure must not move."""
 import os, sys, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np, torch
@@ -16,6 +18,7 @@ from gtsam_ndt_amd import synth
 from gtsam_ndt_amd.matcher import NdtMatcher2D
 REPEATS, CALLS, K = 7, 100, 30
 FUSED = int(sys.argv[sys.argv.index("--fused") + 1]) if "--fused" in sys.argv else None
+LANE_FORK = int(sys.argv[sys.argv.index("--lane-fork") + 1]) if "--lane-fork" in sys.argv else None
 d = synth.make_pair(3)
 tx, ty = torch.from_numpy(d["tx"]).cuda(), torch.from_numpy(d["ty"]).cuda()
 sx, sy = torch.from_numpy(d["sx"]).cuda(), torch.from_numpy(d["sy"]).cuda()
@@ -25,6 +28,8 @@ with NdtMatcher2D(fixed_iterations=K) as m:
     m.set_target(tx, ty)
     if FUSED is not None:
         m.set_tuning("fused_begin", FUSED)
+    if LANE_FORK is not None:
+        m.set_tuning("lane_fork", LANE_FORK)
     for rep in range(REPEATS + 1):              # sample 0 is the warm-up
         for lanes in (1, 2):
             m.set_tuning("async_lanes", lanes)
@@ -40,4 +45,5 @@ for lanes in (1, 2):
     print(f"lanes {lanes}: {np.median(a):.3f} us per launch (min {a.min():.3f}, max {a.max():.3f}, {REPEATS} samples of "
           f"{CALLS} alignments; time / {K + 1} launches) = {np.median(a) * (K + 1):.1f} us per alignment = "
           f"{K / (K + 1) / np.median(a) * 1e3:.1f}k iterations/s; fused_begin {'default' if FUSED is None else FUSED}; "
+          f"lane_fork {'default' if LANE_FORK is None else LANE_FORK}; "
           f"{os.environ.get('NDT_HIP_LIB', 'product library')}; pose {r.pose}")
