@@ -99,7 +99,7 @@ struct ndt2d_handle {
   int check_every = 8;                     // converged mode: launches per chunk
   bool fused_begin = true;                 // NDT_TUNE_FUSED_BEGIN: launch 0 of a single-scan chain is k_iterate_first (no k_begin)
   SearchScratch srch;                      // exhaustive pose search scratch (ndt_search.hpp), allocated on first use
-  // map-to-map alignment (ndt2d_d2d_api.hpp), allocated on first use; both caches follow the grid (grid_changed)
+  // map-to-map alignment (ndt_map_host.hpp, ndt2d_d2d_api.hpp), allocated on first use; both caches follow the grid (grid_changed)
   float4* d_cov = nullptr; size_t cov_cap = 0;            // covariance records of the cached grid ([2 x cells], the layout of grid.rec)
   unsigned int* d_blk = nullptr; size_t blk_cap = 0;      // valid cells per workgroup of k_cov_records | their exclusive scan | the total
   float4* d_comp = nullptr; size_t comp_cap = 0;          // component list: this handle as the source of a map-to-map call
@@ -156,7 +156,7 @@ int stream_blocks(size_t n) {   // streaming kernels: up to 8 blocks per CU
 int32_t upload_static(ndt2d_handle* h);
 
 // The cached grid is about to change (a new target, merged points, a reserved extent, a loaded map): what map-to-map
-// alignment derived from it (ndt2d_d2d_api.hpp) is stale.
+// alignment derived from it (ndt_map_host.hpp) is stale.
 void grid_changed(ndt2d_handle* h) { h->cov_valid = false; h->comp_valid = false; }
 
 // The words a removal adds to a failed call: what the kernels counted in kCountUnder means that points were removed that
@@ -865,6 +865,55 @@ int32_t stage_target(ndt2d_handle* h, const float* x, const float* y, size_t n) 
   return NDT_OK;
 }
 
+// The 2D side of the host code both handles share (ndt_search.hpp, ndt_map_host.hpp)
+template <> struct HandleTraits<ndt2d_handle> {
+  using State = IterState;
+  using Result = ndt2d_result;
+  using Window = ndt2d_search_window;
+  using Hit = ndt2d_search_hit;
+  using Poses = StartPoses;
+  using Maps = StartMaps;
+  static constexpr int kPose = 3, kMaxStarts = ndt::kMaxStarts;
+  static constexpr int kRecord = 2;                        // float4 per covariance record and per component
+  static constexpr const char* kCell = "cell";
+  static constexpr const char* kTraceComponents = "ndt2d: component list";
+  static constexpr const char* kTraceMapMulti = "ndt2d_align_map_multi";
+  static constexpr const char* kMapMultiNoEnd = "the map-to-map multi-start loop did not report its end";
+  static size_t cells(const ndt2d_handle* h) { return (size_t)h->grid.W * h->grid.H; }
+  static int32_t finish(ndt2d_handle* h) { return finish_chunk_run(h); }
+  template <class Out> static void to(const IterState& s, Out* out) { state_to(s, out); }
+  static void launch_cov_records(ndt2d_handle* h, unsigned nb) {
+    hipLaunchKernelGGL(k_cov_records, dim3(nb), dim3(kBlock), 0, h->stream, h->grid, h->prm.min_points, h->prm.eig_ratio,
+                       h->d_cov, h->d_blk);
+  }
+  static void launch_components(ndt2d_handle* h, unsigned nb, unsigned ncell, const unsigned int* offsets, unsigned n) {
+    hipLaunchKernelGGL(k_components, dim3(nb), dim3(kBlock), 0, h->stream, (const float4*)h->d_cov, ncell, offsets, h->d_comp, n);
+  }
+  // one component of the list as ndt2d_get_components hands it out
+  static void unpack_component(const float4* c, size_t i, float* mean_xy, float* cov_abc, int32_t* key) {
+    const float4 a = c[0], b = c[1];
+    if (mean_xy) { mean_xy[2 * i] = a.x; mean_xy[2 * i + 1] = a.y; }
+    if (cov_abc) { cov_abc[3 * i] = a.z; cov_abc[3 * i + 1] = a.w; cov_abc[3 * i + 2] = b.y; }
+    if (key) std::memcpy(&key[i], &b.z, sizeof(int32_t));
+  }
+  static SearchWindow window(const ndt2d_search_window& w) {
+    SearchWindow v;
+    for (int a = 0; a < 3; ++a) { v.center[a] = w.center[a]; v.half_extent[a] = w.half_extent[a]; v.step[a] = w.step[a]; }
+    v.min_sep_trans = w.min_sep_trans; v.min_sep_rot = w.min_sep_rot;
+    return v;
+  }
+  // the walk's peaks as the ABI's hits
+  static void hits_out(const SearchPeak* peaks, int32_t n, const ndt2d_search_window&, ndt2d_search_hit* hits) {
+    for (int32_t q = 0; q < n; ++q) {
+      ndt2d_search_hit& hh = hits[q];
+      std::memset(&hh, 0, sizeof(hh));
+      for (int a = 0; a < 3; ++a) hh.pose[a] = peaks[q].pose[a];
+      hh.score = peaks[q].score;
+      hh.index = peaks[q].index;
+    }
+  }
+};
+
 }  // namespace
 
 // ------------------------------------------------------------------------------ C ABI
@@ -1422,6 +1471,7 @@ extern "C" int32_t ndt2d_align_multi_scan_dev(ndt2d_handle* h, const float* cons
 #include "ndt3d_multi_api.hpp"
 #include "ndt_map_io.hpp"
 #include "ndt_coarsen.hpp"
+#include "ndt_map_host.hpp"
 #include "ndt2d_search.hpp"
 #include "ndt3d_search.hpp"
 #include "ndt2d_d2d_api.hpp"

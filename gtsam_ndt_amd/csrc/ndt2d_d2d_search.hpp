@@ -1,8 +1,8 @@
 // Exhaustive pose search for 2D map-to-map alignment (docs/ALGORITHM.md section 2.15): the map-to-map score of
 // ndt2d_evaluate_map at every pose of an (x, y, theta) lattice, from the source handle's component list and the target
 // handle's covariance records - no points.  Included at the end of ndt2d_api.hip, after ndt2d_search.hpp and
-// ndt2d_d2d_api.hpp: the lattice, the peak selection, the scratch and the separation walk are ndt_search.hpp's, the
-// component list and the covariance records ndt2d_d2d_api.hpp's.
+// ndt2d_d2d_api.hpp: the lattice, the peak selection, the scratch, the separation walk and the host run are
+// ndt_search.hpp's, the component list and the covariance records ndt_map_host.hpp's.
 //
 //   k_search_score_d2d  the score volume, in the shape of k_search_score: one workgroup = one heading x a 16 x 16 tile
 //                       of translations, ONE LANE PER TRANSLATION, a wave an 8 x 8 block.  What a heading makes uniform
@@ -126,44 +126,16 @@ __global__ __launch_bounds__(kSearchThreads) void k_search_score_d2d(const Align
 // ------------------------------------------------------------------------------ host side
 namespace {
 
-// The whole map-to-map search on the TARGET handle's stream and search scratch; the source handle lends its component
-// list.  d_scores != null: only the volume, into the caller's buffer; else the hits.  Returns once the target's stream
-// has drained: nothing reads the source's list any more.
-int32_t search_map_run(ndt2d_handle* t, ndt2d_handle* s, const ndt2d_search_window* w2, int32_t k, ndt2d_search_hit* hits,
+// The whole map-to-map search (search_host_run) on the TARGET handle's stream and search scratch; the source handle lends
+// its component list.  Here: the score launch.
+int32_t search_map_run(ndt2d_handle* t, ndt2d_handle* s, const ndt2d_search_window* w, int32_t k, ndt2d_search_hit* hits,
                        int32_t* n_hits, float* d_scores) {
   TraceRange range(d_scores ? "ndt2d_search_map_scores" : "ndt2d_search_map");
-  const SearchWindow w = search_window(*w2);
-  SearchPlan plan;
-  { const int32_t ls = search_lattice(w, &plan.L); if (ls != NDT_OK) return ls; }
-  if (!t->has_target || !s->has_target) return NDT_ERR_NO_TARGET;
-  if (t->device != s->device) { set_error("map-to-map search: both handles must live on one device"); return NDT_ERR_INVALID_ARG; }
-  if (t->prm.overlap_grids == 4 || s->prm.overlap_grids == 4) {
-    set_error("map-to-map alignment does not take overlapping grids");
-    return NDT_ERR_INVALID_ARG;
-  }
-  HIP_TRY(hipSetDevice(t->device));
-  { const int32_t fs = finish_chunk_run(t); if (fs != NDT_OK) return fs; }
-  if (s != t) { const int32_t fs = finish_chunk_run(s); if (fs != NDT_OK) return fs; }
-  { const int32_t cs = ensure_components(s); if (cs != NDT_OK) return cs; }
-  { const int32_t cs = ensure_cov_records(t); if (cs != NDT_OK) return cs; }
-  if (s != t) HIP_TRY(order_after(t->stream, s->stream, &s->map_ev));       // the list may still be in flight on s's stream
-  { const int32_t us = search_upload_axes(t->srch, t->stream, w, &plan); if (us != NDT_OK) return us; }
-  const SearchLattice& L = plan.L;
-  float* vol = nullptr;
-  { const int32_t vs = search_volume(t->srch, plan.poses(), d_scores, &vol); if (vs != NDT_OK) return vs; }
-  const unsigned grid = (unsigned)std::min<long long>(plan.tasks(), 1ll << 20);
-  hipLaunchKernelGGL(k_search_score_d2d, dim3(grid), dim3(kSearchThreads), 0, t->stream, t->d_static, (const float4*)t->d_cov,
-                     (float)t->prm.d1, (float)t->prm.d2, (const float4*)s->d_comp, s->n_comp, plan.d_x, plan.d_y, plan.d_rot,
-                     L.nx, L.ny, L.nt, vol);
-  HIP_TRY(hipGetLastError());
-  if (d_scores) {
-    HIP_TRY(hipStreamSynchronize(t->stream));
-    return NDT_OK;
-  }
-  SearchPeak peaks[kMaxStarts];
-  { const int32_t ss = search_select(t->srch, t->stream, vol, plan, w, k, peaks, n_hits); if (ss != NDT_OK) return ss; }
-  search_hits_out(peaks, *n_hits, hits);
-  return NDT_OK;
+  return search_host_run(t, s, w, k, hits, n_hits, d_scores, [&](const SearchPlan& plan, unsigned grid, float* vol) {
+    hipLaunchKernelGGL(k_search_score_d2d, dim3(grid), dim3(kSearchThreads), 0, t->stream, t->d_static, (const float4*)t->d_cov,
+                       (float)t->prm.d1, (float)t->prm.d2, (const float4*)s->d_comp, s->n_comp, plan.d_x, plan.d_y, plan.d_rot,
+                       plan.L.nx, plan.L.ny, plan.L.nt, vol);
+  });
 }
 
 }  // namespace
@@ -189,13 +161,11 @@ int32_t ndt2d_search_align_map(ndt2d_handle* target, ndt2d_handle* source, const
   const int32_t st = ndt2d_search_map(target, source, w, k, hits, n_hits);
   if (st != NDT_OK || *n_hits < 1) return st;
   // every hit is a start of one map-to-map chain (ndt2d_align_map_multi: bit for bit ndt2d_align_map from each pose)
-  ndt2d_handle* sources[kMaxStarts];
-  double poses[kMaxStarts][3];
-  for (int32_t q = 0; q < *n_hits; ++q) {
-    sources[q] = source;
-    for (int j = 0; j < 3; ++j) poses[q][j] = hits[q].pose[j];
-  }
-  return ndt2d_align_map_multi(target, sources, &poses[0][0], *n_hits, results);
+  return search_hits_align<ndt2d_handle>(hits, *n_hits, [&](const double* poses) {
+    ndt2d_handle* sources[kMaxStarts];
+    std::fill_n(sources, *n_hits, source);
+    return ndt2d_align_map_multi(target, sources, poses, *n_hits, results);
+  });
 }
 
 }  // extern "C"

@@ -112,56 +112,20 @@ __global__ __launch_bounds__(kSearchThreads) void k_search_score(const AlignStat
 // ------------------------------------------------------------------------------ host side
 namespace {
 
-SearchWindow search_window(const ndt2d_search_window& w) {
-  SearchWindow v;
-  for (int a = 0; a < 3; ++a) { v.center[a] = w.center[a]; v.half_extent[a] = w.half_extent[a]; v.step[a] = w.step[a]; }
-  v.min_sep_trans = w.min_sep_trans; v.min_sep_rot = w.min_sep_rot;
-  return v;
-}
-
-// the walk's peaks as the ABI's hits
-void search_hits_out(const SearchPeak* peaks, int32_t n, ndt2d_search_hit* hits) {
-  for (int32_t q = 0; q < n; ++q) {
-    ndt2d_search_hit& hh = hits[q];
-    std::memset(&hh, 0, sizeof(hh));
-    for (int a = 0; a < 3; ++a) hh.pose[a] = peaks[q].pose[a];
-    hh.score = peaks[q].score;
-    hh.index = peaks[q].index;
-  }
-}
-
-// The whole search on the handle's stream.  d_scores != null: only the volume, into the caller's buffer; else the hits.
-int32_t search_run(ndt2d_handle* h, const float* d_sx, const float* d_sy, size_t n, const ndt2d_search_window* w2,
+// The whole search on the handle's stream (search_host_run): the score launch.
+int32_t search_run(ndt2d_handle* h, const float* d_sx, const float* d_sy, size_t n, const ndt2d_search_window* w,
                    int32_t k, ndt2d_search_hit* hits, int32_t* n_hits, float* d_scores) {
   TraceRange range(d_scores ? "ndt2d_search_scores" : "ndt2d_search");
-  if (!w2) return NDT_ERR_INVALID_ARG;
-  const SearchWindow w = search_window(*w2);
-  SearchPlan plan;
-  { const int32_t ls = search_lattice(w, &plan.L); if (ls != NDT_OK) return ls; }
-  if (!h->has_target) return NDT_ERR_NO_TARGET;
-  HIP_TRY(hipSetDevice(h->device));
-  { const int32_t fs = finish_chunk_run(h); if (fs != NDT_OK) return fs; }
-  { const int32_t us = search_upload_axes(h->srch, h->stream, w, &plan); if (us != NDT_OK) return us; }
-  const SearchLattice& L = plan.L;
-  float* vol = nullptr;
-  { const int32_t vs = search_volume(h->srch, plan.poses(), d_scores, &vol); if (vs != NDT_OK) return vs; }
-  const unsigned grid = (unsigned)std::min<long long>(plan.tasks(), 1ll << 20);
-  const float d1 = (float)h->prm.d1, d2 = (float)h->prm.d2;        // as upload_static
-  if (h->prm.overlap_grids == 4)
-    hipLaunchKernelGGL(k_search_score<4>, dim3(grid), dim3(kSearchThreads), 0, h->stream, h->d_static,
-                       (const float4*)h->grid.rec, d1, d2, d_sx, d_sy, (int)n, plan.d_x, plan.d_y, plan.d_rot, L.nx, L.ny, L.nt, vol);
-  else
-    hipLaunchKernelGGL(k_search_score<1>, dim3(grid), dim3(kSearchThreads), 0, h->stream, h->d_static,
-                       (const float4*)h->grid.rec, d1, d2, d_sx, d_sy, (int)n, plan.d_x, plan.d_y, plan.d_rot, L.nx, L.ny, L.nt, vol);
-  HIP_TRY(hipGetLastError());
-  if (d_scores) {
-    HIP_TRY(hipStreamSynchronize(h->stream));
-    return NDT_OK;
-  }
-  SearchPeak peaks[kMaxStarts];
-  { const int32_t ss = search_select(h->srch, h->stream, vol, plan, w, k, peaks, n_hits); if (ss != NDT_OK) return ss; }
-  search_hits_out(peaks, *n_hits, hits);
-  return NDT_OK;
+  return search_host_run(h, (ndt2d_handle*)nullptr, w, k, hits, n_hits, d_scores, [&](const SearchPlan& plan, unsigned grid, float* vol) {
+    const SearchLattice& L = plan.L;
+    const float d1 = (float)h->prm.d1, d2 = (float)h->prm.d2;        // as upload_static
+    if (h->prm.overlap_grids == 4)
+      hipLaunchKernelGGL(k_search_score<4>, dim3(grid), dim3(kSearchThreads), 0, h->stream, h->d_static,
+                         (const float4*)h->grid.rec, d1, d2, d_sx, d_sy, (int)n, plan.d_x, plan.d_y, plan.d_rot, L.nx, L.ny, L.nt, vol);
+    else
+      hipLaunchKernelGGL(k_search_score<1>, dim3(grid), dim3(kSearchThreads), 0, h->stream, h->d_static,
+                         (const float4*)h->grid.rec, d1, d2, d_sx, d_sy, (int)n, plan.d_x, plan.d_y, plan.d_rot, L.nx, L.ny, L.nt, vol);
+  });
 }
 
 int32_t search_args(ndt2d_handle* h, const float* sx, const float* sy, size_t n, const ndt2d_search_window* w, int32_t k,
@@ -177,8 +141,9 @@ extern "C" {
 
 int32_t ndt2d_search_lattice_size(const ndt2d_search_window* w, int32_t dims[3]) {
   if (!w || !dims) return NDT_ERR_INVALID_ARG;
+  SearchWindow v;
   SearchLattice L;
-  const int32_t st = search_lattice(search_window(*w), &L);
+  const int32_t st = search_lattice_of<ndt2d_handle>(w, &v, &L);
   if (st != NDT_OK) return st;
   dims[0] = L.nt; dims[1] = L.ny; dims[2] = L.nx;
   return NDT_OK;
@@ -197,7 +162,7 @@ int32_t ndt2d_search(ndt2d_handle* h, const float* sx, const float* sy, size_t n
   int32_t st = search_args(h, sx, sy, n, w, k, hits, n_hits);
   if (st != NDT_OK) return st;
   *n_hits = 0;
-  { SearchLattice L; st = search_lattice(search_window(*w), &L); if (st != NDT_OK) return st; }
+  { SearchWindow v; SearchLattice L; st = search_lattice_of<ndt2d_handle>(w, &v, &L); if (st != NDT_OK) return st; }
   if (!h->has_target) return NDT_ERR_NO_TARGET;
   HIP_TRY(hipSetDevice(h->device));
   { const int32_t ss = stage_source(h, sx, sy, n); if (ss != NDT_OK) return ss; }
@@ -215,10 +180,9 @@ int32_t ndt2d_search_align_dev(ndt2d_handle* h, const float* d_sx, const float* 
   if (!results) return NDT_ERR_INVALID_ARG;
   const int32_t st = ndt2d_search_dev(h, d_sx, d_sy, n, w, k, hits, n_hits);
   if (st != NDT_OK || *n_hits == 0) return st;
-  std::vector<double> init(3 * (size_t)*n_hits);
-  for (int32_t q = 0; q < *n_hits; ++q)
-    for (int a = 0; a < 3; ++a) init[3 * q + a] = hits[q].pose[a];
-  return ndt2d_align_multi_start_dev(h, d_sx, d_sy, n, init.data(), *n_hits, results);
+  return search_hits_align<ndt2d_handle>(hits, *n_hits, [&](const double* init) {
+    return ndt2d_align_multi_start_dev(h, d_sx, d_sy, n, init, *n_hits, results);
+  });
 }
 
 }  // extern "C"

@@ -51,7 +51,7 @@ struct ndt3d_handle {
   ndt::AlignDynMulti3* d_dyn_multi = nullptr;   // multi-scan / multi-start chains (ndt3d_multi.hpp), on first use
   ndt::IterState3* h_state_multi = nullptr;     // pinned [kMaxStarts3]
   ndt::SearchScratch srch;                      // exhaustive pose search scratch (ndt_search.hpp), allocated on first use
-  // map-to-map alignment (ndt3d_d2d_api.hpp), allocated on first use; both caches follow the grid (grid_changed3)
+  // map-to-map alignment (ndt_map_host.hpp, ndt3d_d2d_api.hpp), allocated on first use; both caches follow the grid (grid_changed3)
   float4* d_cov = nullptr; size_t cov_cap = 0;            // covariance records, 3 float4 per voxel (k_cov_records3)
   unsigned int* d_blk = nullptr; size_t blk_cap = 0;      // per-workgroup valid counts | their exclusive scan | the total
   float4* d_comp = nullptr; size_t comp_cap = 0;          // component list, 3 float4 per component (k_components3)
@@ -455,6 +455,59 @@ void state3_to(const ndt::IterState3& s, Out* out) {
     out->status = s.status;
   }
 }
+
+// The 3D side of the host code both handles share (ndt_search.hpp, ndt_map_host.hpp)
+template <> struct HandleTraits<ndt3d_handle> {
+  using State = ndt::IterState3;
+  using Result = ndt3d_result;
+  using Window = ndt3d_search_window;
+  using Hit = ndt3d_search_hit;
+  using Poses = ndt::StartPoses3;
+  using Maps = ndt::StartMaps3;
+  static constexpr int kPose = 6, kMaxStarts = ndt::kMaxStarts3;
+  static constexpr int kRecord = 3;                        // float4 per covariance record and per component
+  static constexpr const char* kCell = "voxel";
+  static constexpr const char* kTraceComponents = "ndt3d: component list";
+  static constexpr const char* kTraceMapMulti = "ndt3d_align_map_multi";
+  static constexpr const char* kMapMultiNoEnd = "the 3D map-to-map multi-start loop did not report its end";
+  static size_t cells(const ndt3d_handle* h) { return (size_t)h->grid.W * h->grid.H * h->grid.D; }
+  static int32_t finish(ndt3d_handle* h) { return finish_align3(h); }
+  template <class Out> static void to(const ndt::IterState3& s, Out* out) { state3_to(s, out); }
+  static void launch_cov_records(ndt3d_handle* h, unsigned nb) {
+    hipLaunchKernelGGL(ndt::k_cov_records3, dim3(nb), dim3(ndt::kBlock), 0, h->stream, h->grid, h->prm.min_points,
+                       h->prm.eig_ratio, h->d_cov, h->d_blk);
+  }
+  static void launch_components(ndt3d_handle* h, unsigned nb, unsigned ncell, const unsigned int* offsets, unsigned n) {
+    hipLaunchKernelGGL(ndt::k_components3, dim3(nb), dim3(ndt::kBlock), 0, h->stream, (const float4*)h->d_cov, ncell, offsets,
+                       h->d_comp, n);
+  }
+  // one component of the list as ndt3d_get_components hands it out
+  static void unpack_component(const float4* c, size_t i, float* mean_xyz, float* cov6, int32_t* key) {
+    const float4 a = c[0], b = c[1], d = c[2];
+    if (mean_xyz) { mean_xyz[3 * i] = a.x; mean_xyz[3 * i + 1] = a.y; mean_xyz[3 * i + 2] = a.z; }
+    if (cov6) { cov6[6 * i] = b.x; cov6[6 * i + 1] = b.y; cov6[6 * i + 2] = b.z; cov6[6 * i + 3] = b.w; cov6[6 * i + 4] = d.x; cov6[6 * i + 5] = d.y; }
+    if (key) std::memcpy(&key[i], &a.w, sizeof(int32_t));
+  }
+  // the searched axes of a 3D window: x, y and yaw
+  static SearchWindow window(const ndt3d_search_window& w) {
+    SearchWindow v;
+    const int src[3] = {0, 1, 5};
+    for (int a = 0; a < 3; ++a) { v.center[a] = w.center[src[a]]; v.half_extent[a] = w.half_extent[a]; v.step[a] = w.step[a]; }
+    v.min_sep_trans = w.min_sep_trans; v.min_sep_rot = w.min_sep_rot;
+    return v;
+  }
+  // the peaks as the ABI's hits: the searched (x, y, yaw) from the peak, the pinned coordinates from the window's centre
+  static void hits_out(const SearchPeak* peaks, int32_t n, const ndt3d_search_window& w3, ndt3d_search_hit* hits) {
+    for (int32_t q = 0; q < n; ++q) {
+      ndt3d_search_hit& hh = hits[q];
+      std::memset(&hh, 0, sizeof(hh));
+      hh.pose[0] = peaks[q].pose[0]; hh.pose[1] = peaks[q].pose[1]; hh.pose[5] = peaks[q].pose[2];
+      for (int a = 2; a <= 4; ++a) hh.pose[a] = w3.center[a];
+      hh.score = peaks[q].score;
+      hh.index = peaks[q].index;
+    }
+  }
+};
 
 // a host scan into the handle's staging arrays, behind the alignment in flight
 int32_t stage_source3(ndt3d_handle* h, const float* sx, const float* sy, const float* sz, size_t n) {

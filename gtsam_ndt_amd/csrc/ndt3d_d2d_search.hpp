@@ -1,9 +1,9 @@
 // Exhaustive pose search for 3D map-to-map alignment (docs/ALGORITHM.md section 2.16): the map-to-map score of
 // ndt3d_evaluate_map at every pose of an (x, y, yaw) lattice, z, roll and pitch pinned to the window centre's, from the
 // source handle's component list and the target handle's covariance records - no points.  Included at the end of
-// ndt2d_api.hip, after ndt3d_search.hpp and ndt3d_d2d_api.hpp: the lattice, the peak selection, the scratch and the
-// separation walk are ndt_search.hpp's, the 3D window and hit ndt3d_search.hpp's, the component list and the covariance
-// records ndt3d_d2d_api.hpp's.
+// ndt2d_api.hip, after ndt3d_search.hpp and ndt3d_d2d_api.hpp: the lattice, the peak selection, the scratch, the
+// separation walk and the host run are ndt_search.hpp's, the 3D window and hit HandleTraits<ndt3d_handle>'s, the component
+// list and the covariance records ndt_map_host.hpp's.
 //
 //   k_search_score_d2d3  the score volume, in the shape of k_search_score3 / k_search_score_d2d: one workgroup = one yaw x
 //                        a 16 x 16 tile of translations, ONE LANE PER TRANSLATION, a wave an 8 x 8 block.  R is uniform
@@ -186,41 +186,17 @@ __global__ __launch_bounds__(kSearchThreads, 4) void k_search_score_d2d3(const A
 // ------------------------------------------------------------------------------ host side
 namespace {
 
-// The whole map-to-map search on the TARGET handle's stream and search scratch; the source handle lends its component
-// list.  d_scores != null: only the volume, into the caller's buffer; else the hits.  Returns once the target's stream
-// has drained: nothing reads the source's list any more.
+// The whole map-to-map search (search_host_run) on the TARGET handle's stream and search scratch; the source handle lends
+// its component list.  Here: the score launch, with the pinned coordinates.
 int32_t search_map_run3(ndt3d_handle* t, ndt3d_handle* s, const ndt3d_search_window* w3, int32_t k, ndt3d_search_hit* hits,
                         int32_t* n_hits, float* d_scores) {
   using namespace ndt;
   TraceRange range(d_scores ? "ndt3d_search_map_scores" : "ndt3d_search_map");
-  SearchWindow w;
-  SearchPlan plan;
-  { const int32_t ls = search_lattice3(w3, &w, &plan.L); if (ls != NDT_OK) return ls; }
-  if (!t->has_target || !s->has_target) return NDT_ERR_NO_TARGET;
-  if (t->device != s->device) { set_error("map-to-map search: both handles must live on one device"); return NDT_ERR_INVALID_ARG; }
-  HIP_TRY(hipSetDevice(t->device));
-  { const int32_t fs = finish_align3(t); if (fs != NDT_OK) return fs; }
-  if (s != t) { const int32_t fs = finish_align3(s); if (fs != NDT_OK) return fs; }
-  { const int32_t cs = ensure_components3(s); if (cs != NDT_OK) return cs; }
-  { const int32_t cs = ensure_cov_records3(t); if (cs != NDT_OK) return cs; }
-  if (s != t) HIP_TRY(order_after(t->stream, s->stream, &s->map_ev));       // the list may still be in flight on s's stream
-  { const int32_t us = search_upload_axes(t->srch, t->stream, w, &plan); if (us != NDT_OK) return us; }
-  const SearchLattice& L = plan.L;
-  float* vol = nullptr;
-  { const int32_t vs = search_volume(t->srch, plan.poses(), d_scores, &vol); if (vs != NDT_OK) return vs; }
-  const unsigned grid = (unsigned)std::min<long long>(plan.tasks(), 1ll << 20);
-  hipLaunchKernelGGL(k_search_score_d2d3, dim3(grid), dim3(kSearchThreads), 0, t->stream, t->d_static, (const float4*)t->d_cov,
-                     (float)t->prm.d1, (float)t->prm.d2, (const float4*)s->d_comp, s->n_comp, plan.d_x, plan.d_y, plan.d_rot,
-                     w3->center[2], w3->center[3], w3->center[4], L.nx, L.ny, L.nt, vol);
-  HIP_TRY(hipGetLastError());
-  if (d_scores) {
-    HIP_TRY(hipStreamSynchronize(t->stream));
-    return NDT_OK;
-  }
-  SearchPeak peaks[kMaxStarts3];
-  { const int32_t ss = search_select(t->srch, t->stream, vol, plan, w, k, peaks, n_hits); if (ss != NDT_OK) return ss; }
-  search_hits_out3(peaks, *n_hits, *w3, hits);
-  return NDT_OK;
+  return search_host_run(t, s, w3, k, hits, n_hits, d_scores, [&](const SearchPlan& plan, unsigned grid, float* vol) {
+    hipLaunchKernelGGL(k_search_score_d2d3, dim3(grid), dim3(kSearchThreads), 0, t->stream, t->d_static, (const float4*)t->d_cov,
+                       (float)t->prm.d1, (float)t->prm.d2, (const float4*)s->d_comp, s->n_comp, plan.d_x, plan.d_y, plan.d_rot,
+                       w3->center[2], w3->center[3], w3->center[4], plan.L.nx, plan.L.ny, plan.L.nt, vol);
+  });
 }
 
 }  // namespace
@@ -246,13 +222,11 @@ int32_t ndt3d_search_align_map(ndt3d_handle* target, ndt3d_handle* source, const
   const int32_t st = ndt3d_search_map(target, source, w, k, hits, n_hits);
   if (st != NDT_OK || *n_hits < 1) return st;
   // every hit is a start of one map-to-map chain (ndt3d_align_map_multi: bit for bit ndt3d_align_map from each pose)
-  ndt3d_handle* sources[ndt::kMaxStarts3];
-  double poses[ndt::kMaxStarts3][6];
-  for (int32_t q = 0; q < *n_hits; ++q) {
-    sources[q] = source;
-    for (int j = 0; j < 6; ++j) poses[q][j] = hits[q].pose[j];
-  }
-  return ndt3d_align_map_multi(target, sources, &poses[0][0], *n_hits, results);
+  return search_hits_align<ndt3d_handle>(hits, *n_hits, [&](const double* poses) {
+    ndt3d_handle* sources[ndt::kMaxStarts3];
+    std::fill_n(sources, *n_hits, source);
+    return ndt3d_align_map_multi(target, sources, poses, *n_hits, results);
+  });
 }
 
 }  // extern "C"

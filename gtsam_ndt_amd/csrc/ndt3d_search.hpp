@@ -136,64 +136,18 @@ __global__ __launch_bounds__(kSearchThreads) void k_search_score3(const AlignSta
 // ------------------------------------------------------------------------------ host side
 namespace {
 
-// the searched axes of a 3D window: x, y and yaw
-SearchWindow search_window3(const ndt3d_search_window& w) {
-  SearchWindow v;
-  const int src[3] = {0, 1, 5};
-  for (int a = 0; a < 3; ++a) { v.center[a] = w.center[src[a]]; v.half_extent[a] = w.half_extent[a]; v.step[a] = w.step[a]; }
-  v.min_sep_trans = w.min_sep_trans; v.min_sep_rot = w.min_sep_rot;
-  return v;
-}
-
-int32_t search_lattice3(const ndt3d_search_window* w3, SearchWindow* w, SearchLattice* L) {
-  if (!w3) return NDT_ERR_INVALID_ARG;
-  for (int a = 2; a <= 4; ++a)
-    if (!std::isfinite(w3->center[a])) return NDT_ERR_INVALID_ARG;
-  *w = search_window3(*w3);
-  return search_lattice(*w, L);
-}
-
-// the peaks as the ABI's hits: the searched (x, y, yaw) from the peak, the pinned coordinates from the window's centre
-void search_hits_out3(const SearchPeak* peaks, int32_t n, const ndt3d_search_window& w3, ndt3d_search_hit* hits) {
-  for (int32_t q = 0; q < n; ++q) {
-    ndt3d_search_hit& hh = hits[q];
-    std::memset(&hh, 0, sizeof(hh));
-    hh.pose[0] = peaks[q].pose[0]; hh.pose[1] = peaks[q].pose[1]; hh.pose[5] = peaks[q].pose[2];
-    for (int a = 2; a <= 4; ++a) hh.pose[a] = w3.center[a];
-    hh.score = peaks[q].score;
-    hh.index = peaks[q].index;
-  }
-}
-
-// The whole search on the handle's stream.  d_scores != null: only the volume, into the caller's buffer; else the hits.
+// The whole search on the handle's stream (search_host_run): the score launch, with the pinned coordinates.
 int32_t search_run3(ndt3d_handle* h, const float* d_sx, const float* d_sy, const float* d_sz, size_t n,
                     const ndt3d_search_window* w3, int32_t k, ndt3d_search_hit* hits, int32_t* n_hits, float* d_scores) {
   using namespace ndt;
   TraceRange range(d_scores ? "ndt3d_search_scores" : "ndt3d_search");
-  SearchWindow w;
-  SearchPlan plan;
-  { const int32_t ls = search_lattice3(w3, &w, &plan.L); if (ls != NDT_OK) return ls; }
-  if (!h->has_target) return NDT_ERR_NO_TARGET;
-  HIP_TRY(hipSetDevice(h->device));
-  { const int32_t fs = finish_align3(h); if (fs != NDT_OK) return fs; }
-  { const int32_t us = search_upload_axes(h->srch, h->stream, w, &plan); if (us != NDT_OK) return us; }
-  const SearchLattice& L = plan.L;
-  float* vol = nullptr;
-  { const int32_t vs = search_volume(h->srch, plan.poses(), d_scores, &vol); if (vs != NDT_OK) return vs; }
-  const unsigned grid = (unsigned)std::min<long long>(plan.tasks(), 1ll << 20);
-  const float d1 = (float)h->prm.d1, d2 = (float)h->prm.d2;        // as upload_static3
-  hipLaunchKernelGGL(k_search_score3, dim3(grid), dim3(kSearchThreads), 0, h->stream, h->d_static, (const float4*)h->grid.rec, d1, d2,
-                     d_sx, d_sy, d_sz, (int)n, plan.d_x, plan.d_y, plan.d_rot, w3->center[2], w3->center[3], w3->center[4], L.nx,
-                     L.ny, L.nt, vol);
-  HIP_TRY(hipGetLastError());
-  if (d_scores) {
-    HIP_TRY(hipStreamSynchronize(h->stream));
-    return NDT_OK;
-  }
-  SearchPeak peaks[kMaxStarts3];
-  { const int32_t ss = search_select(h->srch, h->stream, vol, plan, w, k, peaks, n_hits); if (ss != NDT_OK) return ss; }
-  search_hits_out3(peaks, *n_hits, *w3, hits);
-  return NDT_OK;
+  return search_host_run(h, (ndt3d_handle*)nullptr, w3, k, hits, n_hits, d_scores, [&](const SearchPlan& plan, unsigned grid, float* vol) {
+    const SearchLattice& L = plan.L;
+    const float d1 = (float)h->prm.d1, d2 = (float)h->prm.d2;        // as upload_static3
+    hipLaunchKernelGGL(k_search_score3, dim3(grid), dim3(kSearchThreads), 0, h->stream, h->d_static, (const float4*)h->grid.rec, d1, d2,
+                       d_sx, d_sy, d_sz, (int)n, plan.d_x, plan.d_y, plan.d_rot, w3->center[2], w3->center[3], w3->center[4], L.nx,
+                       L.ny, L.nt, vol);
+  });
 }
 
 int32_t search_args3(ndt3d_handle* h, const float* sx, const float* sy, const float* sz, size_t n, const ndt3d_search_window* w,
@@ -211,7 +165,7 @@ int32_t ndt3d_search_lattice_size(const ndt3d_search_window* w, int32_t dims[3])
   if (!w || !dims) return NDT_ERR_INVALID_ARG;
   SearchWindow v;
   SearchLattice L;
-  const int32_t st = search_lattice3(w, &v, &L);
+  const int32_t st = search_lattice_of<ndt3d_handle>(w, &v, &L);
   if (st != NDT_OK) return st;
   dims[0] = L.nt; dims[1] = L.ny; dims[2] = L.nx;
   return NDT_OK;
@@ -230,7 +184,7 @@ int32_t ndt3d_search(ndt3d_handle* h, const float* sx, const float* sy, const fl
   int32_t st = search_args3(h, sx, sy, sz, n, w, k, hits, n_hits);
   if (st != NDT_OK) return st;
   *n_hits = 0;
-  { SearchWindow v; SearchLattice L; st = search_lattice3(w, &v, &L); if (st != NDT_OK) return st; }
+  { SearchWindow v; SearchLattice L; st = search_lattice_of<ndt3d_handle>(w, &v, &L); if (st != NDT_OK) return st; }
   if (!h->has_target) return NDT_ERR_NO_TARGET;
   HIP_TRY(hipSetDevice(h->device));
   { const int32_t ss = stage_source3(h, sx, sy, sz, n); if (ss != NDT_OK) return ss; }
@@ -249,10 +203,9 @@ int32_t ndt3d_search_align_dev(ndt3d_handle* h, const float* d_sx, const float* 
   if (!results) return NDT_ERR_INVALID_ARG;
   const int32_t st = ndt3d_search_dev(h, d_sx, d_sy, d_sz, n, w, k, hits, n_hits);
   if (st != NDT_OK || *n_hits == 0) return st;
-  std::vector<double> init(6 * (size_t)*n_hits);
-  for (int32_t q = 0; q < *n_hits; ++q)
-    for (int a = 0; a < 6; ++a) init[6 * q + a] = hits[q].pose[a];
-  return ndt3d_align_multi_start_dev(h, d_sx, d_sy, d_sz, n, init.data(), *n_hits, results);
+  return search_hits_align<ndt3d_handle>(hits, *n_hits, [&](const double* init) {
+    return ndt3d_align_multi_start_dev(h, d_sx, d_sy, d_sz, n, init, *n_hits, results);
+  });
 }
 
 }  // extern "C"

@@ -480,8 +480,9 @@ inline hipError_t run_multi_chain(hipGraphExec_t exec, hipStream_t stream, int* 
   return e;
 }
 
-// ---- the plan of a call that carries several map-to-map alignments (ndt2d_align_map_multi) --------------------------
-// Pure host functions: tests/cpp/d2d_multi_host_test.cpp walks them without a device.
+// ---- the plan of a call that carries several map-to-map alignments (ndt2d_align_map_multi, ndt3d_align_map_multi) ---
+// Pure host functions: tests/cpp/d2d_multi_host_test.cpp walks them without a device.  The rest of the plan, which
+// makes HIP calls, is ndt_map_host.hpp's run_align_map_multi.
 
 // Workgroups of `threads` threads for n items, at most `cap` (a map-to-map launch: one component per lane, kMaxBlocks rows)
 inline int capped_blocks(long long n, int threads, int cap) {
@@ -507,6 +508,30 @@ inline int distinct_pointers(T* const* in, int m, T** out) {
     if (!seen) out[n++] = in[k];
   }
   return n;
+}
+
+// The kernel arguments of such a call's first launch, from start k's pose init_poses[P k .. P k + P) (P = the pose length
+// of Poses: StartPoses / StartPoses3) and the component list sources[k] has prepared (d_comp, n_comp): sp->p[k], and in
+// *sm (StartMaps / StartMaps3, zeroed by the caller) the list, its length and its workgroups (capped_blocks).  A start
+// whose source has no component - every start, if the target has no valid cell - keeps n = 0 in its slot: the caller
+// answers it on the spot.  Returns the number of the others; *max_blocks = the most workgroups any of them takes (>= 1).
+template <class Poses, class Maps, class Source>
+inline int plan_map_starts(Source* const* sources, const double* init_poses, int m, bool target_has_cells, int threads,
+                           int cap, Poses* sp, Maps* sm, int* max_blocks) {
+  constexpr int P = (int)(sizeof(sp->p[0]) / sizeof(sp->p[0][0]));
+  int live = 0;
+  *max_blocks = 1;
+  for (int k = 0; k < m; ++k) {
+    for (int j = 0; j < P; ++j) sp->p[k][j] = init_poses[P * k + j];
+    const int n = target_has_cells ? sources[k]->n_comp : 0;
+    if (n < 1) { sm->n[k] = 0; continue; }
+    sm->comp[k] = sources[k]->d_comp;
+    sm->n[k] = n;
+    sm->blocks[k] = capped_blocks(n, threads, cap);
+    *max_blocks = sm->blocks[k] > *max_blocks ? sm->blocks[k] : *max_blocks;
+    ++live;
+  }
+  return live;
 }
 
 // The pinned 256-byte block of a handle (h_small): counter shards at 0, the outside count at 128, the cells a removal broke

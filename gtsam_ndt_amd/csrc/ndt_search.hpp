@@ -377,4 +377,66 @@ int32_t search_select(ndt::SearchScratch& s, hipStream_t stream, const float* vo
   return NDT_OK;
 }
 
+// What differs between the dimensions in the host code both handles share, specialised next to each handle
+// (ndt2d_api.hip, ndt3d_api.hpp).  Here: Window and Hit (the ABI's), kPose, kMaxStarts, finish (waits for the alignment
+// in flight), window (the searched axes of a Window) and hits_out (the walk's peaks as the ABI's hits).
+template <class Handle> struct HandleTraits;
+
+// (ndt_map_host.hpp) what a map-to-map call refuses and prepares before it enqueues anything
+template <class H> int32_t prepare_map_pair(H* t, H* s, const char* who, const double* pose);
+
+// The lattice of an ABI window; *w = its searched axes.  Every centre coordinate has to be finite, the pinned ones too.
+template <class H>
+int32_t search_lattice_of(const typename HandleTraits<H>::Window* win, SearchWindow* w, SearchLattice* L) {
+  if (!win) return NDT_ERR_INVALID_ARG;
+  for (int a = 0; a < HandleTraits<H>::kPose; ++a)
+    if (!std::isfinite(win->center[a])) return NDT_ERR_INVALID_ARG;
+  *w = HandleTraits<H>::window(*win);
+  return search_lattice(*w, L);
+}
+
+// The whole search on t's stream and search scratch.  s = null: of a scan; else of s's component list (a map-to-map
+// search: s lends the list, and nothing reads it any more on return).  launch(plan, grid, vol) enqueues the score kernel
+// on t's stream: `grid` workgroups, the volume into vol.  d_scores != null: only the volume, into the caller's buffer;
+// else the hits.
+template <class H, class Launch>
+int32_t search_host_run(H* t, H* s, const typename HandleTraits<H>::Window* win, int32_t k,
+                        typename HandleTraits<H>::Hit* hits, int32_t* n_hits, float* d_scores, Launch&& launch) {
+  using T = HandleTraits<H>;
+  SearchWindow w;
+  SearchPlan plan;
+  { const int32_t ls = search_lattice_of<H>(win, &w, &plan.L); if (ls != NDT_OK) return ls; }
+  if (s) {
+    const int32_t ps = prepare_map_pair(t, s, "search: both", nullptr);
+    if (ps != NDT_OK) return ps;
+  } else {
+    if (!t->has_target) return NDT_ERR_NO_TARGET;
+    HIP_TRY(hipSetDevice(t->device));
+    { const int32_t fs = T::finish(t); if (fs != NDT_OK) return fs; }
+  }
+  { const int32_t us = search_upload_axes(t->srch, t->stream, w, &plan); if (us != NDT_OK) return us; }
+  float* vol = nullptr;
+  { const int32_t vs = search_volume(t->srch, plan.poses(), d_scores, &vol); if (vs != NDT_OK) return vs; }
+  launch(plan, (unsigned)std::min<long long>(plan.tasks(), 1ll << 20), vol);
+  HIP_TRY(hipGetLastError());
+  if (d_scores) {
+    HIP_TRY(hipStreamSynchronize(t->stream));
+    return NDT_OK;
+  }
+  SearchPeak peaks[T::kMaxStarts];
+  { const int32_t ss = search_select(t->srch, t->stream, vol, plan, w, k, peaks, n_hits); if (ss != NDT_OK) return ss; }
+  T::hits_out(peaks, *n_hits, *win, hits);
+  return NDT_OK;
+}
+
+// The hits of a search as the start poses of one multi call: align(poses) gets them as [n_hits][kPose].
+template <class H, class Align>
+int32_t search_hits_align(const typename HandleTraits<H>::Hit* hits, int32_t n_hits, Align&& align) {
+  constexpr int P = HandleTraits<H>::kPose;
+  double poses[HandleTraits<H>::kMaxStarts][P];
+  for (int32_t q = 0; q < n_hits; ++q)
+    for (int j = 0; j < P; ++j) poses[q][j] = hits[q].pose[j];
+  return align(&poses[0][0]);
+}
+
 }  // namespace

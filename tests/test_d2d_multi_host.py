@@ -1,5 +1,6 @@
-"""The plan of an ndt2d_align_map_multi call (csrc/ndt_host.hpp: the distinct source handles, the workgroups per start,
-the power-of-two launch shapes) is made by pure host functions: a stand-alone program walks them.  Built with the
+"""The plan of an ndt2d_align_map_multi / ndt3d_align_map_multi call (csrc/ndt_host.hpp: the distinct source handles, the
+workgroups per start, the power-of-two launch shapes, the start poses and maps of the first launch with the starts
+that are answered on the spot) is made by pure host functions: a stand-alone program walks them.  Built with the
 address and undefined-behaviour sanitizers of the host compiler; it makes no HIP call and needs no GPU."""
 import os
 import subprocess

@@ -40,7 +40,7 @@ def case(d, cell, window, reps):
         res["align_map_ms"] = med_ms(lambda: t.align_map(s, out[0][0].pose), reps)
         res["component_poses_per_s_host"] = res["components"] * res["poses"] / (res["search_map_scores_ms"] * 1e-3)
         res["hits"] = len(out)
-        conv = [(h, r) for h, r in out if r.converged]
+        conv = [(h, r) for h, r in out if r.status == 0]          # (AlignResult3D has no .converged)
         if conv:
             h, r = max(conv, key=lambda hr: hr[1].score)
             res["best_hit"], res["best_pose"], res["iterations"] = list(h.pose), list(r.pose), r.iterations
