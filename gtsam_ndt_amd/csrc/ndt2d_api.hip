@@ -1464,6 +1464,7 @@ extern "C" int32_t ndt2d_align_multi_scan_dev(ndt2d_handle* h, const float* cons
   return multi_align(h, d_sx, d_sy, n, /*shared=*/false, init_poses, m, results);
 }
 
+#include "ndt_batch_host.hpp"
 #include "ndt2d_batch_api.hpp"
 #include "ndt2d_multi_api.hpp"
 #include "ndt3d_api.hpp"

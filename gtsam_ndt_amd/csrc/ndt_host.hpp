@@ -9,6 +9,7 @@
 #include <sched.h>
 
 #include <atomic>
+#include <cstdint>
 #include <cstring>
 #include <initializer_list>
 #include <string>
@@ -532,6 +533,79 @@ inline int plan_map_starts(Source* const* sources, const double* init_poses, int
     ++live;
   }
   return live;
+}
+
+// ---- the device-free half of the batch and multi-device contexts (ndt_batch_host.hpp) -------------------------------
+// Pure host functions: tests/cpp/batch_host_test.cpp walks them without a device.  Offsets are CSR style: pair k's
+// cloud is points off[k] .. off[k + 1] of the concatenated arrays, so an offset array has n_pairs + 1 entries.
+
+// What a batch call accepts of its offsets: none decreases, and no cloud has more than max_cloud points (kBatchMaxCloud:
+// a cloud of a pair is indexed with 32-bit byte offsets on the device)
+inline bool pair_offsets_ok(const uint64_t* toff, const uint64_t* soff, size_t n_pairs, uint64_t max_cloud) {
+  for (size_t k = 0; k < n_pairs; ++k)
+    if (toff[k + 1] < toff[k] || soff[k + 1] < soff[k] || toff[k + 1] - toff[k] > max_cloud || soff[k + 1] - soff[k] > max_cloud)
+      return false;
+  return true;
+}
+
+// The split of n_pairs pairs into n_shards contiguous, work-balanced shards (ndt2d_multi_plan_hinted): shard d gets
+// pairs shard_begin[d] .. shard_begin[d + 1].  false, with shard_begin untouched: an offset decreases.
+inline bool plan_shards(int n_shards, const uint64_t* toff, const uint64_t* soff, size_t n_pairs, int iterations_hint,
+                        const int32_t* pair_iterations, uint64_t* shard_begin) {
+  const double kk = iterations_hint > 0 ? iterations_hint : 30;
+  // work of a pair = its target points once (grid build: three passes) + its source points per iteration; the
+  // iterations from the caller's per-pair hint where it gives one (converged-mode batches: what the candidate took at
+  // the coarser level, or last time), else the common hint
+  auto work = [&](size_t k) {
+    const double it = pair_iterations && pair_iterations[k] > 0 ? (double)pair_iterations[k] : kk;
+    return 3.0 * double(toff[k + 1] - toff[k]) + it * double(soff[k + 1] - soff[k]) + 1.0;
+  };
+  double total = 0;
+  for (size_t k = 0; k < n_pairs; ++k) {
+    if (toff[k + 1] < toff[k] || soff[k + 1] < soff[k]) return false;
+    total += work(k);
+  }
+  size_t k = 0;
+  double acc = 0;
+  shard_begin[0] = 0;
+  for (int d = 1; d <= n_shards; ++d) {
+    const double goal = total * d / n_shards;
+    // a pair goes to the shard in which its midpoint falls: contiguous, deterministic, balanced
+    while (k < n_pairs && acc + 0.5 * work(k) <= goal) acc += work(k++);
+    shard_begin[d] = d == n_shards ? n_pairs : k;
+  }
+  return true;
+}
+
+// The offsets of the shard of pairs k0 .. k1 rebased to its first point, so that only its own points are uploaded:
+// out[0 .. k1 - k0] (k1 - k0 + 1 entries, out[0] = 0)
+inline void rebase_shard(const uint64_t* off, size_t k0, size_t k1, uint64_t* out) {
+  for (size_t k = k0; k <= k1; ++k) out[k - k0] = off[k] - off[k0];
+}
+
+// The layout of the all-gather of result rows (multi_align_dev): every shard sends `stride` rows, the longest shard's
+// number (its own, then zeroed padding), as `count` doubles; shard d's rows sit at row d * stride of every receive buffer.
+struct GatherLayout { size_t stride = 0, count = 0, total = 0; };    // total: the pairs of all shards
+inline GatherLayout gather_layout(const size_t* n_pairs, int n_shards, size_t row_bytes) {
+  GatherLayout g;
+  for (int d = 0; d < n_shards; ++d) {
+    g.stride = n_pairs[d] > g.stride ? n_pairs[d] : g.stride;
+    g.total += n_pairs[d];
+  }
+  g.count = g.stride * (row_bytes / sizeof(double));
+  return g;
+}
+
+// Global pair order out of a receive buffer, padding dropped: copy(to, from, rows) for every shard that has rows, in
+// rows of the caller's array (to) and of the receive buffer (from).  Returns the first result of copy that is not `ok`.
+template <class Status, class Copy>
+inline Status ungather(const size_t* n_pairs, int n_shards, size_t stride, Status ok, Copy&& copy) {
+  size_t k = 0;
+  for (int d = 0; d < n_shards; ++d) {
+    if (n_pairs[d] > 0) { const Status st = copy(k, (size_t)d * stride, n_pairs[d]); if (st != ok) return st; }
+    k += n_pairs[d];
+  }
+  return ok;
 }
 
 // The pinned 256-byte block of a handle (h_small): counter shards at 0, the outside count at 128, the cells a removal broke
