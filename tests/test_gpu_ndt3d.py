@@ -66,6 +66,25 @@ def test_align3d_converged_pose_parity(gpu_lib, small):
     assert r.pose == r2.pose and np.array_equal(r.H, r2.H)        # deterministic
 
 
+def test_host_arrays_of_unequal_length_are_refused(gpu_lib):
+    """The library gets one length for x, y and z: a shorter array is refused in Python, and the matcher then aligns a
+    pair exactly as a matcher does that never saw the refused calls."""
+    from gtsam_ndt_amd.matcher import NdtMatcher3D
+    d = synth3d.make_pair3d(n_elev=6, n_azim=256)
+    x, y, z = d["tx"], d["ty"], d["tz"]
+    with NdtMatcher3D() as m, NdtMatcher3D() as fresh:
+        with pytest.raises(ValueError):
+            m.set_target(x[:10], y[:9], z[:10])
+        m.set_target(x, y, z)
+        with pytest.raises(ValueError):
+            m.align(x[:10], y[:10], z[:9])
+        r = m.align(d["sx"], d["sy"], d["sz"], d["init"])
+        fresh.set_target(x, y, z)
+        want = fresh.align(d["sx"], d["sy"], d["sz"], d["init"])
+    assert r.status >= 0 and r.iterations > 0 and r.n_hit > 0
+    assert r.pose == want.pose and np.array_equal(r.H, want.H) and (r.iterations, r.n_hit) == (want.iterations, want.n_hit)
+
+
 def test_align3d_full_config5(gpu_lib):
     """The full 64 x 2048 = 131072-point pair of BASELINE config 5."""
     from gtsam_ndt_amd.matcher import NdtMatcher3D
