@@ -162,6 +162,8 @@ SIGNATURES = {
     "ndt2d_save_map": (C.c_int32, [_vp, _vp, C.c_size_t, C.POINTER(C.c_size_t)]),
     "ndt2d_load_map": (C.c_int32, [_vp, _vp, C.c_size_t]),
     "ndt2d_coarsen_map": (C.c_int32, [_vp, _vp]),
+    "ndt2d_merge_map": (C.c_int32, [_vp, _vp, _dp, C.POINTER(C.c_size_t)]),
+    "ndt2d_unmerge_map": (C.c_int32, [_vp, _vp, _dp, C.POINTER(C.c_size_t)]),
     "ndt2d_evaluate": (C.c_int32, [_vp, _vp, _vp, C.c_size_t, _dp, C.POINTER(Eval2D)]),
     "ndt2d_evaluate_dev": (C.c_int32, [_vp, _vp, _vp, C.c_size_t, _dp, C.POINTER(Eval2D)]),
     "ndt2d_align": (C.c_int32, [_vp, _vp, _vp, C.c_size_t, _dp, C.POINTER(Result2D)]),
@@ -247,6 +249,8 @@ SIGNATURES = {
     "ndt3d_save_map": (C.c_int32, [_vp, _vp, C.c_size_t, C.POINTER(C.c_size_t)]),
     "ndt3d_load_map": (C.c_int32, [_vp, _vp, C.c_size_t]),
     "ndt3d_coarsen_map": (C.c_int32, [_vp, _vp]),
+    "ndt3d_merge_map": (C.c_int32, [_vp, _vp, _dp, C.POINTER(C.c_size_t)]),
+    "ndt3d_unmerge_map": (C.c_int32, [_vp, _vp, _dp, C.POINTER(C.c_size_t)]),
     "ndt3d_evaluate": (C.c_int32, [_vp, _vp, _vp, _vp, C.c_size_t, _dp, C.POINTER(Eval3D)]),
     "ndt3d_evaluate_dev": (C.c_int32, [_vp, _vp, _vp, _vp, C.c_size_t, _dp, C.POINTER(Eval3D)]),
     "ndt3d_align": (C.c_int32, [_vp, _vp, _vp, _vp, C.c_size_t, _dp, C.POINTER(Result3D)]),

@@ -36,7 +36,7 @@ struct ndt2d_handle {
   int n_valid = 0;
   size_t n_points = 0;
   unsigned int* d_bounds = nullptr;        // [4]
-  int* d_counters = nullptr;               // [kCountWords] shards of valid / overflowed cells, the cells a removal broke
+  int* d_counters = nullptr;               // [kCountAlloc] shards of valid / overflowed cells, the cells a removal broke, a merge's counts
   unsigned long long* d_outside = nullptr; // [1]
   void* h_small = nullptr;                 // pinned scratch (kSmallBytes: counter shards at 0, the outside count at 128, a flag)
   // staging for host-pointer entry points
@@ -1031,7 +1031,7 @@ int32_t ndt2d_create(const ndt2d_params* p, int32_t device_id, ndt2d_handle** ou
   if (hipSetDevice(device_id) != hipSuccess) return fail(NDT_ERR_HIP);
   if (hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking) != hipSuccess) return fail(NDT_ERR_HIP);
   if (hipMalloc((void**)&h->d_bounds, 4 * sizeof(unsigned int)) != hipSuccess) return fail(NDT_ERR_ALLOC);
-  if (hipMalloc((void**)&h->d_counters, ndt::kCountWords * sizeof(int)) != hipSuccess) return fail(NDT_ERR_ALLOC);
+  if (hipMalloc((void**)&h->d_counters, ndt::kCountAlloc * sizeof(int)) != hipSuccess) return fail(NDT_ERR_ALLOC);
   if (hipMalloc((void**)&h->d_parts, kBoundsParts * sizeof(float4)) != hipSuccess) return fail(NDT_ERR_ALLOC);
   if (hipMalloc((void**)&h->d_acc2, 512) != hipSuccess) return fail(NDT_ERR_ALLOC);
   {   // k_chunk_sort: 32 KB of points + up to 32 KB of tile histogram, just over the 64 KB a kernel gets without asking
@@ -1472,6 +1472,7 @@ extern "C" int32_t ndt2d_align_multi_scan_dev(ndt2d_handle* h, const float* cons
 #include "ndt3d_multi_api.hpp"
 #include "ndt_map_io.hpp"
 #include "ndt_coarsen.hpp"
+#include "ndt_merge.hpp"
 #include "ndt_map_host.hpp"
 #include "ndt2d_search.hpp"
 #include "ndt3d_search.hpp"

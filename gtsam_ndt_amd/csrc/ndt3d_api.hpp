@@ -20,7 +20,7 @@ struct ndt3d_handle {
   bool has_target = false;
   int n_valid = 0;
   unsigned int* d_bounds = nullptr;   // [6]
-  int* d_counters = nullptr;          // counter shards of ndt3d_load_map's finalise (the builds keep theirs in d_tiles)
+  int* d_counters = nullptr;          // [kCountAlloc] counter shards of ndt3d_load_map's finalise and all counts of a merge (the builds keep theirs in d_tiles)
   int publish_seq = 0;                // the flag value of the read-back in flight (publish_and_wait)
   float* d_parts3 = nullptr;          // [256][8]: per-workgroup partial bounding boxes (k_bounds3_parts)
   void* h_small = nullptr;            // pinned kSmallBytes (counter shards at 0, the outside count at 128, a flag)
@@ -605,7 +605,7 @@ int32_t ndt3d_create(const ndt3d_params* p, int32_t device_id, ndt3d_handle** ou
   if (hipSetDevice(device_id) != hipSuccess) return fail(NDT_ERR_HIP);
   if (hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking) != hipSuccess) return fail(NDT_ERR_HIP);
   if (hipMalloc((void**)&h->d_bounds, 32) != hipSuccess) return fail(NDT_ERR_ALLOC);
-  if (hipMalloc((void**)&h->d_counters, ndt::kCountInts * sizeof(int)) != hipSuccess) return fail(NDT_ERR_ALLOC);
+  if (hipMalloc((void**)&h->d_counters, ndt::kCountAlloc * sizeof(int)) != hipSuccess) return fail(NDT_ERR_ALLOC);
   if (hipMalloc((void**)&h->d_outside, sizeof(unsigned long long)) != hipSuccess) return fail(NDT_ERR_ALLOC);
   if (hipMalloc((void**)&h->d_static, sizeof(ndt::AlignStatic3)) != hipSuccess) return fail(NDT_ERR_ALLOC);
   if (hipMalloc((void**)&h->d_call, sizeof(ndt::AlignCall3)) != hipSuccess) return fail(NDT_ERR_ALLOC);

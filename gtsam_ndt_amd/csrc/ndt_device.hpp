@@ -83,6 +83,10 @@ constexpr int kCountInts = 2 * kCountShards;
 // which ends the call with an error.
 constexpr int kCountUnder = kCountInts + 2;
 constexpr int kCountWords = kCountInts + 4;
+// ... and behind those, in d_counters only: two 64-bit counts of ndt*_merge_map (ndt_merge.hpp: the points dropped outside the
+// destination, the points filed), so that one fill clears and one copy brings back everything a merge counts
+constexpr int kCountMerge = kCountWords;
+constexpr int kCountAlloc = kCountWords + 4;
 __device__ __forceinline__ int* count_shard(int* counters) { return counters + 2 * (blockIdx.x & (kCountShards - 1)); }
 
 // one add per WORKGROUP: every thread of the workgroup must call it (it has barriers); a, b = this thread's counts

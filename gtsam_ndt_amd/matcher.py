@@ -320,6 +320,23 @@ class _NdtMatcher(_Handle):
         self._check(self._c.coarsen_map(self._h, dst._h), "coarsen_map")
         return int(dst.grid_info().n_valid)
 
+    def _merge(self, fn, what: str, src, pose) -> int:
+        out = C.c_size_t(0)
+        self._check(fn(self._h, src._h, self._dim.pose(pose), C.byref(out)), what)
+        return int(out.value)
+
+    def merge_map(self, src, pose) -> int:
+        """Fold the submap of `src` - a matcher of this dimension whose cell_size is at most this one's - into this
+        matcher's at `pose` (src's frame in this one's: what self.align_map(src) returns), from src's exact per-cell sums
+        alone (ndt2d/ndt3d_merge_map: no points, so it works on a map that came back from load_map).  Each source cell is
+        filed as a block under the cell of its mean.  Returns the number of points that fell outside this grid."""
+        return self._merge(self._c.merge_map, "merge_map", src, pose)
+
+    def unmerge_map(self, src, pose) -> int:
+        """Take out again what merge_map(src, pose) put in - exactly, whatever was added or removed in between
+        (ndt2d/ndt3d_unmerge_map).  Content that is not in the map is an error that leaves this matcher without a target."""
+        return self._merge(self._c.unmerge_map, "unmerge_map", src, pose)
+
     # ---- (ii)+(iii) one evaluation
     def _evaluate(self, coords, pose):
         p = self._dim.pose(pose)
@@ -1095,6 +1112,16 @@ class _NdtMapPyramid(_Pyramid):
             raise ValueError("both pyramids need the same levels")
         return self._descend(zip(self.levels, source.levels), lambda pair, pose: pair[0].align_map(pair[1], pose),
                              tuple(init_pose) if init_pose is not None else None)
+
+    def merge(self, other, pose) -> int:
+        """level.merge_map(other.level, pose) for every level: the other pyramid's submap folded into this one's at `pose`
+        (what self.align_map(other) returns).  Returns the fine level's count of points that fell outside."""
+        if len(other.levels) != len(self.levels):
+            raise ValueError("both pyramids need the same levels")
+        out = 0
+        for mine, theirs in zip(self.levels, other.levels):
+            out = mine.merge_map(theirs, pose)
+        return out
 
 
 class NdtMapPyramid2D(_NdtMapPyramid):

@@ -236,6 +236,32 @@ int32_t ndt2d_load_map(ndt2d_handle* h, const void* buf, size_t bytes);
  * failed load.  ndt_last_error() says which. */
 int32_t ndt2d_coarsen_map(ndt2d_handle* src, ndt2d_handle* dst);
 
+/* Folds the submap of src into the submap of dst at `pose` (x, y, yaw: src's frame in dst's, what ndt2d_align_map(dst,
+ * src) returns), from src's exact per-cell sums alone (docs/ALGORITHM.md section 2.18) - no points, so it works on maps
+ * that came back from ndt2d_load_map.  ndt2d_unmerge_map takes the same contribution out again.
+ * Per cell of src's grid with 0 < n <= 2^20, centre e, sums S, SS (src units c_s 2^-22), k = c_s / c_d, all float64 in a
+ * fixed operation order without contraction, R = (cos, -sin; sin, cos) from libm on the host:
+ *   1. mu = e + S / (n 2^22 / c_s); mu' = (R0 mu_x + R1 mu_y) + t per row; the destination cell is the one dst's own
+ *      float32 binning rule gives (float)mu'.  A block that lands outside dst's interior (the ring counts as outside) is
+ *      dropped whole and its n added to *n_outside (may be NULL).
+ *   2. a = ((R e + t) - centre_dst) 2^22 / c_d;  r = k (R S);  Q = k^2 (R SS R^T).
+ *   3. dn = n, dS_a = llrint(n a_a + r_a), dSS_ab = llrint(n a_a a_b + a_a r_b + a_b r_a + Q_ab) (half to even); where
+ *      n dSS_aa < dS_a^2 (exact), dSS_aa is raised to ceil(dS_a^2 / n), the rule of ndt2d_coarsen_map, so every
+ *      contribution - and by Cauchy-Schwarz every sum of them - passes ndt2d_load_map.
+ *   4. dst's sums += (merge) or -= (unmerge) the contribution by integer atomics: merges commute bit for bit and unmerge
+ *      with the same (src, pose) is the exact inverse whatever was added to or removed from dst in between.
+ *   5. dst's cells are finalised again with dst's min_points / eig_ratio, n_points changes by the merged n, and what
+ *      map-to-map alignment derived from dst is dropped.  src is unchanged; the call returns when dst is ready.
+ * A source cell goes wholly to the cell of its mean, so the result is not the map a rebuild from the points would give;
+ * total count and (within the roundings) the global first and second moments are conserved.
+ * NDT_ERR_INVALID_ARG: a null handle or pose, src == dst, handles on different devices, overlap_grids = 4 on either
+ * side, src's cell_size above dst's, a pose that is not finite; for ndt2d_unmerge_map also content that is not in dst (a
+ * cell's count fell below zero, or reached zero with sums left) - dst then has no target, as after a failed
+ * ndt2d_remove_target_points.  NDT_ERR_NO_TARGET: either handle holds no grid (a reserved one counts).
+ * NDT_ERR_CAPACITY: a destination cell would exceed 2^20 points; dst has no target afterwards. */
+int32_t ndt2d_merge_map(ndt2d_handle* dst, ndt2d_handle* src, const double pose[3], size_t* n_outside);
+int32_t ndt2d_unmerge_map(ndt2d_handle* dst, ndt2d_handle* src, const double pose[3], size_t* n_outside);
+
 int32_t ndt2d_get_grid_info(ndt2d_handle* h, ndt2d_grid_info* info);
 /* Copies the finalised cell records to host arrays of width*height entries each
  * (any pointer may be NULL): count, mean (x,y interleaved), icov (a,b,c interleaved). */
@@ -677,6 +703,11 @@ int32_t ndt3d_load_map(ndt3d_handle* h, const void* buf, size_t bytes);
  * no empty-ring contract - ndt3d_add_target_points* bins a point into a ring voxel of a reserved extent like into any
  * other - so sums found in src's ring are kept: they go to the coarse voxel their place on the lattice names. */
 int32_t ndt3d_coarsen_map(ndt3d_handle* src, ndt3d_handle* dst);
+/* ndt2d_merge_map / ndt2d_unmerge_map for voxel grids: pose = (x, y, z, roll, pitch, yaw), R = Rz Ry Rx as the nine
+ * products of the alignment kernels in their order (float64, host), rows ((R0 x + R1 y) + R2 z) + t, Q a symmetric 3 x 3;
+ * a block is inside where 0 <= f < extent on every axis (no ring in 3D).  Steps, roundings and return values as there. */
+int32_t ndt3d_merge_map(ndt3d_handle* dst, ndt3d_handle* src, const double pose[6], size_t* n_outside);
+int32_t ndt3d_unmerge_map(ndt3d_handle* dst, ndt3d_handle* src, const double pose[6], size_t* n_outside);
 int32_t ndt3d_get_grid_info(ndt3d_handle* h, ndt3d_grid_info* info);
 /* count [cells], mean [cells][3], icov [cells][6] (xx xy xz yy yz zz); any pointer may be NULL */
 int32_t ndt3d_get_grid(ndt3d_handle* h, int32_t* count, float* mean_xyz, float* icov6);

@@ -272,6 +272,22 @@ class NdtMatcherHip {
   // source map's frame into this map's frame; this matcher's parameters drive the solve; source may be *this.
   // The result's covariance carries the point-to-map calibration factors, which are NOT calibrated for this
   // objective: build a noise model from result.information with factors of your own.
+  // Folds `source`'s submap into this matcher's at `pose` (source's frame in this one's: what alignMap(source) returns), from
+  // source's exact per-cell sums alone (ndt2d_merge_map: no points, so a map that came back from loadMap merges too);
+  // source's cell_size is at most this one's.  Returns the points that fell outside this grid.  unmergeMap with the same
+  // arguments takes exactly that out again, whatever was added or removed in between.
+  size_t mergeMap(NdtMatcherHip& source, const Pose2& pose) {
+    size_t outside = 0;
+    const double p[3] = {pose.x, pose.y, pose.theta};
+    check(ndt2d_merge_map(h_, source.h_, p, &outside), "ndt2d_merge_map");
+    return outside;
+  }
+  size_t unmergeMap(NdtMatcherHip& source, const Pose2& pose) {
+    size_t outside = 0;
+    const double p[3] = {pose.x, pose.y, pose.theta};
+    check(ndt2d_unmerge_map(h_, source.h_, p, &outside), "ndt2d_unmerge_map");
+    return outside;
+  }
   MatchResult alignMap(NdtMatcherHip& source, const Pose2& guess = Pose2()) {
     const double init[3] = {guess.x, guess.y, guess.theta};
     ndt2d_result r;
@@ -747,6 +763,19 @@ class NdtMatcherHip3 {
   // Map-to-map alignment (ndt3d_align_map): source's cached voxel grid against this matcher's, no points; the pose maps
   // the source map's frame into this map's frame; this matcher's parameters drive the solve; source may be *this.
   // result.covariance is the plain inverse of the map-to-map Hessian: no calibration exists for this objective.
+  // as NdtMatcherHip::mergeMap / unmergeMap, for voxel grids (ndt3d_merge_map, ndt3d_unmerge_map)
+  size_t mergeMap(NdtMatcherHip3& source, const Pose3& pose) {
+    size_t outside = 0;
+    const double p[6] = {pose.x, pose.y, pose.z, pose.roll, pose.pitch, pose.yaw};
+    check(ndt3d_merge_map(h_, source.h_, p, &outside), "ndt3d_merge_map");
+    return outside;
+  }
+  size_t unmergeMap(NdtMatcherHip3& source, const Pose3& pose) {
+    size_t outside = 0;
+    const double p[6] = {pose.x, pose.y, pose.z, pose.roll, pose.pitch, pose.yaw};
+    check(ndt3d_unmerge_map(h_, source.h_, p, &outside), "ndt3d_unmerge_map");
+    return outside;
+  }
   MatchResult3 alignMap(NdtMatcherHip3& source, const Pose3& guess = Pose3()) {
     const double init[6] = {guess.x, guess.y, guess.z, guess.roll, guess.pitch, guess.yaw};
     ndt3d_result r;
