@@ -4,7 +4,20 @@ against the single-pair kernel on the same inputs (two independent device implem
 import numpy as np
 import pytest
 
+import cell_record_ref as X
+import map_coarsen_ref as R
+
 pytestmark = pytest.mark.gpu
+
+
+def _records_like_the_restatement(m, mean, icov, kw, what):
+    """The fetched means and Sigma^-1 of every valid cell against the float64 restatement of the device formula on the
+    handle's own exact sums (tests/cell_record_ref.py records_float64), at twice the constant of the committed
+    expectations: these clouds have none."""
+    blob = m.save_map()
+    ref = X.records_float64(blob, kw["min_points"], kw["eig_ratio"])
+    np.testing.assert_array_equal(icov[:, 0] != 0, ref["valid"], err_msg=what)
+    X.check_records(dict(mean=mean, icov=icov), ref, R.parse(blob)[0], c=2 * X.C_RECORD, what=what)
 
 # Gradient yardstick: the largest difference between the float32-mirror and the float64 oracle gradients over the seeded
 # cases below whose two hit counts agree, in units of sqrt(|H_ii| * max(score, 1)) (the scale of test_evaluate_parity:
@@ -72,6 +85,7 @@ def test_random_clouds_build_and_evaluate_like_the_oracle(gpu_lib):
             np.testing.assert_array_equal(count.astype(np.int64), g.count, err_msg=f"case {i}")
             assert info.n_valid == g.n_valid, (i, kw)
             np.testing.assert_array_equal(icov[:, 0] != 0, g.valid, err_msg=f"case {i}")
+            _records_like_the_restatement(m, mean, icov, kw, f"case {i} {kw}")
             if g.n_valid == 0:
                 r = m.align(sx, sy, pose)
                 assert r.status == L.NDT_TOO_FEW_CELLS
@@ -142,6 +156,8 @@ def test_random_clouds_3d(gpu_lib):
             count, mean, icov = m.grid()
             np.testing.assert_array_equal(count.astype(np.int64), g.count, err_msg=f"case {i}")
             assert info.n_valid == g.n_valid, (i, kw)
+            np.testing.assert_array_equal(icov[:, 0] != 0, g.valid, err_msg=f"case {i}")
+            _records_like_the_restatement(m, mean, icov, kw, f"case {i} {kw}")
             if g.n_valid == 0:
                 assert m.align(sx, sy, sz, pose).status == L.NDT_TOO_FEW_CELLS
                 continue
