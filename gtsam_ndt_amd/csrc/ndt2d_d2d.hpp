@@ -126,7 +126,7 @@ __global__ __launch_bounds__(kBlock) void k_begin_d2d(MapCall* __restrict__ call
   const int tid = threadIdx.x;
   if (tid >= blocks && tid < kMaxBlocks) {
 #pragma unroll
-    for (int j = 0; j < kNumAcc; ++j) { dyn->partials[0][j][tid] = 0.f; dyn->partials[1][j][tid] = 0.f; }
+    for (int j = 0; j < kNumAcc; ++j) { dyn->rows[0][j][tid] = 0.f; dyn->rows[1][j][tid] = 0.f; }
   }
   if (tid != 0) return;
   call->comp = comp;
@@ -219,7 +219,7 @@ __global__ __launch_bounds__(kBlock) void k_iterate_d2d(const AlignStatic* __res
   int* const host_flag = call->host_flag;
   float4 pv[3];
   {
-    const float* part = &dyn->partials[parity ^ 1][0][0];
+    const float* part = &dyn->rows[parity ^ 1][0][0];     // this chain keeps the table as one row per sum
 #pragma unroll
     for (int v = 0; v < 3; ++v)
       pv[v] = *reinterpret_cast<const float4*>(part + (wave * 3 + v) * kMaxBlocks + lane * 4);
@@ -294,7 +294,7 @@ __global__ __launch_bounds__(kBlock) void k_iterate_d2d(const AlignStatic* __res
 #pragma unroll
       for (int w = 0; w < kBlock / 64; ++w) r += s_wave[w][tid];     // fixed order
     }
-    dyn->partials[parity][tid][blockIdx.x] = r;
+    dyn->rows[parity][tid][blockIdx.x] = r;
   }
 }
 

@@ -17,6 +17,17 @@
   __shared__ float s_t[THREADS / 64][(kNumAcc - 1) * kSumRowStride];
   if (EXP & 8) return;
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  // Where this lane's share of the previous launch's table lies, as one unsigned 32-bit byte offset (the loads keep the
+  // scalar-base form), worked out up here, while the kernel arguments are still on their way.  Waves 0..2 own the three
+  // groups of four sums: the entries of the lane's workgroups 4 lane .. 4 lane + 3, which lie partial_slot's 32 entries
+  // = 512 bytes apart (EXP & 32, tools/exp_tail.hip: slot = workgroup, 64 contiguous bytes).  The other waves read the
+  // entries of workgroups 0..3 of group 0 instead and never look at them.
+  static_assert(partial_slot(4 * 5 + 3) == partial_slot(4 * 5) + 3 * (kMaxBlocks / 8), "entries of a lane's four workgroups");
+  const unsigned wv = __builtin_amdgcn_readfirstlane(wave);     // uniform: the selects below are scalar
+  const unsigned pv_ln = lane & (wv < kNumAcc / 4 ? 63u : 0u);
+  const unsigned pv_off = 16u * ((wv < kNumAcc / 4 ? wv * kMaxBlocks : 0u) +
+                                 ((EXP & 32) ? 4u * pv_ln : (unsigned)partial_slot(4 * (int)pv_ln)));
+  __builtin_amdgcn_sched_barrier(0);     // ... and stays above the wait for them
   const IterState* prev = &dyn->state[parity ^ 1];
   IterState* cur = &dyn->state[parity];
   const bool writer = (blockIdx.x == 0) && (tid == 0);
@@ -26,15 +37,21 @@
   // ps_have are known - the table always exists, so the loads are harmless on every path - but pv[] holds nothing
   // meaningful when ps_done is set or ps_have is clear and must not be used there.
   __builtin_amdgcn_sched_barrier(0);     // the four arguments stay one s_load batch above everything else
-  float4 pv[3];
+  float4 pv[4];
   if (!FIRST && !(EXP & 1)) {
-    // Waves 0..3 own the 12 partial rows.  No exec branch around the loads: hipcc puts the phi copies of the join, and
-    // with them a wait for the rows, at the end of such a branch.  Where there are more than four waves the others read
-    // the first 16 bytes of rows 0..2 instead (one cache line per load and wave) and never look at them.
-    const float* part = &dyn->partials[parity ^ 1][0][0];
-    const int off = (THREADS / 64 <= 4 || wave < 4) ? wave * 3 * kMaxBlocks + lane * 4 : 0;
+    // No exec branch around the loads: hipcc puts the phi copies of the join, and with them a wait for the rows, at the
+    // end of such a branch.
+    if (EXP & 16) {                      // the row-per-sum table: waves 0..3, three rows each (tools/exp_tail.hip)
+      const float* part = &dyn->rows[parity ^ 1][0][0];
+      const int off = (THREADS / 64 <= 4 || wave < 4) ? wave * 3 * kMaxBlocks + lane * 4 : 0;
 #pragma unroll
-    for (int v = 0; v < 3; ++v) pv[v] = *reinterpret_cast<const float4*>(part + off + v * kMaxBlocks);
+      for (int v = 0; v < 3; ++v) pv[v] = *reinterpret_cast<const float4*>(part + off + v * kMaxBlocks);
+    } else {
+      const char* part = reinterpret_cast<const char*>(&dyn->partials[parity ^ 1][0][0]);
+#pragma unroll
+      for (int j = 0; j < 4; ++j)
+        pv[j] = *reinterpret_cast<const float4*>(part + pv_off + 16u * ((EXP & 32) ? j : j * (kMaxBlocks / 8)));
+    }
   }
   // previous state, static and call part: scalar loads, all in ONE batch behind the row loads, one scalar wait
   // (FIRST: the static part alone; the rest are kernel arguments)
@@ -80,17 +97,18 @@
     int n_hit = 0, status = 0;
     bool done = false;
     if (!(EXP & 1)) {
-      // ---- prologue: fixed-order reduction (wave w owns sums 3w..3w+2), then the solve
-      if (wave < 4) {                                          // 3 x 66 doubles fit in the epilogue's buffer
-        // Keep the rows opaque until here: hipcc otherwise hoists the fold's float64 conversions, and with them the
-        // wait for the rows, up to the row loads - in front of the scalar batch and the point loads.
+      // ---- prologue: fixed-order reduction (wave w < 3 owns sums 4w..4w+3), then the solve
+      // Keep the rows opaque until here: hipcc otherwise hoists the fold's float64 conversions, and with them the
+      // wait for the rows, up to the row loads - in front of the scalar batch and the point loads.
+      if ((EXP & 16) ? wave < 4 : wave < kNumAcc / 4) {        // 4 x 66 doubles fit in the epilogue's buffer
 #pragma unroll
-        for (int v = 0; v < 3; ++v) {
+        for (int v = 0; v < ((EXP & 16) ? 3 : 4); ++v) {
           v4f r = {pv[v].x, pv[v].y, pv[v].z, pv[v].w};
           asm volatile("" : "+v"(r));
           pv[v] = make_float4(r.x, r.y, r.z, r.w);
         }
-        fold_rows12(pv, reinterpret_cast<double*>(s_t[wave]), lane, &s_red[wave * 3]);
+        if (EXP & 16) fold_rows12(pv, reinterpret_cast<double*>(s_t[wave]), lane, &s_red[wave * 3]);
+        else fold_packed4(pv, reinterpret_cast<double*>(s_t[wave]), lane, &s_red[wave * 4]);
       }
       __syncthreads();
       unpack_sums(s_red, H, g, score, n_hit);
@@ -160,15 +178,21 @@
   acc_store(A, prm.d2, acc);
   acc[11] = 0.f;
 
-  // ---- epilogue: wave tree -> LDS -> one partial row per block
+  // ---- epilogue: wave tree -> LDS -> this block's entry of the three groups, one 16-byte store each
+  // (EXP & 32, tools/exp_tail.hip: slot = workgroup, so that every 128-byte line has writers on all eight XCDs)
+  const int slot = (EXP & 32) ? (int)blockIdx.x : partial_slot(blockIdx.x);
   if (EXP & 4) {
-    if (tid < kNumAcc) dyn->partials[parity][tid][blockIdx.x] = acc[tid & 1];
+    if (tid < kNumAcc / 4) dyn->partials[parity][tid][slot] = make_float4(acc[0], acc[1], acc[0], acc[1]);
     return;
   }
   {
     const float r = wave_reduce11_lds(acc, s_t[wave], lane);
     if ((lane & 3) == 0 && lane < 4 * (kNumAcc - 1)) s_wave[wave][lane >> 2] = r;
   }
+  // where lane 4g's entry goes, worked out in front of the barrier (pinned: hipcc otherwise sinks the address
+  // arithmetic, a dozen instructions, to the store - the last thing the launch waits for)
+  unsigned out_off = 16u * (((unsigned)parity * (kNumAcc / 4) + (unsigned)(tid >> 2)) * kMaxBlocks + (unsigned)slot);
+  if (!(EXP & 16)) asm volatile("" : "+v"(out_off));
   __syncthreads();
   if (tid < kNumAcc) {
     float r = 0.f;
@@ -176,5 +200,12 @@
 #pragma unroll
       for (int w = 0; w < THREADS / 64; ++w) r += s_wave[w][tid];     // fixed order
     }
-    dyn->partials[parity][tid][blockIdx.x] = r;
+    if (EXP & 16) {
+      dyn->rows[parity][tid][blockIdx.x] = r;
+    } else {
+      // lanes 0..11 hold one sum each: every quad hands its four to its first lane (quad_perm broadcasts, all twelve
+      // lanes still active), and lanes 0, 4 and 8 store 16 bytes each
+      const float4 q = make_float4(dpp_mov<0x00, 0xf>(r), dpp_mov<0x55, 0xf>(r), dpp_mov<0xAA, 0xf>(r), dpp_mov<0xFF, 0xf>(r));
+      if ((tid & 3) == 0) *reinterpret_cast<float4*>(reinterpret_cast<char*>(&dyn->partials[0][0][0]) + out_off) = q;
+    }
   }

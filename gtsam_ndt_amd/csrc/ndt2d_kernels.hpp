@@ -10,7 +10,7 @@
 //                       prologue  = fixed-order reduction of the previous launch's block
 //                                   partials + 3x3 solve + pose update (every block, redundantly)
 //                       body      = transform, lookup, score, Jacobian, per-thread sums
-//                       epilogue  = wave DPP tree -> LDS -> one partial row per block
+//                       epilogue  = wave DPP tree -> LDS -> the block's sums as three 16-byte entries
 #pragma once
 #include "ndt_device.hpp"
 #include "ndt_chain.hpp"
@@ -103,11 +103,24 @@ struct AlignCall {
   int seq;                   // this call's number: what the first launch past the end reports in host_flag[2]
   int pad;
 };
+// partials: what a launch hands to the next, 12 KB per parity.  The single-scan chain (k_iterate, k_iterate_first) keeps
+// it packed by workgroup: entry [g][partial_slot(b)] holds sums 4g .. 4g+3 of workgroup b (sum 11 is the zero pad), so
+// that a workgroup leaves its 11 sums as three 16-byte stores and the fold reads four 16-byte entries per lane.
+// partial_slot puts the eight workgroups that share a 128-byte line on one XCD (consecutive workgroups go round the
+// eight XCDs): a line is merged in one L2 instead of being written in parts from all eight.  Only the speed depends on
+// where the workgroups really run.  The map-to-map chain (k_begin_d2d, k_iterate_d2d) keeps the same bytes as one row of
+// kMaxBlocks entries per sum (rows).  A chain never reads what another chain wrote: its first launch reads no partials.
+__host__ __device__ constexpr int partial_slot(int b) { return (b & 7) * (kMaxBlocks / 8) + (b >> 3); }
 struct AlignDyn {
   IterState state[2];
-  float partials[2][kNumAcc][kMaxBlocks];
+  union {
+    float4 partials[2][kNumAcc / 4][kMaxBlocks];
+    float rows[2][kNumAcc][kMaxBlocks];
+  };
   LineSearch ls[2];       // ping-pong like state; touched only when prm.line_search > 0
 };
+static_assert(kNumAcc % 4 == 0 && sizeof(AlignDyn::partials) == sizeof(AlignDyn::rows) &&
+              offsetof(AlignDyn, partials) % 16 == 0, "the partials table: 24 KB, 16-byte aligned, in either view");
 
 // A scan moved into the map frame with the pose an alignment returned, before it is merged into
 // the submap (ndt2d_add_target_points_dev): float32 products and sums in a fixed order (no
@@ -671,6 +684,27 @@ __device__ __forceinline__ void fold_rows12(const float4* pv, double* t, int lan
   __builtin_amdgcn_wave_barrier();                       // where t is the epilogue's buffer, this wave rewrites it
 }
 
+// The same fold over the packed table of the single-scan chain (AlignDyn::partials), a wave's share: group g of four sums.
+// pv[j] = group g's entry of workgroup 4 lane + j, i.e. its sums 4g .. 4g+3, so component r of pv[0..3] is what
+// fold_rows12 finds in one float4 of row 4g + r.  Per sum the operands, the operations and their order are those of
+// fold_rows12; with four rows all 64 lanes take part in the second step.  t: 4 x 66 doubles.  Three waves (sums
+// 4w .. 4w+3 into s_red + 4w) and a __syncthreads make the 12 sums.
+__device__ __forceinline__ void fold_packed4(const float4* pv, double* t, int lane, double* out) {
+  t[0 * 66 + lane] = (((double)pv[0].x + (double)pv[1].x) + (double)pv[2].x) + (double)pv[3].x;
+  t[1 * 66 + lane] = (((double)pv[0].y + (double)pv[1].y) + (double)pv[2].y) + (double)pv[3].y;
+  t[2 * 66 + lane] = (((double)pv[0].z + (double)pv[1].z) + (double)pv[2].z) + (double)pv[3].z;
+  t[3 * 66 + lane] = (((double)pv[0].w + (double)pv[1].w) + (double)pv[2].w) + (double)pv[3].w;
+  __builtin_amdgcn_wave_barrier();
+  const double* row = t + (lane >> 4) * 66 + (lane & 15);
+  double a = (row[0] + row[16]) + (row[32] + row[48]);
+  a += dpp_mov<0xB1, 0xf>(a);
+  a += dpp_mov<0x4E, 0xf>(a);
+  a += dpp_mov<0x124, 0xf>(a);
+  a += dpp_mov<0x128, 0xf>(a);                           // every lane of the 16-lane row holds its total
+  if ((lane & 15) == 0) out[lane >> 4] = a;
+  __builtin_amdgcn_wave_barrier();                       // t is the epilogue's buffer: this wave rewrites it
+}
+
 // the folded sums -> what gn_update takes
 __device__ __forceinline__ void unpack_sums(const double* s_red, double* H, double* g, double& score, int& n_hit) {
 #pragma unroll
@@ -760,7 +794,8 @@ __device__ __forceinline__ void begin_chain(AlignCall* call, AlignDyn* dyn, cons
 // scalars in one s_load batch, then the first source points are all requested before anything
 // waits for the rows; the cell-record gather is the second.
 // EXP is an ablation mask for tools/exp_iter.hip only (1: no reduce/solve, 2: no body,
-// 4: no epilogue tree, 8: empty); the library instantiates EXP = 0.
+// 4: no epilogue tree, 8: empty) and tools/exp_tail.hip (16: the row-per-sum table with twelve 4-byte stores per
+// workgroup, as it was before the table was packed; 32: packed, but slot = workgroup); the library instantiates EXP = 0.
 //
 // The text of the launch is ndt2d_iterate_text.hpp, shared with k_iterate_first (launch 0 of a chain, FIRST = 1).
 template <int MODE, int EXP = 0, int THREADS = kBlock, int NG = 1>
