@@ -134,6 +134,16 @@ class GridInfo3D(C.Structure):
                 ("width", C.c_int32), ("height", C.c_int32), ("depth", C.c_int32), ("n_valid", C.c_int32)]
 
 
+class PointFit(C.Structure):
+    """ndt_point_fit (40 bytes): the class counts of a per-point fit - they add up to n and count points, not
+    point-grid hits - and the points a selection copied."""
+    _fields_ = [("n_invalid", C.c_uint64), ("n_miss", C.c_uint64), ("n_misfit", C.c_uint64), ("n_fit", C.c_uint64),
+                ("n_selected", C.c_uint64)]
+
+
+# the class byte of a point (NDT_POINT_* of include/ndt_hip.h), by name
+POINT_CLASS = {"invalid": 0, "miss": 1, "misfit": 2, "fit": 3}
+
 _fp = C.POINTER(C.c_float)
 _dp = C.POINTER(C.c_double)
 _vp = C.c_void_p
@@ -166,6 +176,10 @@ SIGNATURES = {
     "ndt2d_unmerge_map": (C.c_int32, [_vp, _vp, _dp, C.POINTER(C.c_size_t)]),
     "ndt2d_evaluate": (C.c_int32, [_vp, _vp, _vp, C.c_size_t, _dp, C.POINTER(Eval2D)]),
     "ndt2d_evaluate_dev": (C.c_int32, [_vp, _vp, _vp, C.c_size_t, _dp, C.POINTER(Eval2D)]),
+    "ndt2d_fit_points_dev": (C.c_int32, [_vp, _vp, _vp, C.c_size_t, _dp, C.c_float, _vp, _vp, C.POINTER(PointFit)]),
+    "ndt2d_fit_points": (C.c_int32, [_vp, _vp, _vp, C.c_size_t, _dp, C.c_float, _vp, _vp, C.POINTER(PointFit)]),
+    "ndt2d_select_points_dev": (C.c_int32, [_vp, _vp, _vp, C.c_size_t, _dp, C.c_float, C.c_uint32, _vp, _vp, _vp,
+                                            C.POINTER(PointFit)]),
     "ndt2d_align": (C.c_int32, [_vp, _vp, _vp, C.c_size_t, _dp, C.POINTER(Result2D)]),
     "ndt2d_align_dev": (C.c_int32, [_vp, _vp, _vp, C.c_size_t, _dp, C.POINTER(Result2D)]),
     "ndt2d_align_dev_async": (C.c_int32, [_vp, _vp, _vp, C.c_size_t, _dp]),
@@ -253,6 +267,10 @@ SIGNATURES = {
     "ndt3d_unmerge_map": (C.c_int32, [_vp, _vp, _dp, C.POINTER(C.c_size_t)]),
     "ndt3d_evaluate": (C.c_int32, [_vp, _vp, _vp, _vp, C.c_size_t, _dp, C.POINTER(Eval3D)]),
     "ndt3d_evaluate_dev": (C.c_int32, [_vp, _vp, _vp, _vp, C.c_size_t, _dp, C.POINTER(Eval3D)]),
+    "ndt3d_fit_points_dev": (C.c_int32, [_vp, _vp, _vp, _vp, C.c_size_t, _dp, C.c_float, _vp, _vp, C.POINTER(PointFit)]),
+    "ndt3d_fit_points": (C.c_int32, [_vp, _vp, _vp, _vp, C.c_size_t, _dp, C.c_float, _vp, _vp, C.POINTER(PointFit)]),
+    "ndt3d_select_points_dev": (C.c_int32, [_vp, _vp, _vp, _vp, C.c_size_t, _dp, C.c_float, C.c_uint32, _vp, _vp, _vp, _vp,
+                                            C.POINTER(PointFit)]),
     "ndt3d_align": (C.c_int32, [_vp, _vp, _vp, _vp, C.c_size_t, _dp, C.POINTER(Result3D)]),
     "ndt3d_align_dev_async": (C.c_int32, [_vp, _vp, _vp, _vp, C.c_size_t, _dp]),
     "ndt3d_align_finish": (C.c_int32, [_vp, C.POINTER(Result3D)]),

@@ -99,6 +99,7 @@ struct ndt2d_handle {
   int check_every = 8;                     // converged mode: launches per chunk
   bool fused_begin = true;                 // NDT_TUNE_FUSED_BEGIN: launch 0 of a single-scan chain is k_iterate_first (no k_begin)
   SearchScratch srch;                      // exhaustive pose search scratch (ndt_search.hpp), allocated on first use
+  PointFitScratch fit;                     // per-point fit and selection scratch (ndt_point_fit.hpp), allocated on first use
   // map-to-map alignment (ndt_map_host.hpp, ndt2d_d2d_api.hpp), allocated on first use; both caches follow the grid (grid_changed)
   float4* d_cov = nullptr; size_t cov_cap = 0;            // covariance records of the cached grid ([2 x cells], the layout of grid.rec)
   unsigned int* d_blk = nullptr; size_t blk_cap = 0;      // valid cells per workgroup of k_cov_records | their exclusive scan | the total
@@ -1076,6 +1077,7 @@ int32_t ndt2d_destroy(ndt2d_handle* h) {
   void* host[] = {h->h_geom, h->h_static, h->h_state, h->h_small, h->h_flag};
   for (void* p : host) if (p) (void)hipHostFree(p);
   h->srch.release();
+  h->fit.release();
   if (h->upload_ev) (void)hipEventDestroy(h->upload_ev);
   if (h->wait_ev) (void)hipEventDestroy(h->wait_ev);
   if (h->map_ev) (void)hipEventDestroy(h->map_ev);
@@ -1473,6 +1475,7 @@ extern "C" int32_t ndt2d_align_multi_scan_dev(ndt2d_handle* h, const float* cons
 #include "ndt_map_io.hpp"
 #include "ndt_coarsen.hpp"
 #include "ndt_merge.hpp"
+#include "ndt_point_fit.hpp"
 #include "ndt_map_host.hpp"
 #include "ndt2d_search.hpp"
 #include "ndt3d_search.hpp"

@@ -51,6 +51,7 @@ struct ndt3d_handle {
   ndt::AlignDynMulti3* d_dyn_multi = nullptr;   // multi-scan / multi-start chains (ndt3d_multi.hpp), on first use
   ndt::IterState3* h_state_multi = nullptr;     // pinned [kMaxStarts3]
   ndt::SearchScratch srch;                      // exhaustive pose search scratch (ndt_search.hpp), allocated on first use
+  ndt::PointFitScratch fit;                     // per-point fit and selection scratch (ndt_point_fit.hpp), allocated on first use
   // map-to-map alignment (ndt_map_host.hpp, ndt3d_d2d_api.hpp), allocated on first use; both caches follow the grid (grid_changed3)
   float4* d_cov = nullptr; size_t cov_cap = 0;            // covariance records, 3 float4 per voxel (k_cov_records3)
   unsigned int* d_blk = nullptr; size_t blk_cap = 0;      // per-workgroup valid counts | their exclusive scan | the total
@@ -633,6 +634,7 @@ int32_t ndt3d_destroy(ndt3d_handle* h) {
   void* host[] = {h->h_static, h->h_state, h->h_small, h->h_flag, h->h_state_multi, h->h_pub3};
   for (void* p : host) if (p) (void)hipHostFree(p);
   h->srch.release();
+  h->fit.release();
   if (h->upload_ev) (void)hipEventDestroy(h->upload_ev);
   if (h->map_ev) (void)hipEventDestroy(h->map_ev);
   if (h->stream) (void)hipStreamDestroy(h->stream);

@@ -640,6 +640,21 @@ inline hipError_t publish_and_wait(hipStream_t stream, int* seq, const int* flag
   return spin_until(stream, [&]() { return flag_raised(flag, want); }, seen);
 }
 
+// Scratch of ndt*_fit_points* / ndt*_select_points* (ndt_point_fit.hpp), grown on first use and freed with the handle.
+struct PointFitScratch {
+  unsigned char* d_cls = nullptr; size_t cls_cap = 0;     // a class per point, where the caller gives no array
+  float* d_m = nullptr; size_t m_cap = 0;                 // m per point on its way to a host array
+  uint4* d_table = nullptr;                               // per tile: the four class counts
+  unsigned int* d_base = nullptr; size_t tile_cap = 0;    // per tile: the kept points in front of it
+  uint4* h_table = nullptr; size_t h_cap = 0;             // pinned (zeroed when it grows): the table's read-back
+  void release() {
+    void* dev[] = {d_cls, d_m, d_table, d_base};
+    for (void* p : dev) if (p) (void)hipFree(p);
+    if (h_table) (void)hipHostFree(h_table);
+    *this = PointFitScratch{};
+  }
+};
+
 }  // namespace ndt
 
 #define HIP_TRY(expr)                                                            \

@@ -66,6 +66,43 @@ class AlignResult3D:
     status: int
 
 
+@dataclass
+class PointFit:
+    """What fit_points / select_points report (ndt_point_fit of include/ndt_hip.h).  The four class counts add up to
+    the scan's length and count points: with overlap_grids = 4 a point in valid cells of several grids is one hit here."""
+    m: object              # float32 [n]: q' Sigma^-1 q of every hit, +inf for a miss, NaN for an invalid point (None after select_points)
+    cls: object            # uint8 [n]: L.POINT_CLASS (None after select_points)
+    n_invalid: int
+    n_miss: int
+    n_misfit: int
+    n_fit: int
+    n_selected: int = 0
+
+    @property
+    def n_hit(self) -> int:
+        return self.n_misfit + self.n_fit
+
+    @property
+    def fitness(self) -> float:
+        """The share of the finite points that lie within max_m of their cell (0 for a scan without one)."""
+        finite = self.n_miss + self.n_misfit + self.n_fit
+        return self.n_fit / finite if finite else 0.0
+
+
+def _keep_mask(keep) -> int:
+    """keep of select_points: a mask of 1 << class, or class names out of L.POINT_CLASS."""
+    if isinstance(keep, str):
+        keep = (keep,)
+    if isinstance(keep, (int, np.integer)):
+        return int(keep)
+    mask = 0
+    for k in keep:
+        if k not in L.POINT_CLASS:
+            raise ValueError(f"keep: {k!r} is not one of {sorted(L.POINT_CLASS)}")
+        mask |= 1 << L.POINT_CLASS[k]
+    return mask
+
+
 def _default_params(prefix: str, overrides: dict) -> L.Params2D:
     p = L.Params2D()
     getattr(L.load(), prefix + "_default_params")(C.byref(p))
@@ -350,6 +387,47 @@ class _NdtMatcher(_Handle):
             self._check(self._c.evaluate(self._h, *[c.ctypes.data for c in a], a[0].size, p, C.byref(out)), "evaluate")
         return self._dim.evaluation(out)
 
+    # ---- per-point fit and selection (docs/ALGORITHM.md section 2.19)
+    def _point_fit(self, fit: L.PointFit, m=None, cls=None) -> PointFit:
+        return PointFit(m, cls, int(fit.n_invalid), int(fit.n_miss), int(fit.n_misfit), int(fit.n_fit), int(fit.n_selected))
+
+    def _fit_points(self, coords, pose, max_m: float) -> PointFit:
+        p = self._dim.pose(pose)
+        fit = L.PointFit()
+        if _is_dev(coords[0]):
+            import torch
+            n = coords[0].numel()
+            m = torch.empty(n, dtype=torch.float32, device=coords[0].device)
+            cls = torch.empty(n, dtype=torch.uint8, device=coords[0].device)
+            self.wait_stream()
+            self._check(self._c.fit_points_dev(self._h, *_dev_ptrs(coords, n), n, p, float(max_m), m.data_ptr(), cls.data_ptr(),
+                                               C.byref(fit)), "fit_points_dev")
+        else:
+            a = _host_coords(coords)
+            m = np.empty(a[0].size, dtype=np.float32)
+            cls = np.empty(a[0].size, dtype=np.uint8)
+            self._check(self._c.fit_points(self._h, *[c.ctypes.data for c in a], a[0].size, p, float(max_m), m.ctypes.data,
+                                           cls.ctypes.data, C.byref(fit)), "fit_points")
+        return self._point_fit(fit, m, cls)
+
+    def _select_points(self, coords, pose, max_m: float, keep):
+        """-> (coords of the kept points, their indices (int64), PointFit without m / cls): of the kind of the input."""
+        import torch
+        host = not _is_dev(coords[0])
+        dev = self._on_device(coords)
+        n = dev[0].numel()
+        out = [torch.empty_like(c) for c in dev]
+        index = torch.empty(n, dtype=torch.int32, device=dev[0].device)      # uint32 words, below 2^31
+        fit = L.PointFit()
+        self._check(self._c.select_points_dev(self._h, *_dev_ptrs(dev, n), n, self._dim.pose(pose), float(max_m),
+                                              _keep_mask(keep), *[o.data_ptr() for o in out], index.data_ptr(),
+                                              C.byref(fit)), "select_points_dev")
+        k = int(fit.n_selected)
+        out, index = tuple(o[:k] for o in out), index[:k].to(torch.int64)
+        if host:
+            out, index = tuple(o.cpu().numpy() for o in out), index.cpu().numpy()
+        return out, index, self._point_fit(fit)
+
     def wait_stream(self, stream=None):
         """Order the handle's stream behind `stream` (default: torch's current stream): device arrays
         written there are complete before the handle's next kernels read them (ndt2d/ndt3d_wait_stream)."""
@@ -587,6 +665,19 @@ class NdtMatcher2D(_NdtMatcher):
     def evaluate(self, sx, sy, pose):
         return self._evaluate((sx, sy), pose)
 
+    def fit_points(self, sx, sy, pose, max_m: float) -> PointFit:
+        """Score every point of the scan against the cached grid at `pose` (ndt2d_fit_points*): m = q' Sigma^-1 q in
+        its cell and a class byte per point (L.POINT_CLASS: fit = a valid cell and m <= max_m), of the kind of the
+        input - numpy arrays or CUDA tensors - and the four class counts."""
+        return self._fit_points((sx, sy), pose, max_m)
+
+    def select_points(self, sx, sy, pose, max_m: float, keep=("fit", "miss")):
+        """The points of the scan whose class at `pose` is in `keep` (class names, or a mask of 1 << class), in the
+        source frame, bit for bit and in their order (ndt2d_select_points_dev): ((x, y), index, PointFit), trimmed to
+        n_selected - what add_target_points(x, y, pose) and remove_target_points take.  The default keeps what fits
+        the map and what extends it, and drops what lies in a mapped cell but off its Gaussian."""
+        return self._select_points((sx, sy), pose, max_m, keep)
+
     def align(self, sx, sy, init_pose=(0.0, 0.0, 0.0)) -> AlignResult:
         return self._align((sx, sy), init_pose)
 
@@ -662,6 +753,15 @@ class NdtMatcher3D(_NdtMatcher):
 
     def evaluate(self, sx, sy, sz, pose):
         return self._evaluate((sx, sy, sz), pose)
+
+    def fit_points(self, sx, sy, sz, pose, max_m: float) -> PointFit:
+        """Per-point m and class against the cached voxel grid (ndt3d_fit_points*), as NdtMatcher2D.fit_points."""
+        return self._fit_points((sx, sy, sz), pose, max_m)
+
+    def select_points(self, sx, sy, sz, pose, max_m: float, keep=("fit", "miss")):
+        """((x, y, z), index, PointFit) of the points whose class is in `keep` (ndt3d_select_points_dev), as
+        NdtMatcher2D.select_points."""
+        return self._select_points((sx, sy, sz), pose, max_m, keep)
 
     def align(self, sx, sy, sz, init_pose=(0.0,) * 6) -> AlignResult3D:
         return self._align((sx, sy, sz), init_pose)

@@ -275,6 +275,47 @@ int32_t ndt2d_evaluate(ndt2d_handle* h, const float* sx, const float* sy, size_t
 int32_t ndt2d_evaluate_dev(ndt2d_handle* h, const float* d_sx, const float* d_sy, size_t n, const double pose[3],
                            ndt2d_eval* out);
 
+/* ---- per-point fit and selection (docs/ALGORITHM.md section 2.19) ---------------------- */
+/* The class of a source point at a pose, one byte per point. */
+enum {
+  NDT_POINT_INVALID = 0,   /* a coordinate is NaN or +-inf (tested on the input, before anything is clamped)        */
+  NDT_POINT_MISS = 1,      /* finite, but no valid cell: outside the grid, on its ring, a cell with n < min_points  */
+  NDT_POINT_MISFIT = 2,    /* in a valid cell, m > max_m                                                            */
+  NDT_POINT_FIT = 3        /* in a valid cell, m <= max_m (a float32 compare)                                       */
+};
+/* What a fit or a selection counted.  The four class counts add up to n.  n_miss + n_misfit + n_fit and
+ * n_misfit + n_fit count POINTS: with overlap_grids = 4 a point in valid cells of several grids is one hit here, where
+ * ndt2d_eval::n_hit counts it once per grid.  n_selected: the points a selection copied (0 after a fit call). */
+typedef struct ndt_point_fit {
+  uint64_t n_invalid, n_miss, n_misfit, n_fit, n_selected;
+} ndt_point_fit;
+
+/* Scores every point of a scan against the cached grid at `pose`.  Image point, cell and m_i = q' Sigma^-1 q are the
+ * float32 operations of the single-scan alignment (the angle wrapped, cos / sin rounded from float64, the fma image, the
+ * key clamped onto the ring; q, Sigma^-1 q, m as three fmas and two multiplies), m_i is not clamped at zero, and with
+ * overlap_grids = 4 it is the least m over the grids whose cell is valid (a hit = any grid's cell valid).
+ *   d_class[i] (may be NULL): the class above.   d_m[i] (may be NULL): m_i for classes 2 and 3, +inf for 1, NaN for 0.
+ * Runs on the handle's stream under the stream contract of ndt2d_evaluate_dev (ndt2d_wait_stream for producers), finishes
+ * a pending asynchronous alignment first (its result stays fetchable) and returns when the outputs and *fit are complete.
+ * Every output is deterministic to the bit.  A grid without a valid cell (a reserved one) is no error: every finite
+ * point is a MISS.
+ * NDT_ERR_INVALID_ARG (ndt_last_error says which): a null handle, scan, pose or fit; n = 0 or above what an alignment
+ * takes; a pose that is not finite; max_m NaN or negative (+inf is legal: every hit fits).  NDT_ERR_NO_TARGET: no grid.
+ * NDT_ERR_ALLOC: the handle's scratch (a byte per point where d_class is NULL, 20 bytes per 1024 points) cannot grow. */
+int32_t ndt2d_fit_points_dev(ndt2d_handle* h, const float* d_sx, const float* d_sy, size_t n, const double pose[3],
+                             float max_m, float* d_m, uint8_t* d_class, ndt_point_fit* fit);
+/* the same with host arrays in and out, the scan staged as ndt2d_evaluate stages it */
+int32_t ndt2d_fit_points(ndt2d_handle* h, const float* sx, const float* sy, size_t n, const double pose[3], float max_m,
+                         float* m, uint8_t* cls, ndt_point_fit* fit);
+/* Fits as above and copies the points whose class is in `keep` (a mask of 1 << class, 1 .. 15) to d_ox / d_oy[0 ..
+ * fit->n_selected): in the SOURCE frame, bit for bit, in ascending index order - what ndt2d_add_target_points_dev(...,
+ * pose) and ndt2d_remove_target_points_dev take.  d_index (may be NULL) receives their indices in the scan.  Elements
+ * past n_selected are not written; the outputs hold n elements and must not overlap the inputs.
+ * NDT_ERR_INVALID_ARG also for keep = 0 or above 15 and for a null d_ox / d_oy. */
+int32_t ndt2d_select_points_dev(ndt2d_handle* h, const float* d_sx, const float* d_sy, size_t n, const double pose[3],
+                                float max_m, uint32_t keep, float* d_ox, float* d_oy, uint32_t* d_index,
+                                ndt_point_fit* fit);
+
 /* ---- full alignment: rows a4-a9 ------------------------------------------------------ */
 int32_t ndt2d_align(ndt2d_handle* h, const float* sx, const float* sy, size_t n,
                     const double init_pose[3], ndt2d_result* out);
@@ -715,6 +756,17 @@ int32_t ndt3d_evaluate(ndt3d_handle* h, const float* sx, const float* sy, const 
                        const double pose[6], ndt3d_eval* out);
 int32_t ndt3d_evaluate_dev(ndt3d_handle* h, const float* d_sx, const float* d_sy, const float* d_sz, size_t n,
                            const double pose[6], ndt3d_eval* out);
+/* ndt2d_fit_points* / ndt2d_select_points_dev for voxel grids: the image is the nested fma of the 3D alignment under
+ * R = Rz Ry Rx (angles wrapped, the nine products in float64, rounded to float32), a point is in the grid where
+ * 0 <= f < extent on every axis (no ring in 3D), m_i is its three-by-three form.  Classes, outputs, stream behaviour and
+ * return values as there. */
+int32_t ndt3d_fit_points_dev(ndt3d_handle* h, const float* d_sx, const float* d_sy, const float* d_sz, size_t n,
+                             const double pose[6], float max_m, float* d_m, uint8_t* d_class, ndt_point_fit* fit);
+int32_t ndt3d_fit_points(ndt3d_handle* h, const float* sx, const float* sy, const float* sz, size_t n,
+                         const double pose[6], float max_m, float* m, uint8_t* cls, ndt_point_fit* fit);
+int32_t ndt3d_select_points_dev(ndt3d_handle* h, const float* d_sx, const float* d_sy, const float* d_sz, size_t n,
+                                const double pose[6], float max_m, uint32_t keep, float* d_ox, float* d_oy, float* d_oz,
+                                uint32_t* d_index, ndt_point_fit* fit);
 int32_t ndt3d_align(ndt3d_handle* h, const float* sx, const float* sy, const float* sz, size_t n,
                     const double init_pose[6], ndt3d_result* out);
 int32_t ndt3d_align_dev(ndt3d_handle* h, const float* d_sx, const float* d_sy, const float* d_sz, size_t n,

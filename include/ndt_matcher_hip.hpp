@@ -267,6 +267,27 @@ class NdtMatcherHip {
     check(ndt2d_evaluate(h_, sx, sy, n, p, &e), "ndt2d_evaluate");
     return e;
   }
+  // Per-point fit of a device scan at a pose (ndt2d_fit_points_dev): m = q' Sigma^-1 q of every point in its cell into
+  // d_m and its class byte (NDT_POINT_*) into d_class - either may be null - and the class counts, which count points.
+  // The scan must be complete on the device, or the handle ordered behind its producer (ndt2d_wait_stream), as for
+  // ndt2d_evaluate_dev.
+  ndt_point_fit fitPointsDev(const float* d_sx, const float* d_sy, size_t n, const Pose2& at, float max_m, float* d_m = nullptr,
+                             uint8_t* d_class = nullptr) {
+    const double p[3] = {at.x, at.y, at.theta};
+    ndt_point_fit f;
+    check(ndt2d_fit_points_dev(h_, d_sx, d_sy, n, p, max_m, d_m, d_class, &f), "ndt2d_fit_points_dev");
+    return f;
+  }
+  // The points whose class is in `keep` (a mask of 1 << NDT_POINT_*), copied to the front of d_ox / d_oy in the source
+  // frame, bit for bit and in their order, their scan indices into d_index (may be null): what addTargetPointsDev(...,
+  // &pose) and removeTargetPointsDev take.  The count is the summary's n_selected.
+  ndt_point_fit selectPointsDev(const float* d_sx, const float* d_sy, size_t n, const Pose2& at, float max_m, uint32_t keep,
+                                float* d_ox, float* d_oy, uint32_t* d_index = nullptr) {
+    const double p[3] = {at.x, at.y, at.theta};
+    ndt_point_fit f;
+    check(ndt2d_select_points_dev(h_, d_sx, d_sy, n, p, max_m, keep, d_ox, d_oy, d_index, &f), "ndt2d_select_points_dev");
+    return f;
+  }
   // Map-to-map alignment (ndt2d_align_map): `source`'s cached grid against this matcher's, no points involved - the
   // loop closure between two submaps, or between a reloaded map and the current one.  guess and the result map the
   // source map's frame into this map's frame; this matcher's parameters drive the solve; source may be *this.
@@ -670,6 +691,21 @@ class NdtMatcherHip3 {
     if (pose) { p[0] = pose->x; p[1] = pose->y; p[2] = pose->z; p[3] = pose->roll; p[4] = pose->pitch; p[5] = pose->yaw; }
     check(ndt3d_remove_target_points_dev(h_, d_x, d_y, d_z, n, pose ? p : nullptr, &outside, producer_stream), "ndt3d_remove_target_points_dev");
     return outside;
+  }
+  // per-point fit and selection against the voxel grid, as NdtMatcherHip::fitPointsDev / selectPointsDev
+  ndt_point_fit fitPointsDev(const float* d_sx, const float* d_sy, const float* d_sz, size_t n, const Pose3& at, float max_m,
+                             float* d_m = nullptr, uint8_t* d_class = nullptr) {
+    const double p[6] = {at.x, at.y, at.z, at.roll, at.pitch, at.yaw};
+    ndt_point_fit f;
+    check(ndt3d_fit_points_dev(h_, d_sx, d_sy, d_sz, n, p, max_m, d_m, d_class, &f), "ndt3d_fit_points_dev");
+    return f;
+  }
+  ndt_point_fit selectPointsDev(const float* d_sx, const float* d_sy, const float* d_sz, size_t n, const Pose3& at, float max_m,
+                                uint32_t keep, float* d_ox, float* d_oy, float* d_oz, uint32_t* d_index = nullptr) {
+    const double p[6] = {at.x, at.y, at.z, at.roll, at.pitch, at.yaw};
+    ndt_point_fit f;
+    check(ndt3d_select_points_dev(h_, d_sx, d_sy, d_sz, n, p, max_m, keep, d_ox, d_oy, d_oz, d_index, &f), "ndt3d_select_points_dev");
+    return f;
   }
   MatchResult3 alignDev(const float* d_sx, const float* d_sy, const float* d_sz, size_t n, const Pose3& guess = Pose3()) {
     const double init[6] = {guess.x, guess.y, guess.z, guess.roll, guess.pitch, guess.yaw};

@@ -1,0 +1,182 @@
+"""ndt2d/ndt3d_fit_points(_dev) and _select_points_dev at the ABI: declared in include/ndt_hip.h, exported, bound in
+gtsam_ndt_amd/_lib.py; sizeof(ndt_point_fit) == 40; every argument error returns its code with a message in
+ndt_last_error; a reserved grid without points gives all-MISS with NDT_OK; a pending asynchronous alignment is
+finished, not corrupted.  What needs a handle needs a device and is marked gpu; the rest runs anywhere."""
+import ctypes as C
+import os
+import re
+import subprocess
+
+import numpy as np
+import pytest
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+HEADER = os.path.join(ROOT, "include", "ndt_hip.h")
+NAMES = [f"ndt{d}d_{f}" for d in (2, 3) for f in ("fit_points_dev", "fit_points", "select_points_dev")]
+
+
+def _prototype(src, name):
+    m = re.search(r"\bint32_t\s+" + name + r"\s*\(([^)]*)\)\s*;", src)
+    assert m, f"{name} is not declared in ndt_hip.h"
+    return [p.strip() for p in re.sub(r"\s+", " ", m.group(1)).split(",")]
+
+
+def test_symbols_are_declared_exported_and_bound(ndt_lib):
+    from gtsam_ndt_amd import _lib
+    src = re.sub(r"/\*.*?\*/", "", open(HEADER).read(), flags=re.S)
+    for name in NAMES:
+        params = _prototype(src, name)
+        assert hasattr(ndt_lib, name), f"{name} is not exported"
+        assert name in _lib.SIGNATURES, f"{name} is not bound"
+        res, args = _lib.SIGNATURES[name]
+        assert res is C.c_int32 and len(args) == len(params), name
+        fn = getattr(ndt_lib, name)
+        assert fn.restype is res and list(fn.argtypes) == list(args)
+        # the scalar arguments sit where the header has them
+        for p, a in zip(params, args):
+            if p.startswith("float max_m"):
+                assert a is C.c_float
+            if p.startswith("uint32_t keep"):
+                assert a is C.c_uint32
+            if p.startswith("size_t n"):
+                assert a is C.c_size_t
+        assert params[-1] == "ndt_point_fit* fit" and args[-1] == C.POINTER(_lib.PointFit)
+    assert ndt_lib.ndt_abi_version() == 1
+    for k, v in (("NDT_POINT_INVALID", 0), ("NDT_POINT_MISS", 1), ("NDT_POINT_MISFIT", 2), ("NDT_POINT_FIT", 3)):
+        assert re.search(r"\b%s\s*=\s*%d\b" % (k, v), src), k
+    assert _lib.POINT_CLASS == {"invalid": 0, "miss": 1, "misfit": 2, "fit": 3}
+
+
+def test_the_summary_is_forty_bytes(tmp_path):
+    from gtsam_ndt_amd import _lib
+    assert C.sizeof(_lib.PointFit) == 40
+    assert [f[0] for f in _lib.PointFit._fields_] == ["n_invalid", "n_miss", "n_misfit", "n_fit", "n_selected"]
+    src = tmp_path / "size.c"
+    src.write_text('#include "ndt_hip.h"\n_Static_assert(sizeof(ndt_point_fit) == 40, "ndt_point_fit");\n'
+                   "_Static_assert(NDT_POINT_FIT == 3 && NDT_POINT_INVALID == 0, \"classes\");\nint main(void) { return 0; }\n")
+    subprocess.run(["gcc", "-std=c11", "-Wall", "-Werror", "-I", os.path.join(ROOT, "include"), "-fsyntax-only", str(src)], check=True)
+
+
+def test_matchers_and_wrappers_offer_the_calls():
+    from gtsam_ndt_amd.matcher import NdtMatcher2D, NdtMatcher3D, _NdtMatcher
+    for cls in (NdtMatcher2D, NdtMatcher3D):
+        assert callable(cls.fit_points) and callable(cls.select_points)
+    assert "_fit_points" in vars(_NdtMatcher) and "_select_points" in vars(_NdtMatcher)       # the shared code
+    wrapper = open(os.path.join(ROOT, "include", "ndt_matcher_hip.hpp")).read()
+    assert wrapper.count("ndt_point_fit fitPointsDev(") == 2 and wrapper.count("ndt_point_fit selectPointsDev(") == 2
+    for name in NAMES:
+        if not name.endswith("fit_points"):
+            assert name + "(" in wrapper, name
+
+
+def test_a_null_handle_is_an_argument_error_with_a_message(ndt_lib):
+    """The one error that needs no device."""
+    from gtsam_ndt_amd import _lib
+    fit = _lib.PointFit()
+    x = np.zeros(4, np.float32)
+    pose = (C.c_double * 6)()
+    p = x.ctypes.data
+    calls = {
+        "ndt2d_fit_points_dev": (None, p, p, 4, pose, 1.0, None, None, C.byref(fit)),
+        "ndt2d_fit_points": (None, p, p, 4, pose, 1.0, None, None, C.byref(fit)),
+        "ndt2d_select_points_dev": (None, p, p, 4, pose, 1.0, 8, p, p, None, C.byref(fit)),
+        "ndt3d_fit_points_dev": (None, p, p, p, 4, pose, 1.0, None, None, C.byref(fit)),
+        "ndt3d_fit_points": (None, p, p, p, 4, pose, 1.0, None, None, C.byref(fit)),
+        "ndt3d_select_points_dev": (None, p, p, p, 4, pose, 1.0, 8, p, p, p, None, C.byref(fit)),
+    }
+    for name, args in calls.items():
+        assert getattr(ndt_lib, name)(*args) == _lib.NDT_ERR_INVALID_ARG, name
+        msg = ndt_lib.ndt_last_error().decode()
+        assert name in msg and "handle" in msg, (name, msg)
+
+
+# ------------------------------------------------------------------------------------------------- with a device
+def _cases(dim):
+    """(what the message must mention, keyword changes to a good call) for fit and select."""
+    nan, inf = float("nan"), float("inf")
+    bad_pose = [0.0] * (3 if dim == 2 else 6)
+    bad_pose[1] = inf
+    common = [("scan", dict(null_coord=0)), ("scan", dict(null_coord=dim - 1)), ("pose", dict(pose=None)), ("fit", dict(fit=False)),
+              ("empty", dict(n=0)), ("more points", dict(n=2 ** 31)), ("not finite", dict(pose=bad_pose)),
+              ("max_m", dict(max_m=nan)), ("max_m", dict(max_m=-1.0))]
+    select = [("keep", dict(keep=0)), ("keep", dict(keep=16)), ("output", dict(null_out=0)), ("output", dict(null_out=dim - 1))]
+    return common, select
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("dim", [2, 3])
+def test_argument_errors_each_return_their_code_and_a_message(gpu_lib, dim):
+    import torch
+    import point_fit_cases as PC
+    from gtsam_ndt_amd import _lib as L
+    from gtsam_ndt_amd.matcher import NdtMatcher2D, NdtMatcher3D
+    fx = PC.fixture(dim)
+    pose0 = fx["final_pose"]
+    n = 700
+    good = PC.dev(tuple(c[:n] for c in fx["source"]))
+    out = [torch.zeros(n, dtype=torch.float32, device="cuda") for _ in range(dim)]
+    prefix = f"ndt{dim}d_"
+
+    def call(m, select, null_coord=None, null_out=None, pose=pose0, fit=True, n=None, max_m=5.0, keep=8):
+        d = [None if a == null_coord else c for a, c in enumerate(good)]
+        fitp = L.PointFit()
+        ptr = lambda t: None if t is None else t.data_ptr()
+        p = None if pose is None else m._dim.pose(pose)
+        nn = good[0].numel() if n is None else n
+        f = C.byref(fitp) if fit else None
+        if select:
+            o = [None if a == null_out else t for a, t in enumerate(out)]
+            st = m._c.select_points_dev(m._h, *[ptr(t) for t in d], nn, p, float(max_m), int(keep), *[ptr(t) for t in o], None, f)
+        else:
+            st = m._c.fit_points_dev(m._h, *[ptr(t) for t in d], nn, p, float(max_m), None, None, f)
+        return st, fitp, gpu_lib.ndt_last_error().decode()
+
+    with PC.matcher(dim) as m, (NdtMatcher2D() if dim == 2 else NdtMatcher3D()) as bare:
+        common, select_only = _cases(dim)
+        ok_fit = call(m, False)
+        ok_sel = call(m, True)
+        assert ok_fit[0] == 0 and ok_sel[0] == 0 and ok_sel[1].n_selected == ok_sel[1].n_fit > 0
+        for select in (False, True):
+            name = prefix + ("select_points_dev" if select else "fit_points_dev")
+            for word, kw in common + (select_only if select else []):
+                st, _, msg = call(m, select, **kw)
+                assert st == L.NDT_ERR_INVALID_ARG, (name, kw, st)
+                assert name in msg and word in msg, (name, kw, msg)
+            st, _, msg = call(bare, select)
+            assert st == L.NDT_ERR_NO_TARGET and name in msg and "target" in msg
+            # +inf is a legal threshold: every hit fits
+            st, f, _ = call(m, select, max_m=float("inf"))
+            assert st == 0 and f.n_misfit == 0 and f.n_fit == ok_fit[1].n_fit + ok_fit[1].n_misfit
+        # the handle is as good as before
+        again = call(m, False)
+        assert PC.fit_tuple(again[1]) == PC.fit_tuple(ok_fit[1])
+        # the host-array call checks the same things
+        x = [np.ascontiguousarray(c[:n]) for c in fx["source"]]
+        fitp = L.PointFit()
+        st = m._c.fit_points(m._h, *[c.ctypes.data for c in x], n, m._dim.pose(pose0), float("nan"), None, None, C.byref(fitp))
+        assert st == L.NDT_ERR_INVALID_ARG and prefix + "fit_points:" in gpu_lib.ndt_last_error().decode()
+        st = m._c.fit_points(m._h, *[c.ctypes.data for c in x], n, m._dim.pose(pose0), 5.0, None, None, C.byref(fitp))
+        assert st == 0 and PC.fit_tuple(fitp) == PC.fit_tuple(ok_fit[1])
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("dim", [2, 3])
+@pytest.mark.parametrize("fixed", [0, 6])
+def test_a_pending_async_alignment_is_finished_not_corrupted(gpu_lib, dim, fixed):
+    import point_fit_cases as PC
+    fx = PC.fixture(dim)
+    n = 900 if dim == 2 else 4096
+    src = PC.dev(tuple(c[:n] for c in fx["source"]))
+    init = (0.0,) * (3 if dim == 2 else 6)
+    with PC.matcher(dim, fixed_iterations=fixed) as m:
+        want = m.align(*src, init)
+        alone = m.fit_points(*src, fx["final_pose"], PC.MAX_M[dim])
+        m.align_async(*src, init)
+        during = m.fit_points(*src, fx["final_pose"], PC.MAX_M[dim])
+        sel, idx, summary = m.select_points(*src, fx["final_pose"], PC.MAX_M[dim])
+        got = m.finish()
+        assert got.pose == want.pose and got.iterations == want.iterations and got.score == want.score
+        assert got.status == want.status and got.n_hit == want.n_hit and np.array_equal(got.H, want.H)
+        assert PC.fit_tuple(during) == PC.fit_tuple(alone)
+        assert during.m.cpu().numpy().tobytes() == alone.m.cpu().numpy().tobytes()
+        assert summary.n_selected == len(idx) == alone.n_fit + alone.n_miss
