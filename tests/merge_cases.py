@@ -18,6 +18,7 @@ SCENES3 = {"tiny": ((-3, -5, -2), (9, 8, 7), 3000), "wide": ((-21, -14, -5), (40
 SINGLE2, CLUSTER2 = (0.3 + 2.0 ** -11, 0.2 + 2.0 ** -11), (1.8 + 2.0 ** -23, 1.8 + 5 * 2.0 ** -23)
 SINGLE3, CLUSTER3 = (0.3 + 2.0 ** -11, 1.2 + 2.0 ** -11, 0.4 + 2.0 ** -11), (1.8 + 2.0 ** -23, 1.8 + 5 * 2.0 ** -23, 1.3 + 3 * 2.0 ** -23)
 _cache = {}
+TILTED = ("steep", "near_gimbal")              # the 3D poses with |roll|, |pitch| >= 0.5 rad
 
 
 def points(dim, scene, seed=17):
@@ -51,7 +52,9 @@ def own_points(dim, scene, n=200, seed=5):
 
 def poses(dim, scene):
     """name -> pose: identity, a whole-cell shift, a general pose, yaw within 1e-3 of +pi and of -pi, and one that puts part
-    of the source outside the destination (in 2D part of it on the destination's ring)."""
+    of the source outside the destination (in 2D part of it on the destination's ring).  3D also: "steep" and
+    "near_gimbal", the attitudes of tilted_cases.ATTITUDES with translations like "general" - roll and pitch of 0.5 rad and
+    more, where the sin roll sin pitch entries of R count (every other pose keeps them below 0.03)."""
     c = C2 if dim == 2 else C3
     if dim == 2:
         out = 4.3 if scene == "tiny" else 60.0
@@ -61,7 +64,8 @@ def poses(dim, scene):
     out = 4.3 if scene == "tiny" else 12.0
     return {"identity": (0.0,) * 6, "shift": (2 * c, -c, c, 0.0, 0.0, 0.0), "general": (0.3217, -0.1934, 0.2781, 0.11, -0.23, 0.7),
             "near_pi": (0.11, 0.07, -0.05, 0.0, 0.0, math.pi - 7e-4), "near_minus_pi": (-0.13, 0.21, 0.04, 0.02, -0.01, -math.pi + 4e-4),
-            "partly_outside": (out, 0.37 * out, 0.4, 0.03, -0.02, 0.05)}
+            "partly_outside": (out, 0.37 * out, 0.4, 0.03, -0.02, 0.05),
+            "steep": (0.2871, -0.2209, 0.3127, 0.7, -0.5, 2.1), "near_gimbal": (-0.3391, 0.1873, 0.2443, 1.2, 1.45, 0.4)}
 
 
 def empty_blob(dim, c, origin, ext):

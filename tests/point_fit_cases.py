@@ -9,7 +9,8 @@ import point_fit_ref as F
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 MAX_M = {2: 5.99, 3: 7.81}          # chi-square 95 % for 2 and 3 degrees of freedom (see point_fit_ref: no hit within tolerance of either)
-# a rotation-free pose with float32 translations, and the rotated ones: the fixture's final pose and one beyond |theta| = 2
+# a rotation-free pose with float32 translations, and the rotated ones: the fixture's final pose, one beyond |theta| = 2
+# and, in 3D, steep_scene's
 EXACT_POSE = {2: (0.09375, -0.078125, 0.0), 3: (0.015625, -0.203125, 0.046875, 0.0, 0.0, 0.0)}
 
 
@@ -26,6 +27,21 @@ def far_pose(dim, final_pose):
     p = list(final_pose)
     p[-1] += 2.5
     return tuple(p)
+
+
+STEEP = (0.7, -0.5, 2.1)            # tilted_cases.ATTITUDES["steep"]: roll and pitch where the sin roll sin pitch entries of R count
+
+
+def steep_scene(fx):
+    """The 3D fixture seen from a steeply tilted sensor frame -> (source, pose): the scan re-expressed, s' = Q' s with
+    Q = R(final)' R(STEEP) in float64 and rounded to float32, and the pose (final translation, STEEP) that puts it where
+    the final pose puts the original - the same images to float32 rounding, so the same mix of fits, misfits and misses,
+    through a rotation matrix none of whose entries is near 0 or 1."""
+    from oracle import ndt3d as o3
+    final = fx["final_pose"]
+    Q = o3.rot_and_derivs(*final[3:])[0].T @ o3.rot_and_derivs(*STEEP)[0]
+    P = np.stack(fx["source"], axis=1).astype(np.float64) @ Q
+    return tuple(np.ascontiguousarray(P[:, a].astype(np.float32)) for a in range(3)), tuple(final[:3]) + STEEP
 
 
 def tiled(coords, n, step=0.004):

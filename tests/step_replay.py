@@ -1,4 +1,5 @@
-"""Replay of single solve / update steps (docs/ALGORITHM.md sections 2.5 and 2.6) against the float64 oracle.  CPU only.
+"""Replay of single solve / update steps (docs/ALGORITHM.md sections 2.5 and 2.6) against the float64 oracle.  CPU only,
+but for one_step_results at the end: the list of alignment drivers the GPU files share.
 
 A result row carries, as doubles, exactly what the device fed its solver: H, g, score, n_hit.  rows[j] holds the pose
 after update j + 1 and the sums of the evaluation behind it, taken at rows[j - 1].pose (include/ndt_hip.h, the trace
@@ -427,3 +428,67 @@ def oracle_case(dim: int, name: str):
     prm = params3d(**opt)
     rows = oracle_rows3d(o3.build_grid3(d["tx"], d["ty"], d["tz"], prm), d["sx"], d["sy"], d["sz"], init, prm)
     return prm, init, rows, replay3d(init, rows, prm)
+
+
+# ----------------------------------------------------------------------------- one update of every driver (needs a GPU)
+SPLIT_FROM = 12              # NDT_TUNE_SPLIT_FROM's default: calls of at least this many starts run the two-kernel chain
+
+
+def device_api(dim):
+    from gtsam_ndt_amd import matcher as M
+    if dim == 2:
+        return M.NdtMatcher2D, M.NdtBatch2D, params2d, replay2d, ("tx", "ty"), ("sx", "sy")
+    return M.NdtMatcher3D, M.NdtBatch3D, params3d, replay3d, ("tx", "ty", "tz"), ("sx", "sy", "sz")
+
+
+def _cuda(arrays):
+    import torch
+    return tuple(torch.from_numpy(np.ascontiguousarray(a)).cuda() for a in arrays)
+
+
+def _starts(init, m):
+    """m starts a millimetre apart: each result is replayed from its own."""
+    step = np.array((1e-3, -1e-3, 1e-4) if len(init) == 3 else (1e-3, -1e-3, 5e-4, 1e-4, -1e-4, 1e-4))
+    return [tuple(np.array(init) + k * step) for k in range(m)]
+
+
+def one_step_results(dim, name, pair=None, init=None):
+    """One update (fixed_iterations = 1) of every alignment driver with the options of case `name`, on the case's own
+    pair and start or on the given ones (tests/test_gpu_tilted3d.py: the tilted pairs).  Yields
+    (driver, result, the pose it started from, the options, whether it evaluates the case's own point-to-map objective)."""
+    Matcher, Batch, params, replay, tk, sk = device_api(dim)
+    case_pair, start, opt, _ = (CASES2D if dim == 2 else CASES3D)[name]
+    d = case_pair() if pair is None else pair
+    init = tuple(start()) if init is None else tuple(init)
+    kw = dict(opt, fixed_iterations=1)
+    kw.pop("max_iterations", None)
+    tgt, src = [d[k] for k in tk], [d[k] for k in sk]
+    singles = [("k_align_small", {}, {}), ("k_iterate", {"short_scan_kernel": 0}, {}),
+               ("k_iterate, 1024 threads", {"short_scan_kernel": 0, "wide_threshold": 500}, {}),
+               ("k_iterate, 4 overlapping grids", {"short_scan_kernel": 0}, {"overlap_grids": 4})] if dim == 2 else \
+        [("k_iterate3", {}, {})]
+    for label, tuning, extra in singles:
+        with Matcher(tuning=tuning, **kw, **extra) as m:
+            m.set_target(*tgt)
+            yield label, m.align(*src, init), init, kw | extra, not extra
+    with Matcher(**kw) as m:
+        m.set_target(*tgt)
+        dev = _cuda(src)
+        for n in (2, SPLIT_FROM):
+            starts = _starts(init, n)
+            for k, r in enumerate(m.align_multi_start(*dev, starts)):
+                yield f"align_multi_start, {n} starts [{k}]", r, starts[k], kw, True
+            for k, r in enumerate(m.align_multi_scan([dev] * n, starts)):
+                yield f"align_multi_scan, {n} scans [{k}]", r, starts[k], kw, True
+    variants = [("batch, small variant", dict(small_variant=True), {}, 0), ("batch, 1024 threads", dict(small_variant=False), {}, 1),
+                ("batch, global tables", dict(global_workgroups=8), GLOBAL2D, 1)] if dim == 2 else \
+        [("batch3, on chip", {}, {}, None), ("batch3, global tables", dict(global_workgroups=8), GLOBAL3D, None)]
+    for label, how, extra, large in variants:
+        with Batch(**how, **kw, **extra) as b:
+            r = b.align([tuple(tgt)], [tuple(src)], [init])[0]
+            assert large is None or b.last_large_count == large, (label, b.last_large_count)
+        yield label, r, init, kw | extra, not extra
+    with Matcher(**kw) as t, Matcher(**kw) as s:
+        t.set_target(*tgt)
+        s.set_target(*src)
+        yield "align_map", t.align_map(s, init), init, kw, False

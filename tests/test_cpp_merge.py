@@ -38,9 +38,9 @@ def _blobs(dim):
     return R.blob_from_points(own, c, origin, ext)[0], R.blob_from_points(MC.points(dim, "tiny"), c)[0]
 
 
-def _run(exe, tmp_path, dim):
+def _run(exe, tmp_path, dim, pose_name="general"):
     dst, src = _blobs(dim)
-    pose = MC.poses(dim, "tiny")["general"]
+    pose = MC.poses(dim, "tiny")[pose_name]
     paths = [str(tmp_path / f"{k}{dim}.map") for k in ("dst", "src", "merged", "back")]
     dst.tofile(paths[0])
     src.tofile(paths[1])
@@ -58,7 +58,17 @@ def test_merge_program_compiles_and_fails_loudly_without_gpu(exe, tmp_path, ndt_
 @pytest.mark.gpu
 @pytest.mark.parametrize("dim", [2, 3])
 def test_merge_through_the_cpp_adapter(exe, tmp_path, gpu_lib, dim):
-    dst, src, pose, paths, r = _run(exe, tmp_path, dim)
+    _merge_through_the_cpp_adapter(exe, tmp_path, dim, "general")
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("pose_name", MC.TILTED)
+def test_merge_through_the_cpp_adapter_at_tilted_poses(exe, tmp_path, gpu_lib, pose_name):
+    _merge_through_the_cpp_adapter(exe, tmp_path, 3, pose_name)
+
+
+def _merge_through_the_cpp_adapter(exe, tmp_path, dim, pose_name):
+    dst, src, pose, paths, r = _run(exe, tmp_path, dim, pose_name)
     assert r.returncode == 0, r.stdout + r.stderr
     want, want_out = M.map_merge_ref(dst, src, pose)
     assert r.stdout.split() == ["outside", str(want_out), str(want_out)]

@@ -4,7 +4,8 @@ ndt3d_load_map of those bytes.
 
 Scenes and poses: merge_cases.py ("tiny" 9 x 8 x 7 voxels of 1 m with a single-point voxel and a degenerate block on which
 the clamp acts - asserted; "wide" 40 x 30 x 12 voxels, 60 000 points; the source at half of the destination's voxel size in
-one case each; all three angles in the general pose; no ring in 3D, so "partly outside" means beyond the extent)."""
+one case each; all three angles in the general pose, and in "steep" and "near_gimbal" roll and pitch of 0.5 to 1.45 rad; no
+ring in 3D, so "partly outside" means beyond the extent)."""
 import numpy as np
 import pytest
 
@@ -16,7 +17,8 @@ pytestmark = pytest.mark.gpu
 DIM = 3
 
 CASES = [("tiny", name, False) for name in ("identity", "shift", "general", "near_pi", "near_minus_pi", "partly_outside")] + \
-        [("tiny", "general", True), ("wide", "general", False), ("wide", "partly_outside", False), ("wide", "near_pi", True)]
+        [("tiny", "general", True), ("wide", "general", False), ("wide", "partly_outside", False), ("wide", "near_pi", True)] + \
+        [("tiny", name, False) for name in MC.TILTED] + [("tiny", "steep", True), ("wide", "near_gimbal", False)]
 
 
 @pytest.mark.parametrize("scene,pose_name,half", CASES)
@@ -51,8 +53,16 @@ def test_merged_submap(gpu_lib, scene, pose_name, half):
 
 
 def test_merges_commute_and_unmerge_inverts(gpu_lib):
+    _merges_commute_and_unmerge_inverts("general", "near_pi", "shift")
+
+
+def test_merges_commute_and_unmerge_inverts_at_tilted_poses(gpu_lib):
+    _merges_commute_and_unmerge_inverts("steep", "near_gimbal", "general")
+
+
+def _merges_commute_and_unmerge_inverts(name_b, name_c, name_new):
     P = MC.poses(DIM, "tiny")
-    tb, tc, t_new = P["general"], P["near_pi"], P["shift"]
+    tb, tc, t_new = P[name_b], P[name_c], P[name_new]
     scan = MC.scan_of(DIM, "tiny", tb)
     with MC.source(DIM, "tiny") as b, MC.source(DIM, "tiny", seed=29) as c, MC.destination(DIM, "tiny") as d1, \
             MC.destination(DIM, "tiny") as d2:
@@ -193,8 +203,16 @@ def test_a_destination_cell_beyond_the_capacity(gpu_lib):
 
 def test_merge_through_the_map_pyramid(gpu_lib):
     """NdtMapPyramid3D.merge folds the other pyramid in level by level: every level holds the reference's bytes."""
+    _merge_through_the_map_pyramid("general")
+
+
+def test_merge_through_the_map_pyramid_at_a_steep_pose(gpu_lib):
+    _merge_through_the_map_pyramid("steep")
+
+
+def _merge_through_the_map_pyramid(pose_name):
     from gtsam_ndt_amd.matcher import NdtMapPyramid3D
-    pose = MC.poses(DIM, "tiny")["general"]
+    pose = MC.poses(DIM, "tiny")[pose_name]
     with MC.source(DIM, "tiny") as src, MC.destination(DIM, "tiny") as dst:
         src_blob, dst_blob = src.save_map(), dst.save_map()
     with NdtMapPyramid3D.from_blob(dst_blob) as pd, NdtMapPyramid3D.from_blob(src_blob) as ps:

@@ -5,7 +5,8 @@ records), on the committed fixtures with NaN / inf, far, ring and displaced poin
    float32 reproduces it and the key exactly.  invalid / miss / hit are equal at EVERY point; |m_dev - m_ref| <=
    K 2^-24 M_abs per hit (K = 8 in 2D, 10 in 3D; point_fit_ref states the count); fit / misfit equal wherever m_ref is
    further than that from max_m, and at most 1 % of the hits may be excused that way.
-2. Rotated poses (the fixture's final pose, and one with |theta| > 2): the same with the image-point uncertainty added
+2. Rotated poses (the fixture's final pose, one with |theta| > 2, and in 3D the scan seen from a frame rolled 0.7 and
+   pitched -0.5 rad): the same with the image-point uncertainty added
    (point_fit_ref), points whose cell coordinate is within it of an integer excused under the same 1 % cap; and the tie
    to the existing path for one grid and 3D: n_misfit + n_fit EQUALS evaluate(...).n_hit, and sum d1 exp(-d2 / 2 m_i)
    over the hits, added in float64 from the returned m, is within 2e-5 relative of its score (the project's standing
@@ -75,8 +76,19 @@ def test_exact_image_pose(scenes, dim, ng):
 def test_rotated_pose(scenes, dim, ng, which):
     m, rec, fx = scenes[dim, ng]
     pose = fx["final_pose"] if which == "final" else PC.far_pose(dim, fx["final_pose"])
+    _rotated_pose(m, rec, fx["source"], pose, dim, ng, which)
+
+
+def test_steep_pose_3d(scenes):
+    """Roll 0.7, pitch -0.5, yaw 2.1 (point_fit_cases.steep_scene): every entry of R away from 0 and 1, the same bound."""
+    m, rec, fx = scenes[3, 1]
+    source, pose = PC.steep_scene(fx)
+    _rotated_pose(m, rec, source, pose, 3, 1, "steep")
+
+
+def _rotated_pose(m, rec, source, pose, dim, ng, which):
     max_m = PC.MAX_M[dim]
-    coords, inj = PC.mixed_scan(rec, fx["source"], pose, N)
+    coords, inj = PC.mixed_scan(rec, source, pose, N)
     ref = F.fit_ref(rec, coords, pose, max_m)
     got = _fit_both_ways(m, coords, pose, max_m)
     fig = _check(ref, got, max_m, f"{which} pose dim {dim} ngrid {ng}")

@@ -147,6 +147,28 @@ def test_matcher_select_points_in_and_out_kinds(scenes, dim):
     assert dfit.n_hit == dfit.n_fit + dfit.n_misfit and 0.0 < dfit.fitness < 1.0
 
 
+def test_selection_at_a_steep_pose_3d(scenes):
+    """The 3D scan seen from a frame rolled 0.7 and pitched -0.5 rad (point_fit_cases.steep_scene): the classes are the
+    reference's within its excuses, the selection is flatnonzero of the device's own classes, the input's bits in scan
+    order, through the raw call and through the matcher."""
+    s = scenes[3]
+    m, rec, max_m = s["m"], s["rec"], s["max_m"]
+    source, pose = PC.steep_scene(PC.fixture(3))
+    n = 3001
+    coords, _ = PC.mixed_scan(rec, source, pose, n)
+    got = m.fit_points(*coords, pose, max_m)
+    fig, fails = F.compare(F.fit_ref(rec, coords, pose, max_m), got.m, got.cls, max_m)
+    assert not fails and set(np.unique(got.cls)) == {0, 1, 2, 3}, (fails, fig)
+    for keep in (FIT_MISS, 1 << F.FIT, 15):
+        out, index, summary = _select(m, PC.dev(coords), pose, max_m, keep)
+        _assert_selection(coords, got.cls, keep, out, index, summary)
+    want = np.flatnonzero(F.keep_mask(got.cls, FIT_MISS))
+    sel, idx, fit = m.select_points(*coords, pose, max_m)
+    assert np.array_equal(idx, want) and fit.n_selected == len(want) > 1000 and np.all(np.diff(idx) > 0)
+    for a in range(3):
+        assert sel[a].tobytes() == coords[a][want].tobytes()
+
+
 @pytest.mark.parametrize("dim", [2, 3])
 def test_the_loop_it_is_for(gpu_lib, dim):
     """The map is built from the target; the scan is the fixture's source plus 200 points moved 0.25 m along the minor

@@ -99,6 +99,35 @@ def test_remove_is_the_exact_inverse_of_add_3d(M, scans):
     assert tiles.max() > 1024                                        # the removed scan did put shared tiles to work
 
 
+def test_add_and_remove_at_a_steep_pose_3d(M, scans):
+    """A scan seen from a sensor frame rolled 0.7 and pitched -0.5 rad (every other pose here stays below 0.006): the
+    scan re-expressed, s' = Q' s with Q = R(pose)' R(steep), lands where the original does.  Added on the device at the
+    steep pose, the grid is the one built from the host-transformed points (_world: numpy's R, float32); removed again,
+    the submap is bit for bit what it was."""
+    (s0, p0), (s1, p1) = scans[0], scans[1]
+    steep = (0.7, -0.5, 2.1)
+    Q = synth3d.rotation(*p1[3:]).T @ synth3d.rotation(*steep)
+    P = np.stack(s1, axis=1).astype(np.float64) @ Q
+    t1 = [np.ascontiguousarray(P[:, a].astype(np.float32)) for a in range(3)]
+    pt = tuple(p1[:3]) + steep
+    w = _world(*t1, pt)
+    seen = ~np.isnan(s1[0])
+    assert np.abs(np.stack(w, 1)[seen] - np.stack(_world(*s1, p1), 1)[seen]).max() < 1e-4          # the same place
+    d0, dt = [_dev(c) for c in s0], [_dev(c) for c in t1]
+    with M() as m, M() as ref, M() as base:
+        for h in (m, ref, base):
+            h.reserve_target(LO, HI)
+            h.add_target_points(*d0, pose=p0)
+        before = _state(base)
+        out = m.add_target_points(*dt, pose=pt)
+        assert ref.add_target_points(*w) == out >= 3                  # host arrays, already in the map frame
+        st = _state(m)
+        _assert_same_state(st, _state(ref))
+        assert st["grid"][0].astype(np.int64).sum() - before["grid"][0].astype(np.int64).sum() == t1[0].size - out > 30000
+        assert m.remove_target_points(*dt, pose=pt) == out
+        _assert_same_state(_state(m), before)
+
+
 def test_host_entry_point_and_remove_everything_3d(M, scans):
     (s0, p0), (s1, p1) = scans[0], scans[1]
     w0, w1 = _world(*s0, p0), _world(*s1, p1)

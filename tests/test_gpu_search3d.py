@@ -101,12 +101,26 @@ def test_search_recovers_a_pose_local_alignment_cannot(gpu_lib, relocal):
 def test_score_volume_matches_the_oracle(gpu_lib, small):
     """The golden pair, a window of 9 x 9 x 36 = 2916 poses with a non-zero pinned z, roll and pitch.  Reference:
     oracle.ndt3d.evaluate3(mirror32=True) at every lattice pose."""
-    from gtsam_ndt_amd.matcher import NdtMatcher3D
-    from oracle import ndt3d as o
     d = small
     c = (d["pose"][0] + 0.05, d["pose"][1] - 0.05, 0.04, 0.012, -0.008, d["pose"][5])
-    window = search.Window(c, (0.8, 0.8, math.pi), (0.2, 0.2, 10.0 * DEG))
-    assert search.dims(window)[0] == (36, 9, 9)
+    _score_volume_matches_the_oracle(d, search.Window(c, (0.8, 0.8, math.pi), (0.2, 0.2, 10.0 * DEG)), (36, 9, 9))
+
+
+def test_score_volume_matches_the_oracle_at_a_steep_pinned_roll_and_pitch(gpu_lib, small):
+    """The same with roll 0.7 and pitch -0.5 pinned: the golden source seen from a frame tilted that far
+    (tilted_cases.tilted_pair), 5 x 5 x 9 = 225 poses round the pose that puts it back onto the target."""
+    import tilted_cases as T
+    t = T.tilted_pair("steep")
+    d = dict(small, sx=t["sx"], sy=t["sy"], sz=t["sz"])
+    c = (d["pose"][0] + 0.05, d["pose"][1] - 0.05, 0.04, 0.7, -0.5, 2.1)
+    _score_volume_matches_the_oracle(d, search.Window(c, (0.4, 0.4, 40.0 * DEG), (0.2, 0.2, 10.0 * DEG)), (9, 5, 5))
+
+
+def _score_volume_matches_the_oracle(d, window, dims):
+    from gtsam_ndt_amd.matcher import NdtMatcher3D
+    from oracle import ndt3d as o
+    c = window[0]
+    assert search.dims(window)[0] == dims
     prm = o.Ndt3Params()
     g = o.build_grid3(d["tx"], d["ty"], d["tz"], prm)
     xs, ys, th = search.lattice(window)

@@ -147,6 +147,33 @@ def test_volume_matches_the_restatement(gpu_lib, case):
     assert np.all(err <= 1e-4 * np.abs(ref) + 1e-3), excess
 
 
+def test_volume_matches_the_restatement_at_a_steep_pinned_roll_and_pitch(gpu_lib):
+    """Roll 0.7 and pitch -0.5 pinned (VOLUME_CASES stays below 0.05): the small pair with its source map built from the
+    scan seen from a frame tilted that far (tilted_cases.map_search_pair), 405 poses round the pose that puts it back.
+    The same restatement, the same bound; tests/test_tilted_ref.py holds the restatement's float32 form within a quarter
+    of it on this lattice."""
+    import tilted_cases as T
+    from gtsam_ndt_amd.matcher import NdtMatcher3D
+    d, window = T.map_search_pair(), T.map_search_window()
+    prm = O.Ndt3Params()
+    tgt, _ = R.build_map(d["tx"], d["ty"], d["tz"], prm)
+    _, comps = R.build_map(d["sx"], d["sy"], d["sz"], prm)
+    assert search.dims(window)[0] == T.MAP_SEARCH_LATTICE and window.center[3:5] == (0.7, -0.5)
+    ref = S.volume(tgt, comps, window, prm)
+    with NdtMatcher3D() as t, NdtMatcher3D() as s:
+        t.set_target(d["tx"], d["ty"], d["tz"])
+        s.set_target(d["sx"], d["sy"], d["sz"])
+        assert s.components()[0].size == comps.n
+        vol = t.search_map_scores(s, *window).cpu().numpy().astype(np.float64)
+    assert vol.shape == ref.shape
+    err = np.abs(vol - ref)
+    excess = float(np.max(err - 1e-4 * np.abs(ref)))
+    print(f"steep: {comps.n} components, lattice {vol.shape}, max(ref) {ref.max():.2f}, largest |vol - ref| {err.max():.3e}, "
+          f"largest |vol - ref| - 1e-4 |ref| {excess:.3e}")
+    assert np.max(ref) > 10.0
+    assert np.all(err <= 1e-4 * np.abs(ref) + 1e-3), excess
+
+
 # ---------------------------------------------------------------------------------------------- 2. the hits
 @pytest.mark.parametrize("case", ["cyclic", "window", "ties", "sparse"])
 def test_hits_are_exactly_the_specification(gpu_lib, case):

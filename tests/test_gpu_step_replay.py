@@ -25,19 +25,10 @@ import step_replay as S
 pytestmark = pytest.mark.gpu
 
 ALL = [(2, n) for n in S.CASES2D] + [(3, n) for n in S.CASES3D]
-SPLIT_FROM = 12              # NDT_TUNE_SPLIT_FROM's default: calls of at least this many starts run the two-kernel chain
+SPLIT_FROM = S.SPLIT_FROM
 
 
-def _api(dim):
-    from gtsam_ndt_amd import matcher as M
-    if dim == 2:
-        return M.NdtMatcher2D, M.NdtBatch2D, S.params2d, S.replay2d, ("tx", "ty"), ("sx", "sy")
-    return M.NdtMatcher3D, M.NdtBatch3D, S.params3d, S.replay3d, ("tx", "ty", "tz"), ("sx", "sy", "sz")
-
-
-def _cuda(arrays):
-    import torch
-    return tuple(torch.from_numpy(np.ascontiguousarray(a)).cuda() for a in arrays)
+_api = S.device_api
 
 
 @pytest.mark.parametrize("dim,name", ALL, ids=[f"{d}d-{n}" for d, n in ALL])
@@ -56,49 +47,7 @@ def test_trace_replays_step_by_step(gpu_lib, dim, name):
     assert set(want) <= S.reached(rep, rows, prm), (want, [(r["kind"], r["rung"], r["limit"]) for r in rep])
 
 
-def _starts(init, m):
-    """m starts a millimetre apart: each result is replayed from its own."""
-    step = np.array((1e-3, -1e-3, 1e-4) if len(init) == 3 else (1e-3, -1e-3, 5e-4, 1e-4, -1e-4, 1e-4))
-    return [tuple(np.array(init) + k * step) for k in range(m)]
-
-
-def _one_step_results(dim, name):
-    """(driver, result, the pose it started from, whether it evaluates the case's own point-to-map objective)"""
-    Matcher, Batch, params, replay, tk, sk = _api(dim)
-    pair, start, opt, _ = (S.CASES2D if dim == 2 else S.CASES3D)[name]
-    d, init = pair(), tuple(start())
-    kw = dict(opt, fixed_iterations=1)
-    kw.pop("max_iterations", None)
-    tgt, src = [d[k] for k in tk], [d[k] for k in sk]
-    singles = [("k_align_small", {}, {}), ("k_iterate", {"short_scan_kernel": 0}, {}),
-               ("k_iterate, 1024 threads", {"short_scan_kernel": 0, "wide_threshold": 500}, {}),
-               ("k_iterate, 4 overlapping grids", {"short_scan_kernel": 0}, {"overlap_grids": 4})] if dim == 2 else \
-        [("k_iterate3", {}, {})]
-    for label, tuning, extra in singles:
-        with Matcher(tuning=tuning, **kw, **extra) as m:
-            m.set_target(*tgt)
-            yield label, m.align(*src, init), init, kw | extra, not extra
-    with Matcher(**kw) as m:
-        m.set_target(*tgt)
-        dev = _cuda(src)
-        for n in (2, SPLIT_FROM):
-            starts = _starts(init, n)
-            for k, r in enumerate(m.align_multi_start(*dev, starts)):
-                yield f"align_multi_start, {n} starts [{k}]", r, starts[k], kw, True
-            for k, r in enumerate(m.align_multi_scan([dev] * n, starts)):
-                yield f"align_multi_scan, {n} scans [{k}]", r, starts[k], kw, True
-    variants = [("batch, small variant", dict(small_variant=True), {}, 0), ("batch, 1024 threads", dict(small_variant=False), {}, 1),
-                ("batch, global tables", dict(global_workgroups=8), S.GLOBAL2D, 1)] if dim == 2 else \
-        [("batch3, on chip", {}, {}, None), ("batch3, global tables", dict(global_workgroups=8), S.GLOBAL3D, None)]
-    for label, how, extra, large in variants:
-        with Batch(**how, **kw, **extra) as b:
-            r = b.align([tuple(tgt)], [tuple(src)], [init])[0]
-            assert large is None or b.last_large_count == large, (label, b.last_large_count)
-        yield label, r, init, kw | extra, not extra
-    with Matcher(**kw) as t, Matcher(**kw) as s:
-        t.set_target(*tgt)
-        s.set_target(*src)
-        yield "align_map", t.align_map(s, init), init, kw, False
+_one_step_results = S.one_step_results
 
 
 @pytest.mark.parametrize("dim", [2, 3])

@@ -86,9 +86,19 @@ def test_counts_and_moments_are_conserved_at_a_general_pose(dim):
     and for the second sums - which reach 2^49 here, where 16 roundings of 2^-53 each are one unit - of the order of a unit
     (the largest is printed).  So this is the issue's "half a unit per contribution plus the clamp's raises" with the
     evaluation error of the float64 formula written out instead of ignored."""
+    _counts_and_moments_are_conserved(dim, "general")
+
+
+@pytest.mark.parametrize("pose_name", MC.TILTED)
+def test_counts_and_moments_are_conserved_at_tilted_poses(pose_name):
+    """The same at roll and pitch of 0.5 rad and more, in 3D."""
+    _counts_and_moments_are_conserved(3, pose_name)
+
+
+def _counts_and_moments_are_conserved(dim, pose_name):
     pts, src = _src_blob(dim)
     dst0 = _dst_blob(dim, own=False)
-    pose = MC.poses(dim, "tiny")["general"]
+    pose = MC.poses(dim, "tiny")[pose_name]
     merged, outside = M.map_merge_ref(dst0, src, pose)
     hs, scells = R.parse(src)
     hd, mcells = R.parse(merged)
@@ -140,11 +150,19 @@ def test_counts_and_moments_are_conserved_at_a_general_pose(dim):
 
 @pytest.mark.parametrize("dim", [2, 3])
 def test_unmerge_inverts_and_merges_commute(dim):
+    _unmerge_inverts_and_merges_commute(dim, "general", "near_pi")
+
+
+def test_unmerge_inverts_and_merges_commute_at_tilted_poses():
+    _unmerge_inverts_and_merges_commute(3, "steep", "near_gimbal")
+
+
+def _unmerge_inverts_and_merges_commute(dim, name_b, name_c):
     pts, b = _src_blob(dim)
     c_blob = R.blob_from_points(MC.points(dim, "tiny", seed=29), MC.C2 if dim == 2 else MC.C3)[0]
     a = _dst_blob(dim)
     P = MC.poses(dim, "tiny")
-    tb, tc = P["general"], P["near_pi"]
+    tb, tc = P[name_b], P[name_c]
     ab, out_b = M.map_merge_ref(a, b, tb)
     assert not np.array_equal(ab, a)
     back, out_b2 = M.map_merge_ref(ab, b, tb, sign=-1)

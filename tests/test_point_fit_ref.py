@@ -50,9 +50,12 @@ def test_classes_partition_the_scan_and_selection_is_stable(scene2, scene3, dim,
         rec = by[ov][2]
     else:
         fx, _, _, rec = scene3
-    for pose in (fx["final_pose"], PC.far_pose(dim, fx["final_pose"])):
+    cases = [(fx["source"], fx["final_pose"]), (fx["source"], PC.far_pose(dim, fx["final_pose"]))]
+    if dim == 3:
+        cases.append(PC.steep_scene(fx))
+    for source, pose in cases:
         n = 2500
-        coords, inj = PC.mixed_scan(rec, fx["source"], pose, n)
+        coords, inj = PC.mixed_scan(rec, source, pose, n)
         r = F.fit_ref(rec, coords, pose, PC.MAX_M[dim])
         cls = r["cls"]
         c = F.counts(cls)
@@ -133,3 +136,20 @@ def test_exact_pose_images_are_single_float32_adds():
         assert not F.is_exact_pose(PC.fixture(dim)["final_pose"], dim)
         R, t = F.rotation32(PC.EXACT_POSE[dim], dim)
         assert np.array_equal(R, np.eye(dim)) and np.array_equal(t, np.array(PC.EXACT_POSE[dim][:dim]))
+
+
+def test_the_steep_scene_is_the_fixture_seen_from_a_tilted_frame(scene3):
+    """steep_scene: the same images as the final pose's to float32 rounding of the source (3 half-ulps of 25 m), so the
+    reference classes nearly every point as there - and the counts stay those of a mixed scene."""
+    fx, _, _, rec = scene3
+    source, pose = PC.steep_scene(fx)
+    assert abs(pose[3]) >= 0.5 and abs(pose[4]) >= 0.5
+    R0, t0 = F.rotation32(fx["final_pose"], 3)
+    R1, t1 = F.rotation32(pose, 3)
+    a = np.stack(fx["source"], 1).astype(np.float64) @ R0.T + t0
+    b = np.stack(source, 1).astype(np.float64) @ R1.T + t1
+    assert np.abs(a - b).max() < 6 * 2.0 ** -24 * np.abs(a).max()          # the source's rounding, and the two float32 R
+    r0 = F.fit_ref(rec, fx["source"], fx["final_pose"], PC.MAX_M[3])
+    r1 = F.fit_ref(rec, source, pose, PC.MAX_M[3])
+    c = F.counts(r1["cls"])
+    assert int((r0["cls"] != r1["cls"]).sum()) <= 8 and c["n_fit"] > 1000 and c["n_misfit"] > 500 and c["n_miss"] > 1500
