@@ -30,7 +30,7 @@ NDT_ERR_RCCL = -7
 TUNING = {"launch_graphs": 1, "wide_threshold": 2, "short_scan_kernel": 3, "chunk_launches": 4, "binned_build": 5,
           "batch_small_variant": 6, "split_from": 8, "single_sync_build": 9,
           "batch_global_workgroups": 10, "async_lanes": 11, "map_multi_from": 12, "fused_begin": 13,
-          "lane_fork": 14}
+          "lane_fork": 14, "async_chains": 15}
 
 HESSIAN_GAUSS_NEWTON = 0
 HESSIAN_NEWTON = 1

@@ -53,13 +53,17 @@ struct ndt2d_handle {
   int* h_flag = nullptr;                   // pinned: [0] raised by the launch that ends a converged-mode loop, [1] progress
   int last_parity = 0;
   bool pending = false;
-  // the second launch chain of asynchronous fixed-iteration calls (ndt_host.hpp: AsyncLane); lane 0 is stream / d_call / d_dyn
-  AsyncLane lane1;
-  AlignCall* d_call1 = nullptr;
-  AlignDyn* d_dyn1 = nullptr;
+  // the further launch chains of asynchronous fixed-iteration calls (ndt_host.hpp: AsyncLane), lane k at index k - 1;
+  // lane 0 is stream / d_call / d_dyn
+  AsyncLane lane[kMaxLanes - 1];
+  AlignCall* d_call_lane[kMaxLanes - 1] = {};
+  AlignDyn* d_dyn_lane[kMaxLanes - 1] = {};
+  static constexpr int kDefaultLanes = 3;  // what a new handle runs (NDT_TUNE_ASYNC_CHAINS): the count DESIGN 7 measured best
   LaneState lanes;
-  bool fork_every_pair = false;            // NDT_TUNE_LANE_FORK = 1: lane 1 forks from the handle's stream at every pair
-  int last_lane = 0;                       // the lane whose d_dyn holds the pending state (last_parity)
+  bool fork_every_pair = false;            // NDT_TUNE_LANE_FORK = 1: the secondary lanes fork from the handle's stream at every round
+  int last_lane = 0;                       // the lane whose AlignDyn holds the pending state (last_parity)
+  AlignCall* call_of(int l) const { return l ? d_call_lane[l - 1] : d_call; }
+  AlignDyn* dyn_of(int l) const { return l ? d_dyn_lane[l - 1] : d_dyn; }
   // binned grid build scratch (ndt2d_build.hpp)
   float* d_bx = nullptr; float* d_by = nullptr; size_t bcap = 0;
   unsigned int* d_tiles = nullptr; size_t tile_cap = 0;   // total[nt] | start[nt+1] | cursor[nt]
@@ -616,7 +620,7 @@ auto with_mode(const ndt2d_params& p, F&& f) {
 }
 
 // the k_iterate of an alignment, for graphs (ensure_graph) and plain launches (launch_iter).  wide: 1024-thread
-// workgroups - a property of the call (its scan size), two calls in flight on the two lanes may differ in it
+// workgroups - a property of the call (its scan size), calls in flight on different lanes may differ in it
 const void* iter_kernel(const ndt2d_handle* h, bool wide) {
   return with_mode(h->prm, [&](auto M, auto NG) {
     return wide ? (const void*)&k_iterate<M, 0, kIterThreadsWide, NG> : (const void*)&k_iterate<M, 0, kIterThreads, NG>;
@@ -647,7 +651,7 @@ void drop_graph(ndt2d_handle* h) {
 // serves every target and every source - of its lane: the per-call and dynamic contexts are baked into it.
 int32_t ensure_graph(ndt2d_handle* h, int launches, int blocks, bool wide, int lane, hipGraphExec_t* exec, int first_parity) {
   HIP_TRY(h->graphs.get(iter_kernel(h, wide), dim3(blocks), dim3(iter_threads(wide)), (void*)h->d_static,
-                        (void*)(lane ? h->d_call1 : h->d_call), (void*)(lane ? h->d_dyn1 : h->d_dyn), launches,
+                        (void*)h->call_of(lane), (void*)h->dyn_of(lane), launches,
                         h->prm.hessian_mode | (wide ? 16 : 0), h->stream, exec, lane, first_parity));
   return NDT_OK;
 }
@@ -679,10 +683,11 @@ int32_t finish_host_fed(ndt2d_handle* h) {
   return NDT_OK;
 }
 
-// The head of every entry point that is about to use the handle's stream for something else than an alternating
-// asynchronous alignment.  Lane 1 needs no wait here: the handle's stream was ordered behind its chain when that was
-// enqueued (AsyncLane::leave).  The alternation starts over and lane 1 is stale from here on (lane_step: kOther): the
-// next asynchronous call records a fresh fork event behind this entry point's work, and its lane-1 partner waits for it.
+// The head of every entry point that is about to use the handle's stream for something else than a rotating
+// asynchronous alignment.  The secondary lanes need no wait here: the handle's stream was ordered behind their chains when
+// those were enqueued (AsyncLane::leave).  The rotation starts over and the secondary lanes are stale from here on
+// (lane_step: kOther): the next asynchronous call records fresh fork events behind this entry point's work, and the
+// calls that follow it on lanes 1 .. N-1 wait for theirs.
 int32_t finish_chunk_run(ndt2d_handle* h) {
   (void)lane_step(h->lanes, LaneEvent::kOther);
   return finish_host_fed(h);
@@ -719,8 +724,8 @@ int32_t run_align(ndt2d_handle* h, const float* d_sx, const float* d_sy, size_t 
   const bool wide = is_wide(h, n);
   const bool chunked = h->use_graph && check_every > 0 && fixed == 0;
   const bool small = h->use_small && h->use_graph && n <= (size_t)kSmallMaxPoints;
-  // Only a whole fixed-iteration chain that nobody waits for alternates between the lanes; everything else runs on
-  // lane 0 and starts the alternation over.
+  // Only a whole fixed-iteration chain that nobody waits for goes round the lanes; everything else runs on
+  // lane 0 and starts the rotation over.
   const LanePlan plan = lane_step(h->lanes, fixed > 0 && h->use_graph && !small && !wait ? LaneEvent::kAsyncFixed : LaneEvent::kOther);
   next_seq(&h->call_seq, h->h_flag);
   if (small) {
@@ -741,26 +746,30 @@ int32_t run_align(ndt2d_handle* h, const float* d_sx, const float* d_sy, size_t 
     return wait ? finish_small_run(h) : NDT_OK;
   }
   hipStream_t stream = h->stream;
-  // the fork: where non-chain work on the handle's stream may precede the pair (or at every pair, NDT_TUNE_LANE_FORK = 1)
-  // (a record that fails must not leave the state claiming a fork: the rule is kept across calls, so lane 1 stays stale)
+  // the fork: where non-chain work on the handle's stream may precede the round (or at every round, NDT_TUNE_LANE_FORK = 1),
+  // one event per secondary lane in use
+  // (a record that fails must not leave the state claiming a fork: the rule is kept across calls, so the lanes stay stale)
   if (h->fork_every_pair ? plan.record_fork : plan.mark) {
-    const hipError_t fe = h->lane1.mark_fork(h->stream);
-    if (fe != hipSuccess) (void)lane_step(h->lanes, LaneEvent::kOther);
-    HIP_TRY(fe);
+    for (int l = 1; l < h->lanes.lanes; ++l) {
+      const hipError_t fe = h->lane[l - 1].mark_fork(h->stream);
+      if (fe != hipSuccess) (void)lane_step(h->lanes, LaneEvent::kOther);
+      HIP_TRY(fe);
+    }
   }
-  if (plan.lane == 1) {
+  AsyncLane* const side = plan.lane ? &h->lane[plan.lane - 1] : nullptr;
+  if (side) {
     if (h->fork_every_pair || plan.wait) {
-      const hipError_t we = h->lane1.enter();
+      const hipError_t we = side->enter();
       if (we != hipSuccess) (void)lane_step(h->lanes, LaneEvent::kOther);
       HIP_TRY(we);
     }
-    stream = h->lane1.stream;
+    stream = side->stream;
   }
   // Launch 0.  Fused (the default): k_iterate_first, a plain launch that evaluates at the initial pose and writes the
   // per-call context from its arguments; launches 1 .. K follow.  Old protocol: k_begin, then launches 0 .. K.
   const int first = h->fused_begin ? 1 : 0;
-  AlignCall* const d_call = plan.lane ? h->d_call1 : h->d_call;
-  AlignDyn* const d_dyn = plan.lane ? h->d_dyn1 : h->d_dyn;
+  AlignCall* const d_call = h->call_of(plan.lane);
+  AlignDyn* const d_dyn = h->dyn_of(plan.lane);
   IterState* const host_state = chunked ? h->h_state : (IterState*)nullptr;
   int* const host_flag = chunked ? h->h_flag : (int*)nullptr;
   if (first) {
@@ -786,11 +795,11 @@ int32_t run_align(ndt2d_handle* h, const float* d_sx, const float* d_sy, size_t 
       h->pending = false;
       return wait ? finish_chunk_run(h) : NDT_OK;
     } else {
-      // (a lane-1 call that fails here leaves lane 1 behind the fork event at most and nothing else: harmless)
+      // (a secondary-lane call that fails here leaves its lane behind the fork event at most and nothing else: harmless)
       const int32_t gs = ensure_graph(h, K + 1 - first, blocks, wide, plan.lane, &exec, first);
       if (gs != NDT_OK) return gs;
       HIP_TRY(hipGraphLaunch(exec, stream));
-      if (plan.lane == 1) HIP_TRY(h->lane1.leave(h->stream));
+      if (side) HIP_TRY(side->leave(h->stream));
       k = K + 1;
     }
   } else {
@@ -813,12 +822,12 @@ int32_t run_align(ndt2d_handle* h, const float* d_sx, const float* d_sy, size_t 
   return NDT_OK;
 }
 
-// The state of the last alignment, from the lane it ran on (the handle's stream is behind both lanes' chains)
+// The state of the last alignment, from the lane it ran on (the handle's stream is behind every lane's chains)
 int32_t fetch_state(ndt2d_handle* h) {
   { const int32_t fs = finish_host_fed(h); if (fs != NDT_OK) return fs; }
   (void)lane_step(h->lanes, LaneEvent::kFinish);
   if (h->pending) {
-    const AlignDyn* dyn = h->last_lane ? h->d_dyn1 : h->d_dyn;
+    const AlignDyn* dyn = h->dyn_of(h->last_lane);
     HIP_TRY(hipMemcpyAsync(h->h_state, &dyn->state[h->last_parity], sizeof(IterState),
                            hipMemcpyDeviceToHost, h->stream));
     HIP_TRY(hipStreamSynchronize(h->stream));
@@ -1052,12 +1061,15 @@ int32_t ndt2d_create(const ndt2d_params* p, int32_t device_id, ndt2d_handle** ou
   if (hipEventCreateWithFlags(&h->upload_ev, hipEventDisableTiming) != hipSuccess) return fail(NDT_ERR_HIP);
   if (pinned_alloc(&h->h_small, kSmallBytes) != hipSuccess) return fail(NDT_ERR_ALLOC);
   if (hipMemset(h->d_dyn, 0, sizeof(AlignDyn)) != hipSuccess) return fail(NDT_ERR_HIP);
-  // lane 1 of the asynchronous fixed-iteration calls: allocated here, never inside a call that may be timed
-  if (h->lane1.create() != hipSuccess) return fail(NDT_ERR_HIP);
-  if (hipMalloc((void**)&h->d_call1, sizeof(AlignCall)) != hipSuccess) return fail(NDT_ERR_ALLOC);
-  if (hipMalloc((void**)&h->d_dyn1, sizeof(AlignDyn)) != hipSuccess) return fail(NDT_ERR_ALLOC);
-  if (hipMemset(h->d_dyn1, 0, sizeof(AlignDyn)) != hipSuccess) return fail(NDT_ERR_HIP);
-  h->graphs.lane1 = h->lane1.stream;
+  // lanes 1 .. kMaxLanes - 1 of the asynchronous fixed-iteration calls: allocated here, never inside a call that may be timed
+  for (int l = 0; l < kMaxLanes - 1; ++l) {
+    if (h->lane[l].create() != hipSuccess) return fail(NDT_ERR_HIP);
+    if (hipMalloc((void**)&h->d_call_lane[l], sizeof(AlignCall)) != hipSuccess) return fail(NDT_ERR_ALLOC);
+    if (hipMalloc((void**)&h->d_dyn_lane[l], sizeof(AlignDyn)) != hipSuccess) return fail(NDT_ERR_ALLOC);
+    if (hipMemset(h->d_dyn_lane[l], 0, sizeof(AlignDyn)) != hipSuccess) return fail(NDT_ERR_HIP);
+    h->graphs.lane_stream[l] = h->lane[l].stream;
+  }
+  h->lanes.lanes = ndt2d_handle::kDefaultLanes;
   *out = h;
   return NDT_OK;
 }
@@ -1067,11 +1079,13 @@ int32_t ndt2d_destroy(ndt2d_handle* h) {
   (void)hipSetDevice(h->device);
   (void)finish_chunk_run(h);
   if (h->stream) (void)hipStreamSynchronize(h->stream);
-  h->graphs.lane1 = nullptr;
-  h->lane1.destroy();                       // joins lane 1 first
+  for (int l = 0; l < kMaxLanes - 1; ++l) {
+    h->graphs.lane_stream[l] = nullptr;
+    h->lane[l].destroy();                   // joins the lane first
+  }
   drop_graph(h);
   if (h->h_state_multi) (void)hipHostFree(h->h_state_multi);
-  void* dev[] = {h->d_acc2, h->d_split, h->d_bxy, h->d_table, h->d_parts, h->d_geom, h->d_dyn_multi, h->d_bounds, h->d_counters, h->d_outside, h->d_static, h->d_call, h->d_dyn, h->d_call1, h->d_dyn1, h->d_bx, h->d_by, h->d_tiles, h->d_tx, h->d_ty, h->d_sx, h->d_sy,
+  void* dev[] = {h->d_acc2, h->d_split, h->d_bxy, h->d_table, h->d_parts, h->d_geom, h->d_dyn_multi, h->d_bounds, h->d_counters, h->d_outside, h->d_static, h->d_call, h->d_dyn, h->d_call_lane[0], h->d_dyn_lane[0], h->d_call_lane[1], h->d_dyn_lane[1], h->d_call_lane[2], h->d_dyn_lane[2], h->d_bx, h->d_by, h->d_tiles, h->d_tx, h->d_ty, h->d_sx, h->d_sy,
                  h->grid.rec, h->grid.acc, h->d_cov, h->d_blk, h->d_comp, h->d_map_call};
   for (void* p : dev) if (p) (void)hipFree(p);
   void* host[] = {h->h_geom, h->h_static, h->h_state, h->h_small, h->h_flag};
@@ -1102,11 +1116,13 @@ int32_t ndt2d_set_tuning(ndt2d_handle* h, int32_t knob, int64_t value) {
       h->use_binned_build = value != 0; if (value) h->build_variant = (int)value; return NDT_OK;
     case NDT_TUNE_SPLIT_FROM: if (value < 1 || value > 1000) return NDT_ERR_INVALID_ARG; h->split_from = (int)value; return NDT_OK;
     case NDT_TUNE_SINGLE_SYNC_BUILD: h->one_round_trip = value != 0; return NDT_OK;
+    // (both set the number of launch chains; finish_chunk_run above has restarted the rotation and made the lanes stale)
     case NDT_TUNE_ASYNC_LANES: if (value < 1 || value > 2) return NDT_ERR_INVALID_ARG; h->lanes.lanes = (int)value; return NDT_OK;
+    case NDT_TUNE_ASYNC_CHAINS: if (value < 1 || value > kMaxLanes) return NDT_ERR_INVALID_ARG; h->lanes.lanes = (int)value; return NDT_OK;
     case NDT_TUNE_MAP_MULTI_FROM: if (value < 1 || value > kMaxStarts + 1) return NDT_ERR_INVALID_ARG; h->map_multi_from = (int)value; return NDT_OK;
     // (the graphs of the two protocols have different first parities in the cache's key and never alias: nothing to drop)
     case NDT_TUNE_FUSED_BEGIN: if (value != 0 && value != 1) return NDT_ERR_INVALID_ARG; h->fused_begin = value != 0; return NDT_OK;
-    // (finish_chunk_run above has made lane 1 stale, so the first pair under either protocol forks)
+    // (finish_chunk_run above has made the lanes stale, so the first round under either protocol forks)
     case NDT_TUNE_LANE_FORK: if (value != 0 && value != 1) return NDT_ERR_INVALID_ARG; h->fork_every_pair = value != 0; return NDT_OK;
     default: return NDT_ERR_INVALID_ARG;
   }
@@ -1117,15 +1133,15 @@ int32_t ndt2d_wait_stream(ndt2d_handle* h, void* producer_stream) {
   HIP_TRY(hipSetDevice(h->device));
   const bool own = (hipStream_t)producer_stream == h->stream;
   HIP_TRY(order_after(h->stream, (hipStream_t)producer_stream, &h->wait_ev));      // (nothing to do for the handle's own stream)
-  // The next asynchronous call may run on lane 1, which is behind the handle's stream only up to its last fork - taken
-  // before this wait, and in a run of asynchronous calls long ago.  So lane 1 waits for the producer too; where that is
-  // the handle's own stream (the caller's work on ndt2d_stream), for an event recorded there now.
+  // The next asynchronous call may run on a secondary lane, which is behind the handle's stream only up to its last fork -
+  // taken before this wait, and in a run of asynchronous calls long ago.  So the lanes in use wait for the producer too;
+  // where that is the handle's own stream (the caller's work on ndt2d_stream), for an event recorded there now.
   if (lane_step(h->lanes, LaneEvent::kWaitStream).both_wait) {
     if (own) {
       if (!h->wait_ev) HIP_TRY(hipEventCreateWithFlags(&h->wait_ev, hipEventDisableTiming));
       HIP_TRY(hipEventRecord(h->wait_ev, h->stream));
     }
-    HIP_TRY(hipStreamWaitEvent(h->lane1.stream, h->wait_ev, 0));
+    for (int l = 1; l < h->lanes.lanes; ++l) HIP_TRY(hipStreamWaitEvent(h->lane[l - 1].stream, h->wait_ev, 0));
   }
   return NDT_OK;
 }

@@ -1,6 +1,6 @@
 // Host-side helpers shared by the C-ABI translation units: per-thread error text, the HIP_TRY
 // macro that turns a hipError_t into NDT_ERR_HIP without throwing, buffer growth and pinned
-// allocation, launch-chain graphs and their cache, the two launch chains ("lanes") of asynchronous
+// allocation, launch-chain graphs and their cache, the launch chains ("lanes") of asynchronous
 // alignments, and the host half of the converged-mode and build read-back protocols (flags in
 // pinned host memory).
 #pragma once
@@ -177,7 +177,7 @@ struct ChainGraphCache {
   struct Slot { int launches = 0, blocks = 0, mode = -1, lane = 0, first_parity = 0; hipGraph_t graph = nullptr; hipGraphExec_t exec = nullptr; unsigned long stamp = 0; };
   Slot slot[kSlots];
   unsigned long clock = 0;
-  hipStream_t lane1 = nullptr;   // the owner's second launch chain (AsyncLane below): replays of lane-1 graphs are queued there
+  hipStream_t lane_stream[3] = {nullptr, nullptr, nullptr};   // the owner's secondary launch chains (AsyncLane below): replays of their graphs are queued there
 
   // lane: a graph bakes the AlignCall / AlignDyn pointers of its launches, so each launch chain of a handle has its own.
   // first_parity: and the parities of its launches, so a chain that starts at launch 1 never gets one that starts at launch 0
@@ -189,7 +189,7 @@ struct ChainGraphCache {
   }
   // the slot to build into: an empty one, else the least recently used (destroyed first).  Replays
   // of the evicted exec may still be queued (a converged-mode loop leaves up to two chunks of no-op
-  // launches behind): the owner's stream (and its second lane) is drained before the exec is destroyed.
+  // launches behind): the owner's stream (and its secondary lanes) is drained before the exec is destroyed.
   Slot* victim(hipStream_t stream) {
     Slot* v = &slot[0];
     for (Slot& s : slot) {
@@ -197,7 +197,7 @@ struct ChainGraphCache {
       if (s.stamp < v->stamp) v = &s;
     }
     if (v->exec) (void)hipStreamSynchronize(stream);
-    if (v->exec && lane1) (void)hipStreamSynchronize(lane1);
+    if (v->exec) for (hipStream_t l : lane_stream) if (l) (void)hipStreamSynchronize(l);
     release(*v);
     return v;
   }
@@ -231,74 +231,79 @@ struct ChainGraphCache {
   }
 };
 
-// ---- two launch chains per handle --------------------------------------------------------------------------------
+// ---- up to four launch chains per handle ---------------------------------------------------------------------------
 // Successive asynchronous fixed-iteration alignments on a handle are independent of one another (own scan, own initial
 // pose, the same read-only grid), and one launch chain leaves the chip idle for most of every launch.  So
-// such calls alternate between two "lanes": lane 0 is the handle's stream and device context, lane 1 a second stream
-// with a context of its own.  The handle's stream stays ordered behind all of them:
+// such calls go round N "lanes" (1 <= N <= kMaxLanes): lane 0 is the handle's stream and device context, lanes 1 .. N-1
+// ("secondary") are streams with a context of their own.  The handle's stream stays ordered behind all of them:
 //   lane-0 call  enqueue the chain on the handle's stream
-//   lane-1 call  enqueue the chain on lane 1, record `done` there, the handle's stream waits for `done`
-// Lane 1 in turn has to be behind everything on the handle's stream that is NOT an alternating chain (a build, an
+//   lane-k call  enqueue the chain on lane k, record its `done` there, the handle's stream waits for `done`
+// A secondary lane in turn has to be behind everything on the handle's stream that is NOT a rotating chain (a build, an
 // update, a synchronous or converged call, a tuning change: `kOther`) - and behind nothing else: its own previous chain
-// is ordered by its stream, and lane 0's chains share nothing writable with it (own AlignCall / AlignDyn / graphs,
-// read-only AlignStatic, grid and scans).  So the fork is taken only when such work may precede the pair:
-//   lane-0 call  if lane 1 is `stale` (a kOther since it last forked; a new handle): record `fork` on the handle's
-//                stream in front of the chain (`mark`)
-//   lane-1 call  if a fork was recorded since lane 1 last waited (`fork_live`): lane 1 waits for it (`wait`) -
-//                everything before its lane-0 partner, not the partner's chain
-// In a run of back-to-back asynchronous calls the first pair forks and lane 1 then runs its chains back to back: a
-// wait for a fork at every pair would put two cross-queue hops (lane 1 ends -> handle's stream records the fork ->
-// lane 1 starts) between a lane's chains for nothing.  NDT_TUNE_LANE_FORK = 1 forks at every pair all the same
+// is ordered by its stream, and the other lanes' chains share nothing writable with it (own AlignCall / AlignDyn /
+// graphs, read-only AlignStatic, grid and scans).  So the fork is taken only when such work may precede the round:
+//   lane-0 call  if the secondary lanes are `stale` (a kOther since the last fork; a new handle): record every secondary
+//                lane's `fork` on the handle's stream in front of the chain (`mark`); a fork is then pending for each
+//                of them (`fork_live`, one bit per lane)
+//   lane-k call  if its bit of `fork_live` is set: lane k waits for its fork (`wait`) - everything before the lane-0
+//                call that recorded it, not that call's chain - and clears the bit
+// In a run of back-to-back asynchronous calls the first round forks and every secondary lane then runs its chains back
+// to back: a wait for a fork at every round would put two cross-queue hops (lane k ends -> handle's stream records the
+// fork -> lane k starts) between a lane's chains for nothing.  NDT_TUNE_LANE_FORK = 1 forks at every round all the same
 // (`record_fork`), to compare the two in one process.
-// Anything else that happens on the handle in between starts the alternation over at lane 0, so a lane-1 call only ever
-// follows a lane-0 call directly, and that call has recorded the fork if one is due.  ndt*_wait_stream is the
-// exception: it orders both lanes behind the producer and keeps the pairing.
+// Anything else that happens on the handle in between starts the rotation over at lane 0, so a lane-k call only ever
+// follows calls on lanes 0 .. k-1 directly, and the lane-0 one has recorded the fork if one is due.  ndt*_wait_stream
+// is the exception: it orders every lane behind the producer and keeps the rotation.
+
+constexpr int kMaxLanes = 4;
 
 enum class LaneEvent {
-  kAsyncFixed,   // an asynchronous call on the fixed-iteration graph path: the kind that alternates
+  kAsyncFixed,   // an asynchronous call on the fixed-iteration graph path: the kind that rotates
   kWaitStream,   // ndt*_wait_stream
   kOther,        // any other entry point that uses the handle's stream (synchronous calls, converged mode, builds, tuning)
-  kFinish        // ndt*_align_finish: both lanes idle afterwards
+  kFinish        // ndt*_align_finish: every lane idle afterwards
 };
 
 struct LaneState {
-  int lanes = 2;           // NDT_TUNE_ASYNC_LANES: 1 = everything on lane 0, as a handle without lanes
-  int next = 0;            // the lane of the next alternating call
-  bool stale = true;       // lane 1 is not known to be behind the non-chain work on the handle's stream
-  bool fork_live = false;  // a fork has been recorded since lane 1 last waited
+  int lanes = 2;           // NDT_TUNE_ASYNC_CHAINS / NDT_TUNE_ASYNC_LANES: 1 = everything on lane 0, as a handle without lanes
+  int next = 0;            // the lane of the next rotating call
+  bool stale = true;       // the secondary lanes are not known to be behind the non-chain work on the handle's stream
+  unsigned fork_live = 0;  // bit k: a fork has been recorded since lane k last waited
 };
 
 struct LanePlan {
   int lane = 0;              // where this call's chain goes
-  bool record_fork = false;  // lane-0 call that may get a partner (where every pair forks: NDT_TUNE_LANE_FORK = 1)
-  bool both_wait = false;    // kWaitStream: lane 1 waits for the producer too
-  bool mark = false;         // lane-0 call: record the fork event at its head, lane 1 is stale
-  bool wait = false;         // lane-1 call: wait for the fork event, one was recorded since the last wait
+  bool record_fork = false;  // lane-0 call that may get partners (where every round forks: NDT_TUNE_LANE_FORK = 1)
+  bool both_wait = false;    // kWaitStream: the secondary lanes wait for the producer too
+  bool mark = false;         // lane-0 call: record the fork events at its head, the secondary lanes are stale
+  bool wait = false;         // lane-k call: wait for the fork event, one was recorded since the last wait
 };
 
-// What an event on the handle does, and the state after it.  Pure: the only place the pairing rule lives.
+// What an event on the handle does, and the state after it.  Pure: the only place the rotation and fork rule lives.
 inline LanePlan lane_step(LaneState& s, LaneEvent ev) {
   LanePlan p;
-  if (s.lanes < 2) { s.next = 0; s.stale = true; s.fork_live = false; return p; }
+  if (s.lanes < 2) { s.next = 0; s.stale = true; s.fork_live = 0; return p; }
+  const int lanes = s.lanes < kMaxLanes ? s.lanes : kMaxLanes;
   switch (ev) {
     case LaneEvent::kAsyncFixed:
+      if (s.next >= lanes) s.next = 0;
       p.lane = s.next;
       p.record_fork = s.next == 0;
       if (s.next == 0) {
         p.mark = s.stale;
-        if (s.stale) { s.fork_live = true; s.stale = false; }
+        if (s.stale) { s.fork_live = (1u << lanes) - 2u; s.stale = false; }
       } else {
-        p.wait = s.fork_live;
-        s.fork_live = false;
+        p.wait = (s.fork_live >> s.next) & 1u;
+        s.fork_live &= ~(1u << s.next);
       }
-      s.next ^= 1;
+      s.next = s.next + 1 < lanes ? s.next + 1 : 0;
       break;
     case LaneEvent::kWaitStream:
       p.both_wait = true;
       break;
     case LaneEvent::kOther:
       s.stale = true;
-      s.fork_live = false;
+      s.fork_live = 0;
       s.next = 0;
       break;
     case LaneEvent::kFinish:
@@ -308,7 +313,7 @@ inline LanePlan lane_step(LaneState& s, LaneEvent ev) {
   return p;
 }
 
-// The stream and events of lane 1 (created with the handle, never inside a call that may be timed)
+// The stream and events of a secondary lane (created with the handle, never inside a call that may be timed)
 struct AsyncLane {
   hipStream_t stream = nullptr;
   hipEvent_t fork = nullptr, done = nullptr;
@@ -325,11 +330,11 @@ struct AsyncLane {
     if (stream) (void)hipStreamDestroy(stream);
     *this = AsyncLane{};
   }
-  // head of a lane-0 call (LanePlan::mark)
+  // head of a lane-0 call (LanePlan::mark), once per secondary lane in use
   hipError_t mark_fork(hipStream_t main) { return hipEventRecord(fork, main); }
-  // head of a lane-1 call (LanePlan::wait): behind everything that preceded the lane-0 call that recorded the fork
+  // head of this lane's call (LanePlan::wait): behind everything that preceded the lane-0 call that recorded the fork
   hipError_t enter() { return hipStreamWaitEvent(stream, fork, 0); }
-  // tail of a lane-1 call: the handle's stream is ordered behind this chain
+  // tail of this lane's call: the handle's stream is ordered behind this chain
   hipError_t leave(hipStream_t main) {
     const hipError_t e = hipEventRecord(done, stream);
     return e == hipSuccess ? hipStreamWaitEvent(main, done, 0) : e;

@@ -328,8 +328,8 @@ int32_t ndt2d_align_dev(ndt2d_handle* h, const float* d_sx, const float* d_sy, s
  * ndt2d_align_finish() keeps the loop fed until it converges, so the d_sx / d_sy buffers must
  * stay valid until it returns (any other call on the handle finishes a loop in flight first).
  * Pipelining: consecutive fixed-iteration calls (scans above the short-scan limit, launch graphs on) may run
- * concurrently, two at a time: the handle alternates them between two launch chains, so that the second call of a
- * pair fills the launch gaps of the first (NDT_TUNE_ASYNC_LANES; 1 = one chain, calls run one after the other).
+ * concurrently, up to four at a time: the handle sends them round its launch chains, so that every call fills the
+ * launch gaps of the others (NDT_TUNE_ASYNC_CHAINS, three by default; 1 = one chain, calls run one after the other).
  * Each alignment stays what it is - own scan, own initial pose, bit-identical result; ndt2d_align_finish returns
  * the last call's result.  Every call's source arrays must stay valid until ndt2d_align_finish returns.
  * Stream contract: when this function returns, ndt2d_stream(h) is ordered behind this alignment and all earlier
@@ -486,10 +486,14 @@ int32_t ndt2d_get_components(ndt2d_handle* h, float* mean_xy, float* cov_abc, in
  *                               geometry on the device and enqueues the whole build at once (one host round trip;
  *                               it falls back by itself when the new grid does not fit the cached storage).
  *                               0: bounding box to the host first, then the build (two round trips)
- *   NDT_TUNE_ASYNC_LANES        2 (default): consecutive fixed-iteration ndt2d_align_dev_async calls overlap in pairs on
- *                               two streams of the handle; 1: one stream, one call after the other (for a caller that
- *                               shares the GPU and wants one queue).  Other values: NDT_ERR_INVALID_ARG.  Results are
- *                               bit-identical either way
+ *   NDT_TUNE_ASYNC_CHAINS       the number of launch chains (streams of the handle) that consecutive fixed-iteration
+ *                               ndt2d_align_dev_async calls go round, 1..4 (default 3): that many of them overlap.
+ *                               1: one stream, one call after the other (for a caller that shares the GPU and wants
+ *                               one queue).  Other values: NDT_ERR_INVALID_ARG.  Results are bit-identical whatever
+ *                               the count.  ndt2d_set_tuning only
+ *   NDT_TUNE_ASYNC_LANES        the same count under its earlier name, 1 or 2 only: 2: such calls overlap in pairs on
+ *                               two streams of the handle; 1: one stream.  Other values: NDT_ERR_INVALID_ARG (a count
+ *                               of 3 or 4 is set with NDT_TUNE_ASYNC_CHAINS)
  *   NDT_TUNE_MAP_MULTI_FROM     ndt2d_align_map_multi calls of at least this many starts run one launch chain for all
  *                               starts; smaller calls run one ndt2d_align_map chain per start (default 2; 1..65, 65:
  *                               never the shared chain).  Results are bit-identical either way.  The same knob, range
@@ -499,10 +503,10 @@ int32_t ndt2d_get_components(ndt2d_handle* h, float* mean_xy, float* cov_abc, in
  *                               kernel writes the arguments into the device context first (K + 2 launches, the protocol
  *                               ndt2d_align_trace always runs).  Other values: NDT_ERR_INVALID_ARG.  Results are
  *                               bit-identical either way.  The same knob on ndt3d_set_tuning
- *   NDT_TUNE_LANE_FORK          0 (default): the second stream of NDT_TUNE_ASYNC_LANES = 2 waits for the handle's stream
+ *   NDT_TUNE_LANE_FORK          0 (default): the further streams of NDT_TUNE_ASYNC_CHAINS >= 2 wait for the handle's stream
  *                               only where something other than such an alignment (a build, an update, a synchronous or
- *                               converged call, a tuning change) precedes a pair of them, and runs its alignments back
- *                               to back otherwise; 1: it waits for the head of its partner at every pair.  Other values:
+ *                               converged call, a tuning change) precedes a round of them, and run their alignments back
+ *                               to back otherwise; 1: each waits for the head of the round's first call at every round.  Other values:
  *                               NDT_ERR_INVALID_ARG.  Results are bit-identical either way.  ndt2d_set_tuning only
  *   NDT_TUNE_BATCH_SMALL_VARIANT (batch contexts) 1 (default): lidar-sized pairs run on the 256-thread
  *                               variant of the batch kernel first; 0: every pair on the 1024-thread one
@@ -527,7 +531,8 @@ enum {
   NDT_TUNE_ASYNC_LANES = 11,
   NDT_TUNE_MAP_MULTI_FROM = 12,
   NDT_TUNE_FUSED_BEGIN = 13,
-  NDT_TUNE_LANE_FORK = 14
+  NDT_TUNE_LANE_FORK = 14,
+  NDT_TUNE_ASYNC_CHAINS = 15
 };
 int32_t ndt2d_set_tuning(ndt2d_handle* h, int32_t knob, int64_t value);
 /* hipStream_t the handle enqueues on (as void*), for event timing by the caller */
@@ -539,8 +544,8 @@ void* ndt2d_stream(ndt2d_handle* h);
  * in producer_stream now (event record + stream wait: the host does not block; NULL = the legacy
  * default stream).  Call it before ndt2d_align_dev / ndt2d_align_dev_async whenever the source
  * arrays were written on a stream that has not been synchronised - ANY stream, the handle's own
- * (ndt2d_stream) included: an asynchronous fixed-iteration alignment may run on the handle's second
- * stream (NDT_TUNE_ASYNC_LANES), which is ordered behind the caller's work on ndt2d_stream only by
+ * (ndt2d_stream) included: an asynchronous fixed-iteration alignment may run on one of the handle's further
+ * streams (NDT_TUNE_ASYNC_CHAINS), which is ordered behind the caller's work on ndt2d_stream only by
  * ndt2d_wait_stream(h, ndt2d_stream(h)).
  * (ndt2d_set_target_dev and ndt2d_add_target_points_dev take the producer stream themselves.) */
 int32_t ndt2d_wait_stream(ndt2d_handle* h, void* producer_stream);

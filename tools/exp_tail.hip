@@ -7,9 +7,10 @@
 //           each; every 128-byte line still has writers on all eight XCDs
 //   xcd     EXP = 0:  packed, slot (b % 8) * 32 + b / 8, so that the eight writers of a 128-byte line sit on one XCD
 //           (the library)
-// Per form: us per launch of one chain and of two chains on two streams (alignments alternating between them), host
-// clock over CALLS alignments, REPEATS samples with the forms alternating inside every sample so that drift hits all
-// alike; median (min - max).  The final state of every form is printed as bits: they must be the same.
+// Per form: us per launch, in aggregate, of N = 1, 2, 3, 4, 6, 8 chains on N non-blocking streams (alignments enqueued
+// round-robin from one host thread), host clock over CALLS alignments, REPEATS samples with the forms alternating inside
+// every sample so that drift hits all alike; median (min - max).  The xcd column at N chains is the ceiling of a handle
+// with N launch chains.  The final state of every form is printed as bits: they must be the same.
 //   hipcc --offload-arch=gfx950 -O3 -fno-slp-vectorize -std=c++17 -Iinclude -Igtsam_ndt_amd/csrc -o tools/bin/exp_tail tools/exp_tail.hip
 #include <hip/hip_runtime.h>
 
@@ -29,7 +30,8 @@ using namespace ndt;
 #ifndef THR
 #define THR 256
 #endif
-constexpr int K = 30, CALLS = 100, REPEATS = 7, NFORM = 3;
+constexpr int K = 30, CALLS = 100, REPEATS = 7, NFORM = 3, NCOUNT = 6, kMaxChains = 8;
+constexpr int kChains[NCOUNT] = {1, 2, 3, 4, 6, 8};
 static const char* const kFormName[NFORM] = {"rows", "packed", "xcd"};
 
 struct Chain {
@@ -50,7 +52,7 @@ hipGraphExec_t capture(const Chain& c, const AlignStatic* d_st) {
   return ge;
 }
 
-// CALLS alignments over `lanes` chains, alternating; us per launch
+// CALLS alignments over `lanes` chains, round-robin; us per launch in aggregate
 double sample(Chain* ch, int lanes, int form, const float* sx, const float* sy, int n) {
   for (int l = 0; l < lanes; ++l) CK(hipStreamSynchronize(ch[l].st));
   const auto t0 = std::chrono::steady_clock::now();
@@ -92,9 +94,9 @@ int main(int argc, char** argv) {
   CK(hipMalloc(&g.rec, 2 * nc * sizeof(float4))); CK(hipMalloc(&g.acc, nc * sizeof(CellAcc)));
   CK(hipMemset(g.acc, 0, nc * sizeof(CellAcc)));
   int* d_cnt; CK(hipMalloc(&d_cnt, 8)); CK(hipMemset(d_cnt, 0, 8));
-  Chain ch[2];
+  Chain ch[kMaxChains];
   for (Chain& c : ch) {
-    CK(hipStreamCreate(&c.st));
+    CK(hipStreamCreateWithFlags(&c.st, hipStreamNonBlocking));
     CK(hipMalloc(&c.call, sizeof(AlignCall))); CK(hipMalloc(&c.dyn, sizeof(AlignDyn)));
     CK(hipMemset(c.dyn, 0, sizeof(AlignDyn)));
   }
@@ -115,18 +117,19 @@ int main(int argc, char** argv) {
     c.ge[1] = capture<32>(c, d_st);
     c.ge[2] = capture<0>(c, d_st);
   }
-  std::vector<double> us[2][NFORM];
+  std::vector<double> us[NCOUNT][NFORM];
   for (int rep = 0; rep <= REPEATS; ++rep)            // sample 0 is the warm-up
-    for (int lanes = 1; lanes <= 2; ++lanes)
+    for (int c = 0; c < NCOUNT; ++c)
       for (int f = 0; f < NFORM; ++f) {
-        const double v = sample(ch, lanes, f, dsx, dsy, n_s);
-        if (rep) us[lanes - 1][f].push_back(v);
+        const double v = sample(ch, kChains[c], f, dsx, dsy, n_s);
+        if (rep) us[c][f].push_back(v);
       }
-  for (int lanes = 1; lanes <= 2; ++lanes) {
+  for (int c = 0; c < NCOUNT; ++c) {
+    const int lanes = kChains[c];
     printf("thr %d n_src %d  %d chain%s, us per launch, median (min - max) of %d samples of %d alignments:", THR, n_s, lanes,
            lanes > 1 ? "s" : "", REPEATS, CALLS);
     for (int f = 0; f < NFORM; ++f) {
-      std::vector<double>& a = us[lanes - 1][f];
+      std::vector<double>& a = us[c][f];
       std::sort(a.begin(), a.end());
       printf("  %s %.3f (%.3f - %.3f)", kFormName[f], a[a.size() / 2], a.front(), a.back());
     }
