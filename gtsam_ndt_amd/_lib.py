@@ -195,6 +195,18 @@ SIGNATURES = {
     "ndt2d_search_scores_dev": (C.c_int32, [_vp, _vp, _vp, C.c_size_t, C.POINTER(SearchWindow2D), _vp]),
     "ndt2d_search_align_dev": (C.c_int32, [_vp, _vp, _vp, C.c_size_t, C.POINTER(SearchWindow2D), C.c_int32, _vp, _vp,
                                            C.POINTER(C.c_int32)]),
+    "ndt2d_score_poses_dev": (C.c_int32, [_vp, _vp, _vp, C.c_size_t, _vp, C.c_size_t, _vp]),
+    "ndt2d_score_poses": (C.c_int32, [_vp, _vp, _vp, C.c_size_t, _vp, C.c_size_t, _vp]),
+    "ndt2d_best_poses_dev": (C.c_int32, [_vp, _vp, _vp, C.c_size_t, _vp, C.c_size_t, C.c_double, C.c_double, C.c_int32, _vp,
+                                         C.POINTER(C.c_int32)]),
+    "ndt2d_best_poses_align_dev": (C.c_int32, [_vp, _vp, _vp, C.c_size_t, _vp, C.c_size_t, C.c_double, C.c_double, C.c_int32,
+                                               _vp, _vp, C.POINTER(C.c_int32)]),
+    "ndt3d_score_poses_dev": (C.c_int32, [_vp, _vp, _vp, _vp, C.c_size_t, _vp, C.c_size_t, _vp]),
+    "ndt3d_score_poses": (C.c_int32, [_vp, _vp, _vp, _vp, C.c_size_t, _vp, C.c_size_t, _vp]),
+    "ndt3d_best_poses_dev": (C.c_int32, [_vp, _vp, _vp, _vp, C.c_size_t, _vp, C.c_size_t, C.c_double, C.c_double, C.c_int32,
+                                         _vp, C.POINTER(C.c_int32)]),
+    "ndt3d_best_poses_align_dev": (C.c_int32, [_vp, _vp, _vp, _vp, C.c_size_t, _vp, C.c_size_t, C.c_double, C.c_double,
+                                               C.c_int32, _vp, _vp, C.POINTER(C.c_int32)]),
     "ndt2d_evaluate_map": (C.c_int32, [_vp, _vp, _dp, C.POINTER(Eval2D)]),
     "ndt2d_align_map": (C.c_int32, [_vp, _vp, _dp, C.POINTER(Result2D)]),
     "ndt2d_align_map_multi": (C.c_int32, [_vp, _vp, _vp, C.c_int32, _vp]),

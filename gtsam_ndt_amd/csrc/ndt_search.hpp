@@ -193,10 +193,14 @@ struct SearchScratch {
   SearchSel* d_sel = nullptr;                                     // selection state and shortlist
   unsigned char* h_axes = nullptr; size_t h_axes_cap = 0;         // pinned: the axes' upload
   SearchSel* h_sel = nullptr;                                     // pinned: the shortlist's read-back
+  // a pose list (ndt_score_poses.hpp): d_vol holds its scores, d_keys its candidates' keys
+  double* d_list = nullptr; size_t list_cap = 0;                  // a host list's upload (doubles)
+  double* d_pick = nullptr;                                       // the shortlisted poses [kSearchShortlist][6]
+  double* h_pick = nullptr;                                       // pinned: their read-back
   void release() {
-    void* dev[] = {d_vol, d_keys, d_axes, d_sel};
+    void* dev[] = {d_vol, d_keys, d_axes, d_sel, d_list, d_pick};
     for (void* p : dev) if (p) (void)hipFree(p);
-    void* host[] = {h_axes, h_sel};
+    void* host[] = {h_axes, h_sel, h_pick};
     for (void* p : host) if (p) (void)hipHostFree(p);
     *this = SearchScratch{};
   }
@@ -347,6 +351,31 @@ int32_t search_volume(ndt::SearchScratch& s, size_t N, float* d_scores, float** 
   return NDT_OK;
 }
 
+// The selection of a search or of a pose list (ndt_score_poses.hpp) in two halves round the caller's key kernel.
+// First: room for `cap` keys and the selection state, cleared (enqueued on `stream`).
+int32_t search_keys_begin(ndt::SearchScratch& s, hipStream_t stream, size_t cap) {
+  using namespace ndt;
+  HIP_TRY(grow(&s.d_keys, &s.keys_cap, cap, cap + cap / 4));
+  if (!s.d_sel) HIP_TRY(hipMalloc((void**)&s.d_sel, sizeof(SearchSel)));
+  if (!s.h_sel) HIP_TRY(pinned_alloc(&s.h_sel, sizeof(SearchSel)));
+  hipLaunchKernelGGL(k_search_sel_clear, dim3(1), dim3(256), 0, stream, s.d_sel);
+  return NDT_OK;
+}
+
+// Then: the keys appended since (at most cap) -> the shortlist in s.d_sel, sorted (enqueued on `stream`).
+void search_keys_shortlist(ndt::SearchScratch& s, hipStream_t stream, size_t cap) {
+  using namespace ndt;
+  SearchSel* sel = s.d_sel;
+  const unsigned hb = (unsigned)std::min<size_t>(std::max<size_t>((cap + 255) / 256, 1), 1024);
+  hipLaunchKernelGGL(k_search_sel_begin, dim3(1), dim3(64), 0, stream, sel, (unsigned)cap);
+  for (int p = 0; p < 8; ++p) {
+    hipLaunchKernelGGL(k_search_sel_hist, dim3(hb), dim3(256), 0, stream, (const unsigned long long*)s.d_keys, sel, p);
+    hipLaunchKernelGGL(k_search_sel_pick, dim3(1), dim3(64), 0, stream, sel, p);
+  }
+  hipLaunchKernelGGL(k_search_collect, dim3(hb), dim3(256), 0, stream, (const unsigned long long*)s.d_keys, sel);
+  hipLaunchKernelGGL(k_search_sort, dim3(1), dim3(kSearchSortThreads), 0, stream, sel);
+}
+
 // Peaks of the volume -> shortlist -> the host's walk: hits[0 .. *n_hits), best first.  Synchronous.
 int32_t search_select(ndt::SearchScratch& s, hipStream_t stream, const float* vol, const SearchPlan& plan, const SearchWindow& w,
                       int32_t k, SearchPeak* hits, int32_t* n_hits) {
@@ -355,21 +384,11 @@ int32_t search_select(ndt::SearchScratch& s, hipStream_t stream, const float* vo
   const size_t N = plan.poses();
   // peaks: at most one in every 2 x 2 x 2 block of the lattice (two neighbours cannot both beat each other)
   const size_t cap = (size_t)((L.nx + 1) / 2) * ((L.ny + 1) / 2) * ((L.nt + 1) / 2);
-  HIP_TRY(grow(&s.d_keys, &s.keys_cap, cap, cap + cap / 4));
-  if (!s.d_sel) HIP_TRY(hipMalloc((void**)&s.d_sel, sizeof(SearchSel)));
-  if (!s.h_sel) HIP_TRY(pinned_alloc(&s.h_sel, sizeof(SearchSel)));
+  { const int32_t bs = search_keys_begin(s, stream, cap); if (bs != NDT_OK) return bs; }
   SearchSel* sel = s.d_sel;
-  const unsigned hb = (unsigned)std::min<size_t>(std::max<size_t>((cap + 255) / 256, 1), 1024);
-  hipLaunchKernelGGL(k_search_sel_clear, dim3(1), dim3(256), 0, stream, sel);
   hipLaunchKernelGGL(k_search_peaks, dim3((unsigned)((N + 255) / 256)), dim3(256), 0, stream, vol, L.nx, L.ny, L.nt, L.cyclic ? 1 : 0,
                      s.d_keys, (unsigned)cap, sel);
-  hipLaunchKernelGGL(k_search_sel_begin, dim3(1), dim3(64), 0, stream, sel, (unsigned)cap);
-  for (int p = 0; p < 8; ++p) {
-    hipLaunchKernelGGL(k_search_sel_hist, dim3(hb), dim3(256), 0, stream, (const unsigned long long*)s.d_keys, sel, p);
-    hipLaunchKernelGGL(k_search_sel_pick, dim3(1), dim3(64), 0, stream, sel, p);
-  }
-  hipLaunchKernelGGL(k_search_collect, dim3(hb), dim3(256), 0, stream, (const unsigned long long*)s.d_keys, sel);
-  hipLaunchKernelGGL(k_search_sort, dim3(1), dim3(kSearchSortThreads), 0, stream, sel);
+  search_keys_shortlist(s, stream, cap);
   HIP_TRY(hipGetLastError());
   HIP_TRY(hipMemcpyAsync(s.h_sel, sel, sizeof(SearchSel), hipMemcpyDeviceToHost, stream));
   HIP_TRY(hipStreamSynchronize(stream));

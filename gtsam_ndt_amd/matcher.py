@@ -600,6 +600,50 @@ class _NdtMatcher(_Handle):
                     "search_align_dev")
         return list(zip(_hits(hits, nh.value), [self._dim.result(r) for r in res[:nh.value]]))
 
+    # ---- the score at a list of poses (ndt2d/ndt3d_score_poses*, _best_poses*; search.select_best restates the hits)
+    def _pose_list(self, poses, device):
+        """The list as a contiguous float64 CUDA tensor [m, 3 | 6] on `device` (a numpy list is uploaded)."""
+        import torch
+        if not _is_dev(poses):
+            poses = torch.from_numpy(self._dim.poses(poses)).to(device)
+        if not (poses.is_cuda and poses.dtype == torch.float64 and poses.is_contiguous() and poses.dim() == 2
+                and poses.shape[1] == self._dim.npose):
+            raise ValueError(f"poses must be a contiguous float64 CUDA tensor [m, {self._dim.npose}]")
+        return poses
+
+    def _score_poses(self, coords, poses):
+        if _is_dev(coords[0]) != _is_dev(poses):
+            raise ValueError("the scan and the poses must both be CUDA tensors or both be host arrays")
+        if _is_dev(poses):
+            import torch
+            poses = self._pose_list(poses, coords[0].device)
+            n, m = coords[0].numel(), poses.shape[0]
+            out = torch.empty(m, dtype=torch.float32, device=poses.device)
+            self.wait_stream()
+            self._check(self._c.score_poses_dev(self._h, *_dev_ptrs(coords, n), n, poses.data_ptr(), m, out.data_ptr()),
+                        "score_poses_dev")
+            return out
+        a, p = _host_coords(coords), self._dim.poses(poses)
+        out = np.empty(p.shape[0], dtype=np.float32)
+        self._check(self._c.score_poses(self._h, *[c.ctypes.data for c in a], a[0].size, p.ctypes.data, p.shape[0],
+                                        out.ctypes.data), "score_poses")
+        return out
+
+    def _best_poses(self, coords, poses, k, min_sep, align: bool):
+        coords = self._on_device(coords)
+        poses = self._pose_list(poses, coords[0].device)
+        self.wait_stream()
+        n, m = coords[0].numel(), poses.shape[0]
+        hits, nh = self._hit_rows(k), C.c_int32(0)
+        args = (self._h, *_dev_ptrs(coords, n), n, poses.data_ptr(), m, float(min_sep[0]), float(min_sep[1]), int(k),
+                C.cast(hits, C.c_void_p))
+        if not align:
+            self._check(self._c.best_poses_dev(*args, C.byref(nh)), "best_poses_dev")
+            return _hits(hits, nh.value)
+        res = (self._dim.Result * max(int(k), 1))()
+        self._check(self._c.best_poses_align_dev(*args, C.cast(res, C.c_void_p), C.byref(nh)), "best_poses_align_dev")
+        return list(zip(_hits(hits, nh.value), [self._dim.result(r) for r in res[:nh.value]]))
+
     # ---- the same search for map-to-map alignment: `source`'s component list instead of a scan
     def search_map(self, source, center, half_extent, step, k: int = 8, min_sep=(0.5, 0.1)):
         """The best k (1..64) well-separated peaks of the map-to-map score (evaluate_map's) over the lattice of the
@@ -719,6 +763,26 @@ class NdtMatcher2D(_NdtMatcher):
         (SearchHit, AlignResult), best lattice score first."""
         return self._search_align((sx, sy), center, half_extent, step, k, min_sep)
 
+    def score_poses(self, sx, sy, poses):
+        """The NDT score of the scan at every pose of a list [m, 3] of (x, y, theta), in one launch
+        (ndt2d_score_poses*): the weights of a particle filter's particles.  CUDA tensors (float32 scan, float64
+        poses) return a float32 CUDA tensor [m]; numpy arrays return a numpy array through the host form; the scan and
+        the poses must be of the same kind (ValueError otherwise: the result's kind would be a guess).  A pose with a
+        non-finite coordinate scores 0."""
+        return self._score_poses((sx, sy), poses)
+
+    def best_poses(self, sx, sy, poses, k: int = 8, min_sep=(0.5, 0.1)):
+        """The best k (1..64) well-separated poses of the list by score (ndt2d_best_poses_dev; search.select_best
+        restates the rule): a list of SearchHit, best first, whose index is the pose's position in the list.  The hits
+        are host objects either way, so the scan and the poses may each be numpy arrays or CUDA tensors: what is on the
+        host is uploaded."""
+        return self._best_poses((sx, sy), poses, k, min_sep, False)
+
+    def best_poses_align(self, sx, sy, poses, k: int = 8, min_sep=(0.5, 0.1)):
+        """best_poses(), then align_multi_start() from the hits' poses (ndt2d_best_poses_align_dev): a list of
+        (SearchHit, AlignResult), best list score first.  Inputs as best_poses."""
+        return self._best_poses((sx, sy), poses, k, min_sep, True)
+
 
 class NdtMatcher3D(_NdtMatcher):
     """3D SE(3) variant (BASELINE config 5); mirrors ndt3d_* of include/ndt_hip.h."""
@@ -804,6 +868,23 @@ class NdtMatcher3D(_NdtMatcher):
         """search(), then align_multi_start() from the hits' poses (ndt3d_search_align_dev): a list of
         (SearchHit, AlignResult3D), best lattice score first."""
         return self._search_align((sx, sy, sz), center, half_extent, step, k, min_sep)
+
+    def score_poses(self, sx, sy, sz, poses):
+        """The NDT score of the scan at every pose of a list [m, 6] of (tx, ty, tz, roll, pitch, yaw), in one launch
+        (ndt3d_score_poses*), as NdtMatcher2D.score_poses: all six coordinates are free, so the list covers what the
+        lattice search pins."""
+        return self._score_poses((sx, sy, sz), poses)
+
+    def best_poses(self, sx, sy, sz, poses, k: int = 8, min_sep=(0.5, 0.1)):
+        """The best k (1..64) well-separated poses of the list (ndt3d_best_poses_dev): translation distance over
+        (x, y, z), rotation distance the largest wrapped difference of roll, pitch and yaw.  Inputs as
+        NdtMatcher2D.best_poses: host arrays are uploaded, where score_poses wants both of one kind."""
+        return self._best_poses((sx, sy, sz), poses, k, min_sep, False)
+
+    def best_poses_align(self, sx, sy, sz, poses, k: int = 8, min_sep=(0.5, 0.1)):
+        """best_poses(), then align_multi_start() from the hits' poses (ndt3d_best_poses_align_dev): a list of
+        (SearchHit, AlignResult3D)."""
+        return self._best_poses((sx, sy, sz), poses, k, min_sep, True)
 
 
 def pyramid_params(fine: L.Params2D | None = None, **overrides):

@@ -1,6 +1,7 @@
 """Host restatement of the exhaustive pose searches (docs/ALGORITHM.md "Exhaustive pose search" and "Exhaustive 3D pose
 search"), in the spirit of synth.scan_points: the lattice of a window and the peak / separation rules, in numpy.  It is
-the specification the tests hold ndt2d_search_* and ndt3d_search_* to; nothing on the GPU path calls it.
+the specification the tests hold ndt2d_search_* and ndt3d_search_* to; nothing on the GPU path calls it.  select_best
+is the same for the hits of a scored pose list (ndt2d_best_poses_dev, ndt3d_best_poses_dev).
 
 A window is (center, half_extent, step); ``Window`` names the three.  2D: each an (x, y, theta) triple.  3D: the
 centre is a 6-vector (tx, ty, tz, roll, pitch, yaw) whose indices 0, 1, 5 are searched (half_extent and step stay
@@ -157,4 +158,43 @@ def select_hits(volume, window, k: int = 8, min_sep=(0.5, 0.1)):
                 break
         if keep:
             hits.append(SearchHit(p if pinned is None else (p[0], p[1], *pinned, p[2]), float(v.reshape(-1)[q]), q))
+    return hits
+
+
+def select_best(scores, poses, k: int = 8, min_sep=(0.5, 0.1)):
+    """The hits of a scored pose list (docs/ALGORITHM.md "Scoring a list of poses"; ndt2d/ndt3d_best_poses_dev):
+    scores [m] float32, poses [m, 3] = (x, y, theta) or [m, 6] = (tx, ty, tz, roll, pitch, yaw).  Candidates are the
+    poses with score > 0; the best min(#candidates, 4096) by (score desc, index asc) are walked in that order, each
+    accepted unless an accepted hit lies closer than min_sep[0] in translation (Euclidean over x, y, and z in 3D) AND
+    closer than min_sep[1] in rotation (the wrapped heading difference; in 3D the largest of the wrapped roll, pitch and
+    yaw differences), both strictly; at most k.  A list of SearchHit whose pose is the list's row, not wrapped."""
+    v = np.asarray(scores, dtype=np.float32).reshape(-1)
+    p = np.asarray(poses, dtype=np.float64)
+    if p.ndim != 2 or p.shape[1] not in (3, 6) or p.shape[0] != v.size:
+        raise ValueError("poses is [m, 3] or [m, 6] with one row per score")
+    nt = 2 if p.shape[1] == 3 else 3
+    cand = np.flatnonzero(v > 0)
+    order = np.lexsort((cand, -v[cand]))[:SHORTLIST]
+    st, sr = float(min_sep[0]), float(min_sep[1])
+    st2 = st * st
+    hits = []
+    for q in cand[order]:
+        if len(hits) >= k:
+            break
+        q = int(q)
+        row = tuple(float(c) for c in p[q])
+        keep = True
+        for hh in hits:
+            d2 = 0.0
+            for a in range(nt):
+                d = row[a] - hh.pose[a]
+                d2 = d2 + d * d
+            dr = 0.0
+            for a in range(nt, len(row)):
+                dr = max(dr, abs(float(wrap(row[a] - hh.pose[a]))))
+            if d2 < st2 and dr < sr:
+                keep = False
+                break
+        if keep:
+            hits.append(SearchHit(row, float(v[q]), q))
     return hits

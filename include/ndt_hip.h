@@ -409,6 +409,48 @@ int32_t ndt2d_search_scores_dev(ndt2d_handle* h, const float* d_sx, const float*
 int32_t ndt2d_search_align_dev(ndt2d_handle* h, const float* d_sx, const float* d_sy, size_t n,
                                const ndt2d_search_window* w, int32_t k, ndt2d_search_hit* hits,
                                ndt2d_result* results, int32_t* n_hits);
+/* Scoring a list of poses (docs/ALGORITHM.md "Scoring a list of poses"): the NDT score of the scan at every pose of a
+ * list of any shape, in one launch - the weights of a particle filter's particles (NDT-MCL), relocalisation from outside
+ * hypotheses, the samples of a caller's own search.  poses is [m][3] = (x, y, theta) in double; theta need not be wrapped.
+ * Score: scores[i] is the score ndt2d_evaluate_dev reports for the scan at poses[3i .. 3i+2] - per point the float32
+ * operations of the single-pose path, summed in another order, the contract of ndt2d_search_scores_dev: the heading is
+ * wrapped, its cos / sin taken in double and rounded to float32, the translation is the float of the double, the cell
+ * key is clamped onto the grid's empty ring, and overlap_grids = 4 is honoured (four lookups per point).  NaN points of
+ * the scan add nothing.  A pose with a non-finite coordinate scores exactly +0.0f (a device list cannot be validated on
+ * the host, and 0 is the weight a particle filter wants for it) and never becomes a hit.  So does a finite pose whose
+ * float32 form is not finite: a translation beyond float32's range, an angle so large that wrapping leaves no finite sine
+ * and cosine (in 3D: a non-finite entry of R).  No pose of a list gives a NaN score.
+ * Bitwise: a pose's score depends on nothing but the handle's grid, the scan and that pose - not on its position in the
+ * list, nor on the rest of the list - and two calls give the same bits.  A list that holds the lattice of a search window
+ * in flat index order, with the axes' doubles of that lattice, gives the volume of ndt2d_search_scores_dev bit for bit
+ * (every pose is summed in the search kernel's order).
+ * Best poses: candidates are the poses with score > 0; the best min(#candidates, 4096) by (score descending, index
+ * ascending) are walked in that order; a candidate is dropped when an accepted hit lies closer than min_sep_trans in
+ * translation (Euclidean over x, y) AND closer than min_sep_rot in rotation (|wrap(dtheta)|), both strictly; at most k
+ * (1..64) hits.  hits[q].pose is the list's pose at hits[q].index bit for bit (not wrapped), hits[q].score its float32
+ * score.  Deterministic to the bit.  A list without a positive score gives NDT_OK and *n_hits = 0.
+ * ndt2d_best_poses_align_dev then refines the hits in one ndt2d_align_multi_start_dev call: results[q] is bit for bit
+ * what that call returns for the hits' poses; nothing is launched for zero hits.
+ * Streams and state: as ndt2d_search_scores_dev - on the handle's stream, behind an asynchronous alignment in flight
+ * (which is finished first), returning once the outputs are complete; producers of the scan and of the list are ordered
+ * by ndt2d_wait_stream.  The handle's grid, parameters and later alignments are untouched.
+ * Errors, found before any device call: a null handle, scan, list or output, n = 0 or above what an alignment takes,
+ * m = 0, k outside 1..64, a separation that is NaN, infinite or negative: NDT_ERR_INVALID_ARG; m > 2^25:
+ * NDT_ERR_CAPACITY (the search's cap: index and key share 32 bits); no grid: NDT_ERR_NO_TARGET.  A grid without a valid
+ * cell is no error: every score is 0. */
+int32_t ndt2d_score_poses_dev(ndt2d_handle* h, const float* d_sx, const float* d_sy, size_t n,
+                              const double* d_poses /* device, [m][3] */, size_t m, float* d_scores /* device, [m] */);
+/* the same with a host scan, a host list and host scores (staged through the handle's scratch) */
+int32_t ndt2d_score_poses(ndt2d_handle* h, const float* sx, const float* sy, size_t n,
+                          const double* poses, size_t m, float* scores);
+/* hits[0 .. *n_hits) (hits has room for k), best first.  Synchronous in the hits (host memory). */
+int32_t ndt2d_best_poses_dev(ndt2d_handle* h, const float* d_sx, const float* d_sy, size_t n, const double* d_poses,
+                             size_t m, double min_sep_trans, double min_sep_rot, int32_t k, ndt2d_search_hit* hits,
+                             int32_t* n_hits);
+/* ndt2d_best_poses_dev, then ndt2d_align_multi_start_dev from the hits' poses (results has room for k) */
+int32_t ndt2d_best_poses_align_dev(ndt2d_handle* h, const float* d_sx, const float* d_sy, size_t n,
+                                   const double* d_poses, size_t m, double min_sep_trans, double min_sep_rot, int32_t k,
+                                   ndt2d_search_hit* hits, ndt2d_result* results, int32_t* n_hits);
 /* ---- map-to-map alignment (distribution-to-distribution NDT; docs/ALGORITHM.md section 2.13) ----------------
  * Aligns the cached grid of `source` to the cached grid of `target` without any of the points either was built from:
  * what a handle keeps after ndt2d_add_target_points_dev, and all that ndt2d_save_map / ndt2d_load_map persist, is
@@ -837,6 +879,27 @@ int32_t ndt3d_search_scores_dev(ndt3d_handle* h, const float* d_sx, const float*
 int32_t ndt3d_search_align_dev(ndt3d_handle* h, const float* d_sx, const float* d_sy, const float* d_sz, size_t n,
                                const ndt3d_search_window* w, int32_t k, ndt3d_search_hit* hits,
                                ndt3d_result* results, int32_t* n_hits);
+/* Scoring a list of 3D poses (docs/ALGORITHM.md "Scoring a list of poses"), the twin of ndt2d_score_poses*: poses is
+ * [m][6] = (tx, ty, tz, roll, pitch, yaw) in double, so the list also covers what the lattice pins - a search over z,
+ * roll or pitch is a list.  scores[i] is the score ndt3d_evaluate_dev reports at poses[6i .. 6i+5]: the three angles
+ * wrapped, the nine products of the rotation in double and rounded to float32, the nested-fma image, the inside test
+ * 0 <= f < extent and the score term of the single-pose path, summed in another order.  NaN points add nothing; a
+ * non-finite pose scores exactly +0.0f and never becomes a hit.  The bitwise properties are those of the 2D calls; the
+ * lattice of an ndt3d_search_window is the list (x, y, center[2], center[3], center[4], yaw) in flat index order, and
+ * then the scores are the volume of ndt3d_search_scores_dev bit for bit.  Best poses: as in 2D, with the translation
+ * distance Euclidean over (x, y, z) and the rotation distance the largest of the wrapped |droll|, |dpitch|, |dyaw|.
+ * ndt3d_best_poses_align_dev refines the hits in one ndt3d_align_multi_start_dev call.  Streams, state and errors are
+ * those of the 2D calls (ndt3d_wait_stream orders the producers). */
+int32_t ndt3d_score_poses_dev(ndt3d_handle* h, const float* d_sx, const float* d_sy, const float* d_sz, size_t n,
+                              const double* d_poses /* device, [m][6] */, size_t m, float* d_scores /* device, [m] */);
+int32_t ndt3d_score_poses(ndt3d_handle* h, const float* sx, const float* sy, const float* sz, size_t n,
+                          const double* poses, size_t m, float* scores);
+int32_t ndt3d_best_poses_dev(ndt3d_handle* h, const float* d_sx, const float* d_sy, const float* d_sz, size_t n,
+                             const double* d_poses, size_t m, double min_sep_trans, double min_sep_rot, int32_t k,
+                             ndt3d_search_hit* hits, int32_t* n_hits);
+int32_t ndt3d_best_poses_align_dev(ndt3d_handle* h, const float* d_sx, const float* d_sy, const float* d_sz, size_t n,
+                                   const double* d_poses, size_t m, double min_sep_trans, double min_sep_rot, int32_t k,
+                                   ndt3d_search_hit* hits, ndt3d_result* results, int32_t* n_hits);
 /* Per-iteration trace, as ndt2d_align_trace (debugging and stage-by-stage parity checks; never on a timed path):
  * rows[j], j < *n_rows <= capacity, is the state after j + 1 updates - the pose after them, H / g / score / n_hit
  * of the evaluation that produced the (j+1)-th update.  out (may be NULL): the final result.  Host arrays. */

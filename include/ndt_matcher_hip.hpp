@@ -253,6 +253,41 @@ class NdtMatcherHip {
     for (int32_t i = 0; i < n_hits; ++i) out.push_back(SearchMatch{to_search_hit(hits[i]), to_match_result(r[i], mode_)});
     return out;
   }
+  // The score at every pose of a list in one launch (ndt2d_score_poses_dev; contract: ndt_hip.h): d_poses is [m][3] =
+  // (x, y, theta) in double, d_scores [m] floats, both device memory - the weights of a particle filter's particles.  A
+  // non-finite pose scores 0.  producer_stream: the stream that wrote the scan and the list.
+  void scorePosesDev(const float* d_sx, const float* d_sy, size_t n, const double* d_poses, size_t m, float* d_scores,
+                     void* producer_stream, bool complete = false) {
+    if (!complete) check(ndt2d_wait_stream(h_, producer_stream), "ndt2d_wait_stream");
+    check(ndt2d_score_poses_dev(h_, d_sx, d_sy, n, d_poses, m, d_scores), "ndt2d_score_poses_dev");
+  }
+  // the best k (1..64) well-separated poses of the list, best first (ndt2d_best_poses_dev): hit.index is the position in
+  // the list, hit.pose the list's pose as it stands there
+  std::vector<SearchHit> bestPosesDev(const float* d_sx, const float* d_sy, size_t n, const double* d_poses, size_t m, int k,
+                                      double min_sep_trans, double min_sep_rot, void* producer_stream, bool complete = false) {
+    if (!complete) check(ndt2d_wait_stream(h_, producer_stream), "ndt2d_wait_stream");
+    std::vector<ndt2d_search_hit> hits(k > 0 ? (size_t)k : 1);
+    int32_t n_hits = 0;
+    check(ndt2d_best_poses_dev(h_, d_sx, d_sy, n, d_poses, m, min_sep_trans, min_sep_rot, (int32_t)k, hits.data(), &n_hits),
+          "ndt2d_best_poses_dev");
+    std::vector<SearchHit> out;
+    for (int32_t i = 0; i < n_hits; ++i) out.push_back(to_search_hit(hits[i]));
+    return out;
+  }
+  // bestPosesDev, then one alignment from every hit in one launch chain (ndt2d_best_poses_align_dev)
+  std::vector<SearchMatch> bestPosesAlignDev(const float* d_sx, const float* d_sy, size_t n, const double* d_poses, size_t m,
+                                             int k, double min_sep_trans, double min_sep_rot, void* producer_stream,
+                                             bool complete = false) {
+    if (!complete) check(ndt2d_wait_stream(h_, producer_stream), "ndt2d_wait_stream");
+    std::vector<ndt2d_search_hit> hits(k > 0 ? (size_t)k : 1);
+    std::vector<ndt2d_result> r(hits.size());
+    int32_t n_hits = 0;
+    check(ndt2d_best_poses_align_dev(h_, d_sx, d_sy, n, d_poses, m, min_sep_trans, min_sep_rot, (int32_t)k, hits.data(), r.data(),
+                                     &n_hits), "ndt2d_best_poses_align_dev");
+    std::vector<SearchMatch> out;
+    for (int32_t i = 0; i < n_hits; ++i) out.push_back(SearchMatch{to_search_hit(hits[i]), to_match_result(r[i], mode_)});
+    return out;
+  }
   static SearchHit to_search_hit(const ndt2d_search_hit& h) {
     SearchHit s;
     s.pose = {h.pose[0], h.pose[1], h.pose[2]};
@@ -777,6 +812,41 @@ class NdtMatcherHip3 {
     int32_t n_hits = 0;
     check(ndt3d_search_align_dev(h_, d_sx, d_sy, d_sz, n, &window, (int32_t)k, hits.data(), r.data(), &n_hits),
           "ndt3d_search_align_dev");
+    std::vector<SearchMatch> out;
+    for (int32_t i = 0; i < n_hits; ++i) out.push_back(SearchMatch{toSearchHit(hits[i]), toMatchResult(r[i])});
+    return out;
+  }
+  // The score at every pose of a list in one launch (ndt3d_score_poses_dev), as NdtMatcherHip::scorePosesDev: d_poses is
+  // [m][6] = (tx, ty, tz, roll, pitch, yaw) in double, all six free - a search over z, roll or pitch is a list.
+  void scorePosesDev(const float* d_sx, const float* d_sy, const float* d_sz, size_t n, const double* d_poses, size_t m,
+                     float* d_scores, void* producer_stream, bool complete = false) {
+    if (!complete) check(ndt3d_wait_stream(h_, producer_stream), "ndt3d_wait_stream");
+    check(ndt3d_score_poses_dev(h_, d_sx, d_sy, d_sz, n, d_poses, m, d_scores), "ndt3d_score_poses_dev");
+  }
+  // the best k (1..64) well-separated poses of the list (ndt3d_best_poses_dev): translation distance over (x, y, z),
+  // rotation distance the largest wrapped difference of roll, pitch and yaw
+  std::vector<SearchHit> bestPosesDev(const float* d_sx, const float* d_sy, const float* d_sz, size_t n, const double* d_poses,
+                                      size_t m, int k, double min_sep_trans, double min_sep_rot, void* producer_stream,
+                                      bool complete = false) {
+    if (!complete) check(ndt3d_wait_stream(h_, producer_stream), "ndt3d_wait_stream");
+    std::vector<ndt3d_search_hit> hits(k > 0 ? (size_t)k : 1);
+    int32_t n_hits = 0;
+    check(ndt3d_best_poses_dev(h_, d_sx, d_sy, d_sz, n, d_poses, m, min_sep_trans, min_sep_rot, (int32_t)k, hits.data(), &n_hits),
+          "ndt3d_best_poses_dev");
+    std::vector<SearchHit> out;
+    for (int32_t i = 0; i < n_hits; ++i) out.push_back(toSearchHit(hits[i]));
+    return out;
+  }
+  // bestPosesDev, then one alignment from every hit in one launch chain (ndt3d_best_poses_align_dev)
+  std::vector<SearchMatch> bestPosesAlignDev(const float* d_sx, const float* d_sy, const float* d_sz, size_t n,
+                                             const double* d_poses, size_t m, int k, double min_sep_trans, double min_sep_rot,
+                                             void* producer_stream, bool complete = false) {
+    if (!complete) check(ndt3d_wait_stream(h_, producer_stream), "ndt3d_wait_stream");
+    std::vector<ndt3d_search_hit> hits(k > 0 ? (size_t)k : 1);
+    std::vector<ndt3d_result> r(hits.size());
+    int32_t n_hits = 0;
+    check(ndt3d_best_poses_align_dev(h_, d_sx, d_sy, d_sz, n, d_poses, m, min_sep_trans, min_sep_rot, (int32_t)k, hits.data(),
+                                     r.data(), &n_hits), "ndt3d_best_poses_align_dev");
     std::vector<SearchMatch> out;
     for (int32_t i = 0; i < n_hits; ++i) out.push_back(SearchMatch{toSearchHit(hits[i]), toMatchResult(r[i])});
     return out;
