@@ -189,6 +189,35 @@ __device__ __forceinline__ void accumulate_component(const PoseF& P, const RotF&
   acc.n_wave += (int)__popcll(__ballot(hit));
 }
 
+// Body of a map-to-map launch for one alignment, shared by k_iterate_d2d and the multi-start chain (k_multi_body_d2d):
+// this workgroup's components (thread -> component assignment i, i + stride, ...; the first one already loaded into ca0,
+// cb0) under the pose P, the thread's sums into acc[kNumAcc].  No __restrict__, the first component by const reference:
+// the parameter shape that leaves both kernels the registers and instruction counts they had (Shared pieces).
+template <int MODE>
+__device__ __forceinline__ void evaluate_components(const PoseF& P, float d2, const float4* comp, const float4* cov, int n, int i,
+                                                    int stride, const float4& ca0, const float4& cb0, float* acc) {
+  float4 ca = ca0, cb = cb0;
+  RotF R;
+  R.c2t = P.cs * P.cs - P.sn * P.sn;
+  R.s2t = 2.f * P.cs * P.sn;
+  Acc2D A;
+  acc_zero(A);
+  while (i < n) {
+    const int i2 = i + stride;
+    float4 na = make_float4(0.f, 0.f, 0.f, 0.f), nb = na;
+    if (i2 < n) { na = comp[2 * (size_t)i2]; nb = comp[2 * (size_t)i2 + 1]; }
+    PointRec r;
+    image_point(P, ca.x, ca.y, r);
+    const int key = image_key(P, P.ox, P.oy, r, true);       // clamped onto the grid: every key is a cell of `cov`
+    r.A = cov[2 * key];
+    r.B = cov[2 * key + 1];
+    accumulate_component<MODE>(P, R, r, ca.z, ca.w, cb.y, A);
+    ca = na; cb = nb; i = i2;
+  }
+  acc_store(A, d2, acc);
+  acc[11] = 0.f;
+}
+
 // Launch k (parity = k & 1) consumes state[parity^1] / partials[parity^1] of launch k-1 and produces state[parity] /
 // partials[parity]: k_iterate's chain, state, flags and reduction (the shared pieces of ndt_chain.hpp and
 // ndt2d_kernels.hpp), with call->blocks workgroups of kBlock threads
@@ -256,31 +285,13 @@ __global__ __launch_bounds__(kBlock) void k_iterate_d2d(const AlignStatic* __res
     copy_state(cur, prev, 1);
   }
 
-  // ---- body: per-component terms at `pose`
+  // ---- body: per-component terms at `pose` (evaluate_components)
   double sn_d, cs_d;
   sincos_wrapped(pose[2], &sn_d, &cs_d);
   const PoseF P = make_pose((float)cs_d, (float)sn_d, (float)pose[0], (float)pose[1], G.ox, G.oy, G.inv_c, G.W, G.H,
                             prm.d1, prm.d2);
-  RotF R;
-  R.c2t = P.cs * P.cs - P.sn * P.sn;
-  R.s2t = 2.f * P.cs * P.sn;
-  Acc2D A;
-  acc_zero(A);
-  while (i < n) {
-    const int i2 = i + stride;
-    float4 na = make_float4(0.f, 0.f, 0.f, 0.f), nb = na;
-    if (i2 < n) { na = comp[2 * (size_t)i2]; nb = comp[2 * (size_t)i2 + 1]; }
-    PointRec r;
-    image_point(P, ca.x, ca.y, r);
-    const int key = image_key(P, P.ox, P.oy, r, true);       // clamped onto the grid: every key is a cell of `cov`
-    r.A = cov[2 * key];
-    r.B = cov[2 * key + 1];
-    accumulate_component<MODE>(P, R, r, ca.z, ca.w, cb.y, A);
-    ca = na; cb = nb; i = i2;
-  }
   float acc[kNumAcc];
-  acc_store(A, prm.d2, acc);
-  acc[11] = 0.f;
+  evaluate_components<MODE>(P, prm.d2, comp, cov, n, i, stride, ca, cb, acc);
 
   // ---- epilogue: wave tree -> LDS -> one partial column entry per sum
   {

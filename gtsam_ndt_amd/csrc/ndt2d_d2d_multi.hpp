@@ -6,11 +6,13 @@
 // iteration of every start - the split chain of ndt2d_multi_start.hpp with another evaluation kernel:
 //   k_begin_d2d_multi   per-call part of the context (the twin of k_begin_multi)
 //   k_multi_solve       unchanged: one workgroup per start folds that start's partial rows and updates its state
-//   k_multi_body_d2d    workgroup (b, h) does for start h what workgroup b of k_iterate_d2d does in its body and epilogue
+//   k_multi_body_d2d    workgroup (b, h) does for start h what workgroup b of k_iterate_d2d does in its body and
+//                       epilogue: the body is the same function, evaluate_components (ndt2d_d2d.hpp)
 //
 // Contract: start h's result is what ndt2d_align_map returns for (target, sources[h], init_poses[h]), bit for bit: the
-// same component -> thread assignment (blocks[h] workgroups, the single call's grid, whatever the launch's width), the
-// same per-thread accumulation order, the same reduction trees, the same update; a finished start is frozen.
+// same component -> thread assignment (blocks[h] workgroups, the single call's grid, whatever the launch's width) handed
+// to one evaluate_components - the per-thread accumulation order is its own -, the same reduction trees
+// (wave_reduce11_lds, then the four waves in fixed order), the same update (k_multi_solve); a finished start is frozen.
 #pragma once
 #include "ndt2d_d2d.hpp"
 #include "ndt2d_multi_start.hpp"
@@ -99,30 +101,12 @@ __global__ __launch_bounds__(kBlock) void k_multi_body_d2d(const AlignStatic* __
   float4 ca = make_float4(0.f, 0.f, 0.f, 0.f), cb = ca;
   if (i < n) { ca = comp[2 * (size_t)i]; cb = comp[2 * (size_t)i + 1]; }
 
-  // ---- body: k_iterate_d2d's
+  // ---- body: the function k_iterate_d2d calls
   const PoseF P = make_pose(pcs, psn, ptx, pty, G.ox, G.oy, G.inv_c, G.W, G.H, prm.d1, prm.d2);
-  RotF R;
-  R.c2t = P.cs * P.cs - P.sn * P.sn;
-  R.s2t = 2.f * P.cs * P.sn;
-  Acc2D A;
-  acc_zero(A);
-  while (i < n) {
-    const int i2 = i + stride;
-    float4 na = make_float4(0.f, 0.f, 0.f, 0.f), nb = na;
-    if (i2 < n) { na = comp[2 * (size_t)i2]; nb = comp[2 * (size_t)i2 + 1]; }
-    PointRec r;
-    image_point(P, ca.x, ca.y, r);
-    const int key = image_key(P, P.ox, P.oy, r, true);       // clamped onto the grid: every key is a cell of `cov`
-    r.A = cov[2 * key];
-    r.B = cov[2 * key + 1];
-    accumulate_component<MODE>(P, R, r, ca.z, ca.w, cb.y, A);
-    ca = na; cb = nb; i = i2;
-  }
   float acc[kNumAcc];
-  acc_store(A, prm.d2, acc);
-  acc[11] = 0.f;
+  evaluate_components<MODE>(P, prm.d2, comp, cov, n, i, stride, ca, cb, acc);
 
-  // ---- epilogue: wave tree -> LDS -> one partial column entry per sum
+  // ---- epilogue: wave tree -> LDS -> one partial column entry per sum (each chain kernel's own text: DESIGN 5.1)
   {
     const float r = wave_reduce11_lds(acc, s_t[wave], lane);
     if ((lane & 3) == 0 && lane < 4 * (kNumAcc - 1)) s_wave[wave][lane >> 2] = r;

@@ -516,13 +516,15 @@ struct PoseF {
   float nhd2;    // -d2/2 * log2(e)
   float d2;
 };
+// -d2/2 * log2(e), the scale of every score's exponent: d1 exp(-d2/2 m) = d1 exp2(nhd2_of(d2) m)
+__device__ __forceinline__ float nhd2_of(float d2) { return -0.5f * d2 * 1.44269504088896340736f; }
 __device__ __forceinline__ PoseF make_pose(float cs, float sn, float tx, float ty, float ox, float oy, float inv_c,
                                            int W, int H, float d1, float d2) {
   PoseF P;
   P.cs = cs; P.sn = sn; P.tx = tx; P.ty = ty; P.ox = ox; P.oy = oy; P.inv_c = inv_c;
   P.W = W; P.wm1 = W - 1; P.hm1 = H - 1;
   P.lg_d1 = __builtin_amdgcn_logf(d1);                 // v_log_f32 = log2
-  P.nhd2 = -0.5f * d2 * 1.44269504088896340736f;
+  P.nhd2 = nhd2_of(d2);
   P.d2 = d2;
   return P;
 }
@@ -578,6 +580,15 @@ __device__ __forceinline__ void lookup_point(const PoseF& P, const float4* __res
   r.B = rec[2 * key + 1];
 }
 
+// m = q' Sigma^-1 q of an image point in the cell whose record it carries, and v = Sigma^-1 q
+__device__ __forceinline__ float mahalanobis2(const PointRec& r, float& vx, float& vy) {
+  const float a = r.A.z, b = r.A.w, c = r.B.y;
+  const float qx = r.px - r.A.x, qy = r.py - r.A.y;
+  vx = fmaf(a, qx, b * qy); vy = fmaf(b, qx, c * qy);
+  return fmaf(qx, vx, qy * vy);
+}
+__device__ __forceinline__ float mahalanobis2(const PointRec& r) { float vx, vy; return mahalanobis2(r, vx, vy); }
+
 struct Acc2D {            // the running sums of one thread (unscaled: d2 is applied in acc_store)
   float h0, h1, h2, h3, h4, h5;   // Hxx Hxy Hyy Hxt Hyt Htt
   float g0, g1, g2, s;            // gx gy gt score
@@ -598,9 +609,8 @@ template <int MODE>
 __device__ __forceinline__ void accumulate_point(const PoseF& P, const PointRec& r, Acc2D& acc) {
   const bool hit = r.B.z > 0.f;                                   // n > 0: a finalised cell
   const float a = r.A.z, b = r.A.w, c = r.B.y;
-  const float qx = r.px - r.A.x, qy = r.py - r.A.y;
-  const float vx = fmaf(a, qx, b * qy), vy = fmaf(b, qx, c * qy);   // Sigma^-1 q
-  const float m = fmaf(qx, vx, qy * vy);
+  float vx, vy;                                                   // Sigma^-1 q
+  const float m = mahalanobis2(r, vx, vy);
 #if defined(NDT_BATCH_ABLATE) && (NDT_BATCH_ABLATE & 4)      // tools only: no transcendental
   const float s = hit ? fmaf(P.nhd2, m, 1.f) : 0.f;
 #else

@@ -16,13 +16,10 @@ namespace ndt {
 
 constexpr int kSearchChunk = 2048;              // source points staged in LDS per round (16 KB)
 
-// The score term of accumulate_point (ndt2d_kernels.hpp), alone: the same float32 operations in the same order.
-__device__ __forceinline__ float search_point_score(const PoseF& P, float px, float py, const float4& A, const float4& B) {
-  const bool hit = B.z > 0.f;
-  const float a = A.z, b = A.w, c = B.y;
-  const float qx = px - A.x, qy = py - A.y;
-  const float vx = fmaf(a, qx, b * qy), vy = fmaf(b, qx, c * qy);
-  const float m = fmaf(qx, vx, qy * vy);
+// The score term of accumulate_point (ndt2d_kernels.hpp), alone: its hit rule and exponent around the shared mahalanobis2.
+__device__ __forceinline__ float search_point_score(const PoseF& P, const PointRec& r) {
+  const bool hit = r.B.z > 0.f;
+  const float m = mahalanobis2(r);
   return hit ? __builtin_amdgcn_exp2f(fmaf(P.nhd2, m, P.lg_d1)) : 0.f;
 }
 
@@ -95,10 +92,10 @@ __global__ __launch_bounds__(kSearchThreads) void k_search_score(const AlignStat
             r[u].A = rec[2 * key];
             r[u].B = rec[2 * key + 1];
           }
-          s0 += search_point_score(P, r[0].px, r[0].py, r[0].A, r[0].B);
-          s1 += search_point_score(P, r[1].px, r[1].py, r[1].A, r[1].B);
-          s0 += search_point_score(P, r[2].px, r[2].py, r[2].A, r[2].B);
-          s1 += search_point_score(P, r[3].px, r[3].py, r[3].A, r[3].B);
+          s0 += search_point_score(P, r[0]);
+          s1 += search_point_score(P, r[1]);
+          s0 += search_point_score(P, r[2]);
+          s1 += search_point_score(P, r[3]);
         }
       }
       total += s0 + s1;

@@ -156,7 +156,6 @@ __device__ __forceinline__ void make_map_pose3(const double* pose, MapPose3& T) 
   T.bx = (float)(-sg); T.by = (float)cg;
 }
 
-struct V3 { float x, y, z; };
 __device__ __forceinline__ float dot3(float a0, float b0, float a1, float b1, float a2, float b2) {
   return fmaf(a0, b0, fmaf(a1, b1, a2 * b2));
 }
@@ -164,6 +163,31 @@ __device__ __forceinline__ float dot3(const V3& a, const V3& b) { return dot3(a.
 // S x for a symmetric S = (xx xy xz yy yz zz)
 __device__ __forceinline__ V3 symv(const float* S, const V3& x) {
   return V3{dot3(S[0], x.x, S[1], x.y, S[2], x.z), dot3(S[1], x.x, S[3], x.y, S[4], x.z), dot3(S[2], x.x, S[4], x.y, S[5], x.z)};
+}
+// S = (R Sg) R' for a symmetric Sg: a source covariance under the pose's rotation (the body, and the staging of the search)
+__device__ __forceinline__ void rotate_cov3(const float* R, const float* Sg, float* S) {
+  float Tm[9];
+#pragma unroll
+  for (int r = 0; r < 3; ++r) {
+    Tm[3 * r] = dot3(R[3 * r], Sg[0], R[3 * r + 1], Sg[1], R[3 * r + 2], Sg[2]);
+    Tm[3 * r + 1] = dot3(R[3 * r], Sg[1], R[3 * r + 1], Sg[3], R[3 * r + 2], Sg[4]);
+    Tm[3 * r + 2] = dot3(R[3 * r], Sg[2], R[3 * r + 1], Sg[4], R[3 * r + 2], Sg[5]);
+  }
+  int q = 0;
+#pragma unroll
+  for (int i = 0; i < 3; ++i)
+#pragma unroll
+    for (int j = i; j < 3; ++j) S[q++] = dot3(Tm[3 * i], R[3 * j], Tm[3 * i + 1], R[3 * j + 1], Tm[3 * i + 2], R[3 * j + 2]);
+}
+// m = q' B q with B = (S + Sigma_j)^-1 by cofactors (the sum's six entries xx xy xz yy yz zz), and v = B q
+__device__ __forceinline__ float mahalanobis_sum3(float axx, float axy, float axz, float ayy, float ayz, float azz, const V3& q,
+                                                  float* B, V3& v) {
+  const float c00 = fmaf(ayy, azz, -ayz * ayz), c01 = fmaf(axz, ayz, -axy * azz), c02 = fmaf(axy, ayz, -axz * ayy);
+  const float c11 = fmaf(axx, azz, -axz * axz), c12 = fmaf(axy, axz, -axx * ayz), c22 = fmaf(axx, ayy, -axy * axy);
+  const float rdet = 1.0f / dot3(axx, c00, axy, c01, axz, c02);
+  B[0] = c00 * rdet; B[1] = c01 * rdet; B[2] = c02 * rdet; B[3] = c11 * rdet; B[4] = c12 * rdet; B[5] = c22 * rdet;
+  v = symv(B, q);
+  return dot3(q, v);
 }
 // a_k x b for the three axes
 template <int K>
@@ -200,32 +224,13 @@ __device__ __forceinline__ void accumulate_component3(const MapPose3& T, const f
                                                       const float4& A4, const float4& B4, const float4& C2, float d1, float d2,
                                                       float nhd2, float* acc) {
   const bool hit = in & (A4.w > 0.f);
-  const float* R = T.R;
-  // S = (R Sg) R'
-  float Tm[9], S[6];
-#pragma unroll
-  for (int r = 0; r < 3; ++r) {
-    Tm[3 * r] = dot3(R[3 * r], Sg[0], R[3 * r + 1], Sg[1], R[3 * r + 2], Sg[2]);
-    Tm[3 * r + 1] = dot3(R[3 * r], Sg[1], R[3 * r + 1], Sg[3], R[3 * r + 2], Sg[4]);
-    Tm[3 * r + 2] = dot3(R[3 * r], Sg[2], R[3 * r + 1], Sg[4], R[3 * r + 2], Sg[5]);
-  }
-  {
-    int q = 0;
-#pragma unroll
-    for (int i = 0; i < 3; ++i)
-#pragma unroll
-      for (int j = i; j < 3; ++j) S[q++] = dot3(Tm[3 * i], R[3 * j], Tm[3 * i + 1], R[3 * j + 1], Tm[3 * i + 2], R[3 * j + 2]);
-  }
+  float S[6];
+  rotate_cov3(T.R, Sg, S);
   const float axx = S[0] + (hit ? B4.x : 1.f), axy = S[1] + (hit ? B4.y : 0.f), axz = S[2] + (hit ? B4.z : 0.f);
   const float ayy = S[3] + (hit ? B4.w : 1.f), ayz = S[4] + (hit ? C2.x : 0.f), azz = S[5] + (hit ? C2.y : 1.f);
-  // B = (S + Sigma_j)^-1 by cofactors
-  const float c00 = fmaf(ayy, azz, -ayz * ayz), c01 = fmaf(axz, ayz, -axy * azz), c02 = fmaf(axy, ayz, -axz * ayy);
-  const float c11 = fmaf(axx, azz, -axz * axz), c12 = fmaf(axy, axz, -axx * ayz), c22 = fmaf(axx, ayy, -axy * axy);
-  const float rdet = 1.0f / dot3(axx, c00, axy, c01, axz, c02);
-  const float B[6] = {c00 * rdet, c01 * rdet, c02 * rdet, c11 * rdet, c12 * rdet, c22 * rdet};
-  const V3 q{px - A4.x, py - A4.y, pz - A4.z};
-  const V3 v = symv(B, q);
-  const float m = dot3(q, v);
+  float B[6];
+  V3 v;
+  const float m = mahalanobis_sum3(axx, axy, axz, ayy, ayz, azz, V3{px - A4.x, py - A4.y, pz - A4.z}, B, v);
   const float s = hit ? d1 * __builtin_amdgcn_exp2f(nhd2 * m) : 0.f;
   const float w = s * d2;
   const V3 Sv = symv(S, v);
@@ -277,6 +282,39 @@ __device__ __forceinline__ void accumulate_component3(const MapPose3& T, const f
   for (int k = 0; k < 3; ++k) acc[24 + k] = fmaf(w, t[k].c, acc[24 + k]);
   acc[27] += s;
   acc[28] += hit ? 1.f : 0.f;
+}
+
+// Body and epilogue of a map-to-map launch for one alignment, shared by k_iterate_d2d3 and the multi-start chain
+// (k_multi_body_d2d3), in the shape of evaluate_block3: this workgroup's components (i, i + stride, ...; the first one
+// already loaded into ca, cb, cc) under the pose T, each mean looked up as a point is (a voxel of `cov` either way),
+// per-thread sums, the wave's sums through LDS, one partial row entry per sum at partial_col[row * kMaxBlocks].
+template <int MODE>
+__device__ __forceinline__ void evaluate_components3(const Grid3Dev& G, const SolveParams& prm, const MapPose3& T,
+                                                     const float4* __restrict__ comp, const float4* __restrict__ cov, int n, int i,
+                                                     int stride, float4 ca, float4 cb, float4 cc, float (*s_wave)[kRowsMap3],
+                                                     float* s_t_wave, float* __restrict__ partial_col) {
+  constexpr int NA = kNumAccMap3;
+  const Extent3F E = extent3(G);
+  const float d1 = prm.d1, d2 = prm.d2;
+  const float nhd2 = nhd2_of(d2);
+  float acc[NA];
+#pragma unroll
+  for (int j = 0; j < NA; ++j) acc[j] = 0.f;
+  while (i < n) {
+    const int i2 = i + stride;
+    float4 na = make_float4(0.f, 0.f, 0.f, 0.f), nb = na, nc = na;
+    if (i2 < n) { na = comp[3 * (size_t)i2]; nb = comp[3 * (size_t)i2 + 1]; nc = comp[3 * (size_t)i2 + 2]; }
+    const V3 p = image3(T.R, T.tx, T.ty, T.tz, ca.x, ca.y, ca.z);
+    const Voxel3 vox = voxel_of3(G, E, p.x, p.y, p.z);
+    const int key = vox.key;
+    const float4 A4 = cov[3 * (size_t)key];
+    const float4 B4 = cov[3 * (size_t)key + 1];
+    const float4 C2 = cov[3 * (size_t)key + 2];
+    const float Sg[6] = {cb.x, cb.y, cb.z, cb.w, cc.x, cc.y};
+    accumulate_component3<MODE>(T, Sg, p.x, p.y, p.z, vox.in, A4, B4, C2, d1, d2, nhd2, acc);
+    ca = na; cb = nb; cc = nc; i = i2;
+  }
+  block_reduce3_store<NA, kRowsMap3>(acc, s_t_wave, s_wave, partial_col);
 }
 
 // Launch k (parity = k & 1) consumes state[parity^1] / partials[parity^1] of launch k-1 and produces state[parity] /
@@ -378,36 +416,11 @@ __global__ __launch_bounds__(kBlock) void k_iterate_d2d3(const AlignStatic3* __r
     copy_state(cur, prev, 1);
   }
 
-  // ---- body: per-component terms at `pose`
+  // ---- body and epilogue: per-component terms at `pose`
   MapPose3 T;
   make_map_pose3(pose, T);
-  const float fW = (float)G.W, fH = (float)G.H, fD = (float)G.D;
-  const float d1 = prm.d1, d2 = prm.d2;
-  const float nhd2 = -0.5f * d2 * 1.44269504088896340736f;
-  float acc[NA];
-#pragma unroll
-  for (int j = 0; j < NA; ++j) acc[j] = 0.f;
-  while (i < n) {
-    const int i2 = i + stride;
-    float4 na = make_float4(0.f, 0.f, 0.f, 0.f), nb = na, nc = na;
-    if (i2 < n) { na = comp[3 * (size_t)i2]; nb = comp[3 * (size_t)i2 + 1]; nc = comp[3 * (size_t)i2 + 2]; }
-    // the image of the mean, the inside test and the key exactly as evaluate_block3 has them for a point
-    const float px = fmaf(T.R[0], ca.x, fmaf(T.R[1], ca.y, fmaf(T.R[2], ca.z, T.tx)));
-    const float py = fmaf(T.R[3], ca.x, fmaf(T.R[4], ca.y, fmaf(T.R[5], ca.z, T.ty)));
-    const float pz = fmaf(T.R[6], ca.x, fmaf(T.R[7], ca.y, fmaf(T.R[8], ca.z, T.tz)));
-    const float fx = (px - G.ox) * G.inv_c, fy = (py - G.oy) * G.inv_c, fz = (pz - G.oz) * G.inv_c;
-    const bool in = (fx >= 0.f) & (fx < fW) & (fy >= 0.f) & (fy < fH) & (fz >= 0.f) & (fz < fD);
-    const int key = in ? (((int)fz * G.H + (int)fy) * G.W + (int)fx) : 0;      // a voxel of `cov` either way
-    const float4 A4 = cov[3 * (size_t)key];
-    const float4 B4 = cov[3 * (size_t)key + 1];
-    const float4 C2 = cov[3 * (size_t)key + 2];
-    const float Sg[6] = {cb.x, cb.y, cb.z, cb.w, cc.x, cc.y};
-    accumulate_component3<MODE>(T, Sg, px, py, pz, in, A4, B4, C2, d1, d2, nhd2, acc);
-    ca = na; cb = nb; cc = nc; i = i2;
-  }
-
-  // ---- epilogue: the wave's sums through LDS, one partial column entry per sum
-  block_reduce3_store<NA, kRowsMap3>(acc, s_t[wave], s_wave, &dyn->partials[parity][0][blockIdx.x]);
+  evaluate_components3<MODE>(G, prm, T, comp, cov, n, i, stride, ca, cb, cc, s_wave, s_t[wave],
+                             &dyn->partials[parity][0][blockIdx.x]);
 }
 
 }  // namespace ndt

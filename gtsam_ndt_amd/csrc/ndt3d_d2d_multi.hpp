@@ -10,11 +10,13 @@
 //                                                 k_begin_multi3; two launches: each argument block stays below 4 KB)
 //   k_multi_solve3<0>    unchanged, in BOTH Hessian modes: k_iterate_d2d3 carries the same 29 sums and the Gauss-Newton
 //                        form of the prologue in both (32 rows, store_state3<0>, no newton_rot_block3)
-//   k_multi_body_d2d3    workgroup (b, h) does for start h what workgroup b of k_iterate_d2d3 does in its body and epilogue
+//   k_multi_body_d2d3    workgroup (b, h) does for start h what workgroup b of k_iterate_d2d3 does in its body and
+//                        epilogue, by calling the same function: evaluate_components3 (ndt3d_d2d.hpp)
 //
 // Contract: start h's result is what ndt3d_align_map returns for (target, sources[h], init_poses[h]), bit for bit: the
-// same component -> thread assignment (blocks[h] workgroups, the single call's grid, whatever the launch's width), the
-// same per-thread accumulation order, the same reduction trees, the same update; a finished start is frozen.
+// same component -> thread assignment (blocks[h] workgroups, the single call's grid, whatever the launch's width) handed
+// to one evaluate_components3 - per-thread accumulation order and reduction trees are its own - and the same update
+// (k_multi_solve3<0>); a finished start is frozen.
 #pragma once
 #include "ndt3d_d2d.hpp"
 #include "ndt3d_multi.hpp"
@@ -113,40 +115,15 @@ __global__ __launch_bounds__(kBlock) void k_multi_body_d2d3(const AlignStatic3* 
   const Grid3Dev G = st->grid;
   if (done || b >= blocks) return;       // uniform; a finished start's list may already be gone: nothing of it is loaded
 
-  const int stride = blocks * kBlock;
-  int i = b * kBlock + tid;
+  const int i = b * kBlock + tid;
   float4 ca = make_float4(0.f, 0.f, 0.f, 0.f), cb = ca, cc = ca;
   if (i < n) { ca = comp[3 * (size_t)i]; cb = comp[3 * (size_t)i + 1]; cc = comp[3 * (size_t)i + 2]; }
 
-  // ---- body: k_iterate_d2d3's
+  // ---- body and epilogue: the function k_iterate_d2d3 calls
   MapPose3 T;
   make_map_pose3(pose, T);
-  const float fW = (float)G.W, fH = (float)G.H, fD = (float)G.D;
-  const float d1 = prm.d1, d2 = prm.d2;
-  const float nhd2 = -0.5f * d2 * 1.44269504088896340736f;
-  float acc[NA];
-#pragma unroll
-  for (int j = 0; j < NA; ++j) acc[j] = 0.f;
-  while (i < n) {
-    const int i2 = i + stride;
-    float4 na = make_float4(0.f, 0.f, 0.f, 0.f), nb = na, nc = na;
-    if (i2 < n) { na = comp[3 * (size_t)i2]; nb = comp[3 * (size_t)i2 + 1]; nc = comp[3 * (size_t)i2 + 2]; }
-    const float px = fmaf(T.R[0], ca.x, fmaf(T.R[1], ca.y, fmaf(T.R[2], ca.z, T.tx)));
-    const float py = fmaf(T.R[3], ca.x, fmaf(T.R[4], ca.y, fmaf(T.R[5], ca.z, T.ty)));
-    const float pz = fmaf(T.R[6], ca.x, fmaf(T.R[7], ca.y, fmaf(T.R[8], ca.z, T.tz)));
-    const float fx = (px - G.ox) * G.inv_c, fy = (py - G.oy) * G.inv_c, fz = (pz - G.oz) * G.inv_c;
-    const bool in = (fx >= 0.f) & (fx < fW) & (fy >= 0.f) & (fy < fH) & (fz >= 0.f) & (fz < fD);
-    const int key = in ? (((int)fz * G.H + (int)fy) * G.W + (int)fx) : 0;      // a voxel of `cov` either way
-    const float4 A4 = cov[3 * (size_t)key];
-    const float4 B4 = cov[3 * (size_t)key + 1];
-    const float4 C2 = cov[3 * (size_t)key + 2];
-    const float Sg[6] = {cb.x, cb.y, cb.z, cb.w, cc.x, cc.y};
-    accumulate_component3<MODE>(T, Sg, px, py, pz, in, A4, B4, C2, d1, d2, nhd2, acc);
-    ca = na; cb = nb; cc = nc; i = i2;
-  }
-
-  // ---- epilogue: the wave's sums through LDS, one partial column entry per sum
-  block_reduce3_store<NA, kRowsMap3>(acc, s_t[wave], s_wave, &dyn->partials[parity][h][0][b]);
+  evaluate_components3<MODE>(G, prm, T, comp, cov, n, i, blocks * kBlock, ca, cb, cc, s_wave, s_t[wave],
+                             &dyn->partials[parity][h][0][b]);
 }
 
 }  // namespace ndt

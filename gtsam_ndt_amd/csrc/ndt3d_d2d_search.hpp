@@ -9,9 +9,10 @@
 //                        a 16 x 16 tile of translations, ONE LANE PER TRANSLATION, a wave an 8 x 8 block.  R is uniform
 //                        over the workgroup (scalar registers).  What does not depend on the translation in x and y is
 //                        done once per component and workgroup while the chunk is staged into LDS: S = (R Sigma_i) R^T
-//                        (27 dot3 products), the image's z, its inside test and the voxel layer's key.  A lane reads
-//                        the component back as broadcasts, forms the image's x and y with its own translation (the
-//                        fmaf order of k_iterate_d2d3: the voxel key is the contract's), gathers its own covariance
+//                        (rotate_cov3, 27 dot3 products), the image's z, its inside test and the voxel layer's key
+//                        (layer_key3).  A lane reads the component back as broadcasts, forms the image's x and y with
+//                        its own translation (image_row3, which evaluate_components3 calls through image3: the voxel
+//                        key is the contract's, in the clamped form voxel_clamped3), gathers its own covariance
 //                        record and keeps a private float sum in component order.  No cross-lane reduction and no
 //                        atomics: the volume is the same bit for bit on every call.  Per component the float32
 //                        arithmetic is the score part of accumulate_component3; only the summation order differs.
@@ -29,23 +30,17 @@ namespace ndt {
 //   s_sb[3 (k / 4) + 0 .. 2] = Syz, Szz and the layer key of components k .. k + 3
 constexpr int kMapSearch3Chunk = 512;
 
-// The score part of accumulate_component3 (ndt3d_d2d.hpp) with S already rotated: the same float32 operations in the
-// same order.  A miss keeps whatever record the clamped key named (all zero for an invalid voxel): S is positive
-// definite on its own, and the term is deselected.
+// The score part of accumulate_component3 (ndt3d_d2d.hpp) with S already rotated: its mahalanobis_sum3 and exponent.
+// A miss keeps whatever record the clamped key named (all zero for an invalid voxel): S is positive definite on its own,
+// and the term is deselected.
 __device__ __forceinline__ float search_component_score3(float px, float py, float pz, bool in, const float4& sa, float syz,
                                                          float szz, const float4& A4, const float4& B4, const float2& C2,
                                                          float d1, float nhd2) {
   const bool hit = in & (A4.w > 0.f);
-  const float axx = sa.x + B4.x, axy = sa.y + B4.y, axz = sa.z + B4.z;
-  const float ayy = sa.w + B4.w, ayz = syz + C2.x, azz = szz + C2.y;
-  // B = (S + Sigma_j)^-1 by cofactors
-  const float c00 = fmaf(ayy, azz, -ayz * ayz), c01 = fmaf(axz, ayz, -axy * azz), c02 = fmaf(axy, ayz, -axz * ayy);
-  const float c11 = fmaf(axx, azz, -axz * axz), c12 = fmaf(axy, axz, -axx * ayz), c22 = fmaf(axx, ayy, -axy * axy);
-  const float rdet = 1.0f / dot3(axx, c00, axy, c01, axz, c02);
-  const float B[6] = {c00 * rdet, c01 * rdet, c02 * rdet, c11 * rdet, c12 * rdet, c22 * rdet};
-  const V3 q{px - A4.x, py - A4.y, pz - A4.z};
-  const V3 v = symv(B, q);
-  const float m = dot3(q, v);
+  float B[6];
+  V3 v;
+  const float m = mahalanobis_sum3(sa.x + B4.x, sa.y + B4.y, sa.z + B4.z, sa.w + B4.w, syz + C2.x, szz + C2.y,
+                                   V3{px - A4.x, py - A4.y, pz - A4.z}, B, v);
   return hit ? d1 * __builtin_amdgcn_exp2f(nhd2 * m) : 0.f;
 }
 
@@ -67,8 +62,8 @@ __global__ __launch_bounds__(kSearchThreads, 4) void k_search_score_d2d3(const A
   const int tiles_x = (nx + kSearchTile - 1) / kSearchTile, tiles_y = (ny + kSearchTile - 1) / kSearchTile;
   const long long nblocks = (long long)tiles_x * tiles_y * nt;
   const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
-  const float fW = (float)G.W, fH = (float)G.H, fD = (float)G.D;
-  const float nhd2 = -0.5f * d2 * 1.44269504088896340736f;   // as k_iterate_d2d3
+  const Extent3F E = extent3(G);
+  const float nhd2 = nhd2_of(d2);
   const int layer = G.W * G.H;
   const unsigned last_cell = (unsigned)(layer * G.D - 1);
   for (long long b = blockIdx.x; b < nblocks; b += gridDim.x) {
@@ -99,27 +94,13 @@ __global__ __launch_bounds__(kSearchThreads, 4) void k_search_score_d2d3(const A
         if (k < m) {
           const float4 ca = comp[3 * (size_t)(base + k)], cb = comp[3 * (size_t)(base + k) + 1],
                        cc = comp[3 * (size_t)(base + k) + 2];
-          const float pz = fmaf(R[6], ca.x, fmaf(R[7], ca.y, fmaf(R[8], ca.z, tz)));
-          const float fz = (pz - G.oz) * G.inv_c;
-          if ((fz >= 0.f) & (fz < fD)) lk = (int)fz * layer;
+          const float pz = image_row3(R + 6, tz, ca.x, ca.y, ca.z);
+          const Voxel3 L = layer_key3(G, E, pz, (unsigned)layer);
+          if (L.in) lk = L.key;
           mu = make_float4(ca.x, ca.y, ca.z, pz);
-          // S = (R Sg) R', accumulate_component3's dot3 order
           const float Sg[6] = {cb.x, cb.y, cb.z, cb.w, cc.x, cc.y};
-          float Tm[9], S[6];
-#pragma unroll
-          for (int r = 0; r < 3; ++r) {
-            Tm[3 * r] = dot3(R[3 * r], Sg[0], R[3 * r + 1], Sg[1], R[3 * r + 2], Sg[2]);
-            Tm[3 * r + 1] = dot3(R[3 * r], Sg[1], R[3 * r + 1], Sg[3], R[3 * r + 2], Sg[4]);
-            Tm[3 * r + 2] = dot3(R[3 * r], Sg[2], R[3 * r + 1], Sg[4], R[3 * r + 2], Sg[5]);
-          }
-          {
-            int q = 0;
-#pragma unroll
-            for (int i = 0; i < 3; ++i)
-#pragma unroll
-              for (int jj = i; jj < 3; ++jj)
-                S[q++] = dot3(Tm[3 * i], R[3 * jj], Tm[3 * i + 1], R[3 * jj + 1], Tm[3 * i + 2], R[3 * jj + 2]);
-          }
+          float S[6];
+          rotate_cov3(R, Sg, S);
           sa = make_float4(S[0], S[1], S[2], S[3]);
           syz = S[4];
           szz = S[5];
@@ -145,16 +126,12 @@ __global__ __launch_bounds__(kSearchThreads, 4) void k_search_score_d2d3(const A
 #pragma unroll
         for (int u = 0; u < 4; ++u) {
           const float4 p = s_mu[k + u];
-          px[u] = fmaf(R[0], p.x, fmaf(R[1], p.y, fmaf(R[2], p.z, tx)));
-          py[u] = fmaf(R[3], p.x, fmaf(R[4], p.y, fmaf(R[5], p.z, ty)));
+          px[u] = image_row3(R, tx, p.x, p.y, p.z);
+          py[u] = image_row3(R + 3, ty, p.x, p.y, p.z);
           pz[u] = p.w;
-          const float fx = (px[u] - G.ox) * G.inv_c, fy = (py[u] - G.oy) * G.inv_c;
-          in[u] = (fx >= 0.f) & (fx < fW) & (fy >= 0.f) & (fy < fH) & (lk[u] >= 0);
-          // ((int)fz * H + (int)fy) * W + (int)fx, the layer's part done at staging.  Outside the grid the key is
-          // meaningless and the record unused: it is clamped into the grid, not selected (k_search_score3: a select
-          // becomes a branch around the key, which splits the four gathers)
-          const unsigned key = min((unsigned)lk[u] + (unsigned)(int)fy * (unsigned)G.W + (unsigned)(int)fx, last_cell);
-          const float4* r = cov + 3 * (size_t)key;
+          const Voxel3 vox = voxel_clamped3(G, E, Voxel3{lk[u], lk[u] >= 0}, px[u], py[u], last_cell);
+          in[u] = vox.in;
+          const float4* r = cov + 3 * (size_t)(unsigned)vox.key;
           A[u] = r[0];
           B[u] = r[1];
           Cc[u] = *reinterpret_cast<const float2*>(r + 2);

@@ -541,6 +541,57 @@ __device__ __forceinline__ void make_rot3(const double* pose, Rot3F& T) {
   T.tx = (float)pose[0]; T.ty = (float)pose[1]; T.tz = (float)pose[2];
 }
 
+// ---- the voxel lookup, stated once for every kernel that looks a point (or a component's mean) up in the voxel grid.
+// One row of the image R p + t; R3 = that row of a row-major R (Rot3F, MapPose3 or a search kernel's scalar copy).
+__device__ __forceinline__ float image_row3(const float* R3, float t, float x, float y, float z) {
+  return fmaf(R3[0], x, fmaf(R3[1], y, fmaf(R3[2], z, t)));
+}
+struct V3 { float x, y, z; };
+__device__ __forceinline__ V3 image3(const float* R, float tx, float ty, float tz, float x, float y, float z) {
+  return V3{image_row3(R, tx, x, y, z), image_row3(R + 3, ty, x, y, z), image_row3(R + 6, tz, x, y, z)};
+}
+// The grid's extents as floats for the inside tests below: a kernel converts them once, above its loops.
+struct Extent3F { float W, H, D; };
+__device__ __forceinline__ Extent3F extent3(const Grid3Dev& G) { return Extent3F{(float)G.W, (float)G.H, (float)G.D}; }
+struct Voxel3 { int key; bool in; };   // by value: as out-parameters the same text reordered three moves in k_iterate3
+// The select form: the key of the voxel an image point lies in, 0 (a voxel of the grid either way) outside the grid.
+__device__ __forceinline__ Voxel3 voxel_of3(const Grid3Dev& G, const Extent3F& E, float px, float py, float pz) {
+  const float fx = (px - G.ox) * G.inv_c, fy = (py - G.oy) * G.inv_c, fz = (pz - G.oz) * G.inv_c;
+  const bool in = (fx >= 0.f) & (fx < E.W) & (fy >= 0.f) & (fy < E.H) & (fz >= 0.f) & (fz < E.D);
+  return Voxel3{in ? (((int)fz * G.H + (int)fy) * G.W + (int)fx) : 0, in};
+}
+// The search form, in two halves.  What depends on the image's z alone - its inside test and (int)fz * layer,
+// layer = W * H - is done once per point where x and y vary per lane (the lattice kernels, at staging) ...
+__device__ __forceinline__ Voxel3 layer_key3(const Grid3Dev& G, const Extent3F& E, float pz, unsigned int layer) {
+  const float fz = (pz - G.oz) * G.inv_c;
+  const bool in_z = (fz >= 0.f) & (fz < E.D);
+  return Voxel3{(int)((unsigned int)(int)fz * layer), in_z};
+}
+// ... and the rest per lane, on top of the layer's key.  Outside the grid the key is meaningless and the record unused:
+// it is clamped into the grid (last_cell = W H D - 1), not selected (voxel_of3 reads record 0 there), because the
+// compiler turns a select into a branch around the key, which splits the four gathers these kernels keep in flight.
+__device__ __forceinline__ Voxel3 voxel_clamped3(const Grid3Dev& G, const Extent3F& E, const Voxel3& layer, float px, float py,
+                                                 unsigned int last_cell) {
+  const float fx = (px - G.ox) * G.inv_c, fy = (py - G.oy) * G.inv_c;
+  const bool in = (fx >= 0.f) & (fx < E.W) & (fy >= 0.f) & (fy < E.H) & layer.in;
+  return Voxel3{(int)min((unsigned int)layer.key + (unsigned int)(int)fy * (unsigned int)G.W + (unsigned int)(int)fx, last_cell), in};
+}
+// m = q' Sigma^-1 q and v = Sigma^-1 q of an image point in the voxel of record (A4 = mean | n, B4 = xx xy xz yy, C2 = yz zz)
+template <class C>
+__device__ __forceinline__ float mahalanobis3(float px, float py, float pz, const float4& A4, const float4& B4, const C& C2,
+                                              float& vx, float& vy, float& vz) {
+  const float qx = px - A4.x, qy = py - A4.y, qz = pz - A4.z;
+  const float cxx = B4.x, cxy = B4.y, cxz = B4.z, cyy = B4.w, cyz = C2.x, czz = C2.y;
+  vx = fmaf(cxx, qx, fmaf(cxy, qy, cxz * qz));
+  vy = fmaf(cxy, qx, fmaf(cyy, qy, cyz * qz));
+  vz = fmaf(cxz, qx, fmaf(cyz, qy, czz * qz));
+  return fmaf(qx, vx, fmaf(qy, vy, qz * vz));
+}
+template <class C>
+__device__ __forceinline__ float mahalanobis3(float px, float py, float pz, const float4& A4, const float4& B4, const C& C2) {
+  float vx, vy, vz; return mahalanobis3(px, py, pz, A4, B4, C2, vx, vy, vz);
+}
+
 // a5 + a6 for one point: p = the untransformed source point, pp = R p + t (both zeroed by the caller when the
 // image lies outside the grid), the voxel record (A4 = mean | n, B4 = Sigma^-1 xx xy xz yy, C2 = yz zz).
 // acc: Htt(6) Htr(9) Hrr(6) g(6) score n_hit [+ M(9) in Newton mode].
@@ -549,12 +600,9 @@ __device__ __forceinline__ void accumulate_point3(const Rot3F& T, float x, float
                                                   float pz, bool in, const float4& A4, const float4& B4,
                                                   const float4& C2, float d1, float d2, float nhd2, float* acc) {
   const bool hit = in & (A4.w > 0.f);
-  const float qx = px - A4.x, qy = py - A4.y, qz = pz - A4.z;
   const float cxx = B4.x, cxy = B4.y, cxz = B4.z, cyy = B4.w, cyz = C2.x, czz = C2.y;
-  const float vx = fmaf(cxx, qx, fmaf(cxy, qy, cxz * qz));
-  const float vy = fmaf(cxy, qx, fmaf(cyy, qy, cyz * qz));
-  const float vz = fmaf(cxz, qx, fmaf(cyz, qy, czz * qz));
-  const float m = fmaf(qx, vx, fmaf(qy, vy, qz * vz));
+  float vx, vy, vz;
+  const float m = mahalanobis3(px, py, pz, A4, B4, C2, vx, vy, vz);
   const float s = hit ? d1 * __builtin_amdgcn_exp2f(nhd2 * m) : 0.f;
   const float w = s * d2;
   float J[3][3], U[3][3];   // J[k] = dR_k p ; U[k] = Sigma^-1 J[k]
@@ -662,9 +710,9 @@ __device__ __forceinline__ void evaluate_block3(const Grid3Dev& G, const SolvePa
   const int stride = kMaxBlocks * kBlock;
   Rot3F T;
   make_rot3(pose, T);
-  const float fW = (float)G.W, fH = (float)G.H, fD = (float)G.D;
+  const Extent3F E = extent3(G);
   const float d1 = prm.d1, d2 = prm.d2;
-  const float nhd2 = -0.5f * d2 * 1.44269504088896340736f;
+  const float nhd2 = nhd2_of(d2);
 
   float acc[NA];
 #pragma unroll
@@ -674,12 +722,9 @@ __device__ __forceinline__ void evaluate_block3(const Grid3Dev& G, const SolvePa
     const int inext = i + stride;
     float xn = 0.f, yn = 0.f, zn = 0.f;
     if (inext < n) { xn = sx[inext]; yn = sy[inext]; zn = sz[inext]; }
-    float px = fmaf(T.R[0], x, fmaf(T.R[1], y, fmaf(T.R[2], z, T.tx)));
-    float py = fmaf(T.R[3], x, fmaf(T.R[4], y, fmaf(T.R[5], z, T.ty)));
-    float pz = fmaf(T.R[6], x, fmaf(T.R[7], y, fmaf(T.R[8], z, T.tz)));
-    const float fx = (px - G.ox) * G.inv_c, fy = (py - G.oy) * G.inv_c, fz = (pz - G.oz) * G.inv_c;
-    const bool in = (fx >= 0.f) & (fx < fW) & (fy >= 0.f) & (fy < fH) & (fz >= 0.f) & (fz < fD);
-    const int key = in ? (((int)fz * G.H + (int)fy) * G.W + (int)fx) : 0;
+    float px = image_row3(T.R, T.tx, x, y, z), py = image_row3(T.R + 3, T.ty, x, y, z), pz = image_row3(T.R + 6, T.tz, x, y, z);
+    const Voxel3 vox = voxel_of3(G, E, px, py, pz);
+    const bool in = vox.in; const int key = vox.key;
     if (!in) { px = py = pz = 0.f; x = y = z = 0.f; }
     const float4 A4 = G.rec[4 * key];
     const float4 B4 = G.rec[4 * key + 1];

@@ -7,10 +7,12 @@
 //                       over the workgroup.  The scan is staged through LDS in chunks and read back as broadcasts; each
 //                       lane gathers its own voxel record (40 of its 64 bytes) and keeps a private float sum in point
 //                       order: no cross-lane reduction, no atomics, the same bits on every call.  Per point the float32
-//                       arithmetic is evaluate_block3's (ndt3d_kernels.hpp); only the summation order differs.
+//                       arithmetic is the single-scan chain's, through the functions it calls (image_row3,
+//                       mahalanobis3, nhd2_of; ndt3d_kernels.hpp); only the summation order differs, and the voxel key
+//                       takes the clamped form (voxel_clamped3) where evaluate_block3 takes voxel_of3's select.
 //                       What does not depend on the translation in x and y - the image's z, its inside test in z and
-//                       the voxel layer's key - is computed once per point and workgroup while the chunk is staged, by
-//                       the operations evaluate_block3 does per point.
+//                       the voxel layer's key (layer_key3) - is computed once per point and workgroup while the chunk
+//                       is staged.
 #pragma once
 
 #include "ndt_search.hpp"
@@ -19,16 +21,11 @@ namespace ndt {
 
 constexpr int kSearch3Chunk = 1024;             // source points staged in LDS per round (16 KB of points + 4 KB of layer keys)
 
-// The score term of accumulate_point3 (ndt3d_kernels.hpp), alone: the same float32 operations in the same order.
+// The score term of accumulate_point3 (ndt3d_kernels.hpp), alone: its hit rule and exponent around the shared mahalanobis3.
 __device__ __forceinline__ float search_point_score3(float px, float py, float pz, bool in, const float4& A4, const float4& B4,
                                                      const float2& C2, float d1, float nhd2) {
   const bool hit = in & (A4.w > 0.f);
-  const float qx = px - A4.x, qy = py - A4.y, qz = pz - A4.z;
-  const float cxx = B4.x, cxy = B4.y, cxz = B4.z, cyy = B4.w, cyz = C2.x, czz = C2.y;
-  const float vx = fmaf(cxx, qx, fmaf(cxy, qy, cxz * qz));
-  const float vy = fmaf(cxy, qx, fmaf(cyy, qy, cyz * qz));
-  const float vz = fmaf(cxz, qx, fmaf(cyz, qy, czz * qz));
-  const float m = fmaf(qx, vx, fmaf(qy, vy, qz * vz));
+  const float m = mahalanobis3(px, py, pz, A4, B4, C2);
   return hit ? d1 * __builtin_amdgcn_exp2f(nhd2 * m) : 0.f;
 }
 
@@ -54,8 +51,8 @@ __global__ __launch_bounds__(kSearchThreads) void k_search_score3(const AlignSta
   const int tiles_x = (nx + kSearchTile - 1) / kSearchTile, tiles_y = (ny + kSearchTile - 1) / kSearchTile;
   const long long nblocks = (long long)tiles_x * tiles_y * nt;
   const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
-  const float fW = (float)G.W, fH = (float)G.H, fD = (float)G.D;
-  const float nhd2 = -0.5f * d2 * 1.44269504088896340736f;   // as evaluate_block3
+  const Extent3F E = extent3(G);
+  const float nhd2 = nhd2_of(d2);
   const int layer = G.W * G.H;
   const unsigned last_cell = (unsigned)(layer * G.D - 1);
   // (a grid-stride loop over the workgroups' tasks, as k_search_score)
@@ -85,9 +82,9 @@ __global__ __launch_bounds__(kSearchThreads) void k_search_score3(const AlignSta
         int lk = -1;
         if (k < m) {
           x = sx[base + k]; y = sy[base + k]; z = sz[base + k];
-          pz = fmaf(R[6], x, fmaf(R[7], y, fmaf(R[8], z, tz)));
-          const float fz = (pz - G.oz) * G.inv_c;
-          if ((fz >= 0.f) & (fz < fD)) lk = (int)fz * layer;
+          pz = image_row3(R + 6, tz, x, y, z);
+          const Voxel3 L = layer_key3(G, E, pz, (unsigned)layer);
+          if (L.in) lk = L.key;
         }
         s_pt[k] = make_float4(x, y, z, pz);
         s_layer[k] = lk;
@@ -106,16 +103,12 @@ __global__ __launch_bounds__(kSearchThreads) void k_search_score3(const AlignSta
 #pragma unroll
         for (int u = 0; u < 4; ++u) {
           const float4 p = s_pt[k + u];
-          px[u] = fmaf(R[0], p.x, fmaf(R[1], p.y, fmaf(R[2], p.z, tx)));
-          py[u] = fmaf(R[3], p.x, fmaf(R[4], p.y, fmaf(R[5], p.z, ty)));
+          px[u] = image_row3(R, tx, p.x, p.y, p.z);
+          py[u] = image_row3(R + 3, ty, p.x, p.y, p.z);
           pz[u] = p.w;
-          const float fx = (px[u] - G.ox) * G.inv_c, fy = (py[u] - G.oy) * G.inv_c;
-          in[u] = (fx >= 0.f) & (fx < fW) & (fy >= 0.f) & (fy < fH) & (lk[u] >= 0);
-          // ((int)fz * H + (int)fy) * W + (int)fx, the layer's part done at staging.  Outside the grid the key is
-          // meaningless and the record unused (evaluate_block3 reads record 0 there): it is clamped into the grid, not
-          // selected, because the compiler turns a select into a branch around the key, which splits the four gathers
-          const unsigned key = min((unsigned)lk[u] + (unsigned)(int)fy * (unsigned)G.W + (unsigned)(int)fx, last_cell);
-          const float4* r = rec + 4 * (size_t)key;
+          const Voxel3 vox = voxel_clamped3(G, E, Voxel3{lk[u], lk[u] >= 0}, px[u], py[u], last_cell);
+          in[u] = vox.in;
+          const float4* r = rec + 4 * (size_t)(unsigned)vox.key;
           A[u] = r[0];
           B[u] = r[1];
           C[u] = *reinterpret_cast<const float2*>(r + 2);

@@ -1,8 +1,8 @@
 // A scan's points scored one by one against the cached grid, and those that fit kept (included behind ndt_merge.hpp: one
 // translation unit; docs/ALGORITHM.md section 2.19).  Every other entry point returns sums over the scan;
 // these write what the sums are made of - m_i = q' Sigma^-1 q of point i in its cell, with the float32 operations of the
-// single-scan alignment (image_point / image_key / accumulate_point in 2D, make_rot3 and the image, key and m of
-// evaluate_block3 / accumulate_point3 in 3D; those device functions are used, not restated, where they stand alone) -
+// single-scan alignment by calling its device functions (image_point / image_key / mahalanobis2 in 2D; make_rot3,
+// image3, voxel_of3 and mahalanobis3 in 3D) -
 // and a class per point, and copy the points of the wanted classes to the front of an output cloud in their order.
 //
 // Three kernels, ordered by their boundaries alone (the rule of ndt2d_kernels.hpp for the chain: no tickets, no atomics
@@ -49,8 +49,8 @@ struct SelectArgs {
   unsigned int n, keep;
 };
 
-// 2D: hit and m of one image point over the NG grids - the lookup of the chain's body (ndt2d_iterate_text.hpp) and the
-// q, vx, vy, m of accumulate_point; the least m of the grids whose cell is valid.
+// 2D: hit and m of one image point over the NG grids - the lookup of the chain's body (ndt2d_iterate_text.hpp) and
+// accumulate_point's mahalanobis2; the least m of the grids whose cell is valid.
 template <int NG>
 __device__ __forceinline__ bool fit_point2(const PoseF& P, const GridDev& G, float x, float y, float& m_out) {
   PointRec r;
@@ -64,10 +64,7 @@ __device__ __forceinline__ bool fit_point2(const PoseF& P, const GridDev& G, flo
     r.A = G.rec[2 * key];
     r.B = G.rec[2 * key + 1];
     const bool valid = r.B.z > 0.f;
-    const float a = r.A.z, b = r.A.w, c = r.B.y;
-    const float qx = r.px - r.A.x, qy = r.py - r.A.y;
-    const float vx = fmaf(a, qx, b * qy), vy = fmaf(b, qx, c * qy);
-    const float m = fmaf(qx, vx, qy * vy);
+    const float m = mahalanobis2(r);
     if (valid && (!hit || m < best)) best = m;
     hit |= valid;
   }
@@ -75,25 +72,16 @@ __device__ __forceinline__ bool fit_point2(const PoseF& P, const GridDev& G, flo
   return hit;
 }
 
-// 3D: the image, the in / key rule and the record loads of evaluate_block3, the q, v, m of accumulate_point3
+// 3D: hit and m of one point through the chain's functions: image3, voxel_of3, the record loads, mahalanobis3
 __device__ __forceinline__ bool fit_point3(const Rot3F& T, const Grid3Dev& G, float x, float y, float z, float& m_out) {
-  const float fW = (float)G.W, fH = (float)G.H, fD = (float)G.D;
-  const float px = fmaf(T.R[0], x, fmaf(T.R[1], y, fmaf(T.R[2], z, T.tx)));
-  const float py = fmaf(T.R[3], x, fmaf(T.R[4], y, fmaf(T.R[5], z, T.ty)));
-  const float pz = fmaf(T.R[6], x, fmaf(T.R[7], y, fmaf(T.R[8], z, T.tz)));
-  const float fx = (px - G.ox) * G.inv_c, fy = (py - G.oy) * G.inv_c, fz = (pz - G.oz) * G.inv_c;
-  const bool in = (fx >= 0.f) & (fx < fW) & (fy >= 0.f) & (fy < fH) & (fz >= 0.f) & (fz < fD);
-  const int key = in ? (((int)fz * G.H + (int)fy) * G.W + (int)fx) : 0;
+  const V3 p = image3(T.R, T.tx, T.ty, T.tz, x, y, z);
+  const Voxel3 vox = voxel_of3(G, extent3(G), p.x, p.y, p.z);
+  const int key = vox.key;
   const float4 A4 = G.rec[4 * key];
   const float4 B4 = G.rec[4 * key + 1];
   const float4 C2 = G.rec[4 * key + 2];
-  const float qx = px - A4.x, qy = py - A4.y, qz = pz - A4.z;
-  const float cxx = B4.x, cxy = B4.y, cxz = B4.z, cyy = B4.w, cyz = C2.x, czz = C2.y;
-  const float vx = fmaf(cxx, qx, fmaf(cxy, qy, cxz * qz));
-  const float vy = fmaf(cxy, qx, fmaf(cyy, qy, cyz * qz));
-  const float vz = fmaf(cxz, qx, fmaf(cyz, qy, czz * qz));
-  m_out = fmaf(qx, vx, fmaf(qy, vy, qz * vz));
-  return in & (A4.w > 0.f);
+  m_out = mahalanobis3(p.x, p.y, p.z, A4, B4, C2);
+  return vox.in & (A4.w > 0.f);
 }
 
 template <int DIM, int NG>

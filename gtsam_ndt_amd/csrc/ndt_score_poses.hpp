@@ -11,9 +11,10 @@
 //                       sum in the search kernels' order (two chains over the even and odd points of a chunk, then
 //                       total += s0 + s1): a list that spells a search lattice gives the search's volume bit for bit, and
 //                       a pose's score depends on nothing but the grid, the scan and that pose.  No cross-lane reduction,
-//                       no atomics.  The per-point arithmetic is the search kernels' device functions.
-//                       3D: the rotation is per lane, so the image's z and its layer key, which k_search_score3 stages
-//                       once per workgroup, are computed per lane by the same operations.
+//                       no atomics.  The per-point arithmetic is the search kernels' device functions (image_key and
+//                       search_point_score; image3, layer_key3, voxel_clamped3 and search_point_score3).
+//                       3D: the rotation is per lane, so layer_key3, which k_search_score3 calls once per point and
+//                       workgroup at staging, is called per lane.
 //                       A pose with a non-finite coordinate scores exactly +0, and so does a finite one whose float32
 //                       form is not finite (a translation beyond float32, an angle whose wrap leaves no finite sine and
 //                       cosine): no pose of the list gives a NaN score.
@@ -106,10 +107,10 @@ __global__ __launch_bounds__(kPoseThreads) void k_score_poses(const AlignStatic*
         // grid needs no barrier - its eight loads stay together - and is 7 % slower with one (2.01 against 1.87 ms on the
         // 1.34M-pose lattice of DESIGN 5.17)
         if (NG > 1) __builtin_amdgcn_sched_barrier(0);
-        s0 += search_point_score(P, r[0].px, r[0].py, r[0].A, r[0].B);
-        s1 += search_point_score(P, r[1].px, r[1].py, r[1].A, r[1].B);
-        s0 += search_point_score(P, r[2].px, r[2].py, r[2].A, r[2].B);
-        s1 += search_point_score(P, r[3].px, r[3].py, r[3].A, r[3].B);
+        s0 += search_point_score(P, r[0]);
+        s1 += search_point_score(P, r[1]);
+        s0 += search_point_score(P, r[2]);
+        s1 += search_point_score(P, r[3]);
       }
     }
     total += s0 + s1;
@@ -131,8 +132,8 @@ __global__ __launch_bounds__(kPoseThreads) __attribute__((amdgpu_waves_per_eu(1,
   const int tid = threadIdx.x;
   const unsigned int i = blockIdx.x * (unsigned int)kPoseThreads + tid;
   const bool live = i < m;
-  const float fW = (float)G.W, fH = (float)G.H, fD = (float)G.D;
-  const float nhd2 = -0.5f * d2 * 1.44269504088896340736f;   // as evaluate_block3
+  const Extent3F E = extent3(G);
+  const float nhd2 = nhd2_of(d2);
   const unsigned int layer = (unsigned int)(G.W * G.H);
   const unsigned int last_cell = layer * (unsigned int)G.D - 1u;
   float R[9], tx, ty, tz;
@@ -173,16 +174,11 @@ __global__ __launch_bounds__(kPoseThreads) __attribute__((amdgpu_waves_per_eu(1,
 #pragma unroll
       for (int u = 0; u < 4; ++u) {
         const float4 q = s_pt[k + u];                        // (a broadcast read: every lane reads the same point)
-        px[u] = fmaf(R[0], q.x, fmaf(R[1], q.y, fmaf(R[2], q.z, tx)));
-        py[u] = fmaf(R[3], q.x, fmaf(R[4], q.y, fmaf(R[5], q.z, ty)));
-        pz[u] = fmaf(R[6], q.x, fmaf(R[7], q.y, fmaf(R[8], q.z, tz)));
-        const float fx = (px[u] - G.ox) * G.inv_c, fy = (py[u] - G.oy) * G.inv_c, fz = (pz[u] - G.oz) * G.inv_c;
-        in[u] = (fx >= 0.f) & (fx < fW) & (fy >= 0.f) & (fy < fH) & (fz >= 0.f) & (fz < fD);
-        // ((int)fz * H + (int)fy) * W + (int)fx.  Outside the grid the key is meaningless and the record unused: it is
-        // clamped into the grid, not selected, as in k_search_score3
-        const unsigned int key = min((unsigned int)(int)fz * layer + (unsigned int)(int)fy * (unsigned int)G.W + (unsigned int)(int)fx,
-                                     last_cell);
-        const float4* r = rec + 4 * (size_t)key;
+        const V3 p = image3(R, tx, ty, tz, q.x, q.y, q.z);
+        px[u] = p.x; py[u] = p.y; pz[u] = p.z;           // (layer_key3 per lane here: the rotation is the lane's)
+        const Voxel3 vox = voxel_clamped3(G, E, layer_key3(G, E, p.z, layer), p.x, p.y, last_cell);
+        in[u] = vox.in;
+        const float4* r = rec + 4 * (size_t)(unsigned int)vox.key;
         A[u] = r[0];
         B[u] = r[1];
         C[u] = *reinterpret_cast<const float2*>(r + 2);
