@@ -214,6 +214,12 @@ SIGNATURES = {
     "ndt2d_search_map_scores": (C.c_int32, [_vp, _vp, C.POINTER(SearchWindow2D), _vp]),
     "ndt2d_search_align_map": (C.c_int32, [_vp, _vp, C.POINTER(SearchWindow2D), C.c_int32, _vp, _vp,
                                            C.POINTER(C.c_int32)]),
+    "ndt2d_score_map_poses_dev": (C.c_int32, [_vp, _vp, _vp, C.c_size_t, _vp, _vp]),
+    "ndt2d_score_map_poses": (C.c_int32, [_vp, _vp, _vp, C.c_size_t, _vp, _vp]),
+    "ndt2d_best_map_poses_dev": (C.c_int32, [_vp, _vp, _vp, C.c_size_t, C.c_double, C.c_double, C.c_int32, _vp,
+                                             C.POINTER(C.c_int32)]),
+    "ndt2d_best_map_poses_align_dev": (C.c_int32, [_vp, _vp, _vp, C.c_size_t, C.c_double, C.c_double, C.c_int32, _vp, _vp,
+                                                   C.POINTER(C.c_int32)]),
     "ndt2d_get_components": (C.c_int32, [_vp, _vp, _vp, _vp, C.c_int32, C.POINTER(C.c_int32)]),
     "ndt3d_evaluate_map": (C.c_int32, [_vp, _vp, _dp, C.POINTER(Eval3D)]),
     "ndt3d_align_map": (C.c_int32, [_vp, _vp, _dp, C.POINTER(Result3D)]),
@@ -257,6 +263,12 @@ SIGNATURES = {
     "ndt3d_search_map_scores": (C.c_int32, [_vp, _vp, C.POINTER(SearchWindow3D), _vp]),
     "ndt3d_search_align_map": (C.c_int32, [_vp, _vp, C.POINTER(SearchWindow3D), C.c_int32, _vp, _vp,
                                            C.POINTER(C.c_int32)]),
+    "ndt3d_score_map_poses_dev": (C.c_int32, [_vp, _vp, _vp, C.c_size_t, _vp, _vp]),
+    "ndt3d_score_map_poses": (C.c_int32, [_vp, _vp, _vp, C.c_size_t, _vp, _vp]),
+    "ndt3d_best_map_poses_dev": (C.c_int32, [_vp, _vp, _vp, C.c_size_t, C.c_double, C.c_double, C.c_int32, _vp,
+                                             C.POINTER(C.c_int32)]),
+    "ndt3d_best_map_poses_align_dev": (C.c_int32, [_vp, _vp, _vp, C.c_size_t, C.c_double, C.c_double, C.c_int32, _vp, _vp,
+                                                   C.POINTER(C.c_int32)]),
     "ndt3d_default_params": (None, [C.POINTER(Params2D)]),
     "ndt3d_create": (C.c_int32, [C.POINTER(Params2D), C.c_int32, C.POINTER(_vp)]),
     "ndt3d_destroy": (C.c_int32, [_vp]),

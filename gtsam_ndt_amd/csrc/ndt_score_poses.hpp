@@ -346,22 +346,16 @@ int32_t pose_walk(const ndt::SearchSel& sel, const double* picked, double min_se
   return m;
 }
 
-// ndt*_best_poses_dev: scores into the scratch, keys, shortlist, the shortlisted poses, the host's walk.  Synchronous.
+// The tail of every best-poses call, of a scan's list and of a map's (ndt_score_map_poses.hpp): the list's scores are
+// enqueued into S.d_vol on `stream`; keys, shortlist, the shortlisted poses, the host's walk.  Synchronous.
 template <class H>
-int32_t best_poses_dev(H* h, const float* const* d_s, size_t n, const double* d_poses, size_t m, double min_sep_trans,
-                       double min_sep_rot, int32_t k, typename HandleTraits<H>::Hit* hits, int32_t* n_hits) {
+int32_t best_poses_select(ndt::SearchScratch& S, hipStream_t stream, const double* d_poses, size_t m, double min_sep_trans,
+                          double min_sep_rot, int32_t k, typename HandleTraits<H>::Hit* hits, int32_t* n_hits) {
   using namespace ndt;
   constexpr int P = HandleTraits<H>::kPose;
-  { const int32_t cs = score_poses_check(h, d_s, n, d_poses, m, hits, true, min_sep_trans, min_sep_rot, k, n_hits); if (cs != NDT_OK) return cs; }
-  *n_hits = 0;
-  HIP_TRY(hipSetDevice(h->device));
-  SearchScratch& S = h->srch;
-  HIP_TRY(grow(&S.d_vol, &S.vol_cap, m, m + m / 4));
-  { const int32_t es = score_poses_enqueue(h, d_s, n, d_poses, m, S.d_vol); if (es != NDT_OK) return es; }
   constexpr size_t pick_bytes = (size_t)kSearchShortlist * 6 * sizeof(double);     // room for either dimension
   if (!S.d_pick) HIP_TRY(hipMalloc((void**)&S.d_pick, pick_bytes));
   if (!S.h_pick) HIP_TRY(pinned_alloc(&S.h_pick, pick_bytes));
-  hipStream_t stream = h->stream;
   { const int32_t bs = search_keys_begin(S, stream, m); if (bs != NDT_OK) return bs; }      // every pose can be a candidate
   SearchSel* sel = S.d_sel;
   hipLaunchKernelGGL(k_pose_keys, dim3((unsigned)((m + 255) / 256)), dim3(256), 0, stream, (const float*)S.d_vol, (unsigned)m, S.d_keys,
@@ -377,6 +371,20 @@ int32_t best_poses_dev(H* h, const float* const* d_s, size_t n, const double* d_
   HIP_TRY(hipStreamSynchronize(stream));
   *n_hits = pose_walk<H>(*S.h_sel, S.h_pick, min_sep_trans, min_sep_rot, k, hits);
   return NDT_OK;
+}
+
+// ndt*_best_poses_dev: scores into the scratch, then the tail above
+template <class H>
+int32_t best_poses_dev(H* h, const float* const* d_s, size_t n, const double* d_poses, size_t m, double min_sep_trans,
+                       double min_sep_rot, int32_t k, typename HandleTraits<H>::Hit* hits, int32_t* n_hits) {
+  using namespace ndt;
+  { const int32_t cs = score_poses_check(h, d_s, n, d_poses, m, hits, true, min_sep_trans, min_sep_rot, k, n_hits); if (cs != NDT_OK) return cs; }
+  *n_hits = 0;
+  HIP_TRY(hipSetDevice(h->device));
+  SearchScratch& S = h->srch;
+  HIP_TRY(grow(&S.d_vol, &S.vol_cap, m, m + m / 4));
+  { const int32_t es = score_poses_enqueue(h, d_s, n, d_poses, m, S.d_vol); if (es != NDT_OK) return es; }
+  return best_poses_select<H>(S, h->stream, d_poses, m, min_sep_trans, min_sep_rot, k, hits, n_hits);
 }
 
 // ndt*_best_poses_align_dev: the hits, then one multi-start call from their poses (nothing for zero hits)

@@ -197,8 +197,9 @@ struct SearchScratch {
   double* d_list = nullptr; size_t list_cap = 0;                  // a host list's upload (doubles)
   double* d_pick = nullptr;                                       // the shortlisted poses [kSearchShortlist][6]
   double* h_pick = nullptr;                                       // pinned: their read-back
+  unsigned int* d_cnt = nullptr; size_t cnt_cap = 0;              // a host list's hit counts (ndt_score_map_poses.hpp)
   void release() {
-    void* dev[] = {d_vol, d_keys, d_axes, d_sel, d_list, d_pick};
+    void* dev[] = {d_vol, d_keys, d_axes, d_sel, d_list, d_pick, d_cnt};
     for (void* p : dev) if (p) (void)hipFree(p);
     void* host[] = {h_axes, h_sel, h_pick};
     for (void* p : host) if (p) (void)hipHostFree(p);

@@ -675,6 +675,55 @@ class _NdtMatcher(_Handle):
                                              C.cast(res, C.c_void_p), C.byref(nh)), "search_align_map")
         return list(zip(_hits(hits, nh.value), [self._dim.result(r) for r in res[:nh.value]]))
 
+    # ---- the map-to-map score at a list of poses (ndt2d/ndt3d_score_map_poses*, _best_map_poses*)
+    def score_map_poses(self, source, poses, with_hits: bool = False):
+        """evaluate_map(source, pose)'s score at every pose of a list [m, 3 | 6] in one launch
+        (ndt2d/ndt3d_score_map_poses*): a CUDA float64 list gives a CUDA float32 tensor [m], a host list a numpy array.
+        with_hits=True: (scores, n_hit), n_hit the uint32 counts of components that fell in a valid target cell
+        (evaluate_map's n_hit).  A non-finite pose scores 0 with count 0.  In 3D every coordinate is free - z, roll and
+        pitch too, which search_map pins."""
+        if _is_dev(poses):
+            import torch
+            poses = self._pose_list(poses, poses.device)
+            m = poses.shape[0]
+            out = torch.empty(m, dtype=torch.float32, device=poses.device)
+            cnt = torch.empty(m, dtype=torch.int32, device=poses.device) if with_hits else None
+            self.wait_stream()
+            self._check(self._c.score_map_poses_dev(self._h, source._h, poses.data_ptr(), m, out.data_ptr(),
+                                                    cnt.data_ptr() if with_hits else None), "score_map_poses_dev")
+            return (out, cnt.view(torch.uint32)) if with_hits else out
+        p = self._dim.poses(poses)
+        out = np.empty(p.shape[0], dtype=np.float32)
+        cnt = np.empty(p.shape[0], dtype=np.uint32) if with_hits else None
+        self._check(self._c.score_map_poses(self._h, source._h, p.ctypes.data, p.shape[0], out.ctypes.data,
+                                            cnt.ctypes.data if with_hits else None), "score_map_poses")
+        return (out, cnt) if with_hits else out
+
+    def _best_map_poses(self, source, poses, k, min_sep, align: bool):
+        poses = self._pose_list(poses, f"cuda:{self._device}")
+        self.wait_stream()
+        hits, nh = self._hit_rows(k), C.c_int32(0)
+        args = (self._h, source._h, poses.data_ptr(), poses.shape[0], float(min_sep[0]), float(min_sep[1]), int(k),
+                C.cast(hits, C.c_void_p))
+        if not align:
+            self._check(self._c.best_map_poses_dev(*args, C.byref(nh)), "best_map_poses_dev")
+            return _hits(hits, nh.value)
+        res = (self._dim.Result * max(int(k), 1))()
+        self._check(self._c.best_map_poses_align_dev(*args, C.cast(res, C.c_void_p), C.byref(nh)), "best_map_poses_align_dev")
+        return list(zip(_hits(hits, nh.value), [self._dim.result(r) for r in res[:nh.value]]))
+
+    def best_map_poses(self, source, poses, k: int = 8, min_sep=(0.5, 0.1)):
+        """The best k (1..64) poses of the list by score_map_poses' score that lie min_sep = (translation, rotation)
+        apart (ndt2d/ndt3d_best_map_poses_dev; search.select_best restates the rule): a list of SearchHit, best first;
+        hit.index is the position in the list, hit.pose the list's row as it stands there."""
+        return self._best_map_poses(source, poses, k, min_sep, False)
+
+    def best_map_poses_align(self, source, poses, k: int = 8, min_sep=(0.5, 0.1)):
+        """best_map_poses(), then align_map() from every hit's pose in one launch chain
+        (ndt2d/ndt3d_best_map_poses_align_dev): a list of (SearchHit, AlignResult), best list score first; result q is
+        bit for bit align_map(source, hit q's pose)."""
+        return self._best_map_poses(source, poses, k, min_sep, True)
+
 
 class NdtMatcher2D(_NdtMatcher):
     """One handle = one device stream + one cached target grid (ndt2d_* of include/ndt_hip.h)."""

@@ -507,6 +507,51 @@ int32_t ndt2d_search_map_scores(ndt2d_handle* target, ndt2d_handle* source, cons
                                 float* d_scores);
 int32_t ndt2d_search_align_map(ndt2d_handle* target, ndt2d_handle* source, const ndt2d_search_window* w,
                                int32_t k, ndt2d_search_hit* hits, ndt2d_result* results, int32_t* n_hits);
+/* Scoring a map at a list of poses (docs/ALGORITHM.md section 2.21): the map-to-map score of `source` against `target`
+ * at every pose of a list of any shape, in one launch - the particles of a submap-level filter, a caller's own samples
+ * round a place-recognition hypothesis, a search over axes the lattice of ndt2d_search_map does not have.  poses is
+ * [m][3] = (x, y, theta) in double; theta need not be wrapped.
+ * Score: scores[i] is the score ndt2d_evaluate_map(target, source, poses[3i .. 3i+2]) reports - the same float32 terms per
+ * component, summed in another order; the arithmetic per component is that of ndt2d_search_map_scores with the heading's
+ * share done per pose: the angle is wrapped, its cos / sin taken in double and rounded to float32, the translation is
+ * the float of the double.  d1 and d2 are the target handle's.
+ * Hit count: n_hit[i] (may be NULL) is the number of source components whose image falls in a valid target cell: exactly
+ * ndt2d_evaluate_map's n_hit at that pose.  It tells a high score from a large overlap; its ratio to the component count
+ * (ndt2d_get_components) is the gate a loop closure wants.  Asking for it changes no score bit.
+ * A pose with a non-finite coordinate scores exactly +0.0f with n_hit 0 and never becomes a hit; so does a finite pose
+ * whose float32 form is not finite (a translation beyond float32, an angle whose wrap leaves no finite sine and cosine).
+ * No pose of a list gives a NaN.
+ * Bitwise: a pose's score and count depend on nothing but the two grids and that pose - not on its position in the list,
+ * nor on the rest of the list - and two calls give the same bits.  A list that holds the lattice of a search window in
+ * flat index order, with the axes' doubles of that lattice (angles in (-pi, pi]), gives the volume of
+ * ndt2d_search_map_scores bit for bit.
+ * Best poses: the rule of ndt2d_best_poses_dev - candidates have score > 0, the best min(#candidates, 4096) by (score
+ * descending, index ascending) are walked, a candidate is dropped when an accepted hit lies closer than min_sep_trans
+ * AND closer than min_sep_rot (both strictly), at most k (1..64) hits; hits[q].pose is the list's row bit for bit.
+ * ndt2d_best_map_poses_align_dev then refines all hits in one ndt2d_align_map_multi call: results[q] is bit for bit what
+ * ndt2d_align_map(target, source, hits[q].pose) returns; nothing is launched for zero hits.
+ * Handles, streams and state: as ndt2d_search_map - the derived data of both handles is ensured, target == source is
+ * legal, everything runs on the target's stream, behind the source's and behind an alignment in flight (which is
+ * finished first); a call returns once the outputs are complete and nothing reads the source's component list any more.
+ * The list's producer is ordered by ndt2d_wait_stream(target, ...).  Grids, parameters and later calls are untouched.
+ * Errors, found before any device call: a null handle, list or score output, m = 0, k outside 1..64, a null hits,
+ * n_hits or results, a separation that is NaN, infinite or negative: NDT_ERR_INVALID_ARG; m > 2^25: NDT_ERR_CAPACITY;
+ * no grid on either handle: NDT_ERR_NO_TARGET; overlap_grids = 4 on either handle or handles on different devices:
+ * NDT_ERR_INVALID_ARG.  A source without a component or a target without a valid cell is no error: every score is 0 and
+ * there are no hits.  *n_hits is 0 wherever it could be written. */
+int32_t ndt2d_score_map_poses_dev(ndt2d_handle* target, ndt2d_handle* source, const double* d_poses /* device, [m][3] */,
+                                  size_t m, float* d_scores /* device, [m] */, uint32_t* d_n_hit /* device, [m]; may be NULL */);
+/* the same with a host list and host outputs (staged through the target's scratch) */
+int32_t ndt2d_score_map_poses(ndt2d_handle* target, ndt2d_handle* source, const double* poses, size_t m,
+                              float* scores, uint32_t* n_hit /* may be NULL */);
+/* hits[0 .. *n_hits) (hits has room for k), best first.  Synchronous in the hits (host memory). */
+int32_t ndt2d_best_map_poses_dev(ndt2d_handle* target, ndt2d_handle* source, const double* d_poses, size_t m,
+                                 double min_sep_trans, double min_sep_rot, int32_t k, ndt2d_search_hit* hits,
+                                 int32_t* n_hits);
+/* ndt2d_best_map_poses_dev, then ndt2d_align_map_multi from the hits' poses (results has room for k) */
+int32_t ndt2d_best_map_poses_align_dev(ndt2d_handle* target, ndt2d_handle* source, const double* d_poses, size_t m,
+                                       double min_sep_trans, double min_sep_rot, int32_t k, ndt2d_search_hit* hits,
+                                       ndt2d_result* results, int32_t* n_hits);
 /* The components of a handle's cached grid, as host copies: mean_xy [2n], cov_abc [3n] = (Sxx, Sxy, Syy), key [n] =
  * iy * width + ix, ascending.  Any pointer may be NULL; *n (if given) is the count, also when capacity is too small
  * for the arrays asked for (NDT_ERR_CAPACITY). */
@@ -966,6 +1011,26 @@ int32_t ndt3d_search_map_scores(ndt3d_handle* target, ndt3d_handle* source, cons
                                 float* d_scores);
 int32_t ndt3d_search_align_map(ndt3d_handle* target, ndt3d_handle* source, const ndt3d_search_window* w,
                                int32_t k, ndt3d_search_hit* hits, ndt3d_result* results, int32_t* n_hits);
+/* Scoring a 3D map at a list of poses (docs/ALGORITHM.md section 2.21), the twin of ndt2d_score_map_poses*: poses is
+ * [m][6] = (tx, ty, tz, roll, pitch, yaw) in double, angles not necessarily wrapped - z, roll and pitch are free here,
+ * where ndt3d_search_map pins them: the loop closure between two submaps of unknown relative height and tilt.
+ * scores[i] is the score and n_hit[i] the n_hit ndt3d_evaluate_map reports at poses[6i .. 6i+5]; a non-finite pose, a
+ * translation beyond float32 or a non-finite entry of R scores exactly +0.0f with n_hit 0.  A list that holds the lattice
+ * of an ndt3d_search_map window in flat index order, rows (x, y, center[2], center[3], center[4], yaw) with the axes'
+ * doubles, gives the volume of ndt3d_search_map_scores bit for bit.  The separation of the best poses is Euclidean over
+ * x, y, z and the largest wrapped difference of the three angles, as for ndt3d_best_poses_dev.
+ * ndt3d_best_map_poses_align_dev refines the hits in one ndt3d_align_map_multi call.  Handles, streams, state and errors:
+ * as ndt2d_score_map_poses*. */
+int32_t ndt3d_score_map_poses_dev(ndt3d_handle* target, ndt3d_handle* source, const double* d_poses /* device, [m][6] */,
+                                  size_t m, float* d_scores /* device, [m] */, uint32_t* d_n_hit /* device, [m]; may be NULL */);
+int32_t ndt3d_score_map_poses(ndt3d_handle* target, ndt3d_handle* source, const double* poses, size_t m,
+                              float* scores, uint32_t* n_hit /* may be NULL */);
+int32_t ndt3d_best_map_poses_dev(ndt3d_handle* target, ndt3d_handle* source, const double* d_poses, size_t m,
+                                 double min_sep_trans, double min_sep_rot, int32_t k, ndt3d_search_hit* hits,
+                                 int32_t* n_hits);
+int32_t ndt3d_best_map_poses_align_dev(ndt3d_handle* target, ndt3d_handle* source, const double* d_poses, size_t m,
+                                       double min_sep_trans, double min_sep_rot, int32_t k, ndt3d_search_hit* hits,
+                                       ndt3d_result* results, int32_t* n_hits);
 /* The components of a handle's cached voxel grid, as host copies: mean_xyz [3n], cov6 [6n] = (xx xy xz yy yz zz) of the
  * regularised covariance, key [n] = (iz * height + iy) * width + ix, ascending.  Any pointer may be NULL; *n (if given) is
  * the count, also when capacity is too small for the arrays asked for (NDT_ERR_CAPACITY). */

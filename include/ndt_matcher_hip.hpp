@@ -398,6 +398,43 @@ class NdtMatcherHip {
     for (int32_t i = 0; i < n_hits; ++i) out.push_back(SearchMatch{to_search_hit(hits[i]), to_match_result(r[i], mode_)});
     return out;
   }
+  // evaluateMap's score at every pose of a list in one launch (ndt2d_score_map_poses_dev; contract: ndt_hip.h): d_poses is
+  // [m][3] = (x, y, theta) in double, d_scores [m] floats, d_n_hit [m] counts of components that fell in a valid cell (may
+  // be null), all device memory - the particles of a submap-level filter, samples round a place-recognition hypothesis.
+  // A non-finite pose scores 0.  producer_stream: the stream that wrote the list.
+  void scoreMapPosesDev(NdtMatcherHip& source, const double* d_poses, size_t m, float* d_scores, uint32_t* d_n_hit,
+                        void* producer_stream, bool complete = false) {
+    if (!complete) check(ndt2d_wait_stream(h_, producer_stream), "ndt2d_wait_stream");
+    check(ndt2d_score_map_poses_dev(h_, source.h_, d_poses, m, d_scores, d_n_hit), "ndt2d_score_map_poses_dev");
+  }
+  // the best k (1..64) well-separated poses of the list, best first (ndt2d_best_map_poses_dev): hit.index is the position
+  // in the list, hit.pose the list's pose as it stands there
+  std::vector<SearchHit> bestMapPosesDev(NdtMatcherHip& source, const double* d_poses, size_t m, int k, double min_sep_trans,
+                                         double min_sep_rot, void* producer_stream, bool complete = false) {
+    if (!complete) check(ndt2d_wait_stream(h_, producer_stream), "ndt2d_wait_stream");
+    std::vector<ndt2d_search_hit> hits(k > 0 ? (size_t)k : 1);
+    int32_t n_hits = 0;
+    check(ndt2d_best_map_poses_dev(h_, source.h_, d_poses, m, min_sep_trans, min_sep_rot, (int32_t)k, hits.data(), &n_hits),
+          "ndt2d_best_map_poses_dev");
+    std::vector<SearchHit> out;
+    for (int32_t i = 0; i < n_hits; ++i) out.push_back(to_search_hit(hits[i]));
+    return out;
+  }
+  // bestMapPosesDev, then alignMap from every hit in one launch chain (ndt2d_best_map_poses_align_dev): result i is bit
+  // for bit what alignMap returns from hit i's pose
+  std::vector<SearchMatch> bestMapPosesAlignDev(NdtMatcherHip& source, const double* d_poses, size_t m, int k,
+                                                double min_sep_trans, double min_sep_rot, void* producer_stream,
+                                                bool complete = false) {
+    if (!complete) check(ndt2d_wait_stream(h_, producer_stream), "ndt2d_wait_stream");
+    std::vector<ndt2d_search_hit> hits(k > 0 ? (size_t)k : 1);
+    std::vector<ndt2d_result> r(hits.size());
+    int32_t n_hits = 0;
+    check(ndt2d_best_map_poses_align_dev(h_, source.h_, d_poses, m, min_sep_trans, min_sep_rot, (int32_t)k, hits.data(), r.data(),
+                                         &n_hits), "ndt2d_best_map_poses_align_dev");
+    std::vector<SearchMatch> out;
+    for (int32_t i = 0; i < n_hits; ++i) out.push_back(SearchMatch{to_search_hit(hits[i]), to_match_result(r[i], mode_)});
+    return out;
+  }
   ndt2d_handle* raw() { return h_; }
 
  private:
@@ -933,6 +970,40 @@ class NdtMatcherHip3 {
     std::vector<ndt3d_result> r(hits.size());
     int32_t n_hits = 0;
     check(ndt3d_search_align_map(h_, source.h_, &window, (int32_t)k, hits.data(), r.data(), &n_hits), "ndt3d_search_align_map");
+    std::vector<SearchMatch> out;
+    for (int32_t i = 0; i < n_hits; ++i) out.push_back(SearchMatch{toSearchHit(hits[i]), toMatchResult(r[i])});
+    return out;
+  }
+  // evaluateMap's score at every pose of a list in one launch (ndt3d_score_map_poses_dev), as
+  // NdtMatcherHip::scoreMapPosesDev: d_poses is [m][6] = (tx, ty, tz, roll, pitch, yaw) in double - z, roll and pitch are
+  // free here, where searchMap pins them: two submaps of unknown relative height and tilt.
+  void scoreMapPosesDev(NdtMatcherHip3& source, const double* d_poses, size_t m, float* d_scores, uint32_t* d_n_hit,
+                        void* producer_stream, bool complete = false) {
+    if (!complete) check(ndt3d_wait_stream(h_, producer_stream), "ndt3d_wait_stream");
+    check(ndt3d_score_map_poses_dev(h_, source.h_, d_poses, m, d_scores, d_n_hit), "ndt3d_score_map_poses_dev");
+  }
+  // the best k (1..64) well-separated poses of the list, best first (ndt3d_best_map_poses_dev)
+  std::vector<SearchHit> bestMapPosesDev(NdtMatcherHip3& source, const double* d_poses, size_t m, int k, double min_sep_trans,
+                                         double min_sep_rot, void* producer_stream, bool complete = false) {
+    if (!complete) check(ndt3d_wait_stream(h_, producer_stream), "ndt3d_wait_stream");
+    std::vector<ndt3d_search_hit> hits(k > 0 ? (size_t)k : 1);
+    int32_t n_hits = 0;
+    check(ndt3d_best_map_poses_dev(h_, source.h_, d_poses, m, min_sep_trans, min_sep_rot, (int32_t)k, hits.data(), &n_hits),
+          "ndt3d_best_map_poses_dev");
+    std::vector<SearchHit> out;
+    for (int32_t i = 0; i < n_hits; ++i) out.push_back(toSearchHit(hits[i]));
+    return out;
+  }
+  // bestMapPosesDev, then alignMap from every hit in one launch chain (ndt3d_best_map_poses_align_dev)
+  std::vector<SearchMatch> bestMapPosesAlignDev(NdtMatcherHip3& source, const double* d_poses, size_t m, int k,
+                                                double min_sep_trans, double min_sep_rot, void* producer_stream,
+                                                bool complete = false) {
+    if (!complete) check(ndt3d_wait_stream(h_, producer_stream), "ndt3d_wait_stream");
+    std::vector<ndt3d_search_hit> hits(k > 0 ? (size_t)k : 1);
+    std::vector<ndt3d_result> r(hits.size());
+    int32_t n_hits = 0;
+    check(ndt3d_best_map_poses_align_dev(h_, source.h_, d_poses, m, min_sep_trans, min_sep_rot, (int32_t)k, hits.data(), r.data(),
+                                         &n_hits), "ndt3d_best_map_poses_align_dev");
     std::vector<SearchMatch> out;
     for (int32_t i = 0; i < n_hits; ++i) out.push_back(SearchMatch{toSearchHit(hits[i]), toMatchResult(r[i])});
     return out;
