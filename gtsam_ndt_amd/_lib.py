@@ -30,7 +30,7 @@ NDT_ERR_RCCL = -7
 TUNING = {"launch_graphs": 1, "wide_threshold": 2, "short_scan_kernel": 3, "chunk_launches": 4, "binned_build": 5,
           "batch_small_variant": 6, "split_from": 8, "single_sync_build": 9,
           "batch_global_workgroups": 10, "async_lanes": 11, "map_multi_from": 12, "fused_begin": 13,
-          "lane_fork": 14, "async_chains": 15}
+          "lane_fork": 14, "async_chains": 15, "particle_team": 16}
 
 HESSIAN_GAUSS_NEWTON = 0
 HESSIAN_NEWTON = 1
@@ -197,12 +197,18 @@ SIGNATURES = {
                                            C.POINTER(C.c_int32)]),
     "ndt2d_score_poses_dev": (C.c_int32, [_vp, _vp, _vp, C.c_size_t, _vp, C.c_size_t, _vp]),
     "ndt2d_score_poses": (C.c_int32, [_vp, _vp, _vp, C.c_size_t, _vp, C.c_size_t, _vp]),
+    "ndt2d_score_particles_dev": (C.c_int32, [_vp, _vp, _vp, C.c_size_t, _vp, C.c_size_t, _vp, _vp]),
+    "ndt2d_score_particles_async": (C.c_int32, [_vp, _vp, _vp, C.c_size_t, _vp, C.c_size_t, _vp, _vp]),
+    "ndt2d_score_particles": (C.c_int32, [_vp, _vp, _vp, C.c_size_t, _vp, C.c_size_t, _vp, _vp]),
     "ndt2d_best_poses_dev": (C.c_int32, [_vp, _vp, _vp, C.c_size_t, _vp, C.c_size_t, C.c_double, C.c_double, C.c_int32, _vp,
                                          C.POINTER(C.c_int32)]),
     "ndt2d_best_poses_align_dev": (C.c_int32, [_vp, _vp, _vp, C.c_size_t, _vp, C.c_size_t, C.c_double, C.c_double, C.c_int32,
                                                _vp, _vp, C.POINTER(C.c_int32)]),
     "ndt3d_score_poses_dev": (C.c_int32, [_vp, _vp, _vp, _vp, C.c_size_t, _vp, C.c_size_t, _vp]),
     "ndt3d_score_poses": (C.c_int32, [_vp, _vp, _vp, _vp, C.c_size_t, _vp, C.c_size_t, _vp]),
+    "ndt3d_score_particles_dev": (C.c_int32, [_vp, _vp, _vp, _vp, C.c_size_t, _vp, C.c_size_t, _vp, _vp]),
+    "ndt3d_score_particles_async": (C.c_int32, [_vp, _vp, _vp, _vp, C.c_size_t, _vp, C.c_size_t, _vp, _vp]),
+    "ndt3d_score_particles": (C.c_int32, [_vp, _vp, _vp, _vp, C.c_size_t, _vp, C.c_size_t, _vp, _vp]),
     "ndt3d_best_poses_dev": (C.c_int32, [_vp, _vp, _vp, _vp, C.c_size_t, _vp, C.c_size_t, C.c_double, C.c_double, C.c_int32,
                                          _vp, C.POINTER(C.c_int32)]),
     "ndt3d_best_poses_align_dev": (C.c_int32, [_vp, _vp, _vp, _vp, C.c_size_t, _vp, C.c_size_t, C.c_double, C.c_double,

@@ -102,6 +102,7 @@ struct ndt2d_handle {
   bool use_graph = true;
   int check_every = 8;                     // converged mode: launches per chunk
   bool fused_begin = true;                 // NDT_TUNE_FUSED_BEGIN: launch 0 of a single-scan chain is k_iterate_first (no k_begin)
+  int particle_team = 0;                   // NDT_TUNE_PARTICLE_TEAM: lanes per pose of ndt2d_score_particles*, 0 = by the list's length
   SearchScratch srch;                      // exhaustive pose search scratch (ndt_search.hpp), allocated on first use
   PointFitScratch fit;                     // per-point fit and selection scratch (ndt_point_fit.hpp), allocated on first use
   // map-to-map alignment (ndt_map_host.hpp, ndt2d_d2d_api.hpp), allocated on first use; both caches follow the grid (grid_changed)
@@ -1124,6 +1125,7 @@ int32_t ndt2d_set_tuning(ndt2d_handle* h, int32_t knob, int64_t value) {
     case NDT_TUNE_FUSED_BEGIN: if (value != 0 && value != 1) return NDT_ERR_INVALID_ARG; h->fused_begin = value != 0; return NDT_OK;
     // (finish_chunk_run above has made the lanes stale, so the first round under either protocol forks)
     case NDT_TUNE_LANE_FORK: if (value != 0 && value != 1) return NDT_ERR_INVALID_ARG; h->fork_every_pair = value != 0; return NDT_OK;
+    case NDT_TUNE_PARTICLE_TEAM: if (value != 0 && value != 64 && value != 256) return NDT_ERR_INVALID_ARG; h->particle_team = (int)value; return NDT_OK;
     default: return NDT_ERR_INVALID_ARG;
   }
 }
@@ -1496,6 +1498,7 @@ extern "C" int32_t ndt2d_align_multi_scan_dev(ndt2d_handle* h, const float* cons
 #include "ndt2d_search.hpp"
 #include "ndt3d_search.hpp"
 #include "ndt_score_poses.hpp"
+#include "ndt_score_particles.hpp"
 #include "ndt2d_d2d_api.hpp"
 #include "ndt2d_d2d_search.hpp"
 #include "ndt3d_d2d_api.hpp"

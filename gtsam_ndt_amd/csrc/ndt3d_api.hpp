@@ -62,6 +62,7 @@ struct ndt3d_handle {
   int map_multi_from = 2;                                 // ndt3d_align_map_multi calls of this many starts use one chain (NDT_TUNE_MAP_MULTI_FROM)
   bool fused_begin = true;                                // NDT_TUNE_FUSED_BEGIN: launch 0 of a chain is k_iterate3_first (no k_begin3)
   hipEvent_t map_ev = nullptr;                            // orders a target handle's stream behind this handle's (order_after)
+  int particle_team = 0;                                  // NDT_TUNE_PARTICLE_TEAM: lanes per pose of ndt3d_score_particles*, 0 = by the list's length
 };
 
 namespace {
@@ -649,6 +650,7 @@ int32_t ndt3d_set_tuning(ndt3d_handle* h, int32_t knob, int64_t value) {
     case NDT_TUNE_MAP_MULTI_FROM: if (value < 1 || value > ndt::kMaxStarts3 + 1) return NDT_ERR_INVALID_ARG; h->map_multi_from = (int)value; return NDT_OK;
     // takes effect with the next alignment; an alignment in flight keeps the protocol it began with
     case NDT_TUNE_FUSED_BEGIN: if (value != 0 && value != 1) return NDT_ERR_INVALID_ARG; h->fused_begin = value != 0; return NDT_OK;
+    case NDT_TUNE_PARTICLE_TEAM: if (value != 0 && value != 64 && value != 256) return NDT_ERR_INVALID_ARG; h->particle_team = (int)value; return NDT_OK;
     default: return NDT_ERR_INVALID_ARG;
   }
 }

@@ -629,6 +629,36 @@ class _NdtMatcher(_Handle):
                                         out.ctypes.data), "score_poses")
         return out
 
+    def _score_particles(self, coords, poses, with_hits: bool, sync: bool):
+        """score_particles() of both matchers (ndt2d/ndt3d_score_particles*): a team of lanes per pose, the hit counts,
+        and with sync=False the asynchronous call with torch's current stream ordered behind the handle's."""
+        if _is_dev(coords[0]) != _is_dev(poses):
+            raise ValueError("the scan and the poses must both be CUDA tensors or both be host arrays")
+        if _is_dev(poses):
+            import torch
+            poses = self._pose_list(poses, coords[0].device)
+            n, m = coords[0].numel(), poses.shape[0]
+            out = torch.empty(m, dtype=torch.float32, device=poses.device)
+            cnt = torch.empty(m, dtype=torch.int32, device=poses.device) if with_hits else None
+            args = (self._h, *_dev_ptrs(coords, n), n, poses.data_ptr(), m, out.data_ptr(), cnt.data_ptr() if with_hits else None)
+            self.wait_stream()
+            if sync:
+                self._check(self._c.score_particles_dev(*args), "score_particles_dev")
+            else:
+                self._check(self._c.score_particles_async(*args), "score_particles_async")
+                # torch's current stream behind the handle's: the outputs can be consumed there in order, and the caching
+                # allocator does not hand the scan, the list or the outputs out again before the launch has read them
+                _torch_stream().wait_stream(torch.cuda.ExternalStream(self.stream))
+            return (out, cnt.view(torch.uint32)) if with_hits else out
+        if not sync:
+            raise ValueError("sync=False takes CUDA tensors: host arrays are staged and fetched by a synchronous call")
+        a, p = _host_coords(coords), self._dim.poses(poses)
+        out = np.empty(p.shape[0], dtype=np.float32)
+        cnt = np.empty(p.shape[0], dtype=np.uint32) if with_hits else None
+        self._check(self._c.score_particles(self._h, *[c.ctypes.data for c in a], a[0].size, p.ctypes.data, p.shape[0],
+                                            out.ctypes.data, cnt.ctypes.data if with_hits else None), "score_particles")
+        return (out, cnt) if with_hits else out
+
     def _best_poses(self, coords, poses, k, min_sep, align: bool):
         coords = self._on_device(coords)
         poses = self._pose_list(poses, coords[0].device)
@@ -820,6 +850,17 @@ class NdtMatcher2D(_NdtMatcher):
         non-finite coordinate scores 0."""
         return self._score_poses((sx, sy), poses)
 
+    def score_particles(self, sx, sy, poses, with_hits: bool = False, sync: bool = True):
+        """score_poses() for SHORT lists - a particle filter's few hundred to few thousand particles - with a team of 64
+        or 256 lanes per pose instead of one lane (ndt2d_score_particles*; tuning knob "particle_team").  It was the faster
+        call at every list size measured, 256 to 1 048 576 poses (4096 particles: 4x in 2D, 17x in 3D): no
+        size was found from which score_poses is faster, which remains for the search volume's bits.  The scores differ from score_poses' only by the
+        order of the float32 sum (docs/ALGORITHM.md), and depend on nothing but the grid, the scan and the pose.  Inputs as
+        score_poses.  with_hits=True: (scores, n_hit), n_hit the uint32 counts of lookups that hit a valid cell -
+        evaluate()'s n_hit at that pose.  sync=False (CUDA tensors only) returns after the enqueue, with torch's current
+        stream ordered behind the handle's: the result is consumed in torch order, with no host synchronisation."""
+        return self._score_particles((sx, sy), poses, with_hits, sync)
+
     def best_poses(self, sx, sy, poses, k: int = 8, min_sep=(0.5, 0.1)):
         """The best k (1..64) well-separated poses of the list by score (ndt2d_best_poses_dev; search.select_best
         restates the rule): a list of SearchHit, best first, whose index is the pose's position in the list.  The hits
@@ -923,6 +964,11 @@ class NdtMatcher3D(_NdtMatcher):
         (ndt3d_score_poses*), as NdtMatcher2D.score_poses: all six coordinates are free, so the list covers what the
         lattice search pins."""
         return self._score_poses((sx, sy, sz), poses)
+
+    def score_particles(self, sx, sy, sz, poses, with_hits: bool = False, sync: bool = True):
+        """score_poses() for short lists, a team of lanes per pose, with hit counts and an asynchronous form
+        (ndt3d_score_particles*), as NdtMatcher2D.score_particles: the faster call at every list size measured."""
+        return self._score_particles((sx, sy, sz), poses, with_hits, sync)
 
     def best_poses(self, sx, sy, sz, poses, k: int = 8, min_sep=(0.5, 0.1)):
         """The best k (1..64) well-separated poses of the list (ndt3d_best_poses_dev): translation distance over

@@ -451,6 +451,40 @@ int32_t ndt2d_best_poses_dev(ndt2d_handle* h, const float* d_sx, const float* d_
 int32_t ndt2d_best_poses_align_dev(ndt2d_handle* h, const float* d_sx, const float* d_sy, size_t n,
                                    const double* d_poses, size_t m, double min_sep_trans, double min_sep_rot, int32_t k,
                                    ndt2d_search_hit* hits, ndt2d_result* results, int32_t* n_hits);
+/* Scoring particles (docs/ALGORITHM.md "Scoring particles: a team of lanes per pose"): ndt2d_score_poses_dev for SHORT
+ * lists - the few hundred to few thousand particles of a particle filter - with the hit count beside the score and an
+ * asynchronous form.  Where ndt2d_score_poses_dev gives every pose one lane, which walks the whole scan, these give every
+ * pose a team of 64 or 256 lanes, which share the scan's points between them.
+ * Score: the pose is formed as ndt2d_score_poses_dev forms it, and every point's term is that call's bit for bit (NaN
+ * points add nothing, a non-finite pose or one whose float32 form is not finite scores exactly +0.0f with count 0, no
+ * score is NaN).  scores[i] differs from ndt2d_score_poses_dev's ONLY by the order of the float32 summation, which is
+ * the one ALGORITHM states over 256 virtual lanes (per-lane sums in point order, a fixed pairing of the four quarters, a
+ * xor butterfly over 64 lanes).  Both sums add the same n * overlap_grids non-negative terms, so they agree to within
+ * 2 * n * overlap_grids * 2^-24 relative, and bit for bit for n <= 2.
+ * n_hit[i] (d_n_hit may be NULL: not written) is the number of (point, grid) lookups that hit a valid cell: exactly what
+ * ndt2d_evaluate_dev reports as n_hit at that pose - what tells a good fit from a small overlap.
+ * Bitwise: a score and a count depend on nothing but the handle's grid, the scan and that pose - not on the pose's
+ * position in the list, not on the list's length, not on the team width (NDT_TUNE_PARTICLE_TEAM) - and two calls give the
+ * same bits.
+ * Which call: ndt2d_score_particles* for every list that does not need ndt2d_score_poses_dev's bits.  Measured (DESIGN
+ * 5.19, MI355X, host to host) it is the faster call at every list size from 256 to 1 048 576 poses, in 2D and in 3D: 4096
+ * particles take 0.05 ms against 0.22 ms (2D, 1440 points) and 0.20 ms against 3.5 ms (3D, 16 384 points); from 65 536
+ * poses on, where one lane per pose fills the device too, it keeps an edge of 1.3x to 1.5x.  No list size was found from
+ * which ndt2d_score_poses_dev is faster.  That call remains the one whose scores are the search volume's bit for bit, and
+ * the one ndt2d_best_poses* select from.
+ * _dev: on the handle's stream, behind an asynchronous alignment in flight (which is finished first); returns when the
+ * outputs are complete.  Argument checks and error codes are those of ndt2d_score_poses_dev.
+ * _async: the same checks and the same launch, returning after the enqueue: the outputs are complete in stream order on
+ * ndt2d_stream(h), and the scan, the list and the outputs must stay alive until then.  Producers on other streams are
+ * ordered with ndt2d_wait_stream, as for every device entry point.
+ * ndt2d_score_particles: host scan, host list, host scores and counts (staged through the handle's scratch). */
+int32_t ndt2d_score_particles_dev(ndt2d_handle* h, const float* d_sx, const float* d_sy, size_t n,
+                                  const double* d_poses /* device, [m][3] */, size_t m, float* d_scores /* device, [m] */,
+                                  uint32_t* d_n_hit /* device, [m], may be NULL */);
+int32_t ndt2d_score_particles_async(ndt2d_handle* h, const float* d_sx, const float* d_sy, size_t n,
+                                    const double* d_poses, size_t m, float* d_scores, uint32_t* d_n_hit);
+int32_t ndt2d_score_particles(ndt2d_handle* h, const float* sx, const float* sy, size_t n,
+                              const double* poses, size_t m, float* scores, uint32_t* n_hit /* may be NULL */);
 /* ---- map-to-map alignment (distribution-to-distribution NDT; docs/ALGORITHM.md section 2.13) ----------------
  * Aligns the cached grid of `source` to the cached grid of `target` without any of the points either was built from:
  * what a handle keeps after ndt2d_add_target_points_dev, and all that ndt2d_save_map / ndt2d_load_map persist, is
@@ -595,6 +629,12 @@ int32_t ndt2d_get_components(ndt2d_handle* h, float* mean_xy, float* cov_abc, in
  *                               converged call, a tuning change) precedes a round of them, and run their alignments back
  *                               to back otherwise; 1: each waits for the head of the round's first call at every round.  Other values:
  *                               NDT_ERR_INVALID_ARG.  Results are bit-identical either way.  ndt2d_set_tuning only
+ *   NDT_TUNE_PARTICLE_TEAM      lanes per pose of ndt2d_score_particles*: 0 (default): 256 (one workgroup per pose) for lists
+ *                               of fewer than 2048 poses and 64 (one wave per pose) from there on - below 256 CUs x 4
+ *                               SIMDs = 1024 poses one wave per pose leaves SIMDs empty, and the wide team was measured
+ *                               ahead up to 1024 and behind from 2048; 64 or 256: that width for every list.
+ *                               Other values: NDT_ERR_INVALID_ARG.  Scores and counts are bit-identical either way.  The
+ *                               same knob on ndt3d_set_tuning for ndt3d_score_particles*
  *   NDT_TUNE_BATCH_SMALL_VARIANT (batch contexts) 1 (default): lidar-sized pairs run on the 256-thread
  *                               variant of the batch kernel first; 0: every pair on the 1024-thread one
  *   NDT_TUNE_BATCH_GLOBAL_WORKGROUPS (batch contexts, 2D and 3D) workgroups of the global-table variant, each with its own
@@ -619,7 +659,8 @@ enum {
   NDT_TUNE_MAP_MULTI_FROM = 12,
   NDT_TUNE_FUSED_BEGIN = 13,
   NDT_TUNE_LANE_FORK = 14,
-  NDT_TUNE_ASYNC_CHAINS = 15
+  NDT_TUNE_ASYNC_CHAINS = 15,
+  NDT_TUNE_PARTICLE_TEAM = 16
 };
 int32_t ndt2d_set_tuning(ndt2d_handle* h, int32_t knob, int64_t value);
 /* hipStream_t the handle enqueues on (as void*), for event timing by the caller */
@@ -945,6 +986,22 @@ int32_t ndt3d_best_poses_dev(ndt3d_handle* h, const float* d_sx, const float* d_
 int32_t ndt3d_best_poses_align_dev(ndt3d_handle* h, const float* d_sx, const float* d_sy, const float* d_sz, size_t n,
                                    const double* d_poses, size_t m, double min_sep_trans, double min_sep_rot, int32_t k,
                                    ndt3d_search_hit* hits, ndt3d_result* results, int32_t* n_hits);
+/* Scoring 3D particles (docs/ALGORITHM.md "Scoring particles: a team of lanes per pose"), the twin of
+ * ndt2d_score_particles*: a team of 64 or 256 lanes per pose of a short list, the hit count beside the score, an
+ * asynchronous form.  poses is [m][6] = (tx, ty, tz, roll, pitch, yaw) in double.  The pose and every point's term are
+ * ndt3d_score_poses_dev's bit for bit; the score differs from that call's only by the summation order, which is the one
+ * ALGORITHM states over 256 virtual lanes; n_hit[i] is what ndt3d_evaluate_dev reports as n_hit at that pose.  A score and
+ * a count depend on nothing but the grid, the scan and the pose - not on the position in the list, the list's length or
+ * the team width - and two calls give the same bits.  They are the faster calls at every list size measured (DESIGN
+ * 5.19); ndt3d_score_poses_dev remains for the search volume's bits and for ndt3d_best_poses*.  Streams, the asynchronous form's contract and the errors are those of the 2D calls
+ * (ndt3d_stream, ndt3d_wait_stream). */
+int32_t ndt3d_score_particles_dev(ndt3d_handle* h, const float* d_sx, const float* d_sy, const float* d_sz, size_t n,
+                                  const double* d_poses /* device, [m][6] */, size_t m, float* d_scores /* device, [m] */,
+                                  uint32_t* d_n_hit /* device, [m], may be NULL */);
+int32_t ndt3d_score_particles_async(ndt3d_handle* h, const float* d_sx, const float* d_sy, const float* d_sz, size_t n,
+                                    const double* d_poses, size_t m, float* d_scores, uint32_t* d_n_hit);
+int32_t ndt3d_score_particles(ndt3d_handle* h, const float* sx, const float* sy, const float* sz, size_t n,
+                              const double* poses, size_t m, float* scores, uint32_t* n_hit /* may be NULL */);
 /* Per-iteration trace, as ndt2d_align_trace (debugging and stage-by-stage parity checks; never on a timed path):
  * rows[j], j < *n_rows <= capacity, is the state after j + 1 updates - the pose after them, H / g / score / n_hit
  * of the evaluation that produced the (j+1)-th update.  out (may be NULL): the final result.  Host arrays. */
@@ -1047,6 +1104,7 @@ int32_t ndt3d_wait_stream(ndt3d_handle* h, void* producer_stream);
  *                               never the shared chain; other values NDT_ERR_INVALID_ARG).  Results are bit-identical
  *                               either way.
  *   NDT_TUNE_FUSED_BEGIN        as on ndt2d_set_tuning, for ndt3d_align* (k_iterate3_first against k_begin3; default 1)
+ *   NDT_TUNE_PARTICLE_TEAM      as on ndt2d_set_tuning, for ndt3d_score_particles* (0, 64 or 256; default 0)
  * Other knobs: NDT_ERR_INVALID_ARG. */
 int32_t ndt3d_set_tuning(ndt3d_handle* h, int32_t knob, int64_t value);
 

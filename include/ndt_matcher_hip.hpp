@@ -261,6 +261,27 @@ class NdtMatcherHip {
     if (!complete) check(ndt2d_wait_stream(h_, producer_stream), "ndt2d_wait_stream");
     check(ndt2d_score_poses_dev(h_, d_sx, d_sy, n, d_poses, m, d_scores), "ndt2d_score_poses_dev");
   }
+  // the handle's stream (hipStream_t as void*): what scoreParticlesAsync's outputs are ordered on
+  void* stream() { return ndt2d_stream(h_); }
+  // scorePosesDev for SHORT lists (a particle filter's particles; the faster call at every size measured): a team of lanes per pose
+  // (ndt2d_score_particles_dev; contract: ndt_hip.h).  d_n_hit [m] (may be null): the lookups that hit a valid cell,
+  // evaluate's n_hit at that pose.  The scores differ from scorePosesDev's only by the order of the float32 sum.
+  void scoreParticlesDev(const float* d_sx, const float* d_sy, size_t n, const double* d_poses, size_t m, float* d_scores,
+                         uint32_t* d_n_hit, void* producer_stream, bool complete = false) {
+    if (!complete) check(ndt2d_wait_stream(h_, producer_stream), "ndt2d_wait_stream");
+    check(ndt2d_score_particles_dev(h_, d_sx, d_sy, n, d_poses, m, d_scores, d_n_hit), "ndt2d_score_particles_dev");
+  }
+  // the same, returning after the enqueue (ndt2d_score_particles_async): the outputs are complete in stream order on
+  // stream() (ndt2d_stream); the scan, the list and the outputs stay alive until then
+  void scoreParticlesAsync(const float* d_sx, const float* d_sy, size_t n, const double* d_poses, size_t m, float* d_scores,
+                           uint32_t* d_n_hit, void* producer_stream, bool complete = false) {
+    if (!complete) check(ndt2d_wait_stream(h_, producer_stream), "ndt2d_wait_stream");
+    check(ndt2d_score_particles_async(h_, d_sx, d_sy, n, d_poses, m, d_scores, d_n_hit), "ndt2d_score_particles_async");
+  }
+  // the same with host arrays (ndt2d_score_particles); n_hit may be null
+  void scoreParticles(const float* sx, const float* sy, size_t n, const double* poses, size_t m, float* scores, uint32_t* n_hit) {
+    check(ndt2d_score_particles(h_, sx, sy, n, poses, m, scores, n_hit), "ndt2d_score_particles");
+  }
   // the best k (1..64) well-separated poses of the list, best first (ndt2d_best_poses_dev): hit.index is the position in
   // the list, hit.pose the list's pose as it stands there
   std::vector<SearchHit> bestPosesDev(const float* d_sx, const float* d_sy, size_t n, const double* d_poses, size_t m, int k,
@@ -859,6 +880,25 @@ class NdtMatcherHip3 {
                      float* d_scores, void* producer_stream, bool complete = false) {
     if (!complete) check(ndt3d_wait_stream(h_, producer_stream), "ndt3d_wait_stream");
     check(ndt3d_score_poses_dev(h_, d_sx, d_sy, d_sz, n, d_poses, m, d_scores), "ndt3d_score_poses_dev");
+  }
+  void* stream() { return ndt3d_stream(h_); }
+  // scorePosesDev for SHORT lists, a team of lanes per pose, with the hit counts (ndt3d_score_particles_dev), as
+  // NdtMatcherHip::scoreParticlesDev; d_n_hit may be null
+  void scoreParticlesDev(const float* d_sx, const float* d_sy, const float* d_sz, size_t n, const double* d_poses, size_t m,
+                         float* d_scores, uint32_t* d_n_hit, void* producer_stream, bool complete = false) {
+    if (!complete) check(ndt3d_wait_stream(h_, producer_stream), "ndt3d_wait_stream");
+    check(ndt3d_score_particles_dev(h_, d_sx, d_sy, d_sz, n, d_poses, m, d_scores, d_n_hit), "ndt3d_score_particles_dev");
+  }
+  // the same, returning after the enqueue (ndt3d_score_particles_async): complete in stream order on stream() (ndt3d_stream)
+  void scoreParticlesAsync(const float* d_sx, const float* d_sy, const float* d_sz, size_t n, const double* d_poses, size_t m,
+                           float* d_scores, uint32_t* d_n_hit, void* producer_stream, bool complete = false) {
+    if (!complete) check(ndt3d_wait_stream(h_, producer_stream), "ndt3d_wait_stream");
+    check(ndt3d_score_particles_async(h_, d_sx, d_sy, d_sz, n, d_poses, m, d_scores, d_n_hit), "ndt3d_score_particles_async");
+  }
+  // the same with host arrays (ndt3d_score_particles); n_hit may be null
+  void scoreParticles(const float* sx, const float* sy, const float* sz, size_t n, const double* poses, size_t m, float* scores,
+                      uint32_t* n_hit) {
+    check(ndt3d_score_particles(h_, sx, sy, sz, n, poses, m, scores, n_hit), "ndt3d_score_particles");
   }
   // the best k (1..64) well-separated poses of the list (ndt3d_best_poses_dev): translation distance over (x, y, z),
   // rotation distance the largest wrapped difference of roll, pitch and yaw
