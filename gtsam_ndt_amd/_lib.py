@@ -284,6 +284,17 @@ SIGNATURES = {
     "ndt3d_reserve_target": (C.c_int32, [_vp, _dp, _dp]),
     "ndt3d_range_image_to_points_dev": (C.c_int32, [_vp, C.c_int32, C.c_int32, _dp, C.c_double, C.c_double, C.c_double,
                                                     C.c_double, _vp, _vp, _vp, _vp]),
+    "ndt2d_sweep_motion": (C.c_int32, [_dp, _dp, _dp]),
+    "ndt3d_sweep_motion": (C.c_int32, [_dp, _dp, _dp]),
+    "ndt2d_motion_twist": (C.c_int32, [_dp, _dp]),
+    "ndt3d_motion_twist": (C.c_int32, [_dp, _dp]),
+    "ndt2d_polar_to_points_deskew_dev": (C.c_int32, [_vp, C.c_size_t, C.c_double, C.c_double, C.c_double, C.c_double, _dp,
+                                                     C.c_double, C.c_double, C.c_double, _vp, _vp, _vp]),
+    "ndt3d_range_image_to_points_deskew_dev": (C.c_int32, [_vp, C.c_int32, C.c_int32, _dp, C.c_double, C.c_double, C.c_double,
+                                                           C.c_double, _dp, C.c_double, C.c_double, C.c_double, _vp, _vp, _vp,
+                                                           _vp]),
+    "ndt2d_deskew_points_dev": (C.c_int32, [_vp, _vp, _vp, C.c_size_t, _dp, C.c_double, _vp, _vp, _vp]),
+    "ndt3d_deskew_points_dev": (C.c_int32, [_vp, _vp, _vp, _vp, C.c_size_t, _dp, C.c_double, _vp, _vp, _vp, _vp]),
     "ndt3d_add_target_points_dev": (C.c_int32, [_vp, _vp, _vp, _vp, C.c_size_t, _dp, C.POINTER(C.c_size_t), _vp]),
     "ndt3d_remove_target_points": (C.c_int32, [_vp, _vp, _vp, _vp, C.c_size_t, C.POINTER(C.c_size_t)]),
     "ndt3d_remove_target_points_dev": (C.c_int32, [_vp, _vp, _vp, _vp, C.c_size_t, _dp, C.POINTER(C.c_size_t), _vp]),

@@ -1504,3 +1504,4 @@ extern "C" int32_t ndt2d_align_multi_scan_dev(ndt2d_handle* h, const float* cons
 #include "ndt3d_d2d_api.hpp"
 #include "ndt3d_d2d_search.hpp"
 #include "ndt_score_map_poses.hpp"
+#include "ndt_deskew.hpp"

@@ -670,17 +670,24 @@ int32_t ndt3d_add_target_points(ndt3d_handle* h, const float* x, const float* y,
   return ndt3d_add_target_points_dev(h, h->d_t[0], h->d_t[1], h->d_t[2], n, nullptr, n_outside, nullptr);
 }
 
+// the cos / sin table of a range image's rings (both conversions); false: an elevation is not finite
+static bool ring_table(const double* elevations, int n_elev, ndt::RingTable* rings) {
+  *rings = ndt::RingTable{};
+  for (int e = 0; e < n_elev; ++e) {
+    if (!std::isfinite(elevations[e])) return false;
+    rings->cs[2 * e] = std::cos(elevations[e]); rings->cs[2 * e + 1] = std::sin(elevations[e]);
+  }
+  return true;
+}
+
 int32_t ndt3d_range_image_to_points_dev(const float* d_ranges, int32_t n_elev, int32_t n_azim, const double* elevations,
                                         double azimuth0, double azimuth_inc, double range_min, double range_max, float* d_x,
                                         float* d_y, float* d_z, void* stream) {
   if (!d_ranges || !elevations || !d_x || !d_y || !d_z || n_elev < 1 || n_elev > ndt::kMaxRings || n_azim < 1 ||
       !std::isfinite(azimuth0) || !std::isfinite(azimuth_inc))
     return NDT_ERR_INVALID_ARG;
-  ndt::RingTable rings{};
-  for (int e = 0; e < n_elev; ++e) {
-    if (!std::isfinite(elevations[e])) return NDT_ERR_INVALID_ARG;
-    rings.cs[2 * e] = std::cos(elevations[e]); rings.cs[2 * e + 1] = std::sin(elevations[e]);
-  }
+  ndt::RingTable rings;
+  if (!ring_table(elevations, n_elev, &rings)) return NDT_ERR_INVALID_ARG;
   const size_t n = (size_t)n_elev * (size_t)n_azim;
   hipLaunchKernelGGL(ndt::k_range_image_to_points, dim3(stream_blocks(n)), dim3(ndt::kBlock), 0, (hipStream_t)stream, d_ranges,
                      n_elev, n_azim, rings, azimuth0, azimuth_inc, (float)range_min, (float)range_max, d_x, d_y, d_z);

@@ -1225,12 +1225,34 @@ def magnusson_constants(outlier_ratio: float, cell_size: float, dim: int = 2):
     return d1.value, d2.value
 
 
-def polar_to_points(ranges, angle_min: float, angle_inc: float, range_min: float = 0.0, range_max: float = 1e30):
-    """Range/bearing scan (torch CUDA float32 tensor) -> (x, y) CUDA tensors, on the device."""
+def _motion(motion, n: int):
+    """A sweep's motion as the C array the de-skewing entry points take: n doubles."""
+    if len(motion) != n:
+        raise ValueError(f"the sweep's motion must have {n} entries")
+    return (C.c_double * n)(*[float(v) for v in motion])
+
+
+def _sweep_frac(frac, n: int):
+    """(frac0, frac_inc) of a conversion's beams or columns; by default they fill the sweep, [0, 1)."""
+    return (0.0, 1.0 / n) if frac is None else (float(frac[0]), float(frac[1]))
+
+
+def polar_to_points(ranges, angle_min: float, angle_inc: float, range_min: float = 0.0, range_max: float = 1e30, *,
+                    motion=None, frac=None, ref_frac: float = 1.0):
+    """Range/bearing scan (torch CUDA float32 tensor) -> (x, y) CUDA tensors, on the device.  motion = (dx, dy, dtheta),
+    the sensor's pose at the end of the sweep in its frame at the start, undoes the motion within the sweep
+    (ndt2d_polar_to_points_deskew_dev): beam i was fired at sweep fraction frac[0] + i * frac[1] (default (0, 1 / n)) and
+    the points come out in the sensor frame at fraction ref_frac (1 = the end of the sweep)."""
     import torch
     n = ranges.numel()
     x = torch.empty(n, dtype=torch.float32, device=ranges.device)
     y = torch.empty(n, dtype=torch.float32, device=ranges.device)
+    if motion is not None:
+        L.check(L.load().ndt2d_polar_to_points_deskew_dev(*_dev_ptrs((ranges,), n), n, float(angle_min), float(angle_inc),
+                                                          float(range_min), float(range_max), _motion(motion, 3),
+                                                          *_sweep_frac(frac, n), float(ref_frac), *_dev_ptrs((x, y), n),
+                                                          _torch_stream_ptr()), "ndt2d_polar_to_points_deskew_dev")
+        return x, y
     L.check(L.load().ndt2d_polar_to_points_dev(*_dev_ptrs((ranges,), n), n, float(angle_min), float(angle_inc),
                                                float(range_min), float(range_max), *_dev_ptrs((x, y), n),
                                                _torch_stream_ptr()), "ndt2d_polar_to_points_dev")
@@ -1238,18 +1260,70 @@ def polar_to_points(ranges, angle_min: float, angle_inc: float, range_min: float
 
 
 def range_image_to_points(ranges, elevations, azimuth0: float, azimuth_inc: float, range_min: float = 0.0,
-                          range_max: float = 1e30):
+                          range_max: float = 1e30, *, motion=None, frac=None, ref_frac: float = 1.0):
     """Range image [n_elev, n_azim] (torch CUDA float32 tensor) of a multi-beam lidar -> (x, y, z) CUDA tensors of
-    n_elev * n_azim points, on the device (ndt3d_range_image_to_points_dev)."""
+    n_elev * n_azim points, on the device (ndt3d_range_image_to_points_dev).  motion = (tx, ty, tz, roll, pitch, yaw)
+    undoes the motion within the sweep (ndt3d_range_image_to_points_deskew_dev): azimuth column j was fired at sweep
+    fraction frac[0] + j * frac[1] (default (0, 1 / n_azim)), the points come out in the sensor frame at ref_frac."""
     import torch
     n_elev, n_azim = ranges.shape
     n = n_elev * n_azim
     out = [torch.empty(n, dtype=torch.float32, device=ranges.device) for _ in range(3)]
     el = (C.c_double * n_elev)(*[float(v) for v in elevations])
+    if motion is not None:
+        L.check(L.load().ndt3d_range_image_to_points_deskew_dev(*_dev_ptrs((ranges,), n), n_elev, n_azim, el, float(azimuth0),
+                                                                float(azimuth_inc), float(range_min), float(range_max),
+                                                                _motion(motion, 6), *_sweep_frac(frac, n_azim),
+                                                                float(ref_frac), *_dev_ptrs(out, n), _torch_stream_ptr()),
+                "ndt3d_range_image_to_points_deskew_dev")
+        return tuple(out)
     L.check(L.load().ndt3d_range_image_to_points_dev(*_dev_ptrs((ranges,), n), n_elev, n_azim, el, float(azimuth0), float(azimuth_inc),
                                                      float(range_min), float(range_max), *_dev_ptrs(out, n),
                                                      _torch_stream_ptr()), "ndt3d_range_image_to_points_dev")
     return tuple(out)
+
+
+def deskew_points(coords, frac, motion, ref_frac: float = 1.0, out=None):
+    """Cartesian device points with a sweep fraction each -> the points in the sensor frame at fraction ref_frac
+    (ndt2d_deskew_points_dev / ndt3d_deskew_points_dev).  coords is a 2- or 3-tuple of CUDA float32 tensors, frac one
+    more of the same length, motion the 3- or 6-vector of the sweep; out (default: new tensors) may be coords itself."""
+    import torch
+    dim = len(coords)
+    if dim not in (2, 3):
+        raise ValueError("coords must be (x, y) or (x, y, z)")
+    n = coords[0].numel()
+    if out is None:
+        out = tuple(torch.empty(n, dtype=torch.float32, device=coords[0].device) for _ in range(dim))
+    if len(out) != dim:
+        raise ValueError("out must have as many tensors as coords")
+    name = f"ndt{dim}d_deskew_points_dev"
+    L.check(getattr(L.load(), name)(*_dev_ptrs((*coords, frac), n), n, _motion(motion, 3 * dim - 3), float(ref_frac),
+                                    *_dev_ptrs(out, n), _torch_stream_ptr()), name)
+    return tuple(out)
+
+
+def sweep_motion(prev, cur):
+    """prev^-1 o cur of two poses (both 3- or both 6-vectors) in one frame: the motion between the last two estimates,
+    the constant-velocity guess of the motion within the next sweep (ndt2d_sweep_motion / ndt3d_sweep_motion)."""
+    n = len(prev)
+    if n not in (3, 6) or len(cur) != n:
+        raise ValueError("poses have 3 or 6 entries, both the same")
+    delta = (C.c_double * n)()
+    name = f"ndt{n // 3 + 1}d_sweep_motion"
+    L.check(getattr(L.load(), name)(_motion(prev, n), _motion(cur, n), delta), name)
+    return tuple(delta)
+
+
+def motion_twist(delta):
+    """The constant twist Log(delta) of a sweep's motion: (vx, vy, omega) or (rho[3], phi[3]) (ndt2d_motion_twist /
+    ndt3d_motion_twist)."""
+    n = len(delta)
+    if n not in (3, 6):
+        raise ValueError("a motion has 3 or 6 entries")
+    xi = (C.c_double * n)()
+    name = f"ndt{n // 3 + 1}d_motion_twist"
+    L.check(getattr(L.load(), name)(_motion(delta, n), xi), name)
+    return tuple(xi)
 
 
 # Coarse-to-fine schedule relative to the finest cell: (cell multiplier, eig_ratio).  Coarse

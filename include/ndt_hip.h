@@ -847,6 +847,45 @@ int32_t ndt3d_add_target_points(ndt3d_handle* h, const float* x, const float* y,
 int32_t ndt3d_range_image_to_points_dev(const float* d_ranges, int32_t n_elev, int32_t n_azim, const double* elevations,
                                         double azimuth0, double azimuth_inc, double range_min, double range_max, float* d_x,
                                         float* d_y, float* d_z, void* stream);
+
+/* ---- sensor motion within a sweep (docs/ALGORITHM.md section 2.23) ---------------------------- */
+/* A spinning lidar takes its returns one after another while the platform moves: `delta` is the sensor's pose at the end
+ * of the sweep in the sensor frame at its start ((dx, dy, dtheta) | (tx, ty, tz, roll, pitch, yaw), R = Rz Ry Rx), the
+ * motion in between is one constant twist xi = Log(delta), and a point p measured at sweep fraction s (0 = start,
+ * 1 = end) is expressed in the sensor frame at fraction ref_frac by p' = Exp((s - ref_frac) xi) p.  s and ref_frac
+ * are not clamped.  Every point is worked in float64 and rounded to float32 once.  With delta all zero, and for a
+ * point whose s equals ref_frac, the result is bit for bit what the entry point without the motion gives (the range
+ * entries) or the input (the point entries).  2D: dtheta is wrapped to (-pi, pi].  3D: a delta that turns by 3.1 rad
+ * or more is NDT_ERR_INVALID_ARG, as is a non-finite delta, ref_frac, frac0 or frac_inc.
+ *
+ * The four helpers need no device.  *_sweep_motion: delta = prev^-1 o cur of two poses in one frame - the motion
+ * between the last two estimates is the constant-velocity guess of the motion within this sweep (pitch =
+ * asin(clamp(-R20)); where |cos pitch| < 1e-12 roll and yaw share an axis and roll = 0 is returned; cur == prev gives
+ * exact zeros).  *_motion_twist: xi = Log(delta), (vx, vy, omega) | (rho[3], phi[3]). */
+int32_t ndt2d_sweep_motion(const double prev[3], const double cur[3], double delta[3]);
+int32_t ndt3d_sweep_motion(const double prev[6], const double cur[6], double delta[6]);
+int32_t ndt2d_motion_twist(const double delta[3], double xi[3]);
+int32_t ndt3d_motion_twist(const double delta[6], double xi[6]);
+/* ndt2d_polar_to_points_dev / ndt3d_range_image_to_points_dev with the motion undone: beam i / azimuth column j (every
+ * ring of it) was fired at fraction frac0 + i * frac_inc.  The unrounded float64 products of the plain conversions go
+ * through the motion; invalid returns become NaN points as there.  Asynchronous on `stream`. */
+int32_t ndt2d_polar_to_points_deskew_dev(const float* d_ranges, size_t n, double angle_min, double angle_inc,
+                                         double range_min, double range_max, const double delta[3], double frac0,
+                                         double frac_inc, double ref_frac, float* d_x, float* d_y, void* stream);
+int32_t ndt3d_range_image_to_points_deskew_dev(const float* d_ranges, int32_t n_elev, int32_t n_azim,
+                                               const double* elevations, double azimuth0, double azimuth_inc,
+                                               double range_min, double range_max, const double delta[6], double frac0,
+                                               double frac_inc, double ref_frac, float* d_x, float* d_y, float* d_z,
+                                               void* stream);
+/* Cartesian device points with a fraction each (drivers that deliver x, y, z, t; non-repetitive scanners).  A point
+ * whose fraction is not finite becomes a NaN point, whatever delta is.  The outputs may be the inputs.  Asynchronous
+ * on `stream`. */
+int32_t ndt2d_deskew_points_dev(const float* d_x, const float* d_y, const float* d_frac, size_t n, const double delta[3],
+                                double ref_frac, float* d_ox, float* d_oy, void* stream);
+int32_t ndt3d_deskew_points_dev(const float* d_x, const float* d_y, const float* d_z, const float* d_frac, size_t n,
+                                const double delta[6], double ref_frac, float* d_ox, float* d_oy, float* d_oz,
+                                void* stream);
+
 /* Empty voxel grid over a chosen extent (lo / hi = min / max corner, x y z), to be filled with
  * ndt3d_add_target_points(_dev): a submap that grows scan by scan, as ndt2d_reserve_target. */
 int32_t ndt3d_reserve_target(ndt3d_handle* h, const double lo[3], const double hi[3]);

@@ -263,6 +263,38 @@ class NdtMatcherHip {
   }
   // the handle's stream (hipStream_t as void*): what scoreParticlesAsync's outputs are ordered on
   void* stream() { return ndt2d_stream(h_); }
+  // The driver side of the boundary, on the caller's stream (no handle involved; all pointers are device pointers):
+  // ranges -> points (ndt2d_polar_to_points_dev) and, with the sensor's motion within the sweep, the same de-skewed
+  // (ndt2d_polar_to_points_deskew_dev): `motion` is the sensor's pose at the end of the sweep in its frame at the start,
+  // beam i was fired at sweep fraction frac0 + i * frac_inc, the points come out in the sensor frame at ref_frac.
+  static void polarToPointsDev(const float* d_ranges, size_t n, double angle_min, double angle_inc, double range_min,
+                               double range_max, float* d_x, float* d_y, void* stream) {
+    check(ndt2d_polar_to_points_dev(d_ranges, n, angle_min, angle_inc, range_min, range_max, d_x, d_y, stream),
+          "ndt2d_polar_to_points_dev");
+  }
+  static void polarToPointsDev(const float* d_ranges, size_t n, double angle_min, double angle_inc, double range_min,
+                               double range_max, const Pose2& motion, double frac0, double frac_inc, double ref_frac,
+                               float* d_x, float* d_y, void* stream) {
+    const double delta[3] = {motion.x, motion.y, motion.theta};
+    check(ndt2d_polar_to_points_deskew_dev(d_ranges, n, angle_min, angle_inc, range_min, range_max, delta, frac0, frac_inc,
+                                           ref_frac, d_x, d_y, stream), "ndt2d_polar_to_points_deskew_dev");
+  }
+  // prev^-1 o cur: the motion between the last two estimates, the constant-velocity guess of the next sweep's motion
+  static Pose2 sweepMotion(const Pose2& prev, const Pose2& cur) {
+    const double p[3] = {prev.x, prev.y, prev.theta}, c[3] = {cur.x, cur.y, cur.theta};
+    double d[3];
+    check(ndt2d_sweep_motion(p, c, d), "ndt2d_sweep_motion");
+    Pose2 out;
+    out.x = d[0]; out.y = d[1]; out.theta = d[2];
+    return out;
+  }
+  // Device points with a sweep fraction each -> the sensor frame at ref_frac (ndt2d_deskew_points_dev); the outputs may
+  // be the inputs
+  static void deskewPointsDev(const float* d_x, const float* d_y, const float* d_frac, size_t n, const Pose2& motion,
+                              double ref_frac, float* d_ox, float* d_oy, void* stream) {
+    const double delta[3] = {motion.x, motion.y, motion.theta};
+    check(ndt2d_deskew_points_dev(d_x, d_y, d_frac, n, delta, ref_frac, d_ox, d_oy, stream), "ndt2d_deskew_points_dev");
+  }
   // scorePosesDev for SHORT lists (a particle filter's particles; the faster call at every size measured): a team of lanes per pose
   // (ndt2d_score_particles_dev; contract: ndt_hip.h).  d_n_hit [m] (may be null): the lookups that hit a valid cell,
   // evaluate's n_hit at that pose.  The scores differ from scorePosesDev's only by the order of the float32 sum.
@@ -882,6 +914,43 @@ class NdtMatcherHip3 {
     check(ndt3d_score_poses_dev(h_, d_sx, d_sy, d_sz, n, d_poses, m, d_scores), "ndt3d_score_poses_dev");
   }
   void* stream() { return ndt3d_stream(h_); }
+  // The driver side of the 3D boundary, on the caller's stream (no handle involved; d_* are device pointers, elevations
+  // a host array of n_elev angles): range image -> points (ndt3d_range_image_to_points_dev) and, with the sensor's
+  // motion within the sweep, the same de-skewed (ndt3d_range_image_to_points_deskew_dev): azimuth column j was fired at
+  // sweep fraction frac0 + j * frac_inc, the points come out in the sensor frame at ref_frac.
+  static void rangeImageToPointsDev(const float* d_ranges, int n_elev, int n_azim, const double* elevations, double azimuth0,
+                                    double azimuth_inc, double range_min, double range_max, float* d_x, float* d_y,
+                                    float* d_z, void* stream) {
+    check(ndt3d_range_image_to_points_dev(d_ranges, n_elev, n_azim, elevations, azimuth0, azimuth_inc, range_min, range_max,
+                                          d_x, d_y, d_z, stream), "ndt3d_range_image_to_points_dev");
+  }
+  static void rangeImageToPointsDev(const float* d_ranges, int n_elev, int n_azim, const double* elevations, double azimuth0,
+                                    double azimuth_inc, double range_min, double range_max, const Pose3& motion,
+                                    double frac0, double frac_inc, double ref_frac, float* d_x, float* d_y, float* d_z,
+                                    void* stream) {
+    const double delta[6] = {motion.x, motion.y, motion.z, motion.roll, motion.pitch, motion.yaw};
+    check(ndt3d_range_image_to_points_deskew_dev(d_ranges, n_elev, n_azim, elevations, azimuth0, azimuth_inc, range_min,
+                                                 range_max, delta, frac0, frac_inc, ref_frac, d_x, d_y, d_z, stream),
+          "ndt3d_range_image_to_points_deskew_dev");
+  }
+  // prev^-1 o cur, as NdtMatcherHip::sweepMotion
+  static Pose3 sweepMotion(const Pose3& prev, const Pose3& cur) {
+    const double p[6] = {prev.x, prev.y, prev.z, prev.roll, prev.pitch, prev.yaw};
+    const double c[6] = {cur.x, cur.y, cur.z, cur.roll, cur.pitch, cur.yaw};
+    double d[6];
+    check(ndt3d_sweep_motion(p, c, d), "ndt3d_sweep_motion");
+    Pose3 out;
+    out.x = d[0]; out.y = d[1]; out.z = d[2]; out.roll = d[3]; out.pitch = d[4]; out.yaw = d[5];
+    return out;
+  }
+  // Device points with a sweep fraction each -> the sensor frame at ref_frac (ndt3d_deskew_points_dev); the outputs may
+  // be the inputs
+  static void deskewPointsDev(const float* d_x, const float* d_y, const float* d_z, const float* d_frac, size_t n,
+                              const Pose3& motion, double ref_frac, float* d_ox, float* d_oy, float* d_oz, void* stream) {
+    const double delta[6] = {motion.x, motion.y, motion.z, motion.roll, motion.pitch, motion.yaw};
+    check(ndt3d_deskew_points_dev(d_x, d_y, d_z, d_frac, n, delta, ref_frac, d_ox, d_oy, d_oz, stream),
+          "ndt3d_deskew_points_dev");
+  }
   // scorePosesDev for SHORT lists, a team of lanes per pose, with the hit counts (ndt3d_score_particles_dev), as
   // NdtMatcherHip::scoreParticlesDev; d_n_hit may be null
   void scoreParticlesDev(const float* d_sx, const float* d_sy, const float* d_sz, size_t n, const double* d_poses, size_t m,
