@@ -722,6 +722,10 @@ int32_t ndt2d_polar_to_points_dev(const float* d_ranges, size_t n, double angle_
  * cells, 32767 occupied: 256 m x 256 m at 0.5 m cells).  Beyond that a pair gets status
  * NDT_ERR_CAPACITY from the _dev entry point, and the host-pointer entry point re-runs it through the
  * single-pair path transparently.
+ * A cell that more than 2^20 target points of a pair fall into: where ndt2d_set_target answers
+ * NDT_ERR_CAPACITY for the whole cloud, the batch kernels (2D and 3D, every variant) make that one cell invalid -
+ * a source point in it is a miss - and align the pair on the other cells; the pair's status says nothing about it
+ * (tests/test_gpu_batch_records.py).
  * overlap_grids = 4: every pair of such a level runs on that third variant (four grids on chip would quarter
  * the capacity to 71 x 71 cells), its four grids back to back in the tables: 256 x 256 cells per grid
  * (128 m x 128 m at 0.5 m cells), 32767 occupied cells over the four; the context then holds one table slab

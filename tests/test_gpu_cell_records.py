@@ -19,8 +19,8 @@ expectation and the float64 restatement of the handle's own save_map stands in a
 
 Each path runs three of the five parameter sets, rotating, so every set meets several paths.
 
-Not covered: the LDS-resident finalise of k_batch / k_batch3 calls the same finalise_sums / finalise_sums3 but has no
-read-back of its records; it stays outside this file."""
+The grid build inside k_batch / k_batch3 has no read-back of its records: tests/test_gpu_batch_records.py holds it to the
+same exact records through one-point probes of every cell of these catalogues (tests/batch_probe_ref.py)."""
 import numpy as np
 import pytest
 
