@@ -141,6 +141,12 @@ class PointFit(C.Structure):
                 ("n_selected", C.c_uint64)]
 
 
+class VoxelFilterInfo(C.Structure):
+    """ndt_voxel_filter_info (24 bytes): the points a voxel filter skipped, the voxels it found occupied, and those
+    with n >= min_points - the length of its outputs."""
+    _fields_ = [("n_invalid", C.c_uint64), ("n_voxels", C.c_uint64), ("n_out", C.c_uint64)]
+
+
 # the class byte of a point (NDT_POINT_* of include/ndt_hip.h), by name
 POINT_CLASS = {"invalid": 0, "miss": 1, "misfit": 2, "fit": 3}
 
@@ -308,6 +314,14 @@ SIGNATURES = {
     "ndt3d_unmerge_map": (C.c_int32, [_vp, _vp, _dp, C.POINTER(C.c_size_t)]),
     "ndt3d_evaluate": (C.c_int32, [_vp, _vp, _vp, _vp, C.c_size_t, _dp, C.POINTER(Eval3D)]),
     "ndt3d_evaluate_dev": (C.c_int32, [_vp, _vp, _vp, _vp, C.c_size_t, _dp, C.POINTER(Eval3D)]),
+    "ndt2d_voxel_filter_dev": (C.c_int32, [_vp, _vp, _vp, C.c_size_t, C.c_double, C.c_uint32, _vp, _vp, _vp, C.c_size_t,
+                                           C.POINTER(VoxelFilterInfo)]),
+    "ndt2d_voxel_filter": (C.c_int32, [_vp, _vp, _vp, C.c_size_t, C.c_double, C.c_uint32, _vp, _vp, _vp, C.c_size_t,
+                                       C.POINTER(VoxelFilterInfo)]),
+    "ndt3d_voxel_filter_dev": (C.c_int32, [_vp, _vp, _vp, _vp, C.c_size_t, C.c_double, C.c_uint32, _vp, _vp, _vp, _vp,
+                                           C.c_size_t, C.POINTER(VoxelFilterInfo)]),
+    "ndt3d_voxel_filter": (C.c_int32, [_vp, _vp, _vp, _vp, C.c_size_t, C.c_double, C.c_uint32, _vp, _vp, _vp, _vp,
+                                       C.c_size_t, C.POINTER(VoxelFilterInfo)]),
     "ndt3d_fit_points_dev": (C.c_int32, [_vp, _vp, _vp, _vp, C.c_size_t, _dp, C.c_float, _vp, _vp, C.POINTER(PointFit)]),
     "ndt3d_fit_points": (C.c_int32, [_vp, _vp, _vp, _vp, C.c_size_t, _dp, C.c_float, _vp, _vp, C.POINTER(PointFit)]),
     "ndt3d_select_points_dev": (C.c_int32, [_vp, _vp, _vp, _vp, C.c_size_t, _dp, C.c_float, C.c_uint32, _vp, _vp, _vp, _vp,

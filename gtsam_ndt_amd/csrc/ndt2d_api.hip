@@ -105,6 +105,7 @@ struct ndt2d_handle {
   int particle_team = 0;                   // NDT_TUNE_PARTICLE_TEAM: lanes per pose of ndt2d_score_particles*, 0 = by the list's length
   SearchScratch srch;                      // exhaustive pose search scratch (ndt_search.hpp), allocated on first use
   PointFitScratch fit;                     // per-point fit and selection scratch (ndt_point_fit.hpp), allocated on first use
+  VoxelFilterScratch vox;                  // voxel-grid scan filter scratch (ndt_voxel_filter.hpp), allocated on first use
   // map-to-map alignment (ndt_map_host.hpp, ndt2d_d2d_api.hpp), allocated on first use; both caches follow the grid (grid_changed)
   float4* d_cov = nullptr; size_t cov_cap = 0;            // covariance records of the cached grid ([2 x cells], the layout of grid.rec)
   unsigned int* d_blk = nullptr; size_t blk_cap = 0;      // valid cells per workgroup of k_cov_records | their exclusive scan | the total
@@ -1093,6 +1094,7 @@ int32_t ndt2d_destroy(ndt2d_handle* h) {
   for (void* p : host) if (p) (void)hipHostFree(p);
   h->srch.release();
   h->fit.release();
+  h->vox.release();
   if (h->upload_ev) (void)hipEventDestroy(h->upload_ev);
   if (h->wait_ev) (void)hipEventDestroy(h->wait_ev);
   if (h->map_ev) (void)hipEventDestroy(h->map_ev);
@@ -1505,3 +1507,4 @@ extern "C" int32_t ndt2d_align_multi_scan_dev(ndt2d_handle* h, const float* cons
 #include "ndt3d_d2d_search.hpp"
 #include "ndt_score_map_poses.hpp"
 #include "ndt_deskew.hpp"
+#include "ndt_voxel_filter.hpp"

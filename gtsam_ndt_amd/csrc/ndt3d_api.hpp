@@ -52,6 +52,7 @@ struct ndt3d_handle {
   ndt::IterState3* h_state_multi = nullptr;     // pinned [kMaxStarts3]
   ndt::SearchScratch srch;                      // exhaustive pose search scratch (ndt_search.hpp), allocated on first use
   ndt::PointFitScratch fit;                     // per-point fit and selection scratch (ndt_point_fit.hpp), allocated on first use
+  ndt::VoxelFilterScratch vox;                  // voxel-grid scan filter scratch (ndt_voxel_filter.hpp), allocated on first use
   // map-to-map alignment (ndt_map_host.hpp, ndt3d_d2d_api.hpp), allocated on first use; both caches follow the grid (grid_changed3)
   float4* d_cov = nullptr; size_t cov_cap = 0;            // covariance records, 3 float4 per voxel (k_cov_records3)
   unsigned int* d_blk = nullptr; size_t blk_cap = 0;      // per-workgroup valid counts | their exclusive scan | the total
@@ -636,6 +637,7 @@ int32_t ndt3d_destroy(ndt3d_handle* h) {
   for (void* p : host) if (p) (void)hipHostFree(p);
   h->srch.release();
   h->fit.release();
+  h->vox.release();
   if (h->upload_ev) (void)hipEventDestroy(h->upload_ev);
   if (h->map_ev) (void)hipEventDestroy(h->map_ev);
   if (h->stream) (void)hipStreamDestroy(h->stream);

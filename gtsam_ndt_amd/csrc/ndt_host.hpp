@@ -660,9 +660,39 @@ struct PointFitScratch {
   }
 };
 
+// What the kernels of ndt*_voxel_filter* (ndt_voxel_filter.hpp) hand to the host and to each other: the occupied box as
+// unsigned maxima (0: no valid point yet, so a memset starts a call), and three counts.
+struct VoxHeader {
+  unsigned int hi[3];        // max over the valid points of i + 2^30 (>= 1)
+  unsigned int lo[3];        // max of 2^30 - i (>= 1)
+  unsigned int n_invalid, n_voxels, n_out, pad;
+};
+
+// Scratch of ndt*_voxel_filter* (ndt_voxel_filter.hpp), grown to need and freed with the handle.
+struct VoxelFilterScratch {
+  VoxHeader* d_hdr = nullptr;
+  VoxHeader* h_hdr = nullptr;                             // pinned: the header's read-back
+  uint2* d_words = nullptr; size_t word_cap = 0;          // per 32 voxels of the box: (occupancy bits, occupied voxels in front)
+  unsigned int* d_chunk_sum = nullptr;                    // per chunk of words: its occupied voxels
+  unsigned int* d_chunk_base = nullptr; size_t chunk_cap = 0;   // ... and those of the chunks in front of it
+  unsigned int* d_cnt = nullptr;                          // per occupied voxel, in the contract's order: n
+  unsigned int* d_key = nullptr;                          // ... its index in the box
+  unsigned long long* d_sum = nullptr; size_t vox_cap = 0;      // ... and the sums of U, [3][vox_cap]
+  unsigned int* d_tile_cnt = nullptr;                     // per tile of voxels: those with n >= min_points
+  unsigned int* d_tile_base = nullptr; size_t tile_cap = 0;     // ... and those of the tiles in front of it
+  float* d_out = nullptr;                                 // the host entry's outputs, [3][out_cap]
+  unsigned int* d_ocnt = nullptr; size_t out_cap = 0;
+  void release() {
+    void* dev[] = {d_hdr, d_words, d_chunk_sum, d_chunk_base, d_cnt, d_key, d_sum, d_tile_cnt, d_tile_base, d_out, d_ocnt};
+    for (void* p : dev) if (p) (void)hipFree(p);
+    if (h_hdr) (void)hipHostFree(h_hdr);
+    *this = VoxelFilterScratch{};
+  }
+};
+
 }  // namespace ndt
 
-#define HIP_TRY(expr)                                                            \
+#define HIP_TRY(expr)                                                           \
   do {                                                                           \
     const hipError_t _e = (expr);                                                \
     if (_e != hipSuccess) {                                                      \

@@ -89,6 +89,14 @@ class PointFit:
         return self.n_fit / finite if finite else 0.0
 
 
+@dataclass
+class VoxelFilterInfo:
+    """What voxel_filter counted (ndt_voxel_filter_info of include/ndt_hip.h)."""
+    n_invalid: int         # points skipped: a coordinate not finite, or a lattice index of 2^30 or more
+    n_voxels: int          # occupied voxels
+    n_out: int             # those with n >= min_points: the length of the outputs
+
+
 def _keep_mask(keep) -> int:
     """keep of select_points: a mask of 1 << class, or class names out of L.POINT_CLASS."""
     if isinstance(keep, str):
@@ -427,6 +435,40 @@ class _NdtMatcher(_Handle):
         if host:
             out, index = tuple(o.cpu().numpy() for o in out), index.cpu().numpy()
         return out, index, self._point_fit(fit)
+
+    # ---- voxel-grid scan filter (docs/ALGORITHM.md section 2.24)
+    def _voxel_filter(self, coords, leaf: float, min_points: int, with_counts: bool, with_info: bool):
+        """-> coords of the centroids [, counts (int64)] [, VoxelFilterInfo]: of the kind of the input, n_out long."""
+        info = L.VoxelFilterInfo()
+        if _is_dev(coords[0]):
+            import torch
+            n = coords[0].numel()
+            out = [torch.empty_like(c) for c in coords]
+            cnt = torch.empty(n, dtype=torch.int32, device=coords[0].device) if with_counts else None     # uint32 words, below 2^31
+            self.wait_stream()
+            self._check(self._c.voxel_filter_dev(self._h, *_dev_ptrs(coords, n), n, float(leaf), int(min_points),
+                                                 *[o.data_ptr() for o in out], cnt.data_ptr() if with_counts else None, n,
+                                                 C.byref(info)), "voxel_filter_dev")
+            k = int(info.n_out)
+            res = [tuple(o[:k] for o in out)]
+            if with_counts:
+                res.append(cnt[:k].to(torch.int64))
+        else:
+            a = _host_coords(coords)
+            n = a[0].size
+            out = [np.empty(n, dtype=np.float32) for _ in a]
+            cnt = np.empty(n, dtype=np.uint32) if with_counts else None
+            self._check(self._c.voxel_filter(self._h, *[c.ctypes.data for c in a], n, float(leaf), int(min_points),
+                                             *[o.ctypes.data for o in out], cnt.ctypes.data if with_counts else None, n,
+                                             C.byref(info)), "voxel_filter")
+            k = int(info.n_out)
+            res = [tuple(o[:k].copy() for o in out)]
+            if with_counts:
+                res.append(cnt[:k].astype(np.int64))
+        self.voxel_filter_info = VoxelFilterInfo(int(info.n_invalid), int(info.n_voxels), int(info.n_out))
+        if with_info:
+            res.append(self.voxel_filter_info)
+        return res[0] if len(res) == 1 else tuple(res)
 
     def wait_stream(self, stream=None):
         """Order the handle's stream behind `stream` (default: torch's current stream): device arrays
@@ -794,6 +836,14 @@ class NdtMatcher2D(_NdtMatcher):
         input - numpy arrays or CUDA tensors - and the four class counts."""
         return self._fit_points((sx, sy), pose, max_m)
 
+    def voxel_filter(self, x, y, leaf: float, min_points: int = 1, with_counts: bool = False, with_info: bool = False):
+        """Downsample a cloud to the centroid of every occupied voxel of the absolute lattice floor(x / leaf)
+        (ndt2d_voxel_filter*; docs/ALGORITHM.md section 2.24): (x, y) of the kind of the input - CUDA tensors or numpy
+        arrays - in ascending lattice order (iy, ix), the same bits for every order of the input.  Voxels with fewer
+        than min_points points are dropped.  with_counts: also the points per emitted voxel; with_info: also the
+        VoxelFilterInfo, which is kept as self.voxel_filter_info either way.  Needs no target."""
+        return self._voxel_filter((x, y), leaf, min_points, with_counts, with_info)
+
     def select_points(self, sx, sy, pose, max_m: float, keep=("fit", "miss")):
         """The points of the scan whose class at `pose` is in `keep` (class names, or a mask of 1 << class), in the
         source frame, bit for bit and in their order (ndt2d_select_points_dev): ((x, y), index, PointFit), trimmed to
@@ -911,6 +961,11 @@ class NdtMatcher3D(_NdtMatcher):
     def fit_points(self, sx, sy, sz, pose, max_m: float) -> PointFit:
         """Per-point m and class against the cached voxel grid (ndt3d_fit_points*), as NdtMatcher2D.fit_points."""
         return self._fit_points((sx, sy, sz), pose, max_m)
+
+    def voxel_filter(self, x, y, z, leaf: float, min_points: int = 1, with_counts: bool = False, with_info: bool = False):
+        """(x, y, z) centroids of the occupied voxels in order (iz, iy, ix) (ndt3d_voxel_filter*), as
+        NdtMatcher2D.voxel_filter."""
+        return self._voxel_filter((x, y, z), leaf, min_points, with_counts, with_info)
 
     def select_points(self, sx, sy, sz, pose, max_m: float, keep=("fit", "miss")):
         """((x, y, z), index, PointFit) of the points whose class is in `keep` (ndt3d_select_points_dev), as

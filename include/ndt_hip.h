@@ -316,6 +316,38 @@ int32_t ndt2d_select_points_dev(ndt2d_handle* h, const float* d_sx, const float*
                                 float max_m, uint32_t keep, float* d_ox, float* d_oy, uint32_t* d_index,
                                 ndt_point_fit* fit);
 
+/* ---- voxel-grid scan filter, exact centroids (docs/ALGORITHM.md section 2.24) ---------- */
+/* What a filter call counted: the points skipped, the occupied voxels, and those with n >= min_points (the outputs). */
+typedef struct ndt_voxel_filter_info {
+  uint64_t n_invalid, n_voxels, n_out;
+} ndt_voxel_filter_info;
+
+/* Downsamples a cloud to one point per occupied voxel of the ABSOLUTE lattice i = floor(x / leaf) per axis (independent
+ * of the cloud's bounding box: a world point lands in the same voxel in every call): the voxel's centroid.  Per point,
+ * in float64 on the float32 input, every operation rounded once: i = floor(x / leaf); centre = (i + 0.5) leaf;
+ * U = llrint((x - centre) (2^22 / leaf)).  A point is invalid - skipped and counted - if a coordinate is not finite or
+ * an |i| >= 2^30.  Per occupied voxel n and the sum of U per axis are integers (uint32, int64), so they do not depend on
+ * the order of the points; the output coordinate is fma((double) sum U, leaf / (n 2^22), centre) rounded to float32 once.
+ * A voxel is emitted iff n >= min_points (1: every occupied voxel; 2 or 3 drop isolated returns), in ascending lattice
+ * order (iy, ix), ix fastest.  d_count (may be NULL) receives n per emitted voxel.  Outputs and *info are the same to the
+ * bit for every permutation of the input and for every launch.
+ * Runs on the handle's stream under the stream contract of ndt2d_fit_points_dev (ndt2d_wait_stream for producers),
+ * finishes a pending asynchronous alignment first (its result stays fetchable) and returns when the outputs and *info
+ * are complete.  It needs no target and leaves a cached grid untouched.  The outputs hold `capacity` elements (n is
+ * always enough) and are never written past info->n_out or capacity.
+ * NDT_ERR_CAPACITY with *info filled: n_out > capacity (retry with n_out).  NDT_ERR_CAPACITY with n_voxels = 0: the
+ * lattice box of the occupied voxels (max - min + 1 per axis) holds more than 2^30 voxels; ndt_last_error says which.
+ * NDT_ERR_INVALID_ARG (ndt_last_error says which): a null handle, input, output or info; n = 0 or above what an
+ * alignment takes; leaf not finite or <= 0; min_points = 0; an output that overlaps an input (pointer ranges).
+ * NDT_ERR_ALLOC: the handle's scratch (32 bytes per occupied voxel, 8 bytes per 32 voxels of the box) cannot grow.
+ * Every point invalid: NDT_OK with n_out = 0. */
+int32_t ndt2d_voxel_filter_dev(ndt2d_handle* h, const float* d_x, const float* d_y, size_t n, double leaf,
+                               uint32_t min_points, float* d_ox, float* d_oy, uint32_t* d_count, size_t capacity,
+                               ndt_voxel_filter_info* info);
+/* the same with host arrays in and out, the cloud staged as ndt2d_fit_points stages its scan */
+int32_t ndt2d_voxel_filter(ndt2d_handle* h, const float* x, const float* y, size_t n, double leaf, uint32_t min_points,
+                           float* ox, float* oy, uint32_t* count, size_t capacity, ndt_voxel_filter_info* info);
+
 /* ---- full alignment: rows a4-a9 ------------------------------------------------------ */
 int32_t ndt2d_align(ndt2d_handle* h, const float* sx, const float* sy, size_t n,
                     const double init_pose[3], ndt2d_result* out);
@@ -943,6 +975,13 @@ int32_t ndt3d_fit_points(ndt3d_handle* h, const float* sx, const float* sy, cons
 int32_t ndt3d_select_points_dev(ndt3d_handle* h, const float* d_sx, const float* d_sy, const float* d_sz, size_t n,
                                 const double pose[6], float max_m, uint32_t keep, float* d_ox, float* d_oy, float* d_oz,
                                 uint32_t* d_index, ndt_point_fit* fit);
+/* ndt2d_voxel_filter* for three coordinates: the same per-axis arithmetic, order (iz, iy, ix) with ix fastest. */
+int32_t ndt3d_voxel_filter_dev(ndt3d_handle* h, const float* d_x, const float* d_y, const float* d_z, size_t n, double leaf,
+                               uint32_t min_points, float* d_ox, float* d_oy, float* d_oz, uint32_t* d_count,
+                               size_t capacity, ndt_voxel_filter_info* info);
+int32_t ndt3d_voxel_filter(ndt3d_handle* h, const float* x, const float* y, const float* z, size_t n, double leaf,
+                           uint32_t min_points, float* ox, float* oy, float* oz, uint32_t* count, size_t capacity,
+                           ndt_voxel_filter_info* info);
 int32_t ndt3d_align(ndt3d_handle* h, const float* sx, const float* sy, const float* sz, size_t n,
                     const double init_pose[6], ndt3d_result* out);
 int32_t ndt3d_align_dev(ndt3d_handle* h, const float* d_sx, const float* d_sy, const float* d_sz, size_t n,

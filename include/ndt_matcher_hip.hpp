@@ -376,6 +376,17 @@ class NdtMatcherHip {
     check(ndt2d_select_points_dev(h_, d_sx, d_sy, n, p, max_m, keep, d_ox, d_oy, d_index, &f), "ndt2d_select_points_dev");
     return f;
   }
+  // Voxel-grid filter of a device cloud (ndt2d_voxel_filter_dev; docs/ALGORITHM.md 2.24): the centroid of every voxel of the
+  // absolute lattice floor(x / leaf) that holds at least min_points points, into d_ox / d_oy[0 .. n_out) in ascending
+  // lattice order (iy, ix) - the same bits for every order of the input - and the points per voxel into d_count (may be
+  // null).  The outputs hold `capacity` elements (n is always enough) and must not overlap the inputs.  Needs no
+  // target; the cloud must be complete on the device, or the handle ordered behind its producer (ndt2d_wait_stream).
+  ndt_voxel_filter_info voxelFilterDev(const float* d_x, const float* d_y, size_t n, double leaf, float* d_ox, float* d_oy,
+                                       size_t capacity, uint32_t min_points = 1, uint32_t* d_count = nullptr) {
+    ndt_voxel_filter_info info;
+    check(ndt2d_voxel_filter_dev(h_, d_x, d_y, n, leaf, min_points, d_ox, d_oy, d_count, capacity, &info), "ndt2d_voxel_filter_dev");
+    return info;
+  }
   // Map-to-map alignment (ndt2d_align_map): `source`'s cached grid against this matcher's, no points involved - the
   // loop closure between two submaps, or between a reloaded map and the current one.  guess and the result map the
   // source map's frame into this map's frame; this matcher's parameters drive the solve; source may be *this.
@@ -832,6 +843,15 @@ class NdtMatcherHip3 {
     check(ndt3d_select_points_dev(h_, d_sx, d_sy, d_sz, n, p, max_m, keep, d_ox, d_oy, d_oz, d_index, &f), "ndt3d_select_points_dev");
     return f;
   }
+  // voxel-grid filter of a device cloud in order (iz, iy, ix) (ndt3d_voxel_filter_dev), as NdtMatcherHip::voxelFilterDev
+  ndt_voxel_filter_info voxelFilterDev(const float* d_x, const float* d_y, const float* d_z, size_t n, double leaf, float* d_ox,
+                                       float* d_oy, float* d_oz, size_t capacity, uint32_t min_points = 1,
+                                       uint32_t* d_count = nullptr) {
+    ndt_voxel_filter_info info;
+    check(ndt3d_voxel_filter_dev(h_, d_x, d_y, d_z, n, leaf, min_points, d_ox, d_oy, d_oz, d_count, capacity, &info),
+          "ndt3d_voxel_filter_dev");
+    return info;
+  }
   MatchResult3 alignDev(const float* d_sx, const float* d_sy, const float* d_sz, size_t n, const Pose3& guess = Pose3()) {
     const double init[6] = {guess.x, guess.y, guess.z, guess.roll, guess.pitch, guess.yaw};
     ndt3d_result r;
@@ -891,8 +911,8 @@ class NdtMatcherHip3 {
     return out;
   }
   // searchDev, then one alignment from every hit in one launch chain (ndt3d_search_align_dev): result i is bit for bit
-  // what alignMultiStartDev returns from the hits' poses.  Search with a subsampled scan and refine with the full one
-  // when the lattice is large.
+  // what alignMultiStartDev returns from the hits' poses.  Search with a subsampled scan (voxelFilterDev, or every 8th
+  // point) and refine with the full one when the lattice is large.
   std::vector<SearchMatch> searchAlignDev(const float* d_sx, const float* d_sy, const float* d_sz, size_t n,
                                           const ndt3d_search_window& window, int k, void* producer_stream,
                                           bool complete = false) {
