@@ -64,6 +64,7 @@ struct ndt3d_handle {
   bool fused_begin = true;                                // NDT_TUNE_FUSED_BEGIN: launch 0 of a chain is k_iterate3_first (no k_begin3)
   hipEvent_t map_ev = nullptr;                            // orders a target handle's stream behind this handle's (order_after)
   int particle_team = 0;                                  // NDT_TUNE_PARTICLE_TEAM: lanes per pose of ndt3d_score_particles*, 0 = by the list's length
+  int neighbourhood = 1;                                  // ndt3d_set_neighbourhood: voxels a point is scored against in the alignment chains (1 or 7)
 };
 
 namespace {
@@ -349,16 +350,41 @@ int32_t set_target3_impl(ndt3d_handle* h, const float* dx, const float* dy, cons
   return upload_static3(h);
 }
 
-// the k_iterate3 of the handle's Hessian, for graphs (ensure_graph3) and plain launches (ndt3d_align_trace)
+// The template arguments of a 3D alignment kernel: f(MODE, NB) with the handle's Hessian and neighbourhood (with_mode's
+// second argument, the 2D grid count, is always 1 in 3D and unused).
+template <class F>
+auto with_mode3(const ndt3d_handle* h, F&& f) {
+  return with_mode(h->prm, [&](auto M, auto) {
+    return h->neighbourhood == 7 ? f(M, std::integral_constant<int, 7>{}) : f(M, std::integral_constant<int, 1>{});
+  });
+}
+// Both enter the key a cached graph is found by (ChainGraphCache compares keys, not kernels): a handle switched between
+// the neighbourhoods must never replay the other one's graph.
+int graph_mode3(const ndt3d_handle* h) { return (h->neighbourhood == 7 ? 0x10 : 0) | h->prm.hessian_mode; }
+
+// the k_iterate3 of the handle's Hessian and neighbourhood, for graphs (ensure_graph3) and plain launches (ndt3d_align_trace)
 const void* iter3_kernel(const ndt3d_handle* h) {
-  return with_mode(h->prm, [](auto M, auto) { return (const void*)&ndt::k_iterate3<M>; });
+  return with_mode3(h, [](auto M, auto NB) { return (const void*)&ndt::k_iterate3<M, NB>; });
+}
+
+// Neighbourhood 7 is a scoring option of the alignment chains alone.  The kernels behind every other entry point that
+// scores points against the grid (the lattice search, the pose lists, the particle scores, the per-point fit) keep the
+// single-voxel score their contracts name, so with 7 set they refuse instead of answering another question.
+int32_t single_voxel_only(const ndt2d_handle*, const char* = nullptr) { return NDT_OK; }
+int32_t single_voxel_only(const ndt3d_handle* h, const char* who = nullptr) {
+  if (h->neighbourhood == 1) return NDT_OK;
+  ndt::last_error() = std::string(who ? who : "this entry point") +
+                      ": scores a point against its own voxel only; the handle's neighbourhood is 7: call "
+                      "ndt3d_set_neighbourhood(h, 1) first (neighbourhood 7 is honoured by evaluate, align, align_trace "
+                      "and the multi-start / multi-scan chains)";
+  return NDT_ERR_INVALID_ARG;
 }
 
 // first_parity 1: the graph follows a k_iterate3_first and starts at launch 1 (the cache keeps the two kinds apart)
 int32_t ensure_graph3(ndt3d_handle* h, int launches, int first_parity) {
   using namespace ndt;
   HIP_TRY(h->graphs.get(iter3_kernel(h), dim3(kMaxBlocks), dim3(kBlock),
-                        (void*)h->d_static, (void*)h->d_call, (void*)h->d_dyn, launches, h->prm.hessian_mode, h->stream,
+                        (void*)h->d_static, (void*)h->d_call, (void*)h->d_dyn, launches, graph_mode3(h), h->stream,
                         &h->graph_exec, 0, first_parity));
   return NDT_OK;
 }
@@ -401,8 +427,8 @@ int32_t begin_align3(ndt3d_handle* h, const float* dx, const float* dy, const fl
   IterState3* const host_state = fixed > 0 ? (IterState3*)nullptr : h->h_state;
   int* const host_flag = fixed > 0 ? (int*)nullptr : h->h_flag;
   if (first) {
-    with_mode(h->prm, [&](auto M, auto) {
-      hipLaunchKernelGGL((k_iterate3_first<M>), dim3(kMaxBlocks), dim3(kBlock), 0, h->stream, (const AlignStatic3*)h->d_static,
+    with_mode3(h, [&](auto M, auto NB) {
+      hipLaunchKernelGGL((k_iterate3_first<M, NB>), dim3(kMaxBlocks), dim3(kBlock), 0, h->stream, (const AlignStatic3*)h->d_static,
                          h->d_call, h->d_dyn, dx, dy, dz, (int)n, pose[0], pose[1], pose[2], pose[3], pose[4], pose[5], fixed,
                          host_state, host_flag, h->call_seq);
       return 0;
@@ -563,13 +589,13 @@ int32_t multi_align3(ndt3d_handle* h, const float* const* sxs, const float* cons
   const int steps = converged_mode ? chunk : K + 1;
   hipGraphExec_t exec = nullptr;
   const void *fs = nullptr, *fb = nullptr;
-  with_mode(h->prm, [&](auto M, auto) { fs = (const void*)&k_multi_solve3<M>; fb = (const void*)&k_multi_body3<M>; });
+  with_mode3(h, [&](auto M, auto NB) { fs = (const void*)&k_multi_solve3<M>; fb = (const void*)&k_multi_body3<M, NB>; return 0; });
   // launch shapes in powers of two (slots >= m are born finished: their workgroups return at once), so that a caller
   // whose m varies from call to call replays one of seven cached graphs instead of instantiating a new one each time
   int mg = 1;
   while (mg < m) mg <<= 1;
   HIP_TRY(h->graphs.get2(fs, dim3(mg), dim3(kBlock), fb, dim3(kMaxBlocks, mg), dim3(kBlock), (void*)h->d_static, (void*)h->d_call,
-                         (void*)h->d_dyn_multi, steps, 0x100000 | (mg << 8) | h->prm.hessian_mode, h->stream, &exec));
+                         (void*)h->d_dyn_multi, steps, 0x100000 | (mg << 8) | graph_mode3(h), h->stream, &exec));
   bool seen = true;
   HIP_TRY(run_multi_chain(exec, h->stream, converged_mode ? h->h_flag : nullptr, steps, K + 1, h->call_seq, h->h_state_multi,
                           h->d_dyn_multi->state[K & 1], kMaxStarts3 * sizeof(IterState3), &seen));
@@ -656,6 +682,24 @@ int32_t ndt3d_set_tuning(ndt3d_handle* h, int32_t knob, int64_t value) {
     default: return NDT_ERR_INVALID_ARG;
   }
 }
+
+int32_t ndt3d_set_neighbourhood(ndt3d_handle* h, int32_t n) {
+  if (!h) { ndt::set_error("ndt3d_set_neighbourhood: the handle is null"); return NDT_ERR_INVALID_ARG; }
+  if (n != 1 && n != 7) {
+    ndt::set_error("ndt3d_set_neighbourhood: the neighbourhood is 1 (own voxel) or 7 (own voxel and its six face neighbours)");
+    return NDT_ERR_INVALID_ARG;
+  }
+  // an alignment in flight keeps the kernels it was enqueued with and is finished first, as the searches do
+  if (h->in_flight) {
+    HIP_TRY(hipSetDevice(h->device));
+    const int32_t fs = finish_align3(h);
+    if (fs != NDT_OK) return fs;
+  }
+  h->neighbourhood = n;
+  return NDT_OK;
+}
+
+int32_t ndt3d_neighbourhood(const ndt3d_handle* h) { return h ? h->neighbourhood : NDT_ERR_INVALID_ARG; }
 
 int32_t ndt3d_wait_stream(ndt3d_handle* h, void* producer_stream) {
   if (!h) return NDT_ERR_INVALID_ARG;

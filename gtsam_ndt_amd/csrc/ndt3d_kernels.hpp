@@ -560,6 +560,15 @@ __device__ __forceinline__ Voxel3 voxel_of3(const Grid3Dev& G, const Extent3F& E
   const bool in = (fx >= 0.f) & (fx < E.W) & (fy >= 0.f) & (fy < E.H) & (fz >= 0.f) & (fz < E.D);
   return Voxel3{in ? (((int)fz * G.H + (int)fy) * G.W + (int)fx) : 0, in};
 }
+// The same with the voxel's integer indices, for a kernel that goes on to the face neighbours: a neighbour is taken by
+// index (ix - 1 from ix = 0 does not exist), never by key arithmetic alone (key - 1 is the last voxel of the row before).
+struct VoxelIndex3 { int key, ix, iy, iz; bool in; };
+__device__ __forceinline__ VoxelIndex3 voxel_index3(const Grid3Dev& G, const Extent3F& E, float px, float py, float pz) {
+  const float fx = (px - G.ox) * G.inv_c, fy = (py - G.oy) * G.inv_c, fz = (pz - G.oz) * G.inv_c;
+  const bool in = (fx >= 0.f) & (fx < E.W) & (fy >= 0.f) & (fy < E.H) & (fz >= 0.f) & (fz < E.D);
+  const int ix = in ? (int)fx : 0, iy = in ? (int)fy : 0, iz = in ? (int)fz : 0;
+  return VoxelIndex3{(iz * G.H + iy) * G.W + ix, ix, iy, iz, in};
+}
 // The search form, in two halves.  What depends on the image's z alone - its inside test and (int)fz * layer,
 // layer = W * H - is done once per point where x and y vary per lane (the lattice kernels, at staging) ...
 __device__ __forceinline__ Voxel3 layer_key3(const Grid3Dev& G, const Extent3F& E, float pz, unsigned int layer) {
@@ -592,26 +601,33 @@ __device__ __forceinline__ float mahalanobis3(float px, float py, float pz, cons
   float vx, vy, vz; return mahalanobis3(px, py, pz, A4, B4, C2, vx, vy, vz);
 }
 
-// a5 + a6 for one point: p = the untransformed source point, pp = R p + t (both zeroed by the caller when the
-// image lies outside the grid), the voxel record (A4 = mean | n, B4 = Sigma^-1 xx xy xz yy, C2 = yz zz).
+// a5 + a6 for one point, in two parts: what no voxel enters, J[k] = dR_k p (once per point), and one term per voxel the
+// point is scored against (the own voxel: accumulate_point3; its face neighbours too: evaluate_block3<., 7>).
+// p = the untransformed source point, pp = R p + t (both zeroed by the caller when the image lies outside the grid),
+// the voxel record (A4 = mean | n, B4 = Sigma^-1 xx xy xz yy, C2 = yz zz).
 // acc: Htt(6) Htr(9) Hrr(6) g(6) score n_hit [+ M(9) in Newton mode].
-template <int MODE>
-__device__ __forceinline__ void accumulate_point3(const Rot3F& T, float x, float y, float z, float px, float py,
-                                                  float pz, bool in, const float4& A4, const float4& B4,
-                                                  const float4& C2, float d1, float d2, float nhd2, float* acc) {
-  const bool hit = in & (A4.w > 0.f);
-  const float cxx = B4.x, cxy = B4.y, cxz = B4.z, cyy = B4.w, cyz = C2.x, czz = C2.y;
-  float vx, vy, vz;
-  const float m = mahalanobis3(px, py, pz, A4, B4, C2, vx, vy, vz);
-  const float s = hit ? d1 * __builtin_amdgcn_exp2f(nhd2 * m) : 0.f;
-  const float w = s * d2;
-  float J[3][3], U[3][3];   // J[k] = dR_k p ; U[k] = Sigma^-1 J[k]
+__device__ __forceinline__ void point_jacobian3(const Rot3F& T, float x, float y, float z, float (*J)[3]) {
   const float* Rd[3] = {T.Ra, T.Rb, T.Rg};
 #pragma unroll
   for (int k = 0; k < 3; ++k) {
     J[k][0] = fmaf(Rd[k][0], x, fmaf(Rd[k][1], y, Rd[k][2] * z));
     J[k][1] = fmaf(Rd[k][3], x, fmaf(Rd[k][4], y, Rd[k][5] * z));
     J[k][2] = fmaf(Rd[k][6], x, fmaf(Rd[k][7], y, Rd[k][8] * z));
+  }
+}
+// One term of a point: its image pp against one voxel's record; hit = the term counts (its weight is zero otherwise).
+template <int MODE, class C>
+__device__ __forceinline__ void accumulate_term3(const float (*J)[3], float x, float y, float z, float px, float py, float pz,
+                                                 bool hit, const float4& A4, const float4& B4, const C& C2, float d1, float d2,
+                                                 float nhd2, float* acc) {
+  const float cxx = B4.x, cxy = B4.y, cxz = B4.z, cyy = B4.w, cyz = C2.x, czz = C2.y;
+  float vx, vy, vz;
+  const float m = mahalanobis3(px, py, pz, A4, B4, C2, vx, vy, vz);
+  const float s = hit ? d1 * __builtin_amdgcn_exp2f(nhd2 * m) : 0.f;
+  const float w = s * d2;
+  float U[3][3];   // U[k] = Sigma^-1 J[k]
+#pragma unroll
+  for (int k = 0; k < 3; ++k) {
     U[k][0] = fmaf(cxx, J[k][0], fmaf(cxy, J[k][1], cxz * J[k][2]));
     U[k][1] = fmaf(cxy, J[k][0], fmaf(cyy, J[k][1], cyz * J[k][2]));
     U[k][2] = fmaf(cxz, J[k][0], fmaf(cyz, J[k][1], czz * J[k][2]));
@@ -665,6 +681,14 @@ __device__ __forceinline__ void accumulate_point3(const Rot3F& T, float x, float
   acc[27] += s;
   acc[28] += hit ? 1.f : 0.f;
 }
+template <int MODE>
+__device__ __forceinline__ void accumulate_point3(const Rot3F& T, float x, float y, float z, float px, float py,
+                                                  float pz, bool in, const float4& A4, const float4& B4,
+                                                  const float4& C2, float d1, float d2, float nhd2, float* acc) {
+  float J[3][3];
+  point_jacobian3(T, x, y, z, J);
+  accumulate_term3<MODE>(J, x, y, z, px, py, pz, in & (A4.w > 0.f), A4, B4, C2, d1, d2, nhd2, acc);
+}
 
 // Epilogue of a 3D chain launch: the wave's NA sums through LDS instead of one DPP tree each (wave_reduce11_lds of the
 // 2D path): park [j][lane] (row stride 66 floats), lane 2j+q adds the 32 values of accumulator j whose lane index is
@@ -701,7 +725,8 @@ __device__ __forceinline__ void block_reduce3_store(const float* acc, float* t, 
 // a4-a7 of one launch for one alignment, shared by k_iterate3 and the multi-scan chain (k_multi_body3): this
 // workgroup's points (thread -> point assignment i, i + stride, ...; the first point already loaded) under `pose`,
 // per-thread sums, the wave's sums through LDS, one partial row entry per sum at partial_col[row * kMaxBlocks].
-template <int MODE>
+// NB = the neighbourhood (ndt3d_set_neighbourhood): 1 = the point's own voxel, 7 = and its six face neighbours.
+template <int MODE, int NB>
 __device__ __forceinline__ void evaluate_block3(const Grid3Dev& G, const SolveParams& prm, const double* pose,
                                                 const float* __restrict__ sx, const float* __restrict__ sy,
                                                 const float* __restrict__ sz, int n, int i, float x, float y, float z,
@@ -718,6 +743,8 @@ __device__ __forceinline__ void evaluate_block3(const Grid3Dev& G, const SolvePa
 #pragma unroll
   for (int j = 0; j < NA; ++j) acc[j] = 0.f;
 
+  static_assert(NB == 1 || NB == 7, "the neighbourhood is the own voxel, or the own voxel and its six face neighbours");
+  if constexpr (NB == 1) {
   while (i < n) {
     const int inext = i + stride;
     float xn = 0.f, yn = 0.f, zn = 0.f;
@@ -731,6 +758,41 @@ __device__ __forceinline__ void evaluate_block3(const Grid3Dev& G, const SolvePa
     const float4 C2 = G.rec[4 * key + 2];
     accumulate_point3<MODE>(T, x, y, z, px, py, pz, in, A4, B4, C2, d1, d2, nhd2, acc);
     x = xn; y = yn; z = zn; i = inext;
+  }
+  } else {
+  // Own voxel and its six face neighbours (docs/ALGORITHM.md 2.25).  A voxel's record is one 64-byte line, so a
+  // candidate costs one line whether or not its Sigma^-1 is read: all seven records are requested at once, in front of
+  // the first term, and a candidate that is off the grid or empty adds a term of weight zero (no branch: the lanes of a
+  // wave disagree on which candidates count).  What does not depend on the voxel - the image and J - is formed once.
+  const int WH = G.W * G.H;
+  while (i < n) {
+    const int inext = i + stride;
+    float xn = 0.f, yn = 0.f, zn = 0.f;
+    if (inext < n) { xn = sx[inext]; yn = sy[inext]; zn = sz[inext]; }
+    float px = image_row3(T.R, T.tx, x, y, z), py = image_row3(T.R + 3, T.ty, x, y, z), pz = image_row3(T.R + 6, T.tz, x, y, z);
+    const VoxelIndex3 vox = voxel_index3(G, E, px, py, pz);
+    const bool in = vox.in;
+    if (!in) { px = py = pz = 0.f; x = y = z = 0.f; }
+    // candidates in the contract's order; one that leaves the grid keeps the own key (a voxel of the grid) and no vote
+    const bool ok[NB] = {in, in && vox.ix > 0, in && vox.ix + 1 < G.W, in && vox.iy > 0, in && vox.iy + 1 < G.H,
+                         in && vox.iz > 0, in && vox.iz + 1 < G.D};
+    const int dk[NB] = {0, -1, 1, -G.W, G.W, -WH, WH};
+    float4 A4[NB], B4[NB];
+    float2 C2[NB];
+#pragma unroll
+    for (int c = 0; c < NB; ++c) {
+      const float4* r = G.rec + 4 * (size_t)(unsigned int)(vox.key + (ok[c] ? dk[c] : 0));
+      A4[c] = r[0];
+      B4[c] = r[1];
+      C2[c] = *reinterpret_cast<const float2*>(r + 2);
+    }
+    float J[3][3];
+    point_jacobian3(T, x, y, z, J);
+#pragma unroll
+    for (int c = 0; c < NB; ++c)
+      accumulate_term3<MODE>(J, x, y, z, px, py, pz, ok[c] & (A4[c].w > 0.f), A4[c], B4[c], C2[c], d1, d2, nhd2, acc);
+    x = xn; y = yn; z = zn; i = inext;
+  }
   }
 
   block_reduce3_store<NA, Acc3<MODE>::kRows>(acc, s_t_wave, s_wave, partial_col);
@@ -788,7 +850,7 @@ __device__ __forceinline__ void store_state3(IterState3* o, const double* pose, 
 // - d2 (J'v)(J'v)' on all 21 entries, and on the rotation block v' d2p'/dp_k dp_l, which is linear in the
 // 3x3 matrix M = sum w v p' (p = the untransformed source point) - nine more sums per thread; the
 // contraction with the six second-derivative matrices of R happens once per launch, in the prologue.
-template <int MODE>
+template <int MODE, int NB>
 __global__ __launch_bounds__(kBlock) void k_iterate3(const AlignStatic3* __restrict__ st,
                                                       const AlignCall3* __restrict__ call,
                                                       AlignDyn3* __restrict__ dyn, int parity) {
@@ -895,7 +957,7 @@ __global__ __launch_bounds__(kBlock) void k_iterate3(const AlignStatic3* __restr
     copy_state(cur, prev, 1);
   }
 
-  evaluate_block3<MODE>(G, prm, pose, sx, sy, sz, n, i, x, y, z, s_wave, s_t[wave], &dyn->partials[parity][0][blockIdx.x]);
+  evaluate_block3<MODE, NB>(G, prm, pose, sx, sy, sz, n, i, x, y, z, s_wave, s_t[wave], &dyn->partials[parity][0][blockIdx.x]);
 }
 
 // Launch 0 of a 3D chain with k_begin3 folded in (k_iterate_first of the 2D path): the evaluation at the initial pose
@@ -918,7 +980,7 @@ __device__ __forceinline__ void clear_line_search3(LineSearch3* o) {
   o->score = 0.0; o->alpha = 0.0; o->trials = 0; o->valid = 0;
 }
 
-template <int MODE>
+template <int MODE, int NB>
 __global__ __launch_bounds__(kBlock) void k_iterate3_first(const AlignStatic3* __restrict__ st, AlignCall3* __restrict__ call,
                                                             AlignDyn3* __restrict__ dyn, const float* sx, const float* sy,
                                                             const float* sz, int n, double p0, double p1, double p2, double p3,
@@ -949,7 +1011,7 @@ __global__ __launch_bounds__(kBlock) void k_iterate3_first(const AlignStatic3* _
     clear_line_search3(&dyn->ls[0]);
     clear_line_search3(&dyn->ls[1]);
   }
-  evaluate_block3<MODE>(G, prm, pose, sx, sy, sz, n, i, x, y, z, s_wave, s_t[wave], &dyn->partials[0][0][blockIdx.x]);
+  evaluate_block3<MODE, NB>(G, prm, pose, sx, sy, sz, n, i, x, y, z, s_wave, s_t[wave], &dyn->partials[0][0][blockIdx.x]);
 }
 
 }  // namespace ndt

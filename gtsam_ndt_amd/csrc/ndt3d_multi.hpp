@@ -194,7 +194,7 @@ __global__ __launch_bounds__(kBlock) void k_multi_solve3(const AlignStatic3* __r
 }
 
 // grid (256, m): the evaluation of start blockIdx.y on block blockIdx.x's share of its scan
-template <int MODE>
+template <int MODE, int NB>
 __global__ __launch_bounds__(kBlock) void k_multi_body3(const AlignStatic3* __restrict__ st, const AlignCall3* __restrict__ call,
                                                          AlignDynMulti3* __restrict__ dyn, int parity) {
   constexpr int NA = Acc3<MODE>::kUsed;
@@ -218,7 +218,7 @@ __global__ __launch_bounds__(kBlock) void k_multi_body3(const AlignStatic3* __re
   float x = 0.f, y = 0.f, z = 0.f;
   if (i < n) { x = sx[i]; y = sy[i]; z = sz[i]; }
   if (done) return;                                     // uniform
-  evaluate_block3<MODE>(G, prm, pose, sx, sy, sz, n, i, x, y, z, s_wave, s_t[wave], &dyn->partials[parity][h][0][blockIdx.x]);
+  evaluate_block3<MODE, NB>(G, prm, pose, sx, sy, sz, n, i, x, y, z, s_wave, s_t[wave], &dyn->partials[parity][h][0][blockIdx.x]);
 }
 
 }  // namespace ndt

@@ -147,7 +147,7 @@ int32_t search_args3(ndt3d_handle* h, const float* sx, const float* sy, const fl
                      int32_t k, const void* hits, const int32_t* n_hits) {
   if (!h || !sx || !sy || !sz || !w || !hits || !n_hits) return NDT_ERR_INVALID_ARG;
   if (n == 0 || n > kMaxSourcePoints || k < 1 || k > ndt::kMaxStarts3) return NDT_ERR_INVALID_ARG;
-  return NDT_OK;
+  return single_voxel_only(h);
 }
 
 }  // namespace
@@ -187,6 +187,7 @@ int32_t ndt3d_search(ndt3d_handle* h, const float* sx, const float* sy, const fl
 int32_t ndt3d_search_scores_dev(ndt3d_handle* h, const float* d_sx, const float* d_sy, const float* d_sz, size_t n,
                                 const ndt3d_search_window* w, float* d_scores) {
   if (!h || !d_sx || !d_sy || !d_sz || !w || !d_scores || n == 0 || n > kMaxSourcePoints) return NDT_ERR_INVALID_ARG;
+  { const int32_t ns = single_voxel_only(h); if (ns != NDT_OK) return ns; }
   return search_run3(h, d_sx, d_sy, d_sz, n, w, 1, nullptr, nullptr, d_scores);
 }
 

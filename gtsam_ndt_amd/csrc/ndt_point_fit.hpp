@@ -274,7 +274,7 @@ int32_t point_fit_check(const H* h, const char* who, const float* const* s, size
     for (int a = 0; a < DIM; ++a) if (!d_o[a]) return bad("a coordinate array of the output is null");
   }
   if (!h->has_target) { ndt::last_error() = std::string(who) + ": the handle holds no target"; return NDT_ERR_NO_TARGET; }
-  return NDT_OK;
+  return single_voxel_only(h, who);
 }
 
 // ndt*_fit_points_dev (d_o null) and ndt*_select_points_dev

@@ -275,7 +275,7 @@ int32_t score_poses_check(const H* h, const float* const* s, size_t n, const voi
     return NDT_ERR_CAPACITY;
   }
   if (!h->has_target) return NDT_ERR_NO_TARGET;
-  return NDT_OK;
+  return single_voxel_only(h);
 }
 
 // the score launch on h's stream, behind the alignment in flight (arguments checked)

@@ -930,11 +930,23 @@ class NdtMatcher3D(_NdtMatcher):
     _dim = _DIM3
     _where_set_target_dev = "set_target_dev"
 
-    def __init__(self, device: int = 0, tuning: dict | None = None, **overrides):
+    def __init__(self, device: int = 0, tuning: dict | None = None, neighbourhood: int = 1, **overrides):
         """tuning: execution-strategy knobs by name (L.TUNING; 3D handles know "single_sync_build",
-        "map_multi_from" and "fused_begin")."""
+        "map_multi_from" and "fused_begin").  neighbourhood: set_neighbourhood() of the new handle."""
         self.params = default_params3d(**overrides)
         self._create(device, tuning)
+        if neighbourhood != 1:
+            self.set_neighbourhood(neighbourhood)
+
+    def set_neighbourhood(self, n: int):
+        """1: a point is scored against the voxel its image lies in; 7: and against that voxel's six face neighbours
+        (ndt3d_set_neighbourhood).  Honoured by evaluate, align*, align_trace, align_multi_start and align_multi_scan;
+        the searches, pose lists, particle scores and per-point fits raise NdtError while 7 is set."""
+        self._check(self._c.set_neighbourhood(self._h, int(n)), "set_neighbourhood")
+
+    @property
+    def neighbourhood(self) -> int:
+        return self._check(self._c.neighbourhood(self._h), "neighbourhood")
 
     def set_target(self, x, y, z):
         return self._set_target((x, y, z))
@@ -1462,6 +1474,13 @@ class NdtPyramid2D(_NdtPyramid):
 
 class NdtPyramid3D(_NdtPyramid):
     _Matcher = NdtMatcher3D
+
+    def __init__(self, device: int = 0, levels=PYRAMID_LEVELS, neighbourhood: int = 1, **overrides):
+        """neighbourhood: NdtMatcher3D.set_neighbourhood() of every level's handle."""
+        super().__init__(device, levels, **overrides)
+        if neighbourhood != 1:
+            for m in self.levels:
+                m.set_neighbourhood(neighbourhood)
 
     def set_target(self, x, y, z):
         return self._set_target((x, y, z))

@@ -1005,6 +1005,26 @@ int32_t ndt3d_align_multi_scan_dev(ndt3d_handle* h, const float* const* d_sx, co
                                    const size_t* n, const double* init_poses, int32_t m, ndt3d_result* results);
 int32_t ndt3d_align_multi_start_dev(ndt3d_handle* h, const float* d_sx, const float* d_sy, const float* d_sz, size_t n,
                                     const double* init_poses, int32_t m, ndt3d_result* results);
+/* The neighbourhood a source point is scored against (docs/ALGORITHM.md 2.25): n = 1 (a new handle) is the voxel its
+ * image lies in; n = 7 adds that voxel's six face neighbours (the "DIRECT7" of PCL's ndt_omp and Autoware), which
+ * makes the score continuous across a voxel face and widens the basin.  The own voxel is found as with 1 (an image
+ * outside the grid or not finite contributes nothing, whatever lies next to it); candidates in the order own, -x, +x,
+ * -y, +y, -z, +z, one that leaves the grid skipped by index; every candidate with a valid record adds one term to the
+ * score, g, H (both Hessian modes) and one to n_hit, which min_hits is compared with.  A scoring option only: the
+ * voxel grid and its records are the same, so the switch costs nothing and nothing is rebuilt; bit for bit
+ * reproducible; with 1 every result is bit for bit what it was before the option existed.
+ *   Honoured by ndt3d_evaluate*, ndt3d_align*, ndt3d_align_dev_async / ndt3d_align_finish, ndt3d_align_trace,
+ *     ndt3d_align_multi_start_dev and ndt3d_align_multi_scan_dev (results[k] bit for bit the single call with 7).
+ *   Refused with 7 set (NDT_ERR_INVALID_ARG, ndt_last_error names the option): ndt3d_search*, ndt3d_score_poses*,
+ *     ndt3d_best_poses*, ndt3d_score_particles*, ndt3d_fit_points* and ndt3d_select_points_dev - their kernels keep the
+ *     single-voxel score their contracts name.  To search with 1 and refine with 7, call the setter in between.
+ *   Unaffected: builds and updates, save / load, coarsen, merge, every map-to-map entry point (components, not
+ *     points), ndt3d_voxel_filter*, and the ndt3d_batch_* / ndt3d_multi_* contexts, which have no such option.
+ * ndt3d_set_neighbourhood: n other than 1 or 7, or a null handle: NDT_ERR_INVALID_ARG (the setting stays).  An
+ * alignment in flight on the handle is finished first; no target is needed and no other device work is done.
+ * ndt3d_neighbourhood returns 1 or 7 (a null handle: NDT_ERR_INVALID_ARG). */
+int32_t ndt3d_set_neighbourhood(ndt3d_handle* h, int32_t n);
+int32_t ndt3d_neighbourhood(const ndt3d_handle* h);
 /* Exhaustive 3D pose search (docs/ALGORITHM.md "Exhaustive 3D pose search"), the twin of ndt2d_search*: the NDT score of
  * the scan at every pose of an (x, y, yaw) lattice against the cached voxel grid, then the best well-separated peaks - a
  * ground vehicle's relocalisation or loop closure whose guess is metres and tens of degrees off.  z, roll and pitch are

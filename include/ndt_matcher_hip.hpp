@@ -785,6 +785,10 @@ class NdtMatcherHip3 {
   void setTarget(const float* x, const float* y, const float* z, size_t n) { check(ndt3d_set_target(h_, x, y, z, n), "ndt3d_set_target"); }
   // execution-strategy knobs of a 3D handle (NDT_TUNE_SINGLE_SYNC_BUILD)
   void setTuning(int32_t knob, int64_t value) { check(ndt3d_set_tuning(h_, knob, value), "ndt3d_set_tuning"); }
+  // 1: a point is scored against its own voxel; 7: and against the six face neighbours (ndt3d_set_neighbourhood).  The
+  // alignments honour it; the searches, pose lists, particle scores and point fits throw while 7 is set.
+  void setNeighbourhood(int32_t n) { check(ndt3d_set_neighbourhood(h_, n), "ndt3d_set_neighbourhood"); }
+  int32_t neighbourhood() const { return ndt3d_neighbourhood(h_); }
   // incremental voxel-grid update: returns the number of points outside the cached extent
   size_t addTargetPoints(const float* x, const float* y, const float* z, size_t n) {
     size_t outside = 0;
