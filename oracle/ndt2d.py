@@ -237,9 +237,35 @@ def welford_cell(xs: np.ndarray, ys: np.ndarray):
 
 
 # ----------------------------------------------------------------------------- a4-a7
+def fma32(a, b, c, stats: dict | None = None):
+    """Correctly rounded float32 fma(a, b, c), elementwise with broadcasting.  The float64 product of two float32 values
+    is exact; the float64 sum is rounded once, and rounding it to float32 again is wrong only where the rounded sum sits
+    exactly on a float32 tie while the true sum does not.  There the exact error term of the float64 sum (Knuth's
+    two-sum) says on which side of the tie the true value lies.  Everywhere else the result is, bit for bit, the plain
+    float64 multiply-add rounded to float32.  stats["settled"] counts the elements decided by the error term,
+    stats["ties"] the true float32 ties (rounded to even by the conversion)."""
+    a, b, c = np.broadcast_arrays(np.asarray(a, np.float32), np.asarray(b, np.float32), np.asarray(c, np.float32))
+    with np.errstate(invalid="ignore", over="ignore"):
+        p, c64 = a.astype(np.float64) * b.astype(np.float64), c.astype(np.float64)
+        s = p + c64
+        r = s.astype(np.float32)
+        r64 = r.astype(np.float64)
+        nb = np.nextafter(r, np.where(s > r64, np.float32(np.inf), np.float32(-np.inf)).astype(np.float32))
+        mid = 0.5 * (r64 + nb.astype(np.float64))                       # exact in float64
+        suspect = np.isfinite(s) & np.isfinite(nb) & (s != r64) & (s == mid)
+        bb = s - p
+        e = (p - (s - bb)) + (c64 - bb)                                 # s + e is the true sum
+        settle = suspect & (e != 0.0)
+        r = np.where(settle, np.where(e > 0.0, np.maximum(r, nb), np.minimum(r, nb)), r).astype(np.float32)
+    if stats is not None:
+        stats["settled"] = stats.get("settled", 0) + int(np.count_nonzero(settle))
+        stats["ties"] = stats.get("ties", 0) + int(np.count_nonzero(suspect & (e == 0.0)))
+    return r
+
+
 def _fma32(a, b, c):
-    """float32 fma emulated through float64 (product exact; one extra rounding, rare)."""
-    return (a.astype(np.float64) * np.float64(b) + np.asarray(c, dtype=np.float64)).astype(np.float32)
+    """fmaf(a, b, c) as the device computes it (one rounding)."""
+    return fma32(a, b, c)
 
 
 def transform(sx, sy, pose, mirror32: bool):

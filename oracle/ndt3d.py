@@ -18,7 +18,7 @@ from dataclasses import dataclass, field
 import numpy as np
 
 from .ndt2d import (NDT_DEGENERATE_HESSIAN, NDT_NOT_CONVERGED, NDT_OK, NDT_TOO_FEW_CELLS,
-                    NDT_TOO_FEW_HITS, wrap_angle)
+                    NDT_TOO_FEW_HITS, fma32, wrap_angle)
 
 JACOBI_SWEEPS = 6
 
@@ -189,16 +189,26 @@ def rot_second_derivs(roll, pitch, yaw):
             (1, 1): Rz @ ddRy @ Rx, (1, 2): dRz @ dRy @ Rx, (2, 2): ddRz @ Ry @ Rx}
 
 
-def evaluate3(grid: Grid3D, sx, sy, sz, pose, prm: Ndt3Params, mirror32: bool = False):
+def evaluate3(grid: Grid3D, sx, sy, sz, pose, prm: Ndt3Params, mirror32: bool = False, chain: bool = False):
     """H (6x6; Gauss-Newton, or the full Newton Hessian with prm.hessian_mode = 1), g (6), score, n_hit
-    of f = -sum d1 exp(-d2/2 q'S^-1 q)."""
+    of f = -sum d1 exp(-d2/2 q'S^-1 q).
+    mirror32: float32 rotation, image and records.  The image is the float64 product rounded once, which differs from the
+    device's by an ulp at some points; with chain=True it is the device's nested-fmaf image to the bit (docs/ALGORITHM.md
+    2.6), so the voxel of every point, and n_hit, are the device's.  (The default stays: the trajectories behind the
+    measured constants of tests/step_replay.py were taken with it.)"""
     P = np.stack([np.asarray(sx), np.asarray(sy), np.asarray(sz)], axis=1)
     R, Ra, Rb, Rg = rot_and_derivs(*pose[3:])
     t = np.array(pose[:3], dtype=np.float64)
     if mirror32:
-        R32 = R.astype(np.float32).astype(np.float64)
         P64 = P.astype(np.float32).astype(np.float64)
-        Pw = (P64 @ R32.T + t.astype(np.float32).astype(np.float64)).astype(np.float32)
+        if chain:
+            # image_row3: p'_r = fmaf(R_r0, x, fmaf(R_r1, y, fmaf(R_r2, z, t_r))), three roundings per row, each exact
+            Rf, tf, Pf = R.astype(np.float32), t.astype(np.float32), P.astype(np.float32)
+            Pw = np.stack([fma32(Rf[r, 0], Pf[:, 0], fma32(Rf[r, 1], Pf[:, 1], fma32(Rf[r, 2], Pf[:, 2], tf[r])))
+                           for r in range(3)], axis=1)
+        else:
+            R32 = R.astype(np.float32).astype(np.float64)
+            Pw = (P64 @ R32.T + t.astype(np.float32).astype(np.float64)).astype(np.float32)
         key, inside = cell_keys3(Pw, grid.o, grid.inv_c, grid.dims)
         mean, icov = (r.astype(np.float64) for r in grid.records32())
         Pw = Pw.astype(np.float64)

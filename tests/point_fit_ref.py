@@ -26,8 +26,9 @@ At a rotated pose the device's image point differs from this one by at most dp =
 
     2 |v|_1 dp + |C|_1 dp^2          (|C|_1: the sum of |c_ab| over the full matrix)
 
-A point whose cell coordinate f = (p - o) / c lies within dp / c + 2^-22 |f| of an integer may fall into the neighbour
-cell on the device: `near` marks it, and a comparison excuses it.
+The cell itself is exact at a rotated pose as well: the key is taken from the device's own float32 image, the fmaf chain
+with a correctly rounded fma (tests/seam_ref.py image2d / image3d).  `near` is therefore empty at every pose; it stays in
+the result for the comparisons that read it.
 """
 import math
 from dataclasses import dataclass
@@ -36,6 +37,8 @@ import numpy as np
 
 from oracle import ndt2d as o2
 from oracle import ndt3d as o3
+
+import seam_ref as S
 
 INVALID, MISS, MISFIT, FIT = 0, 1, 2, 3
 K_ROUND = {2: 8.0, 3: 10.0}
@@ -132,8 +135,8 @@ def is_exact_pose(pose, dim):
 
 def fit_ref(rec: Records, coords, pose, max_m, exact=False):
     """-> dict over the scan's points: cls uint8, m float64 (+inf: miss, NaN: invalid), hit bool, tol float64 (the m
-    tolerance above, rotated terms included unless exact), near bool (a cell coordinate close to an integer: key in doubt
-    at a rotated pose), m_abs."""
+    tolerance above, rotated terms included unless exact), near bool (always False: the key is exact
+    at every pose), m_abs."""
     dim = rec.dim
     P = np.stack([np.asarray(c, dtype=np.float32) for c in coords[:dim]], axis=1)
     n = P.shape[0]
@@ -147,7 +150,13 @@ def fit_ref(rec: Records, coords, pose, max_m, exact=False):
     else:
         img = X.astype(np.float64) @ R.T + t[None, :]
         dp = EPS23 * (np.abs(X.astype(np.float64)).sum(axis=1) + np.abs(t).max())
-    img32 = img.astype(np.float32)
+    if exact:
+        img32 = img.astype(np.float32)
+    else:
+        # the key comes from the device's own image: the fmaf chain of ALGORITHM 2.4 / 2.6 with a correctly rounded fma
+        # (tests/seam_ref.py), so the cell is exact at a rotated pose too; img (float64) and dp remain for the m tolerance
+        chain = S.image2d(X[:, 0], X[:, 1], pose) if dim == 2 else S.image3d(X[:, 0], X[:, 1], X[:, 2], pose)
+        img32 = np.stack(chain, axis=1)
     ng = rec.ngrid
     m_q = np.full((ng, n), np.inf)
     tol_q = np.zeros((ng, n))
@@ -159,9 +168,6 @@ def fit_ref(rec: Records, coords, pose, max_m, exact=False):
             key, inside = o2.cell_keys32(img32[:, 0], img32[:, 1], o[0], o[1], rec.inv_c, rec.ext[0], rec.ext[1])
         else:
             key, inside = o3.cell_keys3(img32, o, rec.inv_c, rec.ext)
-        f = (img - o.astype(np.float64)[None, :]) * float(rec.inv_c)
-        if not exact:                                      # (exact: the float32 key above IS the device's)
-            near |= (np.abs(f - np.rint(f)) <= dp[:, None] * float(rec.inv_c) + EPS22 * np.abs(f)).any(axis=1)
         hit = inside & rec.valid[q][key] & finite
         k = key[hit]
         qv = img[hit] - rec.mean[q][k]

@@ -6,6 +6,7 @@ import pytest
 
 import cell_record_ref as X
 import map_coarsen_ref as R
+import seam_ref as S
 
 pytestmark = pytest.mark.gpu
 
@@ -93,8 +94,8 @@ def test_random_clouds_build_and_evaluate_like_the_oracle(gpu_lib):
             H, gr, score, n_hit = m.evaluate(sx, sy, pose)
             ok = np.isfinite(sx) & np.isfinite(sy)
             Hm, gm, sm, nm = o.evaluate(g, sx[ok], sy[ok], pose, prm, mirror32=True)
-            assert abs(n_hit - nm) <= 2, (i, n_hit, nm)
-            if nm > 2 and n_hit == nm:
+            assert n_hit == nm, (i, n_hit, nm)
+            if nm > 2:
                 hs = max(np.abs(Hm).max(), 1e-30)
                 assert np.abs(H - Hm).max() / hs < 1e-3, (i, kw)
                 assert abs(score - sm) <= 1e-3 * max(sm, 1e-6), (i, score, sm)
@@ -113,6 +114,12 @@ def test_random_clouds_build_and_evaluate_like_the_oracle(gpu_lib):
                 assert rb.status in (L.NDT_TOO_FEW_HITS, L.NDT_DEGENERATE_HESSIAN), (i, rb.status)
             checked += 1
     assert checked >= 40 and n_grad >= 4
+
+
+def _hits3(g, img):
+    """hits of an exact float32 image (tests/seam_ref.py) on an oracle voxel grid"""
+    key, inside, _ = S.keys3d(*img, (g.o, g.inv_c, g.dims))
+    return int((inside & g.valid[np.where(inside, key, 0)]).sum())
 
 
 def _cases3d(n_cases=24, seed=77):
@@ -162,9 +169,9 @@ def test_random_clouds_3d(gpu_lib):
                 assert m.align(sx, sy, sz, pose).status == L.NDT_TOO_FEW_CELLS
                 continue
             H, gr, s, nh = m.evaluate(sx, sy, sz, pose)
-            Hm, gm, sm, nm = o3.evaluate3(g, sx, sy, sz, pose, prm, mirror32=True)
-            assert abs(nh - nm) <= 2, (i, nh, nm)
-            if nm > 3 and nh == nm:
+            Hm, gm, sm, nm = o3.evaluate3(g, sx, sy, sz, pose, prm, mirror32=True, chain=True)
+            assert nh == nm, (i, nh, nm)
+            if nm > 3:
                 hs = max(np.abs(Hm).max(), 1e-30)
                 assert np.abs(H - Hm).max() / hs < 2e-3, (i, kw)
                 assert abs(s - sm) <= 2e-3 * max(sm, 1e-6)
@@ -184,6 +191,12 @@ def test_random_clouds_3d(gpu_lib):
                 rb, rl = b.align([(tx, ty, tz), laced((tx, ty, tz), 9)], [(sx, sy, sz), laced((sx, sy, sz), 7)], [pose, pose])
             assert rb.status == rl.status and rb.n_hit == rl.n_hit and rb.pose == rl.pose and np.array_equal(rb.H, rl.H), i
             if rb.status in (L.NDT_OK, L.NDT_NOT_CONVERGED):
+                # k_batch3 rounds its image once more than k_iterate3 (docs/ALGORITHM.md 2.6: y = R p by the fmaf chain, then
+                # y + t), so the two may disagree on the voxel of a point within an ulp of a seam.  The counts are equal here
+                # because no point of this seed is such a point: the two exact recipes give the same hits (asserted), and
+                # each kernel is held to its own recipe on the seams by tests/test_gpu_seams.py.
+                both = [_hits3(g, image(sx, sy, sz, pose)) for image in (S.image3d, S.image3d_batch)]
+                assert both[0] == both[1] == nm, (i, both, nm)
                 assert rb.n_hit == nh, (i, rb.n_hit, nh)
                 hs = max(np.abs(H).max(), 1e-30)
                 assert np.abs(rb.H - H).max() / hs < 2e-4, (i, kw)
