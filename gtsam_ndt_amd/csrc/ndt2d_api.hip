@@ -448,12 +448,11 @@ int32_t setup_geometry(ndt2d_handle* h, float xmin, float xmax, float ymin, floa
   GridDev& g = h->grid;
   g.cell = c;
   g.cell32 = (float)c;
-  g.inv_c = (float)(1.0 / c);
-  g.ox = (float)((std::floor((double)xmin / c) - 1.0) * c);
-  g.oy = (float)((std::floor((double)ymin / c) - 1.0) * c);
-  const volatile float fx = (xmax - g.ox) * g.inv_c;   // float32 arithmetic, as the kernels
-  const volatile float fy = (ymax - g.oy) * g.inv_c;
-  const double kx = std::floor((double)fx), ky = std::floor((double)fy);
+  g.inv_c = lattice_inv_c(c);
+  const LatticeAxis X = lattice_axis(xmin, xmax, c), Y = lattice_axis(ymin, ymax, c);   // the rule the kernels call
+  g.ox = X.origin;
+  g.oy = Y.origin;
+  const double kx = X.k, ky = Y.k;
   if (!(kx >= 0.0) || !(ky >= 0.0) || (kx + 2.0) * (ky + 2.0) > (double)kMaxCells) {
     set_error("target extent / cell_size needs more than 2^27 cells");
     return NDT_ERR_CAPACITY;
@@ -464,10 +463,9 @@ int32_t setup_geometry(ndt2d_handle* h, float xmin, float xmax, float ymin, floa
   const int extra = g.ngrid > 1 ? 1 : 0;
   g.W = (int)kx + 2 + extra;
   g.H = (int)ky + 2 + extra;
-  static const double kShift[4][2] = {{0.0, 0.0}, {0.5, 0.0}, {0.0, 0.5}, {0.5, 0.5}};
   for (int q = 0; q < kMaxGrids; ++q) {
-    g.gx[q] = (float)((std::floor((double)xmin / c) - 1.0 - kShift[q][0]) * c);
-    g.gy[q] = (float)((std::floor((double)ymin / c) - 1.0 - kShift[q][1]) * c);
+    g.gx[q] = lattice_origin(X.base, overlap_shift(q, 0), c);
+    g.gy[q] = lattice_origin(Y.base, overlap_shift(q, 1), c);
   }
   g.fix_scale = std::ldexp(1.0, kFixShift) / c;
   const size_t ncell = (size_t)g.W * g.H * g.ngrid;     // all grids, back to back
@@ -524,7 +522,8 @@ int32_t set_target_single_sync(ndt2d_handle* h, const float* d_x, const float* d
   for (int j = 0; j < 4; ++j) hb_out[j] = hg->bounds[j];
   *have_bounds = true;
   if (!hg->ok) return NDT_OK;                            // does not fit storage or bound (or no finite point): the usual way
-  // the host's view of the same geometry, from the same bounds; storage is large enough, nothing is reallocated
+  // the host's view of the same geometry, from the same bounds by the function the kernel called (lattice_axis): the
+  // comparison guards the storage and the launch bound; storage is large enough, nothing is reallocated
   const int32_t gs = setup_geometry(h, ordered_to_float(hg->bounds[0]), ordered_to_float(hg->bounds[1]),
                                     ordered_to_float(hg->bounds[2]), ordered_to_float(hg->bounds[3]));
   if (gs != NDT_OK) return NDT_OK;

@@ -306,13 +306,12 @@ __device__ __forceinline__ void process_pair(const BatchArgs& a, const int pair,
         }
         int st = 0, W = 0, H = 0;
         float ox = 0.f, oy = 0.f;
-        const float inv_c = (float)(1.0 / a.cell);
         if (!(xmin <= xmax) || !(ymin <= ymax)) {
           st = 4;                                   // no finite target point -> no valid cell
         } else {
-          ox = (float)((floor((double)xmin / a.cell) - 1.0) * a.cell);
-          oy = (float)((floor((double)ymin / a.cell) - 1.0) * a.cell);
-          const float kx = floorf((xmax - ox) * inv_c), ky = floorf((ymax - oy) * inv_c);
+          const LatticeAxis X = lattice_axis(xmin, xmax, a.cell), Y = lattice_axis(ymin, ymax, a.cell);
+          ox = X.origin; oy = Y.origin;
+          const float kx = X.k, ky = Y.k;
           constexpr float kExtent = NG > 1 ? 3.f : 2.f;        // overlapping grids: one extra column and row
           if (!(kx >= 0.f) || !(ky >= 0.f) || (double)(kx + kExtent) * (double)(ky + kExtent) * NG > (double)Cfg::kMaxCells) {
             st = kStatusCapacity;
@@ -320,8 +319,8 @@ __device__ __forceinline__ void process_pair(const BatchArgs& a, const int pair,
             W = (int)kx + (int)kExtent; H = (int)ky + (int)kExtent;
           }
           if (NG > 1) {                                        // the origins moved down by half a cell
-            reinterpret_cast<float*>(misc)[11] = (float)((floor((double)xmin / a.cell) - 1.5) * a.cell);
-            reinterpret_cast<float*>(misc)[12] = (float)((floor((double)ymin / a.cell) - 1.5) * a.cell);
+            reinterpret_cast<float*>(misc)[11] = lattice_origin(X.base, 0.5, a.cell);
+            reinterpret_cast<float*>(misc)[12] = lattice_origin(Y.base, 0.5, a.cell);
           }
         }
         misc[1] = W; misc[2] = H; misc[3] = st;
@@ -340,8 +339,8 @@ __device__ __forceinline__ void process_pair(const BatchArgs& a, const int pair,
       const float oxs = uniformf(reinterpret_cast<float*>(misc)[11]), oys = uniformf(reinterpret_cast<float*>(misc)[12]);
       gxq[1] = oxs; gyq[1] = oy; gxq[2] = ox; gyq[2] = oys; gxq[3] = oxs; gyq[3] = oys;
     }
-    const float inv_c = (float)(1.0 / a.cell);
-    const float fWm1 = (float)(W - 1), fHm1 = (float)(Hh - 1);
+    const float inv_c = lattice_inv_c(a.cell);
+    const Limit2 hx(W), hy(Hh);
     const int ncell1 = W * Hh;                       // cells of one grid
     const int ncell = NG * ncell1;                   // ... of the tables
     const double fix_scale = 4194304.0 / a.cell;     // 2^kFixShift / c
@@ -371,9 +370,9 @@ __device__ __forceinline__ void process_pair(const BatchArgs& a, const int pair,
         for_each_target_point<Cfg>(tx, ty, nt, [&](float px, float py) {
 #pragma unroll
           for (int q = 0; q < NG; ++q) {
-            const float fx = (px - gxq[q]) * inv_c, fy = (py - gyq[q]) * inv_c;
-            if ((fx >= 1.f) & (fx < fWm1) & (fy >= 1.f) & (fy < fHm1)) {   // ring cells stay empty (in_interior)
-              const int r = q * ncell1 + (int)fy * W + (int)fx - c0;
+            int ix, iy;
+            if (cell_of(px, py, gxq[q], gyq[q], inv_c, hx, hy, ix, iy)) {
+              const int r = q * ncell1 + iy * W + ix - c0;
               if ((unsigned)r < (unsigned)np) atomicAdd(&pc[r], 1u);
             }
           }
@@ -392,9 +391,9 @@ __device__ __forceinline__ void process_pair(const BatchArgs& a, const int pair,
       }
       __syncthreads();
       for_each_target_point<Cfg>(tx, ty, nt, [&](float px, float py) {
-        const float fx = (px - ox) * inv_c, fy = (py - oy) * inv_c;
-        if ((fx >= 1.f) & (fx < fWm1) & (fy >= 1.f) & (fy < fHm1)) {   // ring cells stay empty (in_interior)
-          const int key = (int)fy * W + (int)fx;
+        int ix, iy;
+        if (cell_of(px, py, ox, oy, inv_c, hx, hy, ix, iy)) {
+          const int key = iy * W + ix;
           if (Cfg::kPackedCount) atomicAdd(&cnt_pairs[key >> 1], (key & 1) ? 0x10000u : 1u);   // nt < 65536: no carry
           else atomicAdd(&cnt[key], 1u);
         }
@@ -450,19 +449,13 @@ __device__ __forceinline__ void process_pair(const BatchArgs& a, const int pair,
         for_each_target_point<Cfg>(tx, ty, nt, [&](float px, float py) {
 #pragma unroll
           for (int q = 0; q < NG; ++q) {
-            const float fx = (px - gxq[q]) * inv_c, fy = (py - gyq[q]) * inv_c;
-            if ((fx >= 1.f) & (fx < fWm1) & (fy >= 1.f) & (fy < fHm1)) {   // ring cells stay empty (in_interior)
-              const int ix = (int)fx, iy = (int)fy;
+            int ix, iy;
+            if (cell_of(px, py, gxq[q], gyq[q], inv_c, hx, hy, ix, iy)) {
               const int r = (int)idx[q * ncell1 + iy * W + ix] - 1 - s0;    // slot 0 (no record) gives r < 0
               if ((unsigned)r < (unsigned)np) {
-                const int ux = fix_coord(px, cell_centre(gxq[q], ix, a.cell), fix_scale);
-                const int uy = fix_coord(py, cell_centre(gyq[q], iy, a.cell), fix_scale);
                 unsigned long long* w = ps + r;
-                atomicAdd(w, (unsigned long long)(long long)ux);
-                atomicAdd(w + np, (unsigned long long)(long long)uy);
-                atomicAdd(w + 2 * np, prod64(ux, ux));
-                atomicAdd(w + 3 * np, prod64(ux, uy));
-                atomicAdd(w + 4 * np, prod64(uy, uy));
+                point_terms(px, py, gxq[q], gyq[q], ix, iy, a.cell, fix_scale,
+                            [&](int j, unsigned long long t) { atomicAdd(w + j * np, t); });
               }
             }
           }
@@ -478,19 +471,13 @@ __device__ __forceinline__ void process_pair(const BatchArgs& a, const int pair,
 
       // ---- a2 (2/2): exact fixed-point sums per slot (LDS 64-bit integer atomics)
       for_each_target_point<Cfg>(tx, ty, nt, [&](float px, float py) {
-        const float fx = (px - ox) * inv_c, fy = (py - oy) * inv_c;
-        if ((fx >= 1.f) & (fx < fWm1) & (fy >= 1.f) & (fy < fHm1)) {   // ring cells stay empty (in_interior)
-          const int ix = (int)fx, iy = (int)fy;
+        int ix, iy;
+        if (cell_of(px, py, ox, oy, inv_c, hx, hy, ix, iy)) {
           const int slot = idx[iy * W + ix];
           if (slot) {
-            const int ux = fix_coord(px, cell_centre(ox, ix, a.cell), fix_scale);
-            const int uy = fix_coord(py, cell_centre(oy, iy, a.cell), fix_scale);
             unsigned long long* q = sums + (slot - 1);
-            atomicAdd(q, (unsigned long long)(long long)ux);
-            atomicAdd(q + Cfg::kMaxSlots, (unsigned long long)(long long)uy);
-            atomicAdd(q + 2 * Cfg::kMaxSlots, prod64(ux, ux));
-            atomicAdd(q + 3 * Cfg::kMaxSlots, prod64(ux, uy));
-            atomicAdd(q + 4 * Cfg::kMaxSlots, prod64(uy, uy));
+            point_terms(px, py, ox, oy, ix, iy, a.cell, fix_scale,
+                        [&](int j, unsigned long long t) { atomicAdd(q + j * Cfg::kMaxSlots, t); });
           }
         }
       });

@@ -46,48 +46,45 @@ __global__ __launch_bounds__(1024) void k_build_init(GeomDev* __restrict__ geom,
   }
 }
 
-// a1 on the device: oracle/ndt2d.py grid_geometry, the arithmetic of setup_geometry() on the host (the host
-// recomputes it from the same bounds afterwards and compares).  One thread.
+// a1 on the device (oracle/ndt2d.py grid_geometry): the grid of a bounding box by the rule setup_geometry() on the host
+// calls too (lattice_axis, ndt_lattice.hpp), if it fits the handle's storage and the launch bounds the host chose.  One
+// lane.  grid (may be null) receives the device context's copy.
+__device__ inline bool decide_geometry(const unsigned int b[4], double c, unsigned long long cell_capacity, int tile_bound,
+                                       BinGeom* bin, GridDev* grid) {
+  if (b[0] == 0xFFFFFFFFu || b[1] == 0u) return false;          // no finite point
+  const LatticeAxis X = lattice_axis(ordered_to_float(b[0]), ordered_to_float(b[1]), c);
+  const LatticeAxis Y = lattice_axis(ordered_to_float(b[2]), ordered_to_float(b[3]), c);
+  if (!(X.k >= 0.f && Y.k >= 0.f && ((double)X.k + 2.0) * ((double)Y.k + 2.0) <= (double)cell_capacity)) return false;
+  const int W = (int)X.k + 2, H = (int)Y.k + 2;
+  const int ntx = (W + kTile - 1) >> kTileShift, nty = (H + kTile - 1) >> kTileShift;
+  if ((long long)ntx * nty > (long long)tile_bound) return false;
+  const float inv_c = lattice_inv_c(c);
+  bin->ox = X.origin; bin->oy = Y.origin; bin->inv_c = inv_c; bin->W = W; bin->H = H; bin->ntx = ntx; bin->ntile = ntx * nty;
+  if (grid) {
+    grid->ox = X.origin; grid->oy = Y.origin; grid->inv_c = inv_c; grid->cell32 = (float)c;
+    grid->W = W; grid->H = H; grid->ngrid = 1; grid->pad = 0;
+#pragma unroll
+    for (int q = 0; q < kMaxGrids; ++q) {
+      grid->gx[q] = lattice_origin(X.base, overlap_shift(q, 0), c);
+      grid->gy[q] = lattice_origin(Y.base, overlap_shift(q, 1), c);
+    }
+    grid->cell = c;
+    grid->fix_scale = 4194304.0 / c;
+    static_assert(kFixShift == 22, "fix_scale literal");
+  }
+  return true;
+}
+
+// ... as a kernel of its own, for the binned build.  One thread.
 __global__ void k_geometry(double c, unsigned long long cell_capacity, int tile_bound, GridDev* __restrict__ grid,
                            GeomDev* __restrict__ out) {
   if (threadIdx.x != 0 || blockIdx.x != 0) return;
-  const unsigned int* bounds = out->bounds;
-  GeomDev o = *out;
-  if (!(bounds[0] == 0xFFFFFFFFu || bounds[1] == 0u)) {       // at least one finite point
-    const float xmin = ordered_to_float(bounds[0]), xmax = ordered_to_float(bounds[1]);
-    const float ymin = ordered_to_float(bounds[2]), ymax = ordered_to_float(bounds[3]);
-    const float inv_c = (float)(1.0 / c);
-    const double bx = floor((double)xmin / c), by = floor((double)ymin / c);
-    const float ox = (float)((bx - 1.0) * c), oy = (float)((by - 1.0) * c);
-    const float fx = (xmax - ox) * inv_c, fy = (ymax - oy) * inv_c;
-    const double kx = floor((double)fx), ky = floor((double)fy);
-    if (kx >= 0.0 && ky >= 0.0 && (kx + 2.0) * (ky + 2.0) <= (double)cell_capacity) {
-      const int W = (int)kx + 2, H = (int)ky + 2;
-      const int ntx = (W + kTile - 1) >> kTileShift, nty = (H + kTile - 1) >> kTileShift;
-      if ((long long)ntx * nty <= (long long)tile_bound) {
-        o.bin.ox = ox; o.bin.oy = oy; o.bin.inv_c = inv_c; o.bin.W = W; o.bin.H = H; o.bin.ntx = ntx; o.bin.ntile = ntx * nty;
-        o.ok = 1;
-        grid->ox = ox; grid->oy = oy; grid->inv_c = inv_c; grid->cell32 = (float)c;
-        grid->W = W; grid->H = H; grid->ngrid = 1; grid->pad = 0;
-        const double sh[4][2] = {{0.0, 0.0}, {0.5, 0.0}, {0.0, 0.5}, {0.5, 0.5}};
-#pragma unroll
-        for (int q = 0; q < kMaxGrids; ++q) {
-          grid->gx[q] = (float)((bx - 1.0 - sh[q][0]) * c);
-          grid->gy[q] = (float)((by - 1.0 - sh[q][1]) * c);
-        }
-        grid->cell = c;
-        grid->fix_scale = 4194304.0 / c;
-        static_assert(kFixShift == 22, "fix_scale literal");
-      }
-    }
-  }
-  *out = o;
+  out->ok = decide_geometry(out->bounds, c, cell_capacity, tile_bound, &out->bin, grid) ? 1 : 0;
 }
 
 __device__ __forceinline__ int tile_of(const BinGeom& g, float px, float py) {
-  const float fx = (px - g.ox) * g.inv_c, fy = (py - g.oy) * g.inv_c;
-  const bool in = in_interior(fx, fy, g.W, g.H);      // ring cells stay empty (ndt2d_kernels.hpp)
-  return in ? (((int)fy >> kTileShift) * g.ntx + ((int)fx >> kTileShift)) : -1;
+  int ix, iy;
+  return cell_of(px, py, g.ox, g.oy, g.inv_c, Limit2(g.W), Limit2(g.H), ix, iy) ? ((iy >> kTileShift) * g.ntx + (ix >> kTileShift)) : -1;
 }
 
 // P1: per-tile totals.  LDS histogram per workgroup, one global atomic per touched tile.
@@ -251,17 +248,12 @@ __global__ __launch_bounds__(kBinThreads) void k_tile_accumulate(const float* __
 #pragma unroll
     for (int u = 0; u < 4; ++u) {
       if (i + u * kBinThreads < p1) {
-        const float fx = (px[u] - ox) * g.inv_c, fy = (py[u] - oy) * g.inv_c;
-        const int ix = (int)fx, iy = (int)fy;            // in range: the point was binned by the same formula
-        const int ux = fix_coord(px[u], cell_centre(ox, ix, g.cell), g.fix_scale);
-        const int uy = fix_coord(py[u], cell_centre(oy, iy, g.cell), g.fix_scale);
+        // in range: the point was binned by the same rule (tile_of)
+        const int ix = lattice_index(px[u], ox, g.inv_c), iy = lattice_index(py[u], oy, g.inv_c);
         const int c = ((iy - ty0) << kTileShift) + (ix - tx0);
         atomicAdd(&s_n[c], signed_one<SIGN>());
-        atomicAdd(&s_sum[0][c], signed_term<SIGN>((unsigned long long)(long long)ux));
-        atomicAdd(&s_sum[1][c], signed_term<SIGN>((unsigned long long)(long long)uy));
-        atomicAdd(&s_sum[2][c], signed_term<SIGN>(prod64(ux, ux)));
-        atomicAdd(&s_sum[3][c], signed_term<SIGN>(prod64(ux, uy)));
-        atomicAdd(&s_sum[4][c], signed_term<SIGN>(prod64(uy, uy)));
+        point_terms(px[u], py[u], ox, oy, ix, iy, g.cell, g.fix_scale,
+                    [&](int j, unsigned long long t) { atomicAdd(&s_sum[j][c], signed_term<SIGN>(t)); });
       }
     }
   }

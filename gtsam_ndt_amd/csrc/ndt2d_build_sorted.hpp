@@ -138,40 +138,6 @@ __global__ __launch_bounds__(64) void k_bounds_reduce(const float4* __restrict__
   if (threadIdx.x == 0) { out[0] = b[0]; out[1] = b[1]; out[2] = b[2]; out[3] = b[3]; }
 }
 
-// a1 on the device (oracle/ndt2d.py grid_geometry; the arithmetic of setup_geometry() on the host, which recomputes it
-// from the same bounds afterwards and compares): the grid of a bounding box, if it fits the handle's storage and the
-// launch bounds the host chose.  One lane.  grid (may be null) receives the device context's copy.
-__device__ inline bool decide_geometry(const unsigned int b[4], double c, unsigned long long cell_capacity, int tile_bound,
-                                       BinGeom* bin, GridDev* grid) {
-  if (b[0] == 0xFFFFFFFFu || b[1] == 0u) return false;          // no finite point
-  const float xmin = ordered_to_float(b[0]), xmax = ordered_to_float(b[1]);
-  const float ymin = ordered_to_float(b[2]), ymax = ordered_to_float(b[3]);
-  const float inv_c = (float)(1.0 / c);
-  const double bx = floor((double)xmin / c), by = floor((double)ymin / c);
-  const float ox = (float)((bx - 1.0) * c), oy = (float)((by - 1.0) * c);
-  const float fx = (xmax - ox) * inv_c, fy = (ymax - oy) * inv_c;
-  const double kx = floor((double)fx), ky = floor((double)fy);
-  if (!(kx >= 0.0 && ky >= 0.0 && (kx + 2.0) * (ky + 2.0) <= (double)cell_capacity)) return false;
-  const int W = (int)kx + 2, H = (int)ky + 2;
-  const int ntx = (W + kTile - 1) >> kTileShift, nty = (H + kTile - 1) >> kTileShift;
-  if ((long long)ntx * nty > (long long)tile_bound) return false;
-  bin->ox = ox; bin->oy = oy; bin->inv_c = inv_c; bin->W = W; bin->H = H; bin->ntx = ntx; bin->ntile = ntx * nty;
-  if (grid) {
-    grid->ox = ox; grid->oy = oy; grid->inv_c = inv_c; grid->cell32 = (float)c;
-    grid->W = W; grid->H = H; grid->ngrid = 1; grid->pad = 0;
-    const double sh[4][2] = {{0.0, 0.0}, {0.5, 0.0}, {0.0, 0.5}, {0.5, 0.5}};
-#pragma unroll
-    for (int q = 0; q < kMaxGrids; ++q) {
-      grid->gx[q] = (float)((bx - 1.0 - sh[q][0]) * c);
-      grid->gy[q] = (float)((by - 1.0 - sh[q][1]) * c);
-    }
-    grid->cell = c;
-    grid->fix_scale = 4194304.0 / c;
-    static_assert(kFixShift == 22, "fix_scale literal");
-  }
-  return true;
-}
-
 // A build whose geometry is decided on the device: k_chunk_sort does it in its prologue - EVERY workgroup reduces the
 // partial boxes (4 KB) and applies the rule (the same inputs, the same arithmetic: the same grid everywhere), workgroup 0
 // also writes the result where the gather kernel, the alignments and the host read it.  A kernel of its own for this
@@ -399,17 +365,12 @@ __global__ __launch_bounds__(kGatherThreads) void k_tile_gather(const float2* __
   NDT_STAMP(1);
   const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
   auto add_point = [&](float2 p) {
-    const float fx = (p.x - ox) * inv_c, fy = (p.y - oy) * inv_c;
-    const int cx = (int)fx, cy = (int)fy;              // in range: the point was binned by the same formula
-    const int ux = fix_coord(p.x, cell_centre(ox, cx, cell_size), fix_scale);
-    const int uy = fix_coord(p.y, cell_centre(oy, cy, cell_size), fix_scale);
+    // in range: the point was binned by the same rule (tile_of)
+    const int cx = lattice_index(p.x, ox, inv_c), cy = lattice_index(p.y, oy, inv_c);
     const int c = (cy - ty0) * kTileStride + (cx - tx0);
     atomicAdd(&s_n[c], signed_one<SIGN>());
-    atomicAdd(&s_sum[0][c], signed_term<SIGN>((unsigned long long)(long long)ux));
-    atomicAdd(&s_sum[1][c], signed_term<SIGN>((unsigned long long)(long long)uy));
-    atomicAdd(&s_sum[2][c], signed_term<SIGN>(prod64(ux, ux)));
-    atomicAdd(&s_sum[3][c], signed_term<SIGN>(prod64(ux, uy)));
-    atomicAdd(&s_sum[4][c], signed_term<SIGN>(prod64(uy, uy)));
+    point_terms(p.x, p.y, ox, oy, cx, cy, cell_size, fix_scale,
+                [&](int j, unsigned long long t) { atomicAdd(&s_sum[j][c], signed_term<SIGN>(t)); });
   };
   // A wave per run, four runs in flight: wave w takes the runs w, w + 16, ... of this tile.  The loads of four runs
   // are issued before any point is summed - one load per lane and run covers a run of up to 64 points, which is

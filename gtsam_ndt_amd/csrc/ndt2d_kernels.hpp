@@ -14,6 +14,7 @@
 #pragma once
 #include "ndt_device.hpp"
 #include "ndt_chain.hpp"
+#include "ndt_lattice.hpp"
 
 namespace ndt {
 
@@ -184,26 +185,13 @@ __global__ __launch_bounds__(kBlock) void k_bounds(const float* __restrict__ x,
 // geometry leaves the ring empty by construction (one guard cell either side) except for a
 // boundary point that float32 rounding of (x - ox) * inv_c puts into cell 0 with a cell size that
 // is not a power of two; ndt2d_reserve_target + ndt2d_add_target_points can put points anywhere.
-// Both are handled here: a point whose cell lies on the ring counts as outside the grid
-// (oracle/ndt2d.py cell_keys32(interior=True) states the same rule).
-__device__ __forceinline__ bool in_interior(float fx, float fy, int W, int H) {
-  return (fx >= 1.f) & (fx < (float)(W - 1)) & (fy >= 1.f) & (fy < (float)(H - 1));
-}
-
-// ---------------------------------------------------------------- shared cell arithmetic
-// Used verbatim by the global-memory path (k_accumulate/k_finalise) and by the LDS-resident
-// batch kernel, so both build bit-identical cell records from the same points.
-__device__ __forceinline__ double cell_centre(float o, int i, double cell) {
-  return fma((double)i + 0.5, cell, (double)o);
-}
-// |U| <= 2^21 for a point inside its cell, so the conversion is the single-instruction
-// v_cvt_i32_f64 (an f64 -> i64 conversion is emulated) and products are 32 x 32 -> 64 bit.
-__device__ __forceinline__ int fix_coord(float p, double centre, double fix_scale) {
-  return __double2int_rn(((double)p - centre) * fix_scale);
-}
-__device__ __forceinline__ unsigned long long prod64(int a, int b) {
-  return (unsigned long long)((long long)a * (long long)b);
-}
+// Both are handled by the one rule every build path calls, cell_of<kRing2> (ndt_lattice.hpp): a point
+// whose cell lies on the ring counts as outside the grid (oracle/ndt2d.py cell_keys32(interior=True)
+// states the same rule).  cell_centre, fix_coord and the terms of a point come from the same header,
+// so the global-memory path, the binned builds and the LDS-resident batch kernels build
+// bit-identical cell records from the same points.
+constexpr int kRing2 = 1;
+using Limit2 = LatticeLimit<kRing2>;
 
 // a3 (1/2): exact sums -> Welford form (n, mean, M2) -> Sigma = M2/(n-1) -> eigenvalues, clamp, unit eigenvector of
 // the large one.  float64 scalar code in the order of oracle/ndt2d.py finalise_cell().  Shared by the Sigma^-1
@@ -290,21 +278,14 @@ __global__ __launch_bounds__(kBlock) void k_accumulate(const float* __restrict__
     bool any = false;
     for (int q = 0; q < g.ngrid; ++q) {
       const float ox = g.gx[q], oy = g.gy[q];
-      const float fx = (px - ox) * g.inv_c;
-      const float fy = (py - oy) * g.inv_c;
-      const bool in = in_interior(fx, fy, g.W, g.H);
-      if (in) {
+      int ix, iy;
+      if (cell_of(px, py, ox, oy, g.inv_c, Limit2(g.W), Limit2(g.H), ix, iy)) {
         any = true;
-        const int ix = (int)fx, iy = (int)fy;
-        const int ux = fix_coord(px, cell_centre(ox, ix, g.cell), g.fix_scale);
-        const int uy = fix_coord(py, cell_centre(oy, iy, g.cell), g.fix_scale);
         CellAcc* c = g.acc + (q * ncell + (size_t)iy * g.W + ix);
         atomicAdd(&c->n, signed_one<SIGN>());
-        atomicAdd((unsigned long long*)&c->sx, signed_term<SIGN>((unsigned long long)(long long)ux));
-        atomicAdd((unsigned long long*)&c->sy, signed_term<SIGN>((unsigned long long)(long long)uy));
-        atomicAdd((unsigned long long*)&c->sxx, signed_term<SIGN>(prod64(ux, ux)));
-        atomicAdd((unsigned long long*)&c->sxy, signed_term<SIGN>(prod64(ux, uy)));
-        atomicAdd((unsigned long long*)&c->syy, signed_term<SIGN>(prod64(uy, uy)));
+        point_terms(px, py, ox, oy, ix, iy, g.cell, g.fix_scale, [&](int j, unsigned long long t) {
+          atomicAdd((unsigned long long*)&c->sx + j, signed_term<SIGN>(t));
+        });
       }
     }
     if (!any) outside++;

@@ -233,17 +233,15 @@ int32_t setup_geometry3(ndt3d_handle* h, const float lo[3], const float hi[3]) {
   const double c = h->prm.cell_size;
   Grid3Dev& g = h->grid;
   g.cell = c;
-  g.inv_c = (float)(1.0 / c);
+  g.inv_c = lattice_inv_c(c);
   float o[3];
   int dims[3];
   double ncell_d = 1.0;
   for (int a = 0; a < 3; ++a) {
-    const float mn = lo[a], mx = hi[a];
-    o[a] = (float)((std::floor((double)mn / c) - 1.0) * c);
-    const volatile float f = (mx - o[a]) * g.inv_c;
-    const double k = std::floor((double)f);
-    if (!(k >= 0.0) || k > 1e7) { set_error("target extent too large for the cell size"); return NDT_ERR_CAPACITY; }
-    dims[a] = (int)k + 2;
+    const LatticeAxis A = lattice_axis(lo[a], hi[a], c);          // the rule the kernels call
+    if (!(A.k >= 0.f) || A.k > 1e7f) { set_error("target extent too large for the cell size"); return NDT_ERR_CAPACITY; }
+    o[a] = A.origin;
+    dims[a] = (int)A.k + 2;
     ncell_d *= dims[a];
   }
   if (ncell_d > (double)kMaxCells) { set_error("3D target needs more than 2^27 cells"); return NDT_ERR_CAPACITY; }
@@ -260,7 +258,8 @@ int32_t setup_geometry3(ndt3d_handle* h, const float lo[3], const float hi[3]) {
 // the cached grid's tiles), scan, scatter, tile kernel with the geometry read from device memory - and one publish of the
 // results AND the box.  If
 // the grid does not fit, ok = 0 makes every kernel return and the caller builds the usual way with the box it now has.
-// The host recomputes the geometry from the same box afterwards and compares.
+// The host forms the geometry from the same box afterwards, by the function the kernel called (lattice_axis), and compares:
+// the check guards the storage and the launch bound.
 int32_t set_target3_single_sync(ndt3d_handle* h, const float* dx, const float* dy, const float* dz, size_t n, bool* done,
                                 unsigned int* hb_out, bool* have_bounds) {
   using namespace ndt;

@@ -374,15 +374,14 @@ __device__ __forceinline__ void process_pair3(const Batch3Args& a, const int pai
     if (tid == 0) {
       int st = 0, dims[3] = {0, 0, 0};
       float o[3] = {0.f, 0.f, 0.f};
-      const float inv_c = (float)(1.0 / a.cell);
       double ncell_d = 1.0;
       for (int c = 0; c < 3; ++c) {
         for (int w = 1; w < kB3Waves; ++w) { mn[c] = fminf(mn[c], red[w * 6 + 2 * c]); mx[c] = fmaxf(mx[c], red[w * 6 + 2 * c + 1]); }
         if (!(mn[c] <= mx[c])) { st = 4; break; }     // no finite target point -> no valid voxel
-        o[c] = (float)((floor((double)mn[c] / a.cell) - 1.0) * a.cell);
-        const float k = floorf((mx[c] - o[c]) * inv_c);
-        if (!(k >= 0.f) || k > 65534.f) { st = kStatusCapacity; break; }
-        dims[c] = (int)k + 2;
+        const LatticeAxis A = lattice_axis(mn[c], mx[c], a.cell);
+        o[c] = A.origin;
+        if (!(A.k >= 0.f) || A.k > 65534.f) { st = kStatusCapacity; break; }
+        dims[c] = (int)A.k + 2;
         ncell_d *= (double)dims[c];
       }
       // the voxel table (2 B per voxel) and, during the build, the counts (4 B per voxel) behind it
@@ -399,8 +398,8 @@ __device__ __forceinline__ void process_pair3(const Batch3Args& a, const int pai
   const int st0 = __builtin_amdgcn_readfirstlane(misc[4]);
   const float ox = uniformf(reinterpret_cast<float*>(misc)[5]), oy = uniformf(reinterpret_cast<float*>(misc)[6]),
               oz = uniformf(reinterpret_cast<float*>(misc)[7]);
-  const float inv_c = (float)(1.0 / a.cell);
-  const float fW = (float)W, fH = (float)Hh, fD = (float)D;
+  const float inv_c = lattice_inv_c(a.cell);
+  const Limit3 hx(W), hy(Hh), hz(D);
   const int ncell = W * Hh * D;
   const double fix_scale = 4194304.0 / a.cell;     // 2^kFixShift / c
   static_assert(kFixShift == 22, "fix_scale literal");
@@ -426,10 +425,7 @@ __device__ __forceinline__ void process_pair3(const Batch3Args& a, const int pai
   // (voxel keys are formed with 24-bit multiplies - every index and the key itself stay below 2^21 - which issue at
   // full rate; the 32-bit form compiles to quarter-rate v_mad_u64_u32)
   auto voxel_of = [&](float px, float py, float pz, int& ix, int& iy, int& iz) -> bool {
-    const float fx = (px - ox) * inv_c, fy = (py - oy) * inv_c, fz = (pz - oz) * inv_c;
-    const bool in = (fx >= 0.f) & (fx < fW) & (fy >= 0.f) & (fy < fH) & (fz >= 0.f) & (fz < fD);
-    ix = (int)fx; iy = (int)fy; iz = (int)fz;
-    return in;
+    return cell_of(px, py, pz, ox, oy, oz, inv_c, hx, hy, hz, ix, iy, iz);
   };
 
 #ifdef NDT_B3_PHASE_CLOCKS
@@ -550,12 +546,13 @@ __device__ __forceinline__ void process_pair3(const Batch3Args& a, const int pai
     };
     for_each_target_point_rows3(tx, ty, tz, nt, [&](float px, float py, float pz) {
       int ix, iy, iz;
-      const int key = voxel_of(px, py, pz, ix, iy, iz) ? __mul24(__mul24(iz, Hh) + iy, W) + ix : -1;
+      const bool in = voxel_of(px, py, pz, ix, iy, iz);
+      const int key = in ? __mul24(__mul24(iz, Hh) + iy, W) + ix : -1;
       if (key != cur || run == 256) {
         flush();
         cur = key;
         r = -1;
-        if (key >= 0) {
+        if (in) {
           r = (int)idx[key] - 1 - s0;                                        // no slot: r < 0
           if ((unsigned)r >= (unsigned)np) r = -1;
           ccx = cell_centre(ox, ix, a.cell); ccy = cell_centre(oy, iy, a.cell); ccz = cell_centre(oz, iz, a.cell);
@@ -591,19 +588,9 @@ __device__ __forceinline__ void process_pair3(const Batch3Args& a, const int pai
         if (voxel_of(px, py, pz, ix, iy, iz)) {
           const int r = (int)idx[__mul24(__mul24(iz, Hh) + iy, W) + ix] - 1 - s0;      // no slot: r < 0
           if ((unsigned)r < (unsigned)np) {
-            const int ux = fix_coord(px, cell_centre(ox, ix, a.cell), fix_scale);
-            const int uy = fix_coord(py, cell_centre(oy, iy, a.cell), fix_scale);
-            const int uz = fix_coord(pz, cell_centre(oz, iz, a.cell), fix_scale);
             unsigned long long* q = ps + r;
-            atomicAdd(q, (unsigned long long)(long long)ux);
-            atomicAdd(q + np, (unsigned long long)(long long)uy);
-            atomicAdd(q + 2 * np, (unsigned long long)(long long)uz);
-            atomicAdd(q + 3 * np, prod64(ux, ux));
-            atomicAdd(q + 4 * np, prod64(ux, uy));
-            atomicAdd(q + 5 * np, prod64(ux, uz));
-            atomicAdd(q + 6 * np, prod64(uy, uy));
-            atomicAdd(q + 7 * np, prod64(uy, uz));
-            atomicAdd(q + 8 * np, prod64(uz, uz));
+            point_terms(px, py, pz, ox, oy, oz, ix, iy, iz, a.cell, fix_scale,
+                        [&](int j, unsigned long long t) { atomicAdd(q + j * np, t); });
           }
         }
       });

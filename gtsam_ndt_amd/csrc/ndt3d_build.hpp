@@ -27,9 +27,9 @@ struct BinGeom3 {
 };
 
 __device__ __forceinline__ int tile_of3(const BinGeom3& g, float px, float py, float pz) {
-  const float fx = (px - g.ox) * g.inv_c, fy = (py - g.oy) * g.inv_c, fz = (pz - g.oz) * g.inv_c;
-  const bool in = (fx >= 0.f) & (fx < (float)g.W) & (fy >= 0.f) & (fy < (float)g.H) & (fz >= 0.f) & (fz < (float)g.D);
-  return in ? ((((int)fz >> kT3z) * g.nty + ((int)fy >> kT3y)) * g.ntx + ((int)fx >> kT3x)) : -1;
+  int ix, iy, iz;
+  return cell_of(px, py, pz, g.ox, g.oy, g.oz, g.inv_c, Limit3(g.W), Limit3(g.H), Limit3(g.D), ix, iy, iz)
+             ? (((iz >> kT3z) * g.nty + (iy >> kT3y)) * g.ntx + (ix >> kT3x)) : -1;
 }
 
 // ---- a build whose geometry is decided on the device (one host round trip instead of two: ndt3d_api.hpp
@@ -44,19 +44,18 @@ struct GeomDev3 {
 constexpr int kGeom3Word = 42;
 static_assert(sizeof(GeomDev3) == 17 * 4 && kGeom3Word + 17 <= 64, "GeomDev3 sits in the pad of the accumulator block");
 
-// a1 in 3D on the device: the arithmetic of setup_geometry3() on the host (oracle/ndt3d.py grid_geometry3), which
-// recomputes it from the same bounds afterwards and compares.  One lane.
+// a1 in 3D on the device (oracle/ndt3d.py grid_geometry3): the rule setup_geometry3() on the host calls too (lattice_axis,
+// ndt_lattice.hpp), with the limits of this build.  One lane.
 __device__ inline bool decide_geometry3(const float mn[3], const float mx[3], double c, unsigned long long cell_capacity,
                                         int tile_bound, BinGeom3* bin, Grid3Dev* grid) {
-#pragma clang fp contract(off)
-  const float inv_c = (float)(1.0 / c);
+  const float inv_c = lattice_inv_c(c);
   float o[3];
   int dims[3];
   double ncell_d = 1.0;
   for (int a = 0; a < 3; ++a) {
-    o[a] = (float)((floor((double)mn[a] / c) - 1.0) * c);
-    const float f = (mx[a] - o[a]) * inv_c;
-    const double k = floor((double)f);
+    const LatticeAxis A = lattice_axis(mn[a], mx[a], c);
+    o[a] = A.origin;
+    const double k = A.k;
     if (!(k >= 0.0) || k > 1e7) return false;
     dims[a] = (int)k + 2;
     ncell_d *= dims[a];
@@ -382,23 +381,14 @@ __global__ __launch_bounds__(kBinThreads) void k_tile_accumulate3(const float* _
     for (int u = 0; u < kU; ++u) {
       if (i + u * kBinThreads < q1) {
         const float px = qx[u], py = qy[u], pz = qz[u];
-        const int ix = (int)((px - g.ox) * g.inv_c), iy = (int)((py - g.oy) * g.inv_c), iz = (int)((pz - g.oz) * g.inv_c);
-        const int ux = fix_coord(px, cell_centre(g.ox, ix, g.cell), g.fix_scale);
-        const int uy = fix_coord(py, cell_centre(g.oy, iy, g.cell), g.fix_scale);
-        const int uz = fix_coord(pz, cell_centre(g.oz, iz, g.cell), g.fix_scale);
+        // in range: the point was binned by the same rule (tile_of3)
+        const int ix = lattice_index(px, g.ox, g.inv_c), iy = lattice_index(py, g.oy, g.inv_c), iz = lattice_index(pz, g.oz, g.inv_c);
         const int c = ((((iz - tz0) << kT3y) + (iy - ty0)) << kT3x) + (ix - tx0);
         unsigned long long* w = s_part + c * kCopies3 + copy;
         constexpr int kS = kTile3Cells * kCopies3;          // stride between the nine sums
         atomicAdd(&s_npart[c * kCopies3 + copy], 1u);
-        atomicAdd(w, (unsigned long long)(long long)ux);
-        atomicAdd(w + kS, (unsigned long long)(long long)uy);
-        atomicAdd(w + 2 * kS, (unsigned long long)(long long)uz);
-        atomicAdd(w + 3 * kS, prod64(ux, ux));
-        atomicAdd(w + 4 * kS, prod64(ux, uy));
-        atomicAdd(w + 5 * kS, prod64(ux, uz));
-        atomicAdd(w + 6 * kS, prod64(uy, uy));
-        atomicAdd(w + 7 * kS, prod64(uy, uz));
-        atomicAdd(w + 8 * kS, prod64(uz, uz));
+        point_terms(px, py, pz, g.ox, g.oy, g.oz, ix, iy, iz, g.cell, g.fix_scale,
+                    [&](int j, unsigned long long t) { atomicAdd(w + j * kS, t); });
       }
     }
   }

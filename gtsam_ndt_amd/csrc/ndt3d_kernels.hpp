@@ -228,6 +228,10 @@ __device__ __forceinline__ unsigned long long any_sum3(const CellAcc3& c) {
   return (unsigned long long)(c.s[0] | c.s[1] | c.s[2] | c.ss[0] | c.ss[1] | c.ss[2] | c.ss[3] | c.ss[4] | c.ss[5]);
 }
 
+// A voxel grid keeps no empty ring: every voxel of the grid may receive target points (cell_of<kRing3>, ndt_lattice.hpp).
+constexpr int kRing3 = 0;
+using Limit3 = LatticeLimit<kRing3>;
+
 // SIGN = -1: the points' contributions are taken out of the sums (ndt_device.hpp, "a build with a sign").
 template <int SIGN>
 __global__ __launch_bounds__(kBlock) void k_accumulate3(const float* __restrict__ x, const float* __restrict__ y,
@@ -235,25 +239,16 @@ __global__ __launch_bounds__(kBlock) void k_accumulate3(const float* __restrict_
                                                          unsigned long long* __restrict__ n_outside) {
   for (size_t i = (size_t)blockIdx.x * kBlock + threadIdx.x; i < n; i += (size_t)gridDim.x * kBlock) {
     const float px = x[i], py = y[i], pz = z[i];
-    const float fx = (px - g.ox) * g.inv_c, fy = (py - g.oy) * g.inv_c, fz = (pz - g.oz) * g.inv_c;
-    const bool in = (fx >= 0.f) & (fx < (float)g.W) & (fy >= 0.f) & (fy < (float)g.H) & (fz >= 0.f) & (fz < (float)g.D);
+    int ix, iy, iz;
+    const bool in = cell_of(px, py, pz, g.ox, g.oy, g.oz, g.inv_c, Limit3(g.W), Limit3(g.H), Limit3(g.D), ix, iy, iz);
     if (!in && n_outside) atomicAdd(n_outside, 1ull);
     if (in) {
-      const int ix = (int)fx, iy = (int)fy, iz = (int)fz;
-      const int ux = fix_coord(px, cell_centre(g.ox, ix, g.cell), g.fix_scale);
-      const int uy = fix_coord(py, cell_centre(g.oy, iy, g.cell), g.fix_scale);
-      const int uz = fix_coord(pz, cell_centre(g.oz, iz, g.cell), g.fix_scale);
       CellAcc3* c = g.acc + (((size_t)iz * g.H + iy) * g.W + ix);
       atomicAdd(&c->n, signed_one<SIGN>());
-      atomicAdd((unsigned long long*)&c->s[0], signed_term<SIGN>((unsigned long long)(long long)ux));
-      atomicAdd((unsigned long long*)&c->s[1], signed_term<SIGN>((unsigned long long)(long long)uy));
-      atomicAdd((unsigned long long*)&c->s[2], signed_term<SIGN>((unsigned long long)(long long)uz));
-      atomicAdd((unsigned long long*)&c->ss[0], signed_term<SIGN>(prod64(ux, ux)));
-      atomicAdd((unsigned long long*)&c->ss[1], signed_term<SIGN>(prod64(ux, uy)));
-      atomicAdd((unsigned long long*)&c->ss[2], signed_term<SIGN>(prod64(ux, uz)));
-      atomicAdd((unsigned long long*)&c->ss[3], signed_term<SIGN>(prod64(uy, uy)));
-      atomicAdd((unsigned long long*)&c->ss[4], signed_term<SIGN>(prod64(uy, uz)));
-      atomicAdd((unsigned long long*)&c->ss[5], signed_term<SIGN>(prod64(uz, uz)));
+      static_assert(offsetof(CellAcc3, ss) == 3 * sizeof(long long), "the nine sums are one array");
+      point_terms(px, py, pz, g.ox, g.oy, g.oz, ix, iy, iz, g.cell, g.fix_scale, [&](int j, unsigned long long t) {
+        atomicAdd((unsigned long long*)&c->s[0] + j, signed_term<SIGN>(t));
+      });
     }
   }
 }

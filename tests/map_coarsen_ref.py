@@ -5,6 +5,7 @@ answer; the GPU tests compare byte for byte, header included.
 Blob layout (include/ndt_hip.h, ndt_map_header): 104 header bytes, then per cell DIM int64 first sums, DIM (DIM + 1) / 2
 int64 second sums (xx xy yy | xx xy xz yy yz zz), uint32 n, uint32 pad - x fastest, then y, then z."""
 import struct
+from fractions import Fraction
 
 import numpy as np
 
@@ -150,9 +151,23 @@ def grid_geometry(pts, c):
     return np.array(origin, dtype=np.float32), ext
 
 
+def cell_centres(origin, idx, c):
+    """float64 centres fma(i + 0.5, c, o) [n, dim] of the cells idx [n, dim] (cell_centre, csrc/ndt_lattice.hpp): the sum is
+    formed exactly, as a fraction, and rounded once.  o + (i + 0.5) c in float64 rounds twice and moves the residual of a
+    point in a hundred by one unit."""
+    idx = np.asarray(idx, dtype=np.int64)
+    fc = Fraction(float(c))
+    out = np.zeros(idx.shape)
+    for a in range(idx.shape[1]):
+        fo = Fraction(float(np.float32(origin[a])))
+        once = {int(i): float(Fraction(2 * int(i) + 1, 2) * fc + fo) for i in np.unique(idx[:, a])}
+        out[:, a] = [once[int(i)] for i in idx[:, a]]
+    return out
+
+
 def blob_from_points(pts, c, origin=None, ext=None):
     """The blob ndt*_set_target + ndt*_save_map give for the cloud (float32 binning as the kernels:
-    f = (p - o) * (float)(1 / c), cell = (int)f; U = rint((p - centre) 2^22 / c) with centre = o + (i + 0.5) c in double).
+    f = (p - o) * (float)(1 / c), cell = (int)f; U = rint((p - centre) 2^22 / c) with centre = fma(i + 0.5, c, o) in double).
     origin / ext: bin into this lattice instead of the cloud's own (ndt*_reserve_target + add_target_points)."""
     pts = np.asarray(pts, dtype=np.float32)
     dim = pts.shape[1]
@@ -162,7 +177,7 @@ def blob_from_points(pts, c, origin=None, ext=None):
     inv_c = np.float32(1.0 / c)
     fidx = (pts - origin[None, :]) * inv_c                                  # float32
     idx = fidx.astype(np.int64)
-    centre = origin.astype(np.float64)[None, :] + (idx + 0.5) * c
+    centre = cell_centres(origin, idx, c)
     U = np.rint((pts.astype(np.float64) - centre) * (2.0 ** 22 / c)).astype(np.int64)
     pairs = [(a, b) for a in range(dim) for b in range(a, dim)]
     ncell = int(np.prod(ext))

@@ -83,7 +83,7 @@ def fixed_units(pts, c, origin):
     pts = np.asarray(pts, dtype=np.float32)
     origin = np.asarray(origin, dtype=np.float32)
     idx = ((pts - origin[None, :]) * np.float32(1.0 / c)).astype(np.int64)
-    centre = origin.astype(np.float64)[None, :] + (idx + 0.5) * c
+    centre = R.cell_centres(origin, idx, c)
     return idx, np.rint((pts.astype(np.float64) - centre) * (2.0 ** 22 / c)).astype(np.int64)
 
 
