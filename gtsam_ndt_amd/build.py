@@ -69,7 +69,7 @@ def build_synth(force: bool = False, verbose: bool = False) -> str:
     """The device-side workload generator (include/ndt_synth.h): its own library, so the matcher
     library carries nothing of it.  -ffp-contract=off: it must reproduce synth.py bit for bit."""
     src = os.path.join(CSRC, "ndt_synth.hip")
-    if not force and _newer(SYNTH_LIB, [src, os.path.join(ROOT, "include", "ndt_synth.h")]):
+    if not force and _newer(SYNTH_LIB, [src, os.path.join(CSRC, "ndt_pose.hpp"), os.path.join(ROOT, "include", "ndt_synth.h")]):
         return SYNTH_LIB
     os.makedirs(LIBDIR, exist_ok=True)
     cmd = [hipcc_path(), "--offload-arch=gfx950", "-O2", "-std=c++17", "-fPIC", "-shared", "-Wall", "-ffp-contract=off",

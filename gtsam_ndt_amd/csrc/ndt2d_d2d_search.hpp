@@ -52,13 +52,11 @@ __global__ __launch_bounds__(kSearchThreads) void k_search_score_d2d(const Align
   const GridDev G = st->grid;
   const int tiles_x = (nx + kSearchTile - 1) / kSearchTile, tiles_y = (ny + kSearchTile - 1) / kSearchTile;
   const long long nblocks = (long long)tiles_x * tiles_y * nt;
-  const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
+  const int tid = threadIdx.x;
   for (long long b = blockIdx.x; b < nblocks; b += gridDim.x) {
-    const int j = (int)(b / (tiles_x * tiles_y));
-    const int t = (int)(b - (long long)j * tiles_x * tiles_y);
-    const int ix = (t % tiles_x) * kSearchTile + (wave & 1) * 8 + (lane & 7);
-    const int iy = (t / tiles_x) * kSearchTile + (wave >> 1) * 8 + (lane >> 3);
-    const bool live = ix < nx && iy < ny;
+    const SearchTask task = search_task(b, tiles_x, tiles_y, nx, ny);
+    const int j = task.j, ix = task.ix, iy = task.iy;
+    const bool live = task.live;
     double sn_d, cs_d;
     sincos_wrapped(ath[j], &sn_d, &cs_d);
     const PoseF P = make_pose((float)cs_d, (float)sn_d, ax[min(ix, nx - 1)], ay[min(iy, ny - 1)], G.ox, G.oy, G.inv_c, G.W,
@@ -83,8 +81,8 @@ __global__ __launch_bounds__(kSearchThreads) void k_search_score_d2d(const Align
           const float sa = ca.z, sb = ca.w, sc = cb.y;
           const float hm = 0.5f * (sa + sc), hd = 0.5f * (sa - sc);
           const float u = fmaf(hd, R.c2t, -sb * R.s2t);
-          ms.x = __builtin_amdgcn_fmed3f(ca.x, -1e15f, 1e15f);
-          ms.y = __builtin_amdgcn_fmed3f(ca.y, -1e15f, 1e15f);
+          ms.x = clamp_coord(ca.x);
+          ms.y = clamp_coord(ca.y);
           ms.z = hm + u;
           ms.w = fmaf(hd, R.s2t, sb * R.c2t);
           syy = hm - u;
@@ -104,8 +102,7 @@ __global__ __launch_bounds__(kSearchThreads) void k_search_score_d2d(const Align
 #pragma unroll
         for (int u = 0; u < 4; ++u) {
           c[u] = s_ms[k + u];
-          r[u].px = fmaf(P.cs, c[u].x, fmaf(-P.sn, c[u].y, P.tx));       // image_point
-          r[u].py = fmaf(P.sn, c[u].x, fmaf(P.cs, c[u].y, P.ty));
+          image_clamped(P, c[u].x, c[u].y, r[u]);
           const int key = image_key(P, P.ox, P.oy, r[u], true);          // clamped onto the grid: a cell of `cov`
           r[u].A = cov[2 * key];
           r[u].B = cov[2 * key + 1];

@@ -15,6 +15,7 @@
 #include "ndt_device.hpp"
 #include "ndt_chain.hpp"
 #include "ndt_lattice.hpp"
+#include "ndt_pose.hpp"
 
 namespace ndt {
 
@@ -381,15 +382,6 @@ __device__ __forceinline__ bool solve3(const double* H /*xx xy yy xt yt tt*/, co
   return false;
 }
 
-__device__ __forceinline__ double wrap_angle(double t) {
-  const double pi = 3.141592653589793;
-  if (t > pi || t <= -pi) {
-    t = t - 2.0 * pi * floor((t + pi) / (2.0 * pi));
-    if (t <= -pi) t += 2.0 * pi;
-  }
-  return t;
-}
-
 // sin/cos for |t| <= ~pi (poses are wrapped): quadrant reduction + the classic fdlibm
 // minimax kernels on [-pi/4, pi/4]; error < 1 ulp, no table, no slow path.
 __device__ __forceinline__ void sincos_wrapped(double t, double* sn, double* cs) {
@@ -536,11 +528,14 @@ struct PointRec {
 // one above the maximum), so every out-of-range, infinite or NaN point lands on an invalid
 // cell.  NaN/inf never reach the sums: coordinates are clamped to +-1e15 first (v_med3_f32
 // returns the finite bound for a NaN), which keeps every later product finite.
-__device__ __forceinline__ void image_point(const PoseF& P, float x, float y, PointRec& r) {
-  x = __builtin_amdgcn_fmed3f(x, -1e15f, 1e15f);
-  y = __builtin_amdgcn_fmed3f(y, -1e15f, 1e15f);
+// In two halves, for the kernels that clamp a point once where they stage it and take its image per pose.
+__device__ __forceinline__ float clamp_coord(float v) { return __builtin_amdgcn_fmed3f(v, -1e15f, 1e15f); }
+__device__ __forceinline__ void image_clamped(const PoseF& P, float x, float y, PointRec& r) {
   r.px = fmaf(P.cs, x, fmaf(-P.sn, y, P.tx));
   r.py = fmaf(P.sn, x, fmaf(P.cs, y, P.ty));
+}
+__device__ __forceinline__ void image_point(const PoseF& P, float x, float y, PointRec& r) {
+  image_clamped(P, clamp_coord(x), clamp_coord(y), r);
 }
 __device__ __forceinline__ int image_key(const PoseF& P, float ox, float oy, const PointRec& r, bool live) {
   int ix = floor_to_int((r.px - ox) * P.inv_c), iy = floor_to_int((r.py - oy) * P.inv_c);

@@ -39,16 +39,13 @@ __global__ __launch_bounds__(kSearchThreads) void k_search_score(const AlignStat
   const GridDev G = st->grid;
   const int tiles_x = (nx + kSearchTile - 1) / kSearchTile, tiles_y = (ny + kSearchTile - 1) / kSearchTile;
   const long long nblocks = (long long)tiles_x * tiles_y * nt;
-  const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
+  const int tid = threadIdx.x;
   // (a grid-stride loop over the workgroups' tasks: a lattice of few translations and many headings can need more
   // workgroups than one launch may have threads)
   for (long long b = blockIdx.x; b < nblocks; b += gridDim.x) {
-    const int j = (int)(b / (tiles_x * tiles_y));
-    const int t = (int)(b - (long long)j * tiles_x * tiles_y);
-    // a wave is an 8 x 8 block of translations: its lanes look up neighbouring cells
-    const int ix = (t % tiles_x) * kSearchTile + (wave & 1) * 8 + (lane & 7);
-    const int iy = (t / tiles_x) * kSearchTile + (wave >> 1) * 8 + (lane >> 3);
-    const bool live = ix < nx && iy < ny;
+    const SearchTask task = search_task(b, tiles_x, tiles_y, nx, ny);
+    const int j = task.j, ix = task.ix, iy = task.iy;
+    const bool live = task.live;
     double sn_d, cs_d;
     sincos_wrapped(ath[j], &sn_d, &cs_d);
     const PoseF P = make_pose((float)cs_d, (float)sn_d, ax[min(ix, nx - 1)], ay[min(iy, ny - 1)], G.ox, G.oy, G.inv_c, G.W,
@@ -65,8 +62,8 @@ __global__ __launch_bounds__(kSearchThreads) void k_search_score(const AlignStat
         // exactly 0, so the loop below needs no tail
         float x = 1e15f, y = 1e15f;
         if (k < m) {
-          x = __builtin_amdgcn_fmed3f(sx[base + k], -1e15f, 1e15f);
-          y = __builtin_amdgcn_fmed3f(sy[base + k], -1e15f, 1e15f);
+          x = clamp_coord(sx[base + k]);
+          y = clamp_coord(sy[base + k]);
         }
         s_pt[k] = make_float2(x, y);
       }
@@ -78,10 +75,7 @@ __global__ __launch_bounds__(kSearchThreads) void k_search_score(const AlignStat
         const float qx[4] = {q01.x, q01.z, q23.x, q23.z}, qy[4] = {q01.y, q01.w, q23.y, q23.w};
         PointRec r[4];
 #pragma unroll
-        for (int u = 0; u < 4; ++u) {                                  // image_point
-          r[u].px = fmaf(P.cs, qx[u], fmaf(-P.sn, qy[u], P.tx));
-          r[u].py = fmaf(P.sn, qx[u], fmaf(P.cs, qy[u], P.ty));
-        }
+        for (int u = 0; u < 4; ++u) image_clamped(P, qx[u], qy[u], r[u]);
 #pragma unroll
         for (int g = 0; g < NG; ++g) {
           const float ox = NG == 1 ? G.ox : G.gx[g], oy = NG == 1 ? G.oy : G.gy[g];   // as k_iterate<NG>

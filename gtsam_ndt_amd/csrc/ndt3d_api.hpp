@@ -773,11 +773,9 @@ static int32_t update_target_points3_dev(ndt3d_handle* h, const float* d_x, cons
   const float* p[3] = {d_x, d_y, d_z};
   ndt::Rigid3F T;
   if (pose) {       // the points are moved on the way into the build (count and scatter passes), not by a kernel of their own
-    const double ca = std::cos(pose[3]), sa = std::sin(pose[3]), cb = std::cos(pose[4]), sb = std::sin(pose[4]),
-                 cg = std::cos(pose[5]), sg = std::sin(pose[5]);
-    const double R[9] = {cg * cb, cg * sb * sa - sg * ca, cg * sb * ca + sg * sa,
-                         sg * cb, sg * sb * sa + cg * ca, sg * sb * ca - cg * sa,
-                         -sb, cb * sa, cb * ca};
+    double R[9];
+    ndt::rot3_products(std::sin(pose[3]), std::cos(pose[3]), std::sin(pose[4]), std::cos(pose[4]), std::sin(pose[5]),
+                       std::cos(pose[5]), R);
     for (int j = 0; j < 9; ++j) T.r[j] = (float)R[j];
     for (int j = 0; j < 3; ++j) T.t[j] = (float)pose[j];
   }

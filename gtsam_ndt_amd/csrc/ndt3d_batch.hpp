@@ -259,13 +259,10 @@ __device__ __forceinline__ void accumulate_point3_map(float yx, float yy, float 
 // gradient in pose coordinates, at the pose the sums were taken at.  Float64, once per iteration.
 template <int MODE>
 __device__ __forceinline__ void map_sums_to_pose_frame(const double* pose, const double* sr, double* A, double* g) {
-  double sa, ca, sb, cb, sg, cg;
-  sincos_wrapped(pose[3], &sa, &ca);
-  sincos_wrapped(pose[4], &sb, &cb);
-  sincos_wrapped(pose[5], &sg, &cg);
-  const double R[9] = {cg * cb, cg * sb * sa - sg * ca, cg * sb * ca + sg * sa,
-                       sg * cb, sg * sb * sa + cg * ca, sg * sb * ca - cg * sa,
-                       -sb, cb * sa, cb * ca};
+  const SinCos3 s = sincos_pose3(pose);
+  const double sg = s.sg, cg = s.cg;
+  double R[9];
+  rot3_products(s.sa, s.ca, s.sb, s.cb, s.sg, s.cg, R);
   const double ax[3][3] = {{R[0], -sg, 0.0}, {R[3], cg, 0.0}, {R[6], 0.0, 1.0}};     // columns a_roll, a_pitch, a_yaw
   A[0] = sr[0]; A[1] = sr[1]; A[2] = sr[2]; A[7] = sr[3]; A[8] = sr[4]; A[14] = sr[5];
 #pragma unroll

@@ -145,6 +145,8 @@ struct MapPose3 {
   float bx, by;              // a_pitch
 };
 __device__ __forceinline__ void make_map_pose3(const double* pose, MapPose3& T) {
+  // (its own text of ndt_pose.hpp's rot3_products, as make_rot3: through make_rt3 k_score_map_poses3, which reads R and t
+  // from here, measured outside the run-to-run spread)
   double sa, ca, sb, cb, sg, cg;
   sincos_wrapped(pose[3], &sa, &ca);
   sincos_wrapped(pose[4], &sb, &cb);

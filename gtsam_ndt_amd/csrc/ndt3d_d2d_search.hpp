@@ -61,25 +61,21 @@ __global__ __launch_bounds__(kSearchThreads, 4) void k_search_score_d2d3(const A
   const Grid3Dev G = st->grid;
   const int tiles_x = (nx + kSearchTile - 1) / kSearchTile, tiles_y = (ny + kSearchTile - 1) / kSearchTile;
   const long long nblocks = (long long)tiles_x * tiles_y * nt;
-  const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
+  const int tid = threadIdx.x;
   const Extent3F E = extent3(G);
   const float nhd2 = nhd2_of(d2);
   const int layer = G.W * G.H;
   const unsigned last_cell = (unsigned)(layer * G.D - 1);
   for (long long b = blockIdx.x; b < nblocks; b += gridDim.x) {
-    const int j = (int)(b / (tiles_x * tiles_y));
-    const int t = (int)(b - (long long)j * tiles_x * tiles_y);
-    const int tile_x = (t % tiles_x) * kSearchTile, tile_y = (t / tiles_x) * kSearchTile;
-    const int ix = tile_x + (wave & 1) * 8 + (lane & 7);
-    const int iy = tile_y + (wave >> 1) * 8 + (lane >> 3);
+    const SearchTask task = search_task(b, tiles_x, tiles_y, nx, ny);      // (its `live` is formed again below)
+    const int j = task.j, tile_x = task.tile_x, tile_y = task.tile_y, ix = task.ix, iy = task.iy;
     const double pose[6] = {0.0, 0.0, cz, croll, cpitch, ayaw[j]};
-    MapPose3 T;
-    make_map_pose3(pose, T);                                 // R and tz; the axes of the derivatives are not used
+    const PoseRt3 T = make_rt3(pose);                        // R and tz
     float R[9];
 #pragma unroll
     for (int q = 0; q < 9; ++q) R[q] = search_uniform(T.R[q]);
     const float tz = search_uniform(T.tz);
-    const float tx = ax[min(ix, nx - 1)], ty = ay[min(iy, ny - 1)];   // the float of the double, as make_map_pose3's T.tx
+    const float tx = ax[min(ix, nx - 1)], ty = ay[min(iy, ny - 1)];   // the float of the double, as make_rt3's tx
     float total = 0.f;
     for (int base = 0; base < n; base += kMapSearch3Chunk) {
       const int m = min(kMapSearch3Chunk, n - base);
@@ -131,10 +127,7 @@ __global__ __launch_bounds__(kSearchThreads, 4) void k_search_score_d2d3(const A
           pz[u] = p.w;
           const Voxel3 vox = voxel_clamped3(G, E, Voxel3{lk[u], lk[u] >= 0}, px[u], py[u], last_cell);
           in[u] = vox.in;
-          const float4* r = cov + 3 * (size_t)(unsigned)vox.key;
-          A[u] = r[0];
-          B[u] = r[1];
-          Cc[u] = *reinterpret_cast<const float2*>(r + 2);
+          gather_cov3(cov, vox.key, A[u], B[u], Cc[u]);
         }
         // S is read behind the gathers: its LDS latency hides under theirs, and 24 registers fewer are live across them
         const float4 yz4 = s_sb[3 * (k >> 2)], zz4 = s_sb[3 * (k >> 2) + 1];

@@ -459,20 +459,27 @@ __device__ __forceinline__ bool gn_update3(double* pose, const double* A, const 
   return false;
 }
 
+// The sines and cosines of a (wrapped) pose's roll (a), pitch (b) and yaw (g): what ndt_pose.hpp's products take.
+struct SinCos3 { double sa, ca, sb, cb, sg, cg; };
+__device__ __forceinline__ SinCos3 sincos_pose3(const double* pose) {
+  SinCos3 s;
+  sincos_wrapped(pose[3], &s.sa, &s.ca);
+  sincos_wrapped(pose[4], &s.sb, &s.cb);
+  sincos_wrapped(pose[5], &s.sg, &s.cg);
+  return s;
+}
+
 // Newton form of the rotation block (MODE 1): A[3..5][3..5] += sum_ab (d2R / dk dl)[a][b] M[a][b] with
 // M[3a + b] = sum w v_a p_b (rows 29..37 of the sums), at the pose the sums were taken at.
 __device__ __forceinline__ void newton_rot_block3(const double* pose, const double* M, double* A) {
   // The six second derivatives follow from R and its first derivatives:
   // a roll derivative maps columns (1, 2) -> (col 2, -col 1), a yaw derivative rows (0, 1) ->
   // (-row 1, row 0), and d2Ry = -Ry + e_y e_y' (oracle/ndt3d.py rot_second_derivs states the products).
-  double sa, ca, sb, cb, sg, cg;
-  sincos_wrapped(pose[3], &sa, &ca);
-  sincos_wrapped(pose[4], &sb, &cb);
-  sincos_wrapped(pose[5], &sg, &cg);
-  const double R[9] = {cg * cb, cg * sb * sa - sg * ca, cg * sb * ca + sg * sa,
-                       sg * cb, sg * sb * sa + cg * ca, sg * sb * ca - cg * sa,
-                       -sb, cb * sa, cb * ca};
-  const double Rb[9] = {-cg * sb, cg * cb * sa, cg * cb * ca, -sg * sb, sg * cb * sa, sg * cb * ca, -cb, -sb * sa, -sb * ca};
+  const SinCos3 s = sincos_pose3(pose);
+  const double sa = s.sa, ca = s.ca, sg = s.sg, cg = s.cg;
+  double R[9], Rb[9];
+  rot3_products(s.sa, s.ca, s.sb, s.cb, s.sg, s.cg, R);
+  rot3_pitch_products(s.sa, s.ca, s.sb, s.cb, s.sg, s.cg, Rb);
   auto cols = [&](const double* X) {                       // roll derivative of X: (0, X[:,2], -X[:,1]) . M
     double t2 = 0.0;
 #pragma unroll
@@ -510,12 +517,31 @@ struct Rot3F {
   float R[9], Ra[9], Rb[9], Rg[9];
   float tx, ty, tz;
 };
+// R and t alone, in float32 rounded from float64: what a kernel without derivatives needs of a pose.  The two 3D search
+// kernels call it.
+struct PoseRt3 {
+  float R[9];
+  float tx, ty, tz;
+};
+__device__ __forceinline__ PoseRt3 make_rt3(const double* pose) {
+  PoseRt3 T;
+  double Rd[9];
+  const SinCos3 s = sincos_pose3(pose);
+  rot3_products(s.sa, s.ca, s.sb, s.cb, s.sg, s.cg, Rd);
+#pragma unroll
+  for (int q = 0; q < 9; ++q) T.R[q] = (float)Rd[q];
+  T.tx = (float)pose[0]; T.ty = (float)pose[1]; T.tz = (float)pose[2];
+  return T;
+}
+// make_rot3 keeps its own text for R and t (the same nine products, which its roll and yaw derivatives read): through
+// rot3_products or make_rt3 the same values come out of k_batch3<1> with 32 bytes more scratch (448 -> 480) and out of
+// k_batch3_fallback<1> 19 instructions longer.
 __device__ __forceinline__ void make_rot3(const double* pose, Rot3F& T) {
   double sa, ca, sb, cb, sg, cg;
   sincos_wrapped(pose[3], &sa, &ca);
   sincos_wrapped(pose[4], &sb, &cb);
   sincos_wrapped(pose[5], &sg, &cg);
-  // R = Rz Ry Rx
+  // R = Rz Ry Rx (ndt_pose.hpp rot3_products)
   const double r00 = cg * cb, r01 = cg * sb * sa - sg * ca, r02 = cg * sb * ca + sg * sa;
   const double r10 = sg * cb, r11 = sg * sb * sa + cg * ca, r12 = sg * sb * ca - cg * sa;
   const double r20 = -sb, r21 = cb * sa, r22 = cb * ca;
@@ -526,9 +552,10 @@ __device__ __forceinline__ void make_rot3(const double* pose, Rot3F& T) {
   T.Ra[3] = 0.f; T.Ra[4] = (float)r12; T.Ra[5] = (float)(-r11);
   T.Ra[6] = 0.f; T.Ra[7] = (float)r22; T.Ra[8] = (float)(-r21);
   // d/dpitch = Rz dRy Rx
-  T.Rb[0] = (float)(-cg * sb); T.Rb[1] = (float)(cg * cb * sa); T.Rb[2] = (float)(cg * cb * ca);
-  T.Rb[3] = (float)(-sg * sb); T.Rb[4] = (float)(sg * cb * sa); T.Rb[5] = (float)(sg * cb * ca);
-  T.Rb[6] = (float)(-cb);      T.Rb[7] = (float)(-sb * sa);     T.Rb[8] = (float)(-sb * ca);
+  double Rb[9];
+  rot3_pitch_products(sa, ca, sb, cb, sg, cg, Rb);
+#pragma unroll
+  for (int q = 0; q < 9; ++q) T.Rb[q] = (float)Rb[q];
   // d/dyaw: rows rotate: dR[0,:] = -R[1,:], dR[1,:] = R[0,:], dR[2,:] = 0
   T.Rg[0] = (float)(-r10); T.Rg[1] = (float)(-r11); T.Rg[2] = (float)(-r12);
   T.Rg[3] = (float)r00;    T.Rg[4] = (float)r01;    T.Rg[5] = (float)r02;
@@ -579,6 +606,20 @@ __device__ __forceinline__ Voxel3 voxel_clamped3(const Grid3Dev& G, const Extent
   const float fx = (px - G.ox) * G.inv_c, fy = (py - G.oy) * G.inv_c;
   const bool in = (fx >= 0.f) & (fx < E.W) & (fy >= 0.f) & (fy < E.H) & layer.in;
   return Voxel3{(int)min((unsigned int)layer.key + (unsigned int)(int)fy * (unsigned int)G.W + (unsigned int)(int)fx, last_cell), in};
+}
+// What the score kernels gather of voxel `key` (a clamped key: always a voxel of the grid): 40 bytes of its 64-byte record
+// (A = mean | n, B = Sigma^-1 xx xy xz yy, C = yz zz), or of its 48-byte covariance record (the map-to-map scores).
+__device__ __forceinline__ void gather_rec3(const float4* __restrict__ rec, int key, float4& A, float4& B, float2& C) {
+  const float4* r = rec + 4 * (size_t)(unsigned int)key;
+  A = r[0];
+  B = r[1];
+  C = *reinterpret_cast<const float2*>(r + 2);
+}
+__device__ __forceinline__ void gather_cov3(const float4* __restrict__ cov, int key, float4& A, float4& B, float2& C) {
+  const float4* r = cov + 3 * (size_t)(unsigned int)key;
+  A = r[0];
+  B = r[1];
+  C = *reinterpret_cast<const float2*>(r + 2);
 }
 // m = q' Sigma^-1 q and v = Sigma^-1 q of an image point in the voxel of record (A4 = mean | n, B4 = xx xy xz yy, C2 = yz zz)
 template <class C>

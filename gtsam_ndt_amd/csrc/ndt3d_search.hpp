@@ -50,27 +50,23 @@ __global__ __launch_bounds__(kSearchThreads) void k_search_score3(const AlignSta
   const Grid3Dev G = st->grid;
   const int tiles_x = (nx + kSearchTile - 1) / kSearchTile, tiles_y = (ny + kSearchTile - 1) / kSearchTile;
   const long long nblocks = (long long)tiles_x * tiles_y * nt;
-  const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
+  const int tid = threadIdx.x;
   const Extent3F E = extent3(G);
   const float nhd2 = nhd2_of(d2);
   const int layer = G.W * G.H;
   const unsigned last_cell = (unsigned)(layer * G.D - 1);
   // (a grid-stride loop over the workgroups' tasks, as k_search_score)
   for (long long b = blockIdx.x; b < nblocks; b += gridDim.x) {
-    const int j = (int)(b / (tiles_x * tiles_y));
-    const int t = (int)(b - (long long)j * tiles_x * tiles_y);
-    // a wave is an 8 x 8 block of translations: its lanes look up neighbouring voxels
-    const int ix = (t % tiles_x) * kSearchTile + (wave & 1) * 8 + (lane & 7);
-    const int iy = (t / tiles_x) * kSearchTile + (wave >> 1) * 8 + (lane >> 3);
-    const bool live = ix < nx && iy < ny;
+    const SearchTask task = search_task(b, tiles_x, tiles_y, nx, ny);
+    const int j = task.j, ix = task.ix, iy = task.iy;
+    const bool live = task.live;
     const double pose[6] = {0.0, 0.0, cz, croll, cpitch, ayaw[j]};
-    Rot3F T;
-    make_rot3(pose, T);                                      // R and tz; the derivative matrices are not used
+    const PoseRt3 T = make_rt3(pose);                        // R and tz
     float R[9];
 #pragma unroll
     for (int q = 0; q < 9; ++q) R[q] = search_uniform(T.R[q]);
     const float tz = search_uniform(T.tz);
-    const float tx = ax[min(ix, nx - 1)], ty = ay[min(iy, ny - 1)];   // the float of the double, as make_rot3's T.tx
+    const float tx = ax[min(ix, nx - 1)], ty = ay[min(iy, ny - 1)];   // the float of the double, as make_rt3's tx
     float total = 0.f;
     for (int base = 0; base < n; base += kSearch3Chunk) {
       const int m = min(kSearch3Chunk, n - base);
@@ -108,10 +104,7 @@ __global__ __launch_bounds__(kSearchThreads) void k_search_score3(const AlignSta
           pz[u] = p.w;
           const Voxel3 vox = voxel_clamped3(G, E, Voxel3{lk[u], lk[u] >= 0}, px[u], py[u], last_cell);
           in[u] = vox.in;
-          const float4* r = rec + 4 * (size_t)(unsigned)vox.key;
-          A[u] = r[0];
-          B[u] = r[1];
-          C[u] = *reinterpret_cast<const float2*>(r + 2);
+          gather_rec3(rec, vox.key, A[u], B[u], C[u]);
         }
         s0 += search_point_score3(px[0], py[0], pz[0], in[0], A[0], B[0], C[0], d1, nhd2);
         s1 += search_point_score3(px[1], py[1], pz[1], in[1], A[1], B[1], C[1], d1, nhd2);

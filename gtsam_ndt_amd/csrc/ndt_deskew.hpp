@@ -147,22 +147,8 @@ bool all_finite(const double* v, int n) {
   return true;
 }
 
-double wrap_pi(double t) {                                  // (-pi, pi], as the device's wrap_angle
-  const double pi = 3.141592653589793;
-  if (t > pi || t <= -pi) {
-    t = t - 2.0 * pi * std::floor((t + pi) / (2.0 * pi));
-    if (t <= -pi) t += 2.0 * pi;
-  }
-  return t;
-}
-
 void euler_to_matrix(const double* e, double R[9]) {        // R = Rz(yaw) Ry(pitch) Rx(roll)
-  const double ca = std::cos(e[0]), sa = std::sin(e[0]), cb = std::cos(e[1]), sb = std::sin(e[1]);
-  const double cg = std::cos(e[2]), sg = std::sin(e[2]);
-  const double M[9] = {cg * cb, cg * sb * sa - sg * ca, cg * sb * ca + sg * sa,
-                       sg * cb, sg * sb * sa + cg * ca, sg * sb * ca - cg * sa,
-                       -sb, cb * sa, cb * ca};
-  for (int i = 0; i < 9; ++i) R[i] = M[i];
+  ndt::rot3_products(std::sin(e[0]), std::cos(e[0]), std::sin(e[1]), std::cos(e[1]), std::sin(e[2]), std::cos(e[2]), R);
 }
 
 template <int DIM>
@@ -205,7 +191,7 @@ int32_t ndt2d_sweep_motion(const double prev[3], const double cur[3], double del
   const double dx = cur[0] - prev[0], dy = cur[1] - prev[1];
   delta[0] = c * dx + s * dy;
   delta[1] = c * dy - s * dx;
-  delta[2] = wrap_pi(cur[2] - prev[2]);
+  delta[2] = ndt::wrap_angle(cur[2] - prev[2]);
   return NDT_OK;
 }
 
@@ -238,7 +224,7 @@ int32_t ndt3d_sweep_motion(const double prev[6], const double cur[6], double del
 
 int32_t ndt2d_motion_twist(const double delta[3], double xi[3]) {
   if (!delta || !xi || !all_finite(delta, 3)) return NDT_ERR_INVALID_ARG;
-  const double w = wrap_pi(delta[2]), h = 0.5 * w;
+  const double w = ndt::wrap_angle(delta[2]), h = 0.5 * w;
   const double sh = std::sin(h), ch = std::cos(h), k = ndt::deskew_sinc(h, sh);
   xi[0] = (ch * delta[0] + sh * delta[1]) / k;              // V(w)^-1 = R(-h) / sinc(h)
   xi[1] = (ch * delta[1] - sh * delta[0]) / k;

@@ -1,7 +1,9 @@
 // The target-side lattice rule, stated once for host and device (docs/ALGORITHM.md sections 2.2, 2.6, 2.19): the grid of
 // a cloud, the cell of a target point, and what the point adds to its cell's exact sums.  Plain C++, no HIP types and no
 // handle: every build path and the host geometry call these functions, and tests/cpp/lattice_main.cpp runs them under
-// the host sanitizers.  (The source-side lookups clamp instead of testing and are not stated here.)
+// the host sanitizers.  (The source side is stated elsewhere: how a pose becomes a rotation in ndt_pose.hpp, and the
+// lookups, which clamp instead of testing, in image_point / image_key of ndt2d_kernels.hpp and voxel_of3 / voxel_clamped3 of
+// ndt3d_kernels.hpp.)
 #pragma once
 #include <cmath>
 

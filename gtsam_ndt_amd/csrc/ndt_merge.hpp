@@ -179,22 +179,18 @@ __global__ __launch_bounds__(kMergeThreads) void k_merge(MergeArgs a) {
 namespace {
 
 // The rotation and translation of a pose in float64, formed here and handed to the kernel by value so that there is one
-// right answer: cos / sin from libm, then in 3D the nine products of make_rot3 (R = Rz Ry Rx) in its order, every operation
-// rounded separately.
+// right answer: cos / sin from libm, then in 3D the nine products of R = Rz Ry Rx in the host form of ndt_pose.hpp, every
+// operation rounded separately.
 template <int DIM>
 void merge_rotation(const double* pose, double* R, double* t) {
-#pragma clang fp contract(off)
   for (int i = 0; i < 9; ++i) R[i] = 0.0;
   if (DIM == 2) {
     const double c = std::cos(pose[2]), s = std::sin(pose[2]);
     R[0] = c; R[1] = -s; R[3] = s; R[4] = c;
     t[0] = pose[0]; t[1] = pose[1]; t[2] = 0.0;
   } else {
-    const double sa = std::sin(pose[3]), ca = std::cos(pose[3]), sb = std::sin(pose[4]), cb = std::cos(pose[4]),
-                 sg = std::sin(pose[5]), cg = std::cos(pose[5]);
-    R[0] = cg * cb; R[1] = cg * sb * sa - sg * ca; R[2] = cg * sb * ca + sg * sa;
-    R[3] = sg * cb; R[4] = sg * sb * sa + cg * ca; R[5] = sg * sb * ca - cg * sa;
-    R[6] = -sb;     R[7] = cb * sa;                R[8] = cb * ca;
+    ndt::rot3_products(std::sin(pose[3]), std::cos(pose[3]), std::sin(pose[4]), std::cos(pose[4]), std::sin(pose[5]),
+                       std::cos(pose[5]), R);
     t[0] = pose[0]; t[1] = pose[1]; t[2] = pose[2];
   }
 }

@@ -65,7 +65,7 @@ __global__ __launch_bounds__(kPoseThreads) void k_score_map_poses(const AlignSta
       float syy = 1.f;
       if (k < mc) {
         const float4 ca = comp[2 * (size_t)(base + k)], cb = comp[2 * (size_t)(base + k) + 1];
-        ms = make_float4(__builtin_amdgcn_fmed3f(ca.x, -1e15f, 1e15f), __builtin_amdgcn_fmed3f(ca.y, -1e15f, 1e15f), ca.z, ca.w);
+        ms = make_float4(clamp_coord(ca.x), clamp_coord(ca.y), ca.z, ca.w);
         syy = cb.y;
       }
       s_ms[k] = ms;
@@ -82,8 +82,7 @@ __global__ __launch_bounds__(kPoseThreads) void k_score_map_poses(const AlignSta
 #pragma unroll
       for (int u = 0; u < 4; ++u) {
         c[u] = s_ms[k + u];
-        r[u].px = fmaf(P.cs, c[u].x, fmaf(-P.sn, c[u].y, P.tx));       // image_point
-        r[u].py = fmaf(P.sn, c[u].x, fmaf(P.cs, c[u].y, P.ty));
+        image_clamped(P, c[u].x, c[u].y, r[u]);
         const int key = image_key(P, P.ox, P.oy, r[u], true);          // clamped onto the grid: a cell of `cov`
         r[u].A = cov[2 * key];
         r[u].B = cov[2 * key + 1];

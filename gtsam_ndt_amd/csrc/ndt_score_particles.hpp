@@ -110,12 +110,8 @@ __global__ __launch_bounds__(kParticleLanes) void k_score_particles(const AlignS
     x = sx[jj]; y = sy[jj];
   };
   auto place = [&](int j, float& x, float& y) {
-    x = j < n ? __builtin_amdgcn_fmed3f(x, -1e15f, 1e15f) : 1e15f;
-    y = j < n ? __builtin_amdgcn_fmed3f(y, -1e15f, 1e15f) : 1e15f;
-  };
-  auto image = [&](float x, float y, PointRec& r) {                 // image_point
-    r.px = fmaf(P.cs, x, fmaf(-P.sn, y, P.tx));
-    r.py = fmaf(P.sn, x, fmaf(P.cs, y, P.ty));
+    x = j < n ? clamp_coord(x) : 1e15f;
+    y = j < n ? clamp_coord(y) : 1e15f;
   };
   unsigned int hits = 0;
   if constexpr (TEAM == 256 && NG == 4) {
@@ -130,7 +126,7 @@ __global__ __launch_bounds__(kParticleLanes) void k_score_particles(const AlignS
       PointRec r[4];
 #pragma unroll
       for (int g = 0; g < 4; ++g) {
-        image(x, y, r[g]);
+        image_clamped(P, x, y, r[g]);
         const int key = g * ncell + image_key(P, G.gx[g], G.gy[g], r[g], true);
         r[g].A = rec[2 * key];
         r[g].B = rec[2 * key + 1];
@@ -164,7 +160,7 @@ __global__ __launch_bounds__(kParticleLanes) void k_score_particles(const AlignS
 #pragma unroll
       for (int u = 0; u < 4; ++u) {
         place(base + STRIDE * u + t, x[u], y[u]);
-        image(x[u], y[u], r[u]);
+        image_clamped(P, x[u], y[u], r[u]);
       }
 #pragma unroll
       for (int g = 0; g < NG; ++g) {

@@ -47,7 +47,9 @@ __device__ __forceinline__ void load_pose(const double* __restrict__ poses, unsi
 }
 
 // rec = st->grid.rec, as a kernel argument (global, not flat, gathers).  poses[m][3] = (x, y, theta) in double.  Lanes past
-// m compute the last entry and store nothing.
+// m compute the last entry and store nothing.  The chunk loop is k_search_score's text (a list that spells a lattice
+// gives the search's volume bit for bit only while the two stay in step): as one function for both kernels it measured
+// outside the run-to-run spread at 65 536 poses.
 template <int NG>
 __global__ __launch_bounds__(kPoseThreads) void k_score_poses(const AlignStatic* __restrict__ st, const float4* __restrict__ rec,
                                                               float d1, float d2, const float* __restrict__ sx,
@@ -77,8 +79,8 @@ __global__ __launch_bounds__(kPoseThreads) void k_score_poses(const AlignStatic*
       // image_point's clamp once per point, and the padding onto the grid's empty outer ring, as k_search_score
       float x = 1e15f, y = 1e15f;
       if (k < mc) {
-        x = __builtin_amdgcn_fmed3f(sx[base + k], -1e15f, 1e15f);
-        y = __builtin_amdgcn_fmed3f(sy[base + k], -1e15f, 1e15f);
+        x = clamp_coord(sx[base + k]);
+        y = clamp_coord(sy[base + k]);
       }
       s_pt[k] = make_float2(x, y);
     }
@@ -89,10 +91,7 @@ __global__ __launch_bounds__(kPoseThreads) void k_score_poses(const AlignStatic*
       const float qx[4] = {q01.x, q01.z, q23.x, q23.z}, qy[4] = {q01.y, q01.w, q23.y, q23.w};
       PointRec r[4];
 #pragma unroll
-      for (int u = 0; u < 4; ++u) {                                  // image_point
-        r[u].px = fmaf(P.cs, qx[u], fmaf(-P.sn, qy[u], P.tx));
-        r[u].py = fmaf(P.sn, qx[u], fmaf(P.cs, qy[u], P.ty));
-      }
+      for (int u = 0; u < 4; ++u) image_clamped(P, qx[u], qy[u], r[u]);
 #pragma unroll
       for (int g = 0; g < NG; ++g) {
         const float ox = NG == 1 ? G.ox : G.gx[g], oy = NG == 1 ? G.oy : G.gy[g];
@@ -178,10 +177,7 @@ __global__ __launch_bounds__(kPoseThreads) __attribute__((amdgpu_waves_per_eu(1,
         px[u] = p.x; py[u] = p.y; pz[u] = p.z;           // (layer_key3 per lane here: the rotation is the lane's)
         const Voxel3 vox = voxel_clamped3(G, E, layer_key3(G, E, p.z, layer), p.x, p.y, last_cell);
         in[u] = vox.in;
-        const float4* r = rec + 4 * (size_t)(unsigned int)vox.key;
-        A[u] = r[0];
-        B[u] = r[1];
-        C[u] = *reinterpret_cast<const float2*>(r + 2);
+        gather_rec3(rec, vox.key, A[u], B[u], C[u]);
       }
       __builtin_amdgcn_sched_barrier(0);                     // no wait moves up between the twelve loads
       s0 += search_point_score3(px[0], py[0], pz[0], in[0], A[0], B[0], C[0], d1, nhd2);
@@ -333,7 +329,7 @@ int32_t pose_walk(const ndt::SearchSel& sel, const double* picked, double min_se
     for (int32_t q = 0; q < m && keep; ++q) {
       double d2 = 0.0, dr = 0.0;
       for (int a = 0; a < NT; ++a) { const double d = p[a] - hits[q].pose[a]; d2 = d2 + d * d; }
-      for (int a = NT; a < P; ++a) dr = std::max(dr, std::fabs(search_wrap(p[a] - hits[q].pose[a])));
+      for (int a = NT; a < P; ++a) dr = std::max(dr, std::fabs(ndt::wrap_angle(p[a] - hits[q].pose[a])));
       if (d2 < st2 && dr < sr) keep = false;
     }
     if (!keep) continue;

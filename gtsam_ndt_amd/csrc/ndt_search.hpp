@@ -25,6 +25,25 @@ constexpr long long kSearchMaxPoses = 1ll << 25;
 constexpr int kSearchShortlist = 4096;
 constexpr int kSearchSortThreads = 1024;
 
+// The lattice pose of a lane of the score kernels.  Workgroup task b covers rotation j = b / tiles and translation tile
+// b % tiles (tiles = tiles_x tiles_y); a wave is an 8 x 8 block of translations, so that its lanes look up neighbouring
+// cells.  A lane past the window's edge is not live: it computes a clamped pose and stores nothing.
+struct SearchTask {
+  int j, tile_x, tile_y;            // uniform over the workgroup: the rotation and the tile's first translation
+  int ix, iy;                       // the lane's translation
+  bool live;
+};
+__device__ __forceinline__ SearchTask search_task(long long b, int tiles_x, int tiles_y, int nx, int ny) {
+  const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
+  const long long tiles = (long long)tiles_x * tiles_y;
+  const int j = (int)(b / tiles);
+  const int t = (int)(b - j * tiles);
+  const int tile_x = (t % tiles_x) * kSearchTile, tile_y = (t / tiles_x) * kSearchTile;
+  const int ix = tile_x + (wave & 1) * 8 + (lane & 7);
+  const int iy = tile_y + (wave >> 1) * 8 + (lane >> 3);
+  return SearchTask{j, tile_x, tile_y, ix, iy, ix < nx && iy < ny};
+}
+
 // selection state of one search (device memory; the host copies it back whole once the sort is done)
 struct SearchSel {
   unsigned long long prefix;        // digits of the threshold key chosen so far
@@ -254,17 +273,8 @@ int32_t search_lattice(const SearchWindow& w, SearchLattice* L) {
   return NDT_OK;
 }
 
-// wrap_angle (ndt2d_kernels.hpp) on the host, without contraction: what search.py computes in numpy
-double search_wrap(double t) {
-#pragma clang fp contract(off)
-  if (t > kSearchPi || t <= -kSearchPi) {
-    t = t - 2.0 * kSearchPi * std::floor((t + kSearchPi) / (2.0 * kSearchPi));
-    if (t <= -kSearchPi) t += 2.0 * kSearchPi;
-  }
-  return t;
-}
-
-// the axes in double: x, y, and the wrapped rotations
+// the axes in double: x, y, and the wrapped rotations (ndt_pose.hpp's wrap_angle, on the host without contraction: what
+// search.py computes in numpy)
 void search_axes(const SearchWindow& w, const SearchLattice& L, std::vector<double>* ax) {
 #pragma clang fp contract(off)
   const int n[3] = {L.nx, L.ny, L.nt};
@@ -275,7 +285,7 @@ void search_axes(const SearchWindow& w, const SearchLattice& L, std::vector<doub
       double v;
       if (a == 2 && L.cyclic) v = w.center[2] + (double)i * (2.0 * kSearchPi / (double)n[2]);
       else v = w.center[a] + (double)(i - h) * w.step[a];
-      ax[a][i] = a == 2 ? search_wrap(v) : v;
+      ax[a][i] = a == 2 ? ndt::wrap_angle(v) : v;
     }
   }
 }
@@ -295,7 +305,7 @@ int32_t search_walk(const ndt::SearchSel& sel, const std::vector<double>* ax, co
     bool keep = true;
     for (int32_t q = 0; q < m && keep; ++q) {
       const double dx = p[0] - hits[q].pose[0], dy = p[1] - hits[q].pose[1];
-      const double dt = std::fabs(search_wrap(p[2] - hits[q].pose[2]));
+      const double dt = std::fabs(ndt::wrap_angle(p[2] - hits[q].pose[2]));
       if (dx * dx + dy * dy < st2 && dt < sr) keep = false;
     }
     if (!keep) continue;

@@ -15,6 +15,7 @@
 #include <vector>
 
 #include "../../include/ndt_synth.h"
+#include "ndt_pose.hpp"
 
 namespace {
 
@@ -347,12 +348,8 @@ int32_t ndt_synth_lidar3d_dev(const double* boxes_lo, const double* boxes_hi, in
   a.rlo[0] = -0.5 * L; a.rlo[1] = -0.5 * L; a.rlo[2] = 0.0;
   a.rhi[0] = 0.5 * L; a.rhi[1] = 0.5 * L; a.rhi[2] = height;
   a.o[0] = pose[0]; a.o[1] = pose[1]; a.o[2] = pose[2] + sensor_z;
-  const double ca = std::cos(pose[3]), sa = std::sin(pose[3]), cb = std::cos(pose[4]), sb = std::sin(pose[4]),
-               cg = std::cos(pose[5]), sg = std::sin(pose[5]);
-  const double R[9] = {cg * cb, cg * sb * sa - sg * ca, cg * sb * ca + sg * sa,
-                       sg * cb, sg * sb * sa + cg * ca, sg * sb * ca - cg * sa,
-                       -sb, cb * sa, cb * ca};
-  for (int j = 0; j < 9; ++j) a.R[j] = R[j];
+  ndt::rot3_products(std::sin(pose[3]), std::cos(pose[3]), std::sin(pose[4]), std::cos(pose[4]), std::sin(pose[5]),
+                     std::cos(pose[5]), a.R);
   a.el0 = -24.0;
   a.el_step = n_elev > 1 ? 44.0 / (double)(n_elev - 1) : 0.0;
   a.az_step = 2.0 * 3.141592653589793 / (double)n_azim;

@@ -14,6 +14,7 @@ from fractions import Fraction as Fr
 import numpy as np
 
 import map_coarsen_ref as R
+from seam_ref import rot3d_products
 
 FIX = 2.0 ** 22
 
@@ -27,20 +28,18 @@ def pairs_of(dim):
 
 
 def rotation(dim, pose):
-    """(R [3][3] Python floats, t [3]) as the host forms them: cos / sin from libm (math, not numpy's vector versions); in
-    3D the nine products of the alignment kernels' make_rot3 (R = Rz Ry Rx), in its order."""
+    """(R [3][3] Python floats, t [3]) as the host forms them: cos / sin from libm (math, not numpy's vector versions) at
+    the pose's angles as they are (the host does not wrap them); in 3D the nine products of csrc/ndt_pose.hpp, stated in
+    seam_ref.rot3d_products."""
     pose = [float(v) for v in pose]
     Rm = [[0.0] * 3 for _ in range(3)]
     if dim == 2:
         c, s = math.cos(pose[2]), math.sin(pose[2])
         Rm[0][0], Rm[0][1], Rm[1][0], Rm[1][1] = c, -s, s, c
         return Rm, [pose[0], pose[1], 0.0]
-    sa, ca, sb, cb, sg, cg = (math.sin(pose[3]), math.cos(pose[3]), math.sin(pose[4]), math.cos(pose[4]),
-                              math.sin(pose[5]), math.cos(pose[5]))
-    Rm[0] = [cg * cb, cg * sb * sa - sg * ca, cg * sb * ca + sg * sa]
-    Rm[1] = [sg * cb, sg * sb * sa + cg * ca, sg * sb * ca - cg * sa]
-    Rm[2] = [-sb, cb * sa, cb * ca]
-    return Rm, pose[:3]
+    e = rot3d_products(math.sin(pose[3]), math.cos(pose[3]), math.sin(pose[4]), math.cos(pose[4]),
+                       math.sin(pose[5]), math.cos(pose[5]))
+    return [e[0:3], e[3:6], e[6:9]], pose[:3]
 
 
 def centres(origin32, ext, c):

@@ -120,11 +120,7 @@ def rotation32(pose, dim):
         th = _wrap(pose[2])
         c, s = f32(math.cos(th)), f32(math.sin(th))
         return np.array([[c, -s], [s, c]]), np.array([f32(pose[0]), f32(pose[1])])
-    a, b, g = (_wrap(v) for v in pose[3:6])
-    sa, ca, sb, cb, sg, cg = math.sin(a), math.cos(a), math.sin(b), math.cos(b), math.sin(g), math.cos(g)
-    R = np.array([[cg * cb, cg * sb * sa - sg * ca, cg * sb * ca + sg * sa],
-                  [sg * cb, sg * sb * sa + cg * ca, sg * sb * ca - cg * sa],
-                  [-sb, cb * sa, cb * ca]])
+    R = np.array(S.rot3d_entries(*pose[3:6])).reshape(3, 3)          # wrapped angles, the nine products of csrc/ndt_pose.hpp
     return R.astype(np.float32).astype(np.float64), np.array([f32(v) for v in pose[:3]])
 
 

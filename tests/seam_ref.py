@@ -72,13 +72,26 @@ def rot2d32(theta: float):
     return F32(c), F32(s), (c, s)
 
 
-def rot3d_entries(roll: float, pitch: float, yaw: float):
-    """The nine float64 products of make_rot3 (csrc/ndt3d_kernels.hpp), R = Rz Ry Rx, row-major, wrapped angles."""
-    a, b, g = (o2.wrap_angle(float(v)) for v in (roll, pitch, yaw))
-    sa, ca, sb, cb, sg, cg = math.sin(a), math.cos(a), math.sin(b), math.cos(b), math.sin(g), math.cos(g)
+def rot3d_products(sa, ca, sb, cb, sg, cg):
+    """rot3_products of csrc/ndt_pose.hpp in its host form: the nine float64 products of R = Rz Ry Rx, row-major, from the
+    sines and cosines of roll (a), pitch (b) and yaw (g), every operation rounded separately.  The one Python statement:
+    map_merge_ref.rotation and point_fit_ref.rotation32 call it, tests/test_pose_host.py holds the C++ to it bit for bit."""
     return [cg * cb, cg * sb * sa - sg * ca, cg * sb * ca + sg * sa,
             sg * cb, sg * sb * sa + cg * ca, sg * sb * ca - cg * sa,
             -sb, cb * sa, cb * ca]
+
+
+def rot3d_pitch_products(sa, ca, sb, cb, sg, cg):
+    """rot3_pitch_products of csrc/ndt_pose.hpp in its host form: dR/dpitch = Rz dRy Rx, row-major."""
+    return [-cg * sb, cg * cb * sa, cg * cb * ca,
+            -sg * sb, sg * cb * sa, sg * cb * ca,
+            -cb, -sb * sa, -sb * ca]
+
+
+def rot3d_entries(roll: float, pitch: float, yaw: float):
+    """The nine float64 products of the kernels' R (make_rt3, make_rot3; csrc/ndt3d_kernels.hpp) at the wrapped angles."""
+    a, b, g = (o2.wrap_angle(float(v)) for v in (roll, pitch, yaw))
+    return rot3d_products(math.sin(a), math.cos(a), math.sin(b), math.cos(b), math.sin(g), math.cos(g))
 
 
 def rot3d32(roll, pitch, yaw):
