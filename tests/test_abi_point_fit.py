@@ -62,11 +62,11 @@ def test_matchers_and_wrappers_offer_the_calls():
     for cls in (NdtMatcher2D, NdtMatcher3D):
         assert callable(cls.fit_points) and callable(cls.select_points)
     assert "_fit_points" in vars(_NdtMatcher) and "_select_points" in vars(_NdtMatcher)       # the shared code
-    wrapper = open(os.path.join(ROOT, "include", "ndt_matcher_hip.hpp")).read()
-    assert wrapper.count("ndt_point_fit fitPointsDev(") == 2 and wrapper.count("ndt_point_fit selectPointsDev(") == 2
+    import adapter_calls as AC                                  # the C++ adapter's call record
+    assert AC.both_call("fitPointsDev", "fit_points_dev") and AC.both_call("selectPointsDev", "select_points_dev")
     for name in NAMES:
         if not name.endswith("fit_points"):
-            assert name + "(" in wrapper, name
+            assert name in AC.all_called(), name
 
 
 def test_a_null_handle_is_an_argument_error_with_a_message(ndt_lib):

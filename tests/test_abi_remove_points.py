@@ -42,8 +42,11 @@ def test_matchers_offer_remove_beside_add():
 
 
 def test_cpp_wrapper_has_the_remove_twins():
-    src = open(os.path.join(ROOT, "include", "ndt_matcher_hip.hpp")).read()
-    for name in ("ndt2d_remove_target_points(", "ndt2d_remove_target_points_dev(", "ndt3d_remove_target_points(",
-                 "ndt3d_remove_target_points_dev("):
-        assert name in src, name
-    assert src.count("size_t removeTargetPoints(") == 2 and src.count("size_t removeTargetPointsDev(") == 2
+    import adapter_calls as AC                                  # the C++ adapter's call record
+    assert AC.both_call("removeTargetPoints", "remove_target_points")
+    assert AC.both_call("removeTargetPointsDev", "remove_target_points_dev")
+    # ... and nothing but them: the remove twins call what their add twins call, with "remove" for "add"
+    for cls in ("NdtMatcherHip", "NdtMatcherHip3"):
+        for m in ("TargetPoints", "TargetPointsDev"):
+            add, remove = AC.calls()[f"{cls}.add{m}"], AC.calls()[f"{cls}.remove{m}"]
+            assert [f.replace("_add_", "_remove_") for f in add] == remove, (cls, m)

@@ -60,12 +60,13 @@ def test_matchers_and_wrappers_offer_the_calls():
         assert callable(cls.score_map_poses) and callable(cls.best_map_poses) and callable(cls.best_map_poses_align)
     for shared in ("score_map_poses", "best_map_poses", "best_map_poses_align"):           # the shared code
         assert shared in vars(_NdtMatcher)
-    wrapper = open(os.path.join(ROOT, "include", "ndt_matcher_hip.hpp")).read()
-    for method in ("void scoreMapPosesDev(", "std::vector<SearchHit> bestMapPosesDev(", "std::vector<SearchMatch> bestMapPosesAlignDev("):
-        assert wrapper.count(method) == 2, method
+    import adapter_calls as AC                                  # the C++ adapter's call record
+    for method, fn in (("scoreMapPosesDev", "score_map_poses_dev"), ("bestMapPosesDev", "best_map_poses_dev"),
+                       ("bestMapPosesAlignDev", "best_map_poses_align_dev")):
+        assert AC.both_call(method, fn), method
     for name in NAMES:
         if name.endswith("_dev"):
-            assert name + "(" in wrapper, name
+            assert name in AC.all_called(), name
 
 
 def test_argument_errors_are_found_without_a_device(ndt_lib):

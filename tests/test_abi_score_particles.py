@@ -60,11 +60,12 @@ def test_matchers_and_wrappers_offer_the_calls():
         assert list(sig.parameters) == ["self", *coords, "poses", "with_hits", "sync"]
         assert sig.parameters["with_hits"].default is False and sig.parameters["sync"].default is True
     assert "_score_particles" in vars(_NdtMatcher)                         # the shared code
-    wrapper = open(os.path.join(ROOT, "include", "ndt_matcher_hip.hpp")).read()
-    for method in ("void scoreParticlesDev(", "void scoreParticlesAsync(", "void scoreParticles("):
-        assert wrapper.count(method) == 2, method
+    import adapter_calls as AC                                  # the C++ adapter's call record
+    for method, fn in (("scoreParticlesDev", "score_particles_dev"), ("scoreParticlesAsync", "score_particles_async"),
+                       ("scoreParticles", "score_particles")):
+        assert AC.both_call(method, fn), method
     for name in NAMES:
-        assert name + "(" in wrapper, name
+        assert name in AC.all_called(), name
 
 
 def test_a_null_handle_is_an_argument_error(ndt_lib):

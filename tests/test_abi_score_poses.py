@@ -55,12 +55,13 @@ def test_matchers_and_wrappers_offer_the_calls():
         assert callable(cls.score_poses) and callable(cls.best_poses) and callable(cls.best_poses_align)
     assert "_score_poses" in vars(_NdtMatcher) and "_best_poses" in vars(_NdtMatcher)           # the shared code
     assert callable(search.select_best)
-    wrapper = open(os.path.join(ROOT, "include", "ndt_matcher_hip.hpp")).read()
-    for method in ("void scorePosesDev(", "std::vector<SearchHit> bestPosesDev(", "std::vector<SearchMatch> bestPosesAlignDev("):
-        assert wrapper.count(method) == 2, method
+    import adapter_calls as AC                                  # the C++ adapter's call record
+    for method, fn in (("scorePosesDev", "score_poses_dev"), ("bestPosesDev", "best_poses_dev"),
+                       ("bestPosesAlignDev", "best_poses_align_dev")):
+        assert AC.both_call(method, fn), method
     for name in NAMES:
         if name.endswith("_dev"):
-            assert name + "(" in wrapper, name
+            assert name in AC.all_called(), name
 
 
 def test_a_null_handle_is_an_argument_error(ndt_lib):

@@ -130,5 +130,5 @@ def test_the_three_entry_points_are_declared_exported_and_bound(ndt_lib):
     from gtsam_ndt_amd.matcher import NdtMatcher2D
     for m in ("align_map", "evaluate_map", "components"):
         assert callable(getattr(NdtMatcher2D, m))
-    wrapper = open(os.path.join(ROOT, "include", "ndt_matcher_hip.hpp")).read()
-    assert "alignMap(NdtMatcherHip& source" in wrapper
+    import adapter_calls as AC                                  # the C++ adapter's call record
+    assert "ndt2d_align_map" in AC.calls()["NdtMatcherHip.alignMap"]

@@ -104,5 +104,5 @@ def test_the_three_entry_points_are_declared_exported_and_bound(ndt_lib):
     from gtsam_ndt_amd.matcher import NdtMatcher2D
     for m in ("search_map", "search_map_scores", "search_align_map"):
         assert callable(getattr(NdtMatcher2D, m))
-    wrapper = open(os.path.join(ROOT, "include", "ndt_matcher_hip.hpp")).read()
-    assert "searchAlignMap(NdtMatcherHip& source" in wrapper
+    import adapter_calls as AC                                  # the C++ adapter's call record
+    assert "ndt2d_search_align_map" in AC.calls()["NdtMatcherHip.searchAlignMap"]
