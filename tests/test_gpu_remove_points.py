@@ -10,17 +10,12 @@ import numpy as np
 import pytest
 
 from gtsam_ndt_amd import synth
+from handle_life import moved2d as _world      # ndt2d_add_target_points_dev's float32 restatement
 
 pytestmark = pytest.mark.gpu
 
 VARIANTS = (0, 1, 2)
 POSES = [(8.0 + 1.5 * k, 10.0 + 0.8 * k, 0.1 * k) for k in range(6)]
-
-
-def _world(x, y, pose):
-    """ndt2d_add_target_points_dev's float32 restatement (tests/test_gpu_scan_sequence.py pins it to the device's)."""
-    c, s = np.float32(math.cos(pose[2])), np.float32(math.sin(pose[2]))
-    return ((c * x - s * y) + np.float32(pose[0])).astype(np.float32), ((s * x + c * y) + np.float32(pose[1])).astype(np.float32)
 
 
 def _state(m):

@@ -7,23 +7,13 @@ import numpy as np
 import pytest
 
 from gtsam_ndt_amd import synth3d
+from handle_life import moved3d as _world     # ndt3d_add_target_points_dev's float32 restatement
 
 pytestmark = pytest.mark.gpu
 
 POSES = [(0.0, 0.0, 0.0, 0.0, 0.0, 0.0), (0.6, 0.3, 0.02, 0.004, -0.006, 0.05), (1.3, 0.5, -0.01, -0.005, 0.004, 0.11),
          (1.9, 1.1, 0.03, 0.006, 0.002, 0.16)]
 LO, HI = (-22.0, -22.0, -3.0), (22.0, 22.0, 6.0)
-
-
-def _world(x, y, z, pose):
-    """ndt3d_add_target_points_dev's float32 restatement (tests/test_gpu_scan_sequence3d.py pins it to the device's)."""
-    R = synth3d.rotation(*pose[3:]).astype(np.float32)
-    t = np.asarray(pose[:3], np.float32)
-    out = []
-    for r in range(3):
-        a, b, c = R[r, 0] * x, R[r, 1] * y, R[r, 2] * z
-        out.append((((a + b) + c) + t[r]).astype(np.float32))
-    return out
 
 
 def _dev(a):
