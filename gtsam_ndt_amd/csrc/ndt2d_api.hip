@@ -19,6 +19,7 @@
 #include "ndt2d_d2d.hpp"
 #include "ndt2d_d2d_multi.hpp"
 #include "ndt_host.hpp"
+#include "ndt_chain_host.hpp"
 #include "ndt_search.hpp"
 
 #include <atomic>
@@ -40,8 +41,8 @@ struct ndt2d_handle {
   unsigned long long* d_outside = nullptr; // [1]
   void* h_small = nullptr;                 // pinned scratch (kSmallBytes: counter shards at 0, the outside count at 128, a flag)
   // staging for host-pointer entry points
-  float* d_tx = nullptr; float* d_ty = nullptr; size_t tcap = 0;
-  float* d_sx = nullptr; float* d_sy = nullptr; size_t scap = 0;
+  float* d_t[2] = {nullptr, nullptr}; size_t tcap = 0;
+  float* d_s[2] = {nullptr, nullptr}; size_t scap = 0;
   // alignment context (see ndt2d_kernels.hpp: who writes what)
   AlignStatic* d_static = nullptr;
   AlignCall* d_call = nullptr;
@@ -51,8 +52,7 @@ struct ndt2d_handle {
   hipEvent_t wait_ev = nullptr;            // ndt2d_wait_stream's event
   IterState* h_state = nullptr;            // pinned
   int* h_flag = nullptr;                   // pinned: [0] raised by the launch that ends a converged-mode loop, [1] progress
-  int last_parity = 0;
-  bool pending = false;
+  ChainFlight flight;                      // what the last single-pair alignment left in flight (ndt_chain_host.hpp)
   // the further launch chains of asynchronous fixed-iteration calls (ndt_host.hpp: AsyncLane), lane k at index k - 1;
   // lane 0 is stream / d_call / d_dyn
   AsyncLane lane[kMaxLanes - 1];
@@ -61,7 +61,6 @@ struct ndt2d_handle {
   static constexpr int kDefaultLanes = 3;  // what a new handle runs (NDT_TUNE_ASYNC_CHAINS): the count DESIGN 7 measured best
   LaneState lanes;
   bool fork_every_pair = false;            // NDT_TUNE_LANE_FORK = 1: the secondary lanes fork from the handle's stream at every round
-  int last_lane = 0;                       // the lane whose AlignDyn holds the pending state (last_parity)
   AlignCall* call_of(int l) const { return l ? d_call_lane[l - 1] : d_call; }
   AlignDyn* dyn_of(int l) const { return l ? d_dyn_lane[l - 1] : d_dyn; }
   // binned grid build scratch (ndt2d_build.hpp)
@@ -88,13 +87,9 @@ struct ndt2d_handle {
   int publish_seq = 0;                     // k_build_publish's flag value of the build in flight (small_flag(h_small))
   // hipGraph of the launch chain (launch-bound inner loop: one replay instead of K+1 launches)
   ChainGraphCache graphs;
-  hipGraphExec_t graph_exec = nullptr;     // the one a map-to-map call selected last (owned by `graphs`)
   AlignDynMulti* d_dyn_multi = nullptr;    // multi-start chains (ndt2d_multi_start.hpp), allocated on first use
   IterState* h_state_multi = nullptr;      // pinned [kMaxStarts]
   int split_from = 12;                     // multi-start / multi-scan calls of this many starts use the split chain (NDT_TUNE_SPLIT_FROM)
-  ChunkRun chunk_run;                      // converged-mode loop begun by ndt2d_align_dev_async
-  int call_seq = 0;                        // alignments enqueued so far (never 0 once one has run)
-  bool small_run = false;                  // a k_align_small launch whose flag has not been waited for
   // execution strategy knobs (ndt2d_set_tuning; results do not depend on them beyond float32 summation order)
   bool use_small = true;                   // short scans run the whole loop in one workgroup (k_align_small)
   bool use_wide = true;                    // 1024-thread workgroups for large scans ...
@@ -119,9 +114,9 @@ struct ndt2d_handle {
 
 namespace {
 
+template <> struct HandleTraits<ndt2d_handle>;   // (below; the shared chain code is used before it)
+
 constexpr size_t kMaxCells = (size_t)1 << 27;
-// k_iterate indexes points with int and looks three strides (of up to 256 x 1024 threads) ahead
-constexpr size_t kMaxSourcePoints = 0x7fffffffull - 4ull * kMaxBlocks * 1024ull;
 #ifndef NDT_ITER_THREADS
 #define NDT_ITER_THREADS 256
 #endif
@@ -398,11 +393,11 @@ int32_t accumulate_and_finalise(ndt2d_handle* h, const float* d_x, const float* 
   }
   // the other paths take the points as they are: move them into the map frame first
   if (move && move->use) {
-    HIP_TRY(grow({grow_buf(&h->d_tx), grow_buf(&h->d_ty)}, &h->tcap, n, n + n / 4 + 1024));
+    HIP_TRY(grow({grow_buf(&h->d_t[0]), grow_buf(&h->d_t[1])}, &h->tcap, n, n + n / 4 + 1024));
     hipLaunchKernelGGL(k_transform_points, dim3((unsigned)((n + kBlock - 1) / kBlock)), dim3(kBlock), 0, h->stream, d_x, d_y,
-                       n, move->cs, move->sn, move->tx, move->ty, h->d_tx, h->d_ty);
+                       n, move->cs, move->sn, move->tx, move->ty, h->d_t[0], h->d_t[1]);
     HIP_TRY(hipGetLastError());
-    d_x = h->d_tx; d_y = h->d_ty;
+    d_x = h->d_t[0]; d_y = h->d_t[1];
   }
   HIP_TRY(hipMemsetAsync(h->d_outside, 0, sizeof(unsigned long long), h->stream));
   if (h->use_binned_build && ntile_ll <= kBinMaxTiles && n <= 0xFFFFFFFFull) {
@@ -620,7 +615,7 @@ auto with_mode(const ndt2d_params& p, F&& f) {
   return p.overlap_grids == 4 ? f(Zero{}, Four{}) : f(Zero{}, One{});
 }
 
-// the k_iterate of an alignment, for graphs (ensure_graph) and plain launches (launch_iter).  wide: 1024-thread
+// the k_iterate of an alignment, for graphs and plain launches (scan_chain).  wide: 1024-thread
 // workgroups - a property of the call (its scan size), calls in flight on different lanes may differ in it
 const void* iter_kernel(const ndt2d_handle* h, bool wide) {
   return with_mode(h->prm, [&](auto M, auto NG) {
@@ -636,99 +631,43 @@ const void* first_kernel(const ndt2d_handle* h, bool wide) {
 int iter_threads(bool wide) { return wide ? kIterThreadsWide : kIterThreads; }
 bool is_wide(const ndt2d_handle* h, size_t n) { return h->use_wide && n >= h->wide_threshold; }
 
-void launch_iter(ndt2d_handle* h, bool wide, int blocks, int k) {
-  (void)launch_chain_kernel(iter_kernel(h, wide), dim3(blocks), dim3(iter_threads(wide)), h->d_static, h->d_call, h->d_dyn, k & 1,
-                            h->stream);
+// The k_iterate chain of a scan of n points on `lane`: the kernels read everything (grid, source pointers, n, parameters,
+// state) from device memory, so one graph of it serves every target and every source - of its lane: the per-call and
+// dynamic contexts are baked into it.
+ChainLaunch scan_chain(const ndt2d_handle* h, size_t n, int lane) {
+  const bool wide = is_wide(h, n);
+  return {iter_kernel(h, wide), dim3(blocks_for(n)), dim3(iter_threads(wide)), h->d_static, h->call_of(lane), h->dyn_of(lane)};
 }
 
-void drop_graph(ndt2d_handle* h) {
-  h->graphs.clear();
-  h->graph_exec = nullptr;
+// the first launch of the old protocol, on `lane` and its stream: launches 0 .. K follow
+void launch_begin(ndt2d_handle* h, int lane, hipStream_t stream, const float* const* d_s, size_t n, const double* pose, int fixed,
+                  IterState* host_state, int* host_flag) {
+  hipLaunchKernelGGL(k_begin, dim3(1), dim3(64), 0, stream, h->call_of(lane), h->dyn_of(lane), d_s[0], d_s[1], (int)n, pose[0],
+                     pose[1], pose[2], fixed, host_state, host_flag, h->flight.call_seq);
 }
 
-// Graph of `launches` consecutive k_iterate launches starting at parity `first_parity` (1: launch 0 is a k_iterate_first
-// in front of the graph; 0: the old protocol behind k_begin - the cache keeps the two apart).  The kernels read
-// everything (grid, source pointers, n, parameters, state) from device memory, so one graph
-// serves every target and every source - of its lane: the per-call and dynamic contexts are baked into it.
-int32_t ensure_graph(ndt2d_handle* h, int launches, int blocks, bool wide, int lane, hipGraphExec_t* exec, int first_parity) {
-  HIP_TRY(h->graphs.get(iter_kernel(h, wide), dim3(blocks), dim3(iter_threads(wide)), (void*)h->d_static,
-                        (void*)h->call_of(lane), (void*)h->dyn_of(lane), launches,
-                        h->prm.hessian_mode | (wide ? 16 : 0), h->stream, exec, lane, first_parity));
-  return NDT_OK;
-}
-
-// Wait for a single-workgroup alignment: its last thread raises the flag in pinned host memory
-// after writing the state there, so the result is on the host the moment the spin ends.
-int32_t finish_small_run(ndt2d_handle* h) {
-  if (!h->small_run) return NDT_OK;
-  h->small_run = false;
-  // No stream sync once the flag is up: the kernel read the scan into registers at its start and
-  // raises the flag as its last action, so the caller's source buffers are already free.
-  bool seen = false;
-  HIP_TRY(spin_until(h->stream, [&]() { return __atomic_load_n(&h->h_flag[0], __ATOMIC_ACQUIRE) != 0; }, &seen));
-  HIP_TRY(hipGetLastError());
-  h->pending = !seen;            // not seen after real syncs: the kernel has ended anyway, fetch_state copies dyn->state[0]
-  h->last_parity = 0;
-  return NDT_OK;
-}
-
-// Waits for what the host has to keep fed or listen for (a short-scan launch, a converged-mode loop); both run on lane 0.
-int32_t finish_host_fed(ndt2d_handle* h) {
-  { const int32_t fs = finish_small_run(h); if (fs != NDT_OK) return fs; }
-  if (!h->chunk_run.active) return NDT_OK;
-  bool seen = false;
-  HIP_TRY(chunk_run_finish(h->chunk_run, h->stream, h->h_flag, &seen));
-  HIP_TRY(hipGetLastError());
-  if (!seen) { set_error("the Gauss-Newton loop did not report its end"); return NDT_ERR_HIP; }
-  h->pending = false;                                  // the finishing launch wrote the result into h_state
-  return NDT_OK;
-}
-
-// The head of every entry point that is about to use the handle's stream for something else than a rotating
-// asynchronous alignment.  The secondary lanes need no wait here: the handle's stream was ordered behind their chains when
-// those were enqueued (AsyncLane::leave).  The rotation starts over and the secondary lanes are stale from here on
-// (lane_step: kOther): the next asynchronous call records fresh fork events behind this entry point's work, and the
-// calls that follow it on lanes 1 .. N-1 wait for theirs.
-int32_t finish_chunk_run(ndt2d_handle* h) {
-  (void)lane_step(h->lanes, LaneEvent::kOther);
-  return finish_host_fed(h);
-}
-
-// The result of an alignment against a grid with no valid cell (IterState or IterState3): the initial pose, NDT_TOO_FEW_CELLS
-template <class State>
-State no_cell_state(const double* pose) {
-  State s;
-  std::memset(&s, 0, sizeof(s));
-  for (size_t j = 0; j < sizeof(s.pose) / sizeof(s.pose[0]); ++j) s.pose[j] = pose[j];
-  s.status = NDT_TOO_FEW_CELLS;
-  return s;
-}
-
-// Enqueue the Gauss-Newton loop.  check_every > 0: poll the done flag every that many
-// launches (synchronous early exit); 0: enqueue all launches, finished ones are no-ops.
-int32_t run_align(ndt2d_handle* h, const float* d_sx, const float* d_sy, size_t n, const double pose[3],
-                  int fixed_override, int check_every, bool wait = true, bool own_source = false) {
+// Enqueue the Gauss-Newton loop of ndt2d_evaluate* (fixed_override = 1) and ndt2d_align* (-1).  wait: the caller fetches
+// the state next; own_source: the scan is in the handle's staging arrays.  The head of the chain: everything behind
+// launch 0 is run_chain_tail's.
+int32_t begin_align(ndt2d_handle* h, const float* const* d_s, size_t n, const double* pose, int fixed_override, bool wait,
+                    bool own_source) {
   TraceRange range("ndt2d_align: Gauss-Newton loop");
   if (!h->has_target) return NDT_ERR_NO_TARGET;
   { const int32_t fs = finish_host_fed(h); if (fs != NDT_OK) return fs; }     // an unfinished asynchronous call
   if (n == 0 || n > kMaxSourcePoints || !pose) { (void)lane_step(h->lanes, LaneEvent::kOther); return NDT_ERR_INVALID_ARG; }
   if (h->n_valid < 1) {
     (void)lane_step(h->lanes, LaneEvent::kOther);
-    h->pending = false;
+    h->flight.how = ChainFlight::kOnHost;
     *h->h_state = no_cell_state<IterState>(pose);
-    h->h_state->done = 2;               // marks "result already on the host"
     return NDT_OK;
   }
-  const int fixed = fixed_override >= 0 ? fixed_override : h->prm.fixed_iterations;
-  const int K = fixed > 0 ? fixed : h->prm.max_iterations;
-  const int blocks = blocks_for(n);
-  const bool wide = is_wide(h, n);
-  const bool chunked = h->use_graph && check_every > 0 && fixed == 0;
+  const ChainPlan p = chain_plan(fixed_override, h->prm.fixed_iterations, h->prm.max_iterations, h->use_graph, h->check_every,
+                                 h->fused_begin);
   const bool small = h->use_small && h->use_graph && n <= (size_t)kSmallMaxPoints;
   // Only a whole fixed-iteration chain that nobody waits for goes round the lanes; everything else runs on
   // lane 0 and starts the rotation over.
-  const LanePlan plan = lane_step(h->lanes, fixed > 0 && h->use_graph && !small && !wait ? LaneEvent::kAsyncFixed : LaneEvent::kOther);
-  next_seq(&h->call_seq, h->h_flag);
+  const LanePlan plan = lane_step(h->lanes, p.fixed > 0 && h->use_graph && !small && !wait ? LaneEvent::kAsyncFixed : LaneEvent::kOther);
+  next_seq(&h->flight.call_seq, h->h_flag);
   if (small) {
     // short scan: the whole loop in one launch of one workgroup (ndt2d_small.hpp)
     const bool lo = n <= (size_t)kSmallLoPoints;
@@ -737,14 +676,12 @@ int32_t run_align(ndt2d_handle* h, const float* d_sx, const float* d_sy, size_t 
     });
     int ni = (int)n;
     IterState* dev_state = &h->d_dyn->state[0];
-    void* args[] = {&h->d_static, &d_sx, &d_sy, &ni, (void*)&pose[0], (void*)&pose[1], (void*)&pose[2], (void*)&fixed,
-                    &dev_state, &h->h_state, &h->h_flag};
+    void* args[] = {&h->d_static, (void*)&d_s[0], (void*)&d_s[1], &ni, (void*)&pose[0], (void*)&pose[1], (void*)&pose[2],
+                    (void*)&p.fixed, &dev_state, &h->h_state, &h->h_flag};
     (void)hipLaunchKernel(func, dim3(1), dim3(lo ? kSmallThreadsLo : kSmallThreadsHi), args, 0, h->stream);
     HIP_TRY(hipGetLastError());
-    h->small_run = true;
-    h->pending = false;
-    h->last_lane = 0;
-    return wait ? finish_small_run(h) : NDT_OK;
+    h->flight.how = ChainFlight::kSmallRun;              // its last thread writes h_state, then raises the flag
+    return NDT_OK;
   }
   hipStream_t stream = h->stream;
   // the fork: where non-chain work on the handle's stream may precede the round (or at every round, NDT_TUNE_LANE_FORK = 1),
@@ -768,73 +705,20 @@ int32_t run_align(ndt2d_handle* h, const float* d_sx, const float* d_sy, size_t 
   }
   // Launch 0.  Fused (the default): k_iterate_first, a plain launch that evaluates at the initial pose and writes the
   // per-call context from its arguments; launches 1 .. K follow.  Old protocol: k_begin, then launches 0 .. K.
-  const int first = h->fused_begin ? 1 : 0;
-  AlignCall* const d_call = h->call_of(plan.lane);
-  AlignDyn* const d_dyn = h->dyn_of(plan.lane);
-  IterState* const host_state = chunked ? h->h_state : (IterState*)nullptr;
-  int* const host_flag = chunked ? h->h_flag : (int*)nullptr;
-  if (first) {
-    int ni = (int)n, fi = fixed;
-    void* args[] = {&h->d_static, (void*)&d_call, (void*)&d_dyn, &d_sx, &d_sy, &ni, (void*)&pose[0], (void*)&pose[1],
-                    (void*)&pose[2], &fi, (void*)&host_state, (void*)&host_flag, &h->call_seq};
-    (void)hipLaunchKernel(first_kernel(h, wide), dim3(blocks), dim3(iter_threads(wide)), args, 0, stream);
+  const bool wide = is_wide(h, n);
+  const ChainLaunch c = scan_chain(h, n, plan.lane);
+  IterState* const host_state = p.chunked ? h->h_state : (IterState*)nullptr;
+  int* const host_flag = p.chunked ? h->h_flag : (int*)nullptr;
+  if (p.first) {
+    int ni = (int)n;
+    void* args[] = {(void*)&c.a0, (void*)&c.a1, (void*)&c.a2, (void*)&d_s[0], (void*)&d_s[1], &ni, (void*)&pose[0], (void*)&pose[1],
+                    (void*)&pose[2], (void*)&p.fixed, (void*)&host_state, (void*)&host_flag, &h->flight.call_seq};
+    (void)hipLaunchKernel(first_kernel(h, wide), c.grid, c.block, args, 0, stream);
   } else {
-    hipLaunchKernelGGL(k_begin, dim3(1), dim3(64), 0, stream, d_call, d_dyn, d_sx, d_sy, (int)n, pose[0], pose[1], pose[2], fixed,
-                       host_state, host_flag, h->call_seq);
+    launch_begin(h, plan.lane, stream, d_s, n, pose, p.fixed, host_state, host_flag);
   }
-  int k = first;
-  hipGraphExec_t exec = nullptr;
-  if (h->use_graph) {
-    if (chunked) {
-      // converged mode: chunks of launches until the finishing launch raises the host flag
-      const int chunk = check_every + (check_every & 1);
-      const int32_t gs = ensure_graph(h, chunk, blocks, wide, 0, &exec, first);
-      if (gs != NDT_OK) return gs;
-      h->chunk_run.drain = !own_source;                // the handle's own staging arrays outlive the call
-      h->chunk_run.seq = h->call_seq;
-      HIP_TRY(chunk_run_begin(h->chunk_run, exec, h->stream, chunk, K + 1, first));
-      h->pending = false;
-      return wait ? finish_chunk_run(h) : NDT_OK;
-    } else {
-      // (a secondary-lane call that fails here leaves its lane behind the fork event at most and nothing else: harmless)
-      const int32_t gs = ensure_graph(h, K + 1 - first, blocks, wide, plan.lane, &exec, first);
-      if (gs != NDT_OK) return gs;
-      HIP_TRY(hipGraphLaunch(exec, stream));
-      if (side) HIP_TRY(side->leave(h->stream));
-      k = K + 1;
-    }
-  } else {
-    for (; k <= K; ++k) {
-      launch_iter(h, wide, blocks, k);
-      if (check_every > 0 && fixed == 0 && k < K && (k % check_every) == check_every - 1) {
-        HIP_TRY(hipGetLastError());
-        HIP_TRY(hipMemcpyAsync(h->h_state, &h->d_dyn->state[k & 1], sizeof(IterState), hipMemcpyDeviceToHost,
-                               h->stream));
-        HIP_TRY(hipStreamSynchronize(h->stream));
-        if (h->h_state->done) { ++k; break; }
-      }
-    }
-  }
-  HIP_TRY(hipGetLastError());
-  h->last_parity = (k - 1) & 1;
-  h->last_lane = plan.lane;
-  h->h_state->done = 0;
-  h->pending = true;
-  return NDT_OK;
-}
-
-// The state of the last alignment, from the lane it ran on (the handle's stream is behind every lane's chains)
-int32_t fetch_state(ndt2d_handle* h) {
-  { const int32_t fs = finish_host_fed(h); if (fs != NDT_OK) return fs; }
-  (void)lane_step(h->lanes, LaneEvent::kFinish);
-  if (h->pending) {
-    const AlignDyn* dyn = h->dyn_of(h->last_lane);
-    HIP_TRY(hipMemcpyAsync(h->h_state, &dyn->state[h->last_parity], sizeof(IterState),
-                           hipMemcpyDeviceToHost, h->stream));
-    HIP_TRY(hipStreamSynchronize(h->stream));
-    h->pending = false;
-  }
-  return NDT_OK;
+  // (drain: the handle's own staging arrays outlive the call)
+  return run_chain_tail(h, c, h->prm.hessian_mode | (wide ? 16 : 0), plan.lane, stream, side, p, !own_source);
 }
 
 void sym6_to_9(const double* s, double* H) {
@@ -858,25 +742,7 @@ void state_to(const IterState& s, Out* out) {
   }
 }
 
-// a host scan into the handle's staging arrays, behind the alignment in flight
-int32_t stage_source(ndt2d_handle* h, const float* sx, const float* sy, size_t n) {
-  { const int32_t fs = finish_chunk_run(h); if (fs != NDT_OK) return fs; }
-  HIP_TRY(grow({grow_buf(&h->d_sx), grow_buf(&h->d_sy)}, &h->scap, n, n + n / 4 + 1024));
-  HIP_TRY(hipMemcpyAsync(h->d_sx, sx, n * sizeof(float), hipMemcpyHostToDevice, h->stream));
-  HIP_TRY(hipMemcpyAsync(h->d_sy, sy, n * sizeof(float), hipMemcpyHostToDevice, h->stream));
-  return NDT_OK;
-}
-
-// the same for a host target cloud
-int32_t stage_target(ndt2d_handle* h, const float* x, const float* y, size_t n) {
-  { const int32_t fs = finish_chunk_run(h); if (fs != NDT_OK) return fs; }
-  HIP_TRY(grow({grow_buf(&h->d_tx), grow_buf(&h->d_ty)}, &h->tcap, n, n + n / 4 + 1024));
-  HIP_TRY(hipMemcpyAsync(h->d_tx, x, n * sizeof(float), hipMemcpyHostToDevice, h->stream));
-  HIP_TRY(hipMemcpyAsync(h->d_ty, y, n * sizeof(float), hipMemcpyHostToDevice, h->stream));
-  return NDT_OK;
-}
-
-// The 2D side of the host code both handles share (ndt_search.hpp, ndt_map_host.hpp)
+// The 2D side of the host code both handles share (ndt_chain_host.hpp, ndt_search.hpp, ndt_map_host.hpp)
 template <> struct HandleTraits<ndt2d_handle> {
   using State = IterState;
   using Result = ndt2d_result;
@@ -884,14 +750,20 @@ template <> struct HandleTraits<ndt2d_handle> {
   using Hit = ndt2d_search_hit;
   using Poses = StartPoses;
   using Maps = StartMaps;
-  static constexpr int kPose = 3, kMaxStarts = ndt::kMaxStarts;
+  static constexpr int kDim = 2, kPose = 3, kMaxStarts = ndt::kMaxStarts;
   static constexpr int kRecord = 2;                        // float4 per covariance record and per component
+  // the state of a fixed chain is copied at fetch_state, from the lane the chain ran on (3D: the copy is enqueued behind the chain)
+  static constexpr bool kQueuedFetch = false;
   static constexpr const char* kCell = "cell";
   static constexpr const char* kTraceComponents = "ndt2d: component list";
+  static constexpr const char* kTraceAlignTrace = "ndt2d_align_trace";
+  static constexpr const char* kTraceMapPair = "ndt2d_align_map: Gauss-Newton loop";
   static constexpr const char* kTraceMapMulti = "ndt2d_align_map_multi";
   static constexpr const char* kMapMultiNoEnd = "the map-to-map multi-start loop did not report its end";
   static size_t cells(const ndt2d_handle* h) { return (size_t)h->grid.W * h->grid.H; }
-  static int32_t finish(ndt2d_handle* h) { return finish_chunk_run(h); }
+  template <class... A> static int32_t begin(A... a) { return begin_align(a...); }
+  template <class... A> static ChainLaunch scan_chain(A... a) { return ::scan_chain(a...); }
+  template <class... A> static void launch_begin(A... a) { ::launch_begin(a...); }
   template <class Out> static void to(const IterState& s, Out* out) { state_to(s, out); }
   static void launch_cov_records(ndt2d_handle* h, unsigned nb) {
     hipLaunchKernelGGL(k_cov_records, dim3(nb), dim3(kBlock), 0, h->stream, h->grid, h->prm.min_points, h->prm.eig_ratio,
@@ -1078,15 +950,15 @@ int32_t ndt2d_create(const ndt2d_params* p, int32_t device_id, ndt2d_handle** ou
 int32_t ndt2d_destroy(ndt2d_handle* h) {
   if (!h) return NDT_OK;
   (void)hipSetDevice(h->device);
-  (void)finish_chunk_run(h);
+  (void)finish(h);
   if (h->stream) (void)hipStreamSynchronize(h->stream);
   for (int l = 0; l < kMaxLanes - 1; ++l) {
     h->graphs.lane_stream[l] = nullptr;
     h->lane[l].destroy();                   // joins the lane first
   }
-  drop_graph(h);
+  h->graphs.clear();
   if (h->h_state_multi) (void)hipHostFree(h->h_state_multi);
-  void* dev[] = {h->d_acc2, h->d_split, h->d_bxy, h->d_table, h->d_parts, h->d_geom, h->d_dyn_multi, h->d_bounds, h->d_counters, h->d_outside, h->d_static, h->d_call, h->d_dyn, h->d_call_lane[0], h->d_dyn_lane[0], h->d_call_lane[1], h->d_dyn_lane[1], h->d_call_lane[2], h->d_dyn_lane[2], h->d_bx, h->d_by, h->d_tiles, h->d_tx, h->d_ty, h->d_sx, h->d_sy,
+  void* dev[] = {h->d_acc2, h->d_split, h->d_bxy, h->d_table, h->d_parts, h->d_geom, h->d_dyn_multi, h->d_bounds, h->d_counters, h->d_outside, h->d_static, h->d_call, h->d_dyn, h->d_call_lane[0], h->d_dyn_lane[0], h->d_call_lane[1], h->d_dyn_lane[1], h->d_call_lane[2], h->d_dyn_lane[2], h->d_bx, h->d_by, h->d_tiles, h->d_t[0], h->d_t[1], h->d_s[0], h->d_s[1],
                  h->grid.rec, h->grid.acc, h->d_cov, h->d_blk, h->d_comp, h->d_map_call};
   for (void* p : dev) if (p) (void)hipFree(p);
   void* host[] = {h->h_geom, h->h_static, h->h_state, h->h_small, h->h_flag};
@@ -1107,7 +979,7 @@ void* ndt2d_stream(ndt2d_handle* h) { return h ? (void*)h->stream : nullptr; }
 int32_t ndt2d_set_tuning(ndt2d_handle* h, int32_t knob, int64_t value) {
   if (!h) return NDT_ERR_INVALID_ARG;
   HIP_TRY(hipSetDevice(h->device));
-  { const int32_t fs = finish_chunk_run(h); if (fs != NDT_OK) return fs; }
+  { const int32_t fs = finish(h); if (fs != NDT_OK) return fs; }
   switch (knob) {
     case NDT_TUNE_LAUNCH_GRAPHS: h->use_graph = value != 0; return NDT_OK;
     case NDT_TUNE_WIDE_THRESHOLD: h->use_wide = value > 0; if (value > 0) h->wide_threshold = (size_t)value; return NDT_OK;
@@ -1118,13 +990,13 @@ int32_t ndt2d_set_tuning(ndt2d_handle* h, int32_t knob, int64_t value) {
       h->use_binned_build = value != 0; if (value) h->build_variant = (int)value; return NDT_OK;
     case NDT_TUNE_SPLIT_FROM: if (value < 1 || value > 1000) return NDT_ERR_INVALID_ARG; h->split_from = (int)value; return NDT_OK;
     case NDT_TUNE_SINGLE_SYNC_BUILD: h->one_round_trip = value != 0; return NDT_OK;
-    // (both set the number of launch chains; finish_chunk_run above has restarted the rotation and made the lanes stale)
+    // (both set the number of launch chains; finish above has restarted the rotation and made the lanes stale)
     case NDT_TUNE_ASYNC_LANES: if (value < 1 || value > 2) return NDT_ERR_INVALID_ARG; h->lanes.lanes = (int)value; return NDT_OK;
     case NDT_TUNE_ASYNC_CHAINS: if (value < 1 || value > kMaxLanes) return NDT_ERR_INVALID_ARG; h->lanes.lanes = (int)value; return NDT_OK;
     case NDT_TUNE_MAP_MULTI_FROM: if (value < 1 || value > kMaxStarts + 1) return NDT_ERR_INVALID_ARG; h->map_multi_from = (int)value; return NDT_OK;
     // (the graphs of the two protocols have different first parities in the cache's key and never alias: nothing to drop)
     case NDT_TUNE_FUSED_BEGIN: if (value != 0 && value != 1) return NDT_ERR_INVALID_ARG; h->fused_begin = value != 0; return NDT_OK;
-    // (finish_chunk_run above has made the lanes stale, so the first round under either protocol forks)
+    // (finish above has made the lanes stale, so the first round under either protocol forks)
     case NDT_TUNE_LANE_FORK: if (value != 0 && value != 1) return NDT_ERR_INVALID_ARG; h->fork_every_pair = value != 0; return NDT_OK;
     case NDT_TUNE_PARTICLE_TEAM: if (value != 0 && value != 64 && value != 256) return NDT_ERR_INVALID_ARG; h->particle_team = (int)value; return NDT_OK;
     default: return NDT_ERR_INVALID_ARG;
@@ -1152,14 +1024,15 @@ int32_t ndt2d_wait_stream(ndt2d_handle* h, void* producer_stream) {
 int32_t ndt2d_set_target(ndt2d_handle* h, const float* x, const float* y, size_t n) {
   if (!h || !x || !y || n == 0) return NDT_ERR_INVALID_ARG;
   HIP_TRY(hipSetDevice(h->device));
-  { const int32_t ss = stage_target(h, x, y, n); if (ss != NDT_OK) return ss; }
-  return ndt2d_set_target_dev(h, h->d_tx, h->d_ty, n, nullptr);
+  const float* const t[2] = {x, y};
+  { const int32_t ss = stage_target(h, t, n); if (ss != NDT_OK) return ss; }
+  return ndt2d_set_target_dev(h, h->d_t[0], h->d_t[1], n, nullptr);
 }
 
 int32_t ndt2d_set_target_dev(ndt2d_handle* h, const float* d_x, const float* d_y, size_t n, void* stream) {
   if (!h || !d_x || !d_y || n == 0) return NDT_ERR_INVALID_ARG;
   HIP_TRY(hipSetDevice(h->device));
-  { const int32_t fs = finish_chunk_run(h); if (fs != NDT_OK) return fs; }
+  { const int32_t fs = finish(h); if (fs != NDT_OK) return fs; }
   if (stream) HIP_TRY(hipStreamSynchronize((hipStream_t)stream));   // producer of d_x/d_y
   return set_target_impl(h, d_x, d_y, n);
 }
@@ -1169,7 +1042,7 @@ int32_t ndt2d_reserve_target(ndt2d_handle* h, double xmin, double ymin, double x
       !std::isfinite(ymax))
     return NDT_ERR_INVALID_ARG;
   HIP_TRY(hipSetDevice(h->device));
-  { const int32_t fs = finish_chunk_run(h); if (fs != NDT_OK) return fs; }
+  { const int32_t fs = finish(h); if (fs != NDT_OK) return fs; }
   h->has_target = false;
   grid_changed(h);
   const int32_t gs = setup_geometry(h, (float)xmin, (float)xmax, (float)ymin, (float)ymax);
@@ -1193,7 +1066,7 @@ int32_t update_target_points_dev(ndt2d_handle* h, const float* d_x, const float*
   // (a wrapped count is told from a full cell by its size: removed_cell_broken, ndt2d_kernels.hpp)
   if (sign < 0 && n >= 0xFFF00000ull) { set_error("more points to remove than a call can take (2^32 - 2^20)"); return NDT_ERR_INVALID_ARG; }
   HIP_TRY(hipSetDevice(h->device));
-  { const int32_t fs = finish_chunk_run(h); if (fs != NDT_OK) return fs; }
+  { const int32_t fs = finish(h); if (fs != NDT_OK) return fs; }
   grid_changed(h);
   // order after the caller's producer stream, as ndt2d_set_target_dev does
   if (stream) HIP_TRY(order_after(h->stream, (hipStream_t)stream));
@@ -1225,16 +1098,18 @@ int32_t ndt2d_remove_target_points(ndt2d_handle* h, const float* x, const float*
   if (!h || !x || !y || n == 0) return NDT_ERR_INVALID_ARG;
   if (!h->has_target) return NDT_ERR_NO_TARGET;
   HIP_TRY(hipSetDevice(h->device));
-  { const int32_t ss = stage_target(h, x, y, n); if (ss != NDT_OK) return ss; }
-  return ndt2d_remove_target_points_dev(h, h->d_tx, h->d_ty, n, nullptr, n_outside, nullptr);
+  const float* const t[2] = {x, y};
+  { const int32_t ss = stage_target(h, t, n); if (ss != NDT_OK) return ss; }
+  return ndt2d_remove_target_points_dev(h, h->d_t[0], h->d_t[1], n, nullptr, n_outside, nullptr);
 }
 
 int32_t ndt2d_add_target_points(ndt2d_handle* h, const float* x, const float* y, size_t n, size_t* n_outside) {
   if (!h || !x || !y || n == 0) return NDT_ERR_INVALID_ARG;
   if (!h->has_target) return NDT_ERR_NO_TARGET;
   HIP_TRY(hipSetDevice(h->device));
-  { const int32_t ss = stage_target(h, x, y, n); if (ss != NDT_OK) return ss; }
-  return ndt2d_add_target_points_dev(h, h->d_tx, h->d_ty, n, nullptr, n_outside, nullptr);
+  const float* const t[2] = {x, y};
+  { const int32_t ss = stage_target(h, t, n); if (ss != NDT_OK) return ss; }
+  return ndt2d_add_target_points_dev(h, h->d_t[0], h->d_t[1], n, nullptr, n_outside, nullptr);
 }
 
 int32_t ndt2d_get_grid_info(ndt2d_handle* h, ndt2d_grid_info* info) {
@@ -1280,99 +1155,40 @@ int32_t ndt2d_get_grid(ndt2d_handle* h, int32_t* count, float* mean_xy, float* i
 
 int32_t ndt2d_evaluate(ndt2d_handle* h, const float* sx, const float* sy, size_t n, const double pose[3],
                        ndt2d_eval* out) {
-  if (!h || !sx || !sy || !pose || !out || n == 0) return NDT_ERR_INVALID_ARG;
-  if (!h->has_target) return NDT_ERR_NO_TARGET;
-  HIP_TRY(hipSetDevice(h->device));
-  { const int32_t ss = stage_source(h, sx, sy, n); if (ss != NDT_OK) return ss; }
-  return ndt2d_evaluate_dev(h, h->d_sx, h->d_sy, n, pose, out);
+  const float* const s[2] = {sx, sy};
+  return evaluate_host(h, s, n, pose, out);
 }
 
-// the same with the scan already on the device (order the handle behind its producer with ndt2d_wait_stream first)
 int32_t ndt2d_evaluate_dev(ndt2d_handle* h, const float* d_sx, const float* d_sy, size_t n, const double pose[3],
                            ndt2d_eval* out) {
-  if (!h || !d_sx || !d_sy || !pose || !out || n == 0) return NDT_ERR_INVALID_ARG;
-  if (!h->has_target) return NDT_ERR_NO_TARGET;
-  HIP_TRY(hipSetDevice(h->device));
-  int32_t st = run_align(h, d_sx, d_sy, n, pose, /*fixed_override=*/1, /*check_every=*/0);
-  if (st != NDT_OK) return st;
-  st = fetch_state(h);
-  if (st != NDT_OK) return st;
-  state_to(*h->h_state, out);
-  return NDT_OK;
+  const float* const s[2] = {d_sx, d_sy};
+  return evaluate_dev(h, s, n, pose, out);
 }
 
 int32_t ndt2d_align_trace(ndt2d_handle* h, const float* sx, const float* sy, size_t n, const double init_pose[3],
                           ndt2d_result* rows, int32_t capacity, int32_t* n_rows, ndt2d_result* out) {
-  if (!h || !sx || !sy || !init_pose || !rows || capacity < 1 || !n_rows || n == 0 || n > kMaxSourcePoints)
-    return NDT_ERR_INVALID_ARG;
-  *n_rows = 0;
-  if (!h->has_target) return NDT_ERR_NO_TARGET;
-  TraceRange range("ndt2d_align_trace");
-  HIP_TRY(hipSetDevice(h->device));
-  { const int32_t fs = finish_chunk_run(h); if (fs != NDT_OK) return fs; }
-  if (h->n_valid < 1) {
-    state_to(no_cell_state<IterState>(init_pose), &rows[0]);
-    if (out) *out = rows[0];
-    return NDT_OK;
-  }
-  { const int32_t ss = stage_source(h, sx, sy, n); if (ss != NDT_OK) return ss; }
-  // the launch-per-iteration kernels, one plain launch and one state fetch per iteration
-  const int fixed = h->prm.fixed_iterations;
-  const int K = fixed > 0 ? fixed : h->prm.max_iterations;
-  const bool wide = is_wide(h, n);
-  next_seq(&h->call_seq);
-  hipLaunchKernelGGL(k_begin, dim3(1), dim3(64), 0, h->stream, h->d_call, h->d_dyn, h->d_sx, h->d_sy, (int)n, init_pose[0],
-                     init_pose[1], init_pose[2], fixed, (IterState*)nullptr, (int*)nullptr, h->call_seq);
-  for (int k = 0; k <= K; ++k) {
-    launch_iter(h, wide, blocks_for(n), k);
-    HIP_TRY(hipGetLastError());
-    if (k == 0) continue;                                  // launch 0 only evaluates
-    HIP_TRY(hipMemcpyAsync(h->h_state, &h->d_dyn->state[k & 1], sizeof(IterState), hipMemcpyDeviceToHost, h->stream));
-    HIP_TRY(hipStreamSynchronize(h->stream));
-    if (*n_rows < capacity) state_to(*h->h_state, &rows[(*n_rows)++]);
-    if (h->h_state->done) break;
-  }
-  h->pending = false;
-  h->h_state->done = 2;                                     // the final state is in h_state
-  if (out) state_to(*h->h_state, out);
-  return NDT_OK;
+  const float* const s[2] = {sx, sy};
+  return align_trace(h, s, n, init_pose, rows, capacity, n_rows, out);
 }
 
-int32_t ndt2d_align_finish(ndt2d_handle* h, ndt2d_result* out) {
-  if (!h || !out) return NDT_ERR_INVALID_ARG;
-  HIP_TRY(hipSetDevice(h->device));
-  const int32_t st = fetch_state(h);
-  if (st != NDT_OK) return st;
-  state_to(*h->h_state, out);
-  return NDT_OK;
-}
+int32_t ndt2d_align_finish(ndt2d_handle* h, ndt2d_result* out) { return align_finish(h, out); }
 
 int32_t ndt2d_align_dev_async(ndt2d_handle* h, const float* d_sx, const float* d_sy, size_t n,
                               const double init_pose[3]) {
-  if (!h || !d_sx || !d_sy || !init_pose) return NDT_ERR_INVALID_ARG;
-  HIP_TRY(hipSetDevice(h->device));
-  // converged mode: the first two chunks are enqueued here, ndt2d_align_finish keeps the loop fed
-  return run_align(h, d_sx, d_sy, n, init_pose, -1, h->check_every, /*wait=*/false);
+  const float* const s[2] = {d_sx, d_sy};
+  return align_dev_async(h, s, n, init_pose);
 }
 
 int32_t ndt2d_align_dev(ndt2d_handle* h, const float* d_sx, const float* d_sy, size_t n,
                         const double init_pose[3], ndt2d_result* out) {
-  if (!h || !d_sx || !d_sy || !init_pose || !out) return NDT_ERR_INVALID_ARG;
-  HIP_TRY(hipSetDevice(h->device));
-  const int32_t st = run_align(h, d_sx, d_sy, n, init_pose, -1, h->check_every);
-  if (st != NDT_OK) return st;
-  return ndt2d_align_finish(h, out);
+  const float* const s[2] = {d_sx, d_sy};
+  return align_dev(h, s, n, init_pose, out);
 }
 
 int32_t ndt2d_align(ndt2d_handle* h, const float* sx, const float* sy, size_t n, const double init_pose[3],
                     ndt2d_result* out) {
-  if (!h || !sx || !sy || !init_pose || !out || n == 0) return NDT_ERR_INVALID_ARG;
-  if (!h->has_target) return NDT_ERR_NO_TARGET;
-  HIP_TRY(hipSetDevice(h->device));
-  { const int32_t ss = stage_source(h, sx, sy, n); if (ss != NDT_OK) return ss; }
-  const int32_t rs = run_align(h, h->d_sx, h->d_sy, n, init_pose, -1, h->check_every, /*wait=*/true, /*own_source=*/true);
-  if (rs != NDT_OK) return rs;
-  return ndt2d_align_finish(h, out);
+  const float* const s[2] = {sx, sy};
+  return align_host(h, s, n, init_pose, out);
 }
 
 }  // extern "C"
@@ -1409,7 +1225,7 @@ int32_t multi_align(ndt2d_handle* h, const float* const* sxs, const float* const
   if (!h->has_target) return NDT_ERR_NO_TARGET;
   TraceRange range(shared ? "ndt2d_align_multi_start" : "ndt2d_align_multi_scan");
   HIP_TRY(hipSetDevice(h->device));
-  { const int32_t fs = finish_chunk_run(h); if (fs != NDT_OK) return fs; }
+  { const int32_t fs = finish(h); if (fs != NDT_OK) return fs; }
   if (h->n_valid < 1) {
     for (int32_t k = 0; k < m; ++k) state_to(no_cell_state<IterState>(&init_poses[3 * k]), &results[k]);
     return NDT_OK;
@@ -1433,7 +1249,7 @@ int32_t multi_align(ndt2d_handle* h, const float* const* sxs, const float* const
   // then everybody evaluates): the 256-fold redundant prologues of the fused kernel cost more than the
   // second kernel boundary there.
   const void* func = multi_kernel(h->prm, wide, shared, split, nh);
-  next_seq(&h->call_seq, h->h_flag);
+  next_seq(&h->flight.call_seq, h->h_flag);
   StartPoses sp{};
   StartScans sc{};
   for (int k = 0; k < m; ++k) {
@@ -1443,7 +1259,7 @@ int32_t multi_align(ndt2d_handle* h, const float* const* sxs, const float* const
   // AlignCall.n doubles as the "armed" word of the chain: the scan size when shared, any non-zero value otherwise
   hipLaunchKernelGGL(k_begin_multi, dim3(1), dim3(64), 0, h->stream, h->d_call, h->d_dyn_multi, sxs[0], sys[0], (int)n_max, sp, sc,
                      (int)m, fixed, converged_mode ? h->h_state_multi : (IterState*)nullptr,
-                     converged_mode ? h->h_flag : (int*)nullptr, h->call_seq);
+                     converged_mode ? h->h_flag : (int*)nullptr, h->flight.call_seq);
   HIP_TRY(hipGetLastError());
   const int launches = converged_mode ? h->check_every + (h->check_every & 1) : K + 1;
   hipGraphExec_t exec = nullptr;
@@ -1461,7 +1277,7 @@ int32_t multi_align(ndt2d_handle* h, const float* const* sxs, const float* const
                            (void*)h->d_dyn_multi, launches, (key & ~(0xff << 8)) | (mg << 8) | (mg << 20), h->stream, &exec));
   }
   bool seen = true;
-  HIP_TRY(run_multi_chain(exec, h->stream, converged_mode ? h->h_flag : nullptr, launches, K + 1, h->call_seq, h->h_state_multi,
+  HIP_TRY(run_multi_chain(exec, h->stream, converged_mode ? h->h_flag : nullptr, launches, K + 1, h->flight.call_seq, h->h_state_multi,
                           h->d_dyn_multi->state[K & 1], kMaxStarts * sizeof(IterState), &seen));
   if (!seen) { set_error("the multi-start loop did not report its end"); return NDT_ERR_HIP; }
   for (int k = 0; k < m; ++k) state_to(h->h_state_multi[k], &results[k]);

@@ -156,8 +156,9 @@ int32_t ndt2d_search(ndt2d_handle* h, const float* sx, const float* sy, size_t n
   { SearchWindow v; SearchLattice L; st = search_lattice_of<ndt2d_handle>(w, &v, &L); if (st != NDT_OK) return st; }
   if (!h->has_target) return NDT_ERR_NO_TARGET;
   HIP_TRY(hipSetDevice(h->device));
-  { const int32_t ss = stage_source(h, sx, sy, n); if (ss != NDT_OK) return ss; }
-  return ndt2d_search_dev(h, h->d_sx, h->d_sy, n, w, k, hits, n_hits);
+  const float* const s[2] = {sx, sy};
+  { const int32_t ss = stage_source(h, s, n); if (ss != NDT_OK) return ss; }
+  return ndt2d_search_dev(h, h->d_s[0], h->d_s[1], n, w, k, hits, n_hits);
 }
 
 int32_t ndt2d_search_scores_dev(ndt2d_handle* h, const float* d_sx, const float* d_sy, size_t n,

@@ -41,13 +41,14 @@ struct ndt3d_handle {
   ndt::IterState3* h_state = nullptr;
   unsigned long long* d_outside = nullptr;   // [1] points of the last build / update outside the extent
   int* h_flag = nullptr;              // pinned: raised by the launch that ends a converged-mode loop
-  int call_seq = 0;                   // alignments enqueued so far
   ndt::ChainGraphCache graphs;
-  hipGraphExec_t graph_exec = nullptr;   // selected by ensure_graph3, owned by `graphs`
-  // an alignment in flight (ndt3d_align_dev_async ... ndt3d_align_finish): 0 none, 1 fixed-K chain with
-  // the state copy enqueued behind it, 2 converged-mode chunk loop
-  int in_flight = 0;
-  ndt::ChunkRun chunk_run;
+  ndt::ChainFlight flight;            // what the last single-pair alignment left in flight (ndt_chain_host.hpp)
+  // To the shared chain code this is a handle with one lane that cannot be raised (ndt3d_set_tuning refuses the lane
+  // knobs, no secondary stream exists), always on graphs, with chunks of 8 launches.
+  ndt::LaneState lanes{1};
+  static constexpr bool use_graph = true;
+  static constexpr int check_every = 8;
+  ndt::AlignDyn3* dyn_of(int) const { return d_dyn; }
   ndt::AlignDynMulti3* d_dyn_multi = nullptr;   // multi-scan / multi-start chains (ndt3d_multi.hpp), on first use
   ndt::IterState3* h_state_multi = nullptr;     // pinned [kMaxStarts3]
   ndt::SearchScratch srch;                      // exhaustive pose search scratch (ndt_search.hpp), allocated on first use
@@ -68,6 +69,8 @@ struct ndt3d_handle {
 };
 
 namespace {
+
+template <> struct HandleTraits<ndt3d_handle>;   // (below; the shared chain code is used before it)
 
 // everything that changes the voxel grid's sums or geometry drops what map-to-map alignment derived from them
 void grid_changed3(ndt3d_handle* h) { h->cov_valid = false; h->comp_valid = false; }
@@ -361,7 +364,7 @@ auto with_mode3(const ndt3d_handle* h, F&& f) {
 // the neighbourhoods must never replay the other one's graph.
 int graph_mode3(const ndt3d_handle* h) { return (h->neighbourhood == 7 ? 0x10 : 0) | h->prm.hessian_mode; }
 
-// the k_iterate3 of the handle's Hessian and neighbourhood, for graphs (ensure_graph3) and plain launches (ndt3d_align_trace)
+// the k_iterate3 of the handle's Hessian and neighbourhood, for graphs and plain launches (scan_chain)
 const void* iter3_kernel(const ndt3d_handle* h) {
   return with_mode3(h, [](auto M, auto NB) { return (const void*)&ndt::k_iterate3<M, NB>; });
 }
@@ -379,87 +382,50 @@ int32_t single_voxel_only(const ndt3d_handle* h, const char* who = nullptr) {
   return NDT_ERR_INVALID_ARG;
 }
 
-// first_parity 1: the graph follows a k_iterate3_first and starts at launch 1 (the cache keeps the two kinds apart)
-int32_t ensure_graph3(ndt3d_handle* h, int launches, int first_parity) {
-  using namespace ndt;
-  HIP_TRY(h->graphs.get(iter3_kernel(h), dim3(kMaxBlocks), dim3(kBlock),
-                        (void*)h->d_static, (void*)h->d_call, (void*)h->d_dyn, launches, graph_mode3(h), h->stream,
-                        &h->graph_exec, 0, first_parity));
-  return NDT_OK;
+// the k_iterate3 chain of a scan: one launch shape for every size, the handle's one lane
+ChainLaunch scan_chain(const ndt3d_handle* h, size_t, int) {
+  return {iter3_kernel(h), dim3(ndt::kMaxBlocks), dim3(ndt::kBlock), h->d_static, h->d_call, h->d_dyn};
 }
 
-// waits for the alignment in flight, if any; the final state is in h->h_state afterwards
-int32_t finish_align3(ndt3d_handle* h) {
-  using namespace ndt;
-  const int kind = h->in_flight;
-  h->in_flight = 0;
-  if (kind == 1) {
-    HIP_TRY(hipStreamSynchronize(h->stream));
-  } else if (kind == 2) {
-    bool seen = false;
-    HIP_TRY(chunk_run_finish(h->chunk_run, h->stream, h->h_flag, &seen));
-    HIP_TRY(hipGetLastError());
-    if (!seen) { ndt::set_error("the Gauss-Newton loop did not report its end"); return NDT_ERR_HIP; }
-  }
-  return NDT_OK;
+// the first launch of the old protocol: launches 0 .. K follow
+void launch_begin(ndt3d_handle* h, int, hipStream_t stream, const float* const* d_s, size_t n, const double* pose, int fixed,
+                  ndt::IterState3* host_state, int* host_flag) {
+  hipLaunchKernelGGL(ndt::k_begin3, dim3(1), dim3(64), 0, stream, h->d_call, h->d_dyn, d_s[0], d_s[1], d_s[2], (int)n, pose[0],
+                     pose[1], pose[2], pose[3], pose[4], pose[5], fixed, host_state, host_flag, h->flight.call_seq);
 }
 
-// enqueues the loop; finish_align3 leaves the final state in h->h_state
-int32_t begin_align3(ndt3d_handle* h, const float* dx, const float* dy, const float* dz, size_t n, const double* pose,
-                     int fixed_override) {
+// Enqueue the Gauss-Newton loop of ndt3d_evaluate* (fixed_override = 1) and ndt3d_align* (-1): the head of the chain
+// (the 2D head's arguments; a 3D call has no lane to choose and always drains); everything behind launch 0 is
+// run_chain_tail's.
+int32_t begin_align(ndt3d_handle* h, const float* const* d_s, size_t n, const double* pose, int fixed_override, bool, bool) {
   using namespace ndt;
   TraceRange range("ndt3d_align: Gauss-Newton loop");
   if (!h->has_target) return NDT_ERR_NO_TARGET;
-  // a converged-mode loop needs the host to keep it fed: finish it.  A fixed-K chain in flight is
-  // simply followed on the stream (the caller gave up its result by not fetching it).
-  if (h->in_flight == 2) { const int32_t fs = finish_align3(h); if (fs != NDT_OK) return fs; }
+  { const int32_t fs = finish_host_fed(h); if (fs != NDT_OK) return fs; }     // an unfinished asynchronous call
   if (n == 0 || n > kMaxSourcePoints) return NDT_ERR_INVALID_ARG;
   if (h->n_valid < 1) {
+    h->flight.how = ChainFlight::kOnHost;
     *h->h_state = no_cell_state<IterState3>(pose);
     return NDT_OK;
   }
-  const int fixed = fixed_override >= 0 ? fixed_override : h->prm.fixed_iterations;
-  next_seq(&h->call_seq, h->h_flag);
+  const ChainPlan p = chain_plan(fixed_override, h->prm.fixed_iterations, h->prm.max_iterations, h->use_graph, h->check_every,
+                                 h->fused_begin);
+  next_seq(&h->flight.call_seq, h->h_flag);
   // Launch 0.  Fused (the default): k_iterate3_first evaluates at the initial pose and writes the per-call context from
   // its arguments; launches 1 .. K follow.  Old protocol: k_begin3, then launches 0 .. K.
-  const int first = h->fused_begin ? 1 : 0;
-  IterState3* const host_state = fixed > 0 ? (IterState3*)nullptr : h->h_state;
-  int* const host_flag = fixed > 0 ? (int*)nullptr : h->h_flag;
-  if (first) {
+  IterState3* const host_state = p.chunked ? h->h_state : (IterState3*)nullptr;
+  int* const host_flag = p.chunked ? h->h_flag : (int*)nullptr;
+  if (p.first) {
     with_mode3(h, [&](auto M, auto NB) {
       hipLaunchKernelGGL((k_iterate3_first<M, NB>), dim3(kMaxBlocks), dim3(kBlock), 0, h->stream, (const AlignStatic3*)h->d_static,
-                         h->d_call, h->d_dyn, dx, dy, dz, (int)n, pose[0], pose[1], pose[2], pose[3], pose[4], pose[5], fixed,
-                         host_state, host_flag, h->call_seq);
+                         h->d_call, h->d_dyn, d_s[0], d_s[1], d_s[2], (int)n, pose[0], pose[1], pose[2], pose[3], pose[4], pose[5],
+                         p.fixed, host_state, host_flag, h->flight.call_seq);
       return 0;
     });
   } else {
-    hipLaunchKernelGGL(k_begin3, dim3(1), dim3(64), 0, h->stream, h->d_call, h->d_dyn, dx, dy, dz, (int)n, pose[0], pose[1],
-                       pose[2], pose[3], pose[4], pose[5], fixed, host_state, host_flag, h->call_seq);
+    launch_begin(h, 0, h->stream, d_s, n, pose, p.fixed, host_state, host_flag);
   }
-  const int K = fixed > 0 ? fixed : h->prm.max_iterations;
-  if (fixed > 0) {
-    const int32_t gs = ensure_graph3(h, K + 1 - first, first);
-    if (gs != NDT_OK) return gs;
-    HIP_TRY(hipGraphLaunch(h->graph_exec, h->stream));
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(hipMemcpyAsync(h->h_state, &h->d_dyn->state[K & 1], sizeof(IterState3), hipMemcpyDeviceToHost, h->stream));
-    h->in_flight = 1;
-  } else {
-    const int chunk = 8;
-    const int32_t gs = ensure_graph3(h, chunk, first);
-    if (gs != NDT_OK) return gs;
-    h->chunk_run.drain = true;
-    h->chunk_run.seq = h->call_seq;
-    HIP_TRY(chunk_run_begin(h->chunk_run, h->graph_exec, h->stream, chunk, K + 1, first));
-    h->in_flight = 2;
-  }
-  return NDT_OK;
-}
-
-int32_t run_align3(ndt3d_handle* h, const float* dx, const float* dy, const float* dz, size_t n, const double* pose,
-                   int fixed_override) {
-  const int32_t st = begin_align3(h, dx, dy, dz, n, pose, fixed_override);
-  return st != NDT_OK ? st : finish_align3(h);
+  return run_chain_tail(h, scan_chain(h, n, 0), graph_mode3(h), 0, h->stream, nullptr, p, /*drain=*/true);
 }
 
 void unpack_h21(const double* s, double* H) {
@@ -492,14 +458,21 @@ template <> struct HandleTraits<ndt3d_handle> {
   using Hit = ndt3d_search_hit;
   using Poses = ndt::StartPoses3;
   using Maps = ndt::StartMaps3;
-  static constexpr int kPose = 6, kMaxStarts = ndt::kMaxStarts3;
+  static constexpr int kDim = 3, kPose = 6, kMaxStarts = ndt::kMaxStarts3;
   static constexpr int kRecord = 3;                        // float4 per covariance record and per component
+  // The copy of a fixed chain's state is enqueued directly behind the chain, so that fetch_state is a stream synchronise
+  // ("the whole chain and the fetch of its final state are enqueued", include/ndt_hip.h); 2D copies at fetch_state.
+  static constexpr bool kQueuedFetch = true;
   static constexpr const char* kCell = "voxel";
   static constexpr const char* kTraceComponents = "ndt3d: component list";
+  static constexpr const char* kTraceAlignTrace = "ndt3d_align_trace";
+  static constexpr const char* kTraceMapPair = "ndt3d_align_map: Gauss-Newton loop";
   static constexpr const char* kTraceMapMulti = "ndt3d_align_map_multi";
   static constexpr const char* kMapMultiNoEnd = "the 3D map-to-map multi-start loop did not report its end";
   static size_t cells(const ndt3d_handle* h) { return (size_t)h->grid.W * h->grid.H * h->grid.D; }
-  static int32_t finish(ndt3d_handle* h) { return finish_align3(h); }
+  template <class... A> static int32_t begin(A... a) { return begin_align(a...); }
+  template <class... A> static ChainLaunch scan_chain(A... a) { return ::scan_chain(a...); }
+  template <class... A> static void launch_begin(A... a) { ::launch_begin(a...); }
   template <class Out> static void to(const ndt::IterState3& s, Out* out) { state3_to(s, out); }
   static void launch_cov_records(ndt3d_handle* h, unsigned nb) {
     hipLaunchKernelGGL(ndt::k_cov_records3, dim3(nb), dim3(ndt::kBlock), 0, h->stream, h->grid, h->prm.min_points,
@@ -537,24 +510,6 @@ template <> struct HandleTraits<ndt3d_handle> {
   }
 };
 
-// a host scan into the handle's staging arrays, behind the alignment in flight
-int32_t stage_source3(ndt3d_handle* h, const float* sx, const float* sy, const float* sz, size_t n) {
-  { const int32_t fs = finish_align3(h); if (fs != NDT_OK) return fs; }
-  HIP_TRY(grow({grow_buf(&h->d_s[0]), grow_buf(&h->d_s[1]), grow_buf(&h->d_s[2])}, &h->scap, n, n + n / 4 + 1024));
-  const float* src[3] = {sx, sy, sz};
-  for (int a = 0; a < 3; ++a) HIP_TRY(hipMemcpyAsync(h->d_s[a], src[a], n * sizeof(float), hipMemcpyHostToDevice, h->stream));
-  return NDT_OK;
-}
-
-// the same for a host target cloud
-int32_t stage_target3(ndt3d_handle* h, const float* x, const float* y, const float* z, size_t n) {
-  { const int32_t fs = finish_align3(h); if (fs != NDT_OK) return fs; }
-  HIP_TRY(grow({grow_buf(&h->d_t[0]), grow_buf(&h->d_t[1]), grow_buf(&h->d_t[2])}, &h->tcap, n, n + n / 4 + 1024));
-  const float* src[3] = {x, y, z};
-  for (int a = 0; a < 3; ++a) HIP_TRY(hipMemcpyAsync(h->d_t[a], src[a], n * sizeof(float), hipMemcpyHostToDevice, h->stream));
-  return NDT_OK;
-}
-
 // m alignments against the cached voxel grid in one launch chain (ndt3d_multi.hpp)
 int32_t multi_align3(ndt3d_handle* h, const float* const* sxs, const float* const* sys, const float* const* szs, const size_t* ns,
                      bool shared, const double* init_poses, int32_t m, ndt3d_result* results) {
@@ -562,7 +517,7 @@ int32_t multi_align3(ndt3d_handle* h, const float* const* sxs, const float* cons
   if (!h->has_target) return NDT_ERR_NO_TARGET;
   TraceRange range(shared ? "ndt3d_align_multi_start" : "ndt3d_align_multi_scan");
   HIP_TRY(hipSetDevice(h->device));
-  { const int32_t fs = finish_align3(h); if (fs != NDT_OK) return fs; }
+  { const int32_t fs = finish(h); if (fs != NDT_OK) return fs; }
   if (h->n_valid < 1) {
     for (int32_t k = 0; k < m; ++k) state3_to(no_cell_state<IterState3>(&init_poses[6 * k]), &results[k]);
     return NDT_OK;
@@ -571,7 +526,7 @@ int32_t multi_align3(ndt3d_handle* h, const float* const* sxs, const float* cons
   const int fixed = h->prm.fixed_iterations;
   const int K = fixed > 0 ? fixed : h->prm.max_iterations;
   const bool converged_mode = fixed == 0;
-  next_seq(&h->call_seq, h->h_flag);
+  next_seq(&h->flight.call_seq, h->h_flag);
   StartPoses3 sp{};
   StartScans3 sc{};
   for (int k = 0; k < m; ++k) {
@@ -582,10 +537,9 @@ int32_t multi_align3(ndt3d_handle* h, const float* const* sxs, const float* cons
   hipLaunchKernelGGL(k_begin_multi3_scans, dim3(1), dim3(64), 0, h->stream, h->d_dyn_multi, sc, (int)m);
   hipLaunchKernelGGL(k_begin_multi3, dim3(1), dim3(64), 0, h->stream, h->d_call, h->d_dyn_multi, sp, (int)m, fixed,
                      converged_mode ? h->h_state_multi : (IterState3*)nullptr, converged_mode ? h->h_flag : (int*)nullptr,
-                     h->call_seq);
+                     h->flight.call_seq);
   HIP_TRY(hipGetLastError());
-  const int chunk = 8;
-  const int steps = converged_mode ? chunk : K + 1;
+  const int steps = converged_mode ? h->check_every : K + 1;
   hipGraphExec_t exec = nullptr;
   const void *fs = nullptr, *fb = nullptr;
   with_mode3(h, [&](auto M, auto NB) { fs = (const void*)&k_multi_solve3<M>; fb = (const void*)&k_multi_body3<M, NB>; return 0; });
@@ -596,7 +550,7 @@ int32_t multi_align3(ndt3d_handle* h, const float* const* sxs, const float* cons
   HIP_TRY(h->graphs.get2(fs, dim3(mg), dim3(kBlock), fb, dim3(kMaxBlocks, mg), dim3(kBlock), (void*)h->d_static, (void*)h->d_call,
                          (void*)h->d_dyn_multi, steps, 0x100000 | (mg << 8) | graph_mode3(h), h->stream, &exec));
   bool seen = true;
-  HIP_TRY(run_multi_chain(exec, h->stream, converged_mode ? h->h_flag : nullptr, steps, K + 1, h->call_seq, h->h_state_multi,
+  HIP_TRY(run_multi_chain(exec, h->stream, converged_mode ? h->h_flag : nullptr, steps, K + 1, h->flight.call_seq, h->h_state_multi,
                           h->d_dyn_multi->state[K & 1], kMaxStarts3 * sizeof(IterState3), &seen));
   if (!seen) { set_error("the 3D multi-scan loop did not report its end"); return NDT_ERR_HIP; }
   for (int k = 0; k < m; ++k) state3_to(h->h_state_multi[k], &results[k]);
@@ -651,7 +605,7 @@ int32_t ndt3d_create(const ndt3d_params* p, int32_t device_id, ndt3d_handle** ou
 int32_t ndt3d_destroy(ndt3d_handle* h) {
   if (!h) return NDT_OK;
   (void)hipSetDevice(h->device);
-  (void)finish_align3(h);
+  (void)finish(h);
   if (h->stream) (void)hipStreamSynchronize(h->stream);
   h->graphs.clear();
   void* dev[] = {h->d_parts3, h->d_bounds, h->d_counters, h->d_outside, h->d_static, h->d_call, h->d_dyn, h->d_t[0], h->d_t[1], h->d_t[2],
@@ -689,9 +643,9 @@ int32_t ndt3d_set_neighbourhood(ndt3d_handle* h, int32_t n) {
     return NDT_ERR_INVALID_ARG;
   }
   // an alignment in flight keeps the kernels it was enqueued with and is finished first, as the searches do
-  if (h->in_flight) {
+  if (h->flight.waits()) {
     HIP_TRY(hipSetDevice(h->device));
-    const int32_t fs = finish_align3(h);
+    const int32_t fs = finish(h);
     if (fs != NDT_OK) return fs;
   }
   h->neighbourhood = n;
@@ -711,7 +665,8 @@ int32_t ndt3d_add_target_points(ndt3d_handle* h, const float* x, const float* y,
   if (!h || !x || !y || !z || n == 0) return NDT_ERR_INVALID_ARG;
   if (!h->has_target) return NDT_ERR_NO_TARGET;
   HIP_TRY(hipSetDevice(h->device));
-  { const int32_t ss = stage_target3(h, x, y, z, n); if (ss != NDT_OK) return ss; }
+  const float* const t[3] = {x, y, z};
+  { const int32_t ss = stage_target(h, t, n); if (ss != NDT_OK) return ss; }
   return ndt3d_add_target_points_dev(h, h->d_t[0], h->d_t[1], h->d_t[2], n, nullptr, n_outside, nullptr);
 }
 
@@ -748,7 +703,7 @@ int32_t ndt3d_reserve_target(ndt3d_handle* h, const double lo[3], const double h
     l[a] = (float)lo[a]; u[a] = (float)hi[a];
   }
   HIP_TRY(hipSetDevice(h->device));
-  { const int32_t fs = finish_align3(h); if (fs != NDT_OK) return fs; }
+  { const int32_t fs = finish(h); if (fs != NDT_OK) return fs; }
   h->has_target = false;
   grid_changed3(h);
   { const int32_t gs = setup_geometry3(h, l, u); if (gs != NDT_OK) return gs; }
@@ -768,7 +723,7 @@ static int32_t update_target_points3_dev(ndt3d_handle* h, const float* d_x, cons
   // (a wrapped count is told from a full voxel by its size: removed_cell_broken, ndt2d_kernels.hpp)
   if (sign < 0 && n >= 0xFFF00000ull) { set_error("more points to remove than a call can take (2^32 - 2^20)"); return NDT_ERR_INVALID_ARG; }
   HIP_TRY(hipSetDevice(h->device));
-  { const int32_t fs = finish_align3(h); if (fs != NDT_OK) return fs; }
+  { const int32_t fs = finish(h); if (fs != NDT_OK) return fs; }
   if (stream) HIP_TRY(ndt::order_after(h->stream, (hipStream_t)stream));
   const float* p[3] = {d_x, d_y, d_z};
   ndt::Rigid3F T;
@@ -801,14 +756,15 @@ int32_t ndt3d_remove_target_points(ndt3d_handle* h, const float* x, const float*
   if (!h || !x || !y || !z || n == 0) return NDT_ERR_INVALID_ARG;
   if (!h->has_target) return NDT_ERR_NO_TARGET;
   HIP_TRY(hipSetDevice(h->device));
-  { const int32_t ss = stage_target3(h, x, y, z, n); if (ss != NDT_OK) return ss; }
+  const float* const t[3] = {x, y, z};
+  { const int32_t ss = stage_target(h, t, n); if (ss != NDT_OK) return ss; }
   return ndt3d_remove_target_points_dev(h, h->d_t[0], h->d_t[1], h->d_t[2], n, nullptr, n_outside, nullptr);
 }
 
 int32_t ndt3d_set_target_dev(ndt3d_handle* h, const float* d_x, const float* d_y, const float* d_z, size_t n, void* stream) {
   if (!h || !d_x || !d_y || !d_z || n == 0) return NDT_ERR_INVALID_ARG;
   HIP_TRY(hipSetDevice(h->device));
-  { const int32_t fs = finish_align3(h); if (fs != NDT_OK) return fs; }
+  { const int32_t fs = finish(h); if (fs != NDT_OK) return fs; }
   if (stream) HIP_TRY(hipStreamSynchronize((hipStream_t)stream));   // producer of the device arrays
   return set_target3_impl(h, d_x, d_y, d_z, n);
 }
@@ -816,7 +772,8 @@ int32_t ndt3d_set_target_dev(ndt3d_handle* h, const float* d_x, const float* d_y
 int32_t ndt3d_set_target(ndt3d_handle* h, const float* x, const float* y, const float* z, size_t n) {
   if (!h || !x || !y || !z || n == 0) return NDT_ERR_INVALID_ARG;
   HIP_TRY(hipSetDevice(h->device));
-  { const int32_t ss = stage_target3(h, x, y, z, n); if (ss != NDT_OK) return ss; }
+  const float* const t[3] = {x, y, z};
+  { const int32_t ss = stage_target(h, t, n); if (ss != NDT_OK) return ss; }
   return ndt3d_set_target_dev(h, h->d_t[0], h->d_t[1], h->d_t[2], n, nullptr);
 }
 
@@ -857,74 +814,28 @@ int32_t ndt3d_get_grid(ndt3d_handle* h, int32_t* count, float* mean_xyz, float* 
 
 int32_t ndt3d_evaluate(ndt3d_handle* h, const float* sx, const float* sy, const float* sz, size_t n,
                        const double pose[6], ndt3d_eval* out) {
-  if (!h || !sx || !sy || !sz || !pose || !out || n == 0) return NDT_ERR_INVALID_ARG;
-  if (!h->has_target) return NDT_ERR_NO_TARGET;
-  HIP_TRY(hipSetDevice(h->device));
-  { const int32_t ss = stage_source3(h, sx, sy, sz, n); if (ss != NDT_OK) return ss; }
-  return ndt3d_evaluate_dev(h, h->d_s[0], h->d_s[1], h->d_s[2], n, pose, out);
+  const float* const s[3] = {sx, sy, sz};
+  return evaluate_host(h, s, n, pose, out);
 }
 
 int32_t ndt3d_evaluate_dev(ndt3d_handle* h, const float* d_sx, const float* d_sy, const float* d_sz, size_t n,
                            const double pose[6], ndt3d_eval* out) {
-  if (!h || !d_sx || !d_sy || !d_sz || !pose || !out || n == 0) return NDT_ERR_INVALID_ARG;
-  if (!h->has_target) return NDT_ERR_NO_TARGET;
-  HIP_TRY(hipSetDevice(h->device));
-  const int32_t st = run_align3(h, d_sx, d_sy, d_sz, n, pose, 1);
-  if (st != NDT_OK) return st;
-  state3_to(*h->h_state, out);
-  return NDT_OK;
+  const float* const s[3] = {d_sx, d_sy, d_sz};
+  return evaluate_dev(h, s, n, pose, out);
 }
 
 int32_t ndt3d_align_dev_async(ndt3d_handle* h, const float* d_sx, const float* d_sy, const float* d_sz, size_t n,
                               const double init_pose[6]) {
-  if (!h || !d_sx || !d_sy || !d_sz || !init_pose) return NDT_ERR_INVALID_ARG;
-  HIP_TRY(hipSetDevice(h->device));
-  return begin_align3(h, d_sx, d_sy, d_sz, n, init_pose, -1);
+  const float* const s[3] = {d_sx, d_sy, d_sz};
+  return align_dev_async(h, s, n, init_pose);
 }
 
-int32_t ndt3d_align_finish(ndt3d_handle* h, ndt3d_result* out) {
-  if (!h || !out) return NDT_ERR_INVALID_ARG;
-  HIP_TRY(hipSetDevice(h->device));
-  const int32_t st = finish_align3(h);
-  if (st != NDT_OK) return st;
-  state3_to(*h->h_state, out);
-  return NDT_OK;
-}
+int32_t ndt3d_align_finish(ndt3d_handle* h, ndt3d_result* out) { return align_finish(h, out); }
 
-// Per-iteration trace, as ndt2d_align_trace: one plain k_iterate3 launch and one state fetch per iteration.
 int32_t ndt3d_align_trace(ndt3d_handle* h, const float* sx, const float* sy, const float* sz, size_t n,
                           const double init_pose[6], ndt3d_result* rows, int32_t capacity, int32_t* n_rows, ndt3d_result* out) {
-  using namespace ndt;
-  if (!h || !sx || !sy || !sz || !init_pose || !rows || capacity < 1 || !n_rows || n == 0 || n > kMaxSourcePoints)
-    return NDT_ERR_INVALID_ARG;
-  *n_rows = 0;
-  if (!h->has_target) return NDT_ERR_NO_TARGET;
-  TraceRange range("ndt3d_align_trace");
-  HIP_TRY(hipSetDevice(h->device));
-  if (h->n_valid < 1) {
-    state3_to(no_cell_state<IterState3>(init_pose), &rows[0]);
-    if (out) *out = rows[0];
-    return NDT_OK;
-  }
-  { const int32_t us = stage_source3(h, sx, sy, sz, n); if (us != NDT_OK) return us; }
-  const int fixed = h->prm.fixed_iterations;
-  const int K = fixed > 0 ? fixed : h->prm.max_iterations;
-  next_seq(&h->call_seq);
-  hipLaunchKernelGGL(k_begin3, dim3(1), dim3(64), 0, h->stream, h->d_call, h->d_dyn, h->d_s[0], h->d_s[1], h->d_s[2], (int)n,
-                     init_pose[0], init_pose[1], init_pose[2], init_pose[3], init_pose[4], init_pose[5], fixed,
-                     (IterState3*)nullptr, (int*)nullptr, h->call_seq);
-  const void* iterate = iter3_kernel(h);
-  for (int k = 0; k <= K; ++k) {
-    (void)launch_chain_kernel(iterate, dim3(kMaxBlocks), dim3(kBlock), h->d_static, h->d_call, h->d_dyn, k & 1, h->stream);
-    HIP_TRY(hipGetLastError());
-    if (k == 0) continue;                                  // launch 0 only evaluates
-    HIP_TRY(hipMemcpyAsync(h->h_state, &h->d_dyn->state[k & 1], sizeof(IterState3), hipMemcpyDeviceToHost, h->stream));
-    HIP_TRY(hipStreamSynchronize(h->stream));
-    if (*n_rows < capacity) state3_to(*h->h_state, &rows[(*n_rows)++]);
-    if (h->h_state->done) break;
-  }
-  if (out) state3_to(*h->h_state, out);
-  return NDT_OK;
+  const float* const s[3] = {sx, sy, sz};
+  return align_trace(h, s, n, init_pose, rows, capacity, n_rows, out);
 }
 
 int32_t ndt3d_align_multi_scan_dev(ndt3d_handle* h, const float* const* d_sx, const float* const* d_sy, const float* const* d_sz,
@@ -946,20 +857,14 @@ void* ndt3d_stream(ndt3d_handle* h) { return h ? (void*)h->stream : nullptr; }
 
 int32_t ndt3d_align_dev(ndt3d_handle* h, const float* d_sx, const float* d_sy, const float* d_sz, size_t n,
                         const double init_pose[6], ndt3d_result* out) {
-  if (!h || !d_sx || !d_sy || !d_sz || !init_pose || !out) return NDT_ERR_INVALID_ARG;
-  const int32_t st = ndt3d_align_dev_async(h, d_sx, d_sy, d_sz, n, init_pose);
-  if (st != NDT_OK) return st;
-  return ndt3d_align_finish(h, out);
+  const float* const s[3] = {d_sx, d_sy, d_sz};
+  return align_dev(h, s, n, init_pose, out);
 }
 
 int32_t ndt3d_align(ndt3d_handle* h, const float* sx, const float* sy, const float* sz, size_t n,
                     const double init_pose[6], ndt3d_result* out) {
-  if (!h || !sx || !sy || !sz || !init_pose || !out || n == 0) return NDT_ERR_INVALID_ARG;
-  if (!h->has_target) return NDT_ERR_NO_TARGET;
-  HIP_TRY(hipSetDevice(h->device));
-  const int32_t st = stage_source3(h, sx, sy, sz, n);
-  if (st != NDT_OK) return st;
-  return ndt3d_align_dev(h, h->d_s[0], h->d_s[1], h->d_s[2], n, init_pose, out);
+  const float* const s[3] = {sx, sy, sz};
+  return align_host(h, s, n, init_pose, out);
 }
 
 }  // extern "C"

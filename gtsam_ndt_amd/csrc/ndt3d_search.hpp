@@ -173,7 +173,8 @@ int32_t ndt3d_search(ndt3d_handle* h, const float* sx, const float* sy, const fl
   { SearchWindow v; SearchLattice L; st = search_lattice_of<ndt3d_handle>(w, &v, &L); if (st != NDT_OK) return st; }
   if (!h->has_target) return NDT_ERR_NO_TARGET;
   HIP_TRY(hipSetDevice(h->device));
-  { const int32_t ss = stage_source3(h, sx, sy, sz, n); if (ss != NDT_OK) return ss; }
+  const float* const s[3] = {sx, sy, sz};
+  { const int32_t ss = stage_source(h, s, n); if (ss != NDT_OK) return ss; }
   return ndt3d_search_dev(h, h->d_s[0], h->d_s[1], h->d_s[2], n, w, k, hits, n_hits);
 }
 

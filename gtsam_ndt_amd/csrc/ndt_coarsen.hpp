@@ -181,8 +181,8 @@ int32_t ndt2d_coarsen_map(ndt2d_handle* src, ndt2d_handle* dst) {
   int f = 0;
   { const int32_t cs = check_coarsen_args(src, dst, &f); if (cs != NDT_OK) return cs; }
   HIP_TRY(hipSetDevice(dst->device));
-  { const int32_t fs = finish_chunk_run(src); if (fs != NDT_OK) return fs; }
-  { const int32_t fs = finish_chunk_run(dst); if (fs != NDT_OK) return fs; }
+  { const int32_t fs = finish(src); if (fs != NDT_OK) return fs; }
+  { const int32_t fs = finish(dst); if (fs != NDT_OK) return fs; }
   dst->has_target = false;
   grid_changed(dst);
   const GridDev& s = src->grid;
@@ -221,8 +221,8 @@ int32_t ndt3d_coarsen_map(ndt3d_handle* src, ndt3d_handle* dst) {
   int f = 0;
   { const int32_t cs = check_coarsen_args(src, dst, &f); if (cs != NDT_OK) return cs; }
   HIP_TRY(hipSetDevice(dst->device));
-  { const int32_t fs = finish_align3(src); if (fs != NDT_OK) return fs; }
-  { const int32_t fs = finish_align3(dst); if (fs != NDT_OK) return fs; }
+  { const int32_t fs = finish(src); if (fs != NDT_OK) return fs; }
+  { const int32_t fs = finish(dst); if (fs != NDT_OK) return fs; }
   dst->has_target = false;
   grid_changed3(dst);
   const Grid3Dev& s = src->grid;

@@ -1,8 +1,9 @@
 // Host-side helpers shared by the C-ABI translation units: per-thread error text, the HIP_TRY
 // macro that turns a hipError_t into NDT_ERR_HIP without throwing, buffer growth and pinned
 // allocation, launch-chain graphs and their cache, the launch chains ("lanes") of asynchronous
-// alignments, and the host half of the converged-mode and build read-back protocols (flags in
-// pinned host memory).
+// alignments, the plan of a single-pair chain and the record of what it leaves in flight (their users
+// are ndt_chain_host.hpp's), and the host half of the converged-mode and build read-back protocols
+// (flags in pinned host memory).
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -33,22 +34,28 @@ inline GrowBuf grow_buf(T** p, size_t per = 1) { return {reinterpret_cast<void**
 // each is freed and allocated again with `want` elements (the caller's slack rule; want >= need): the contents are lost.
 // On failure *cap is 0 and the buffers not allocated yet are null, so the next call tries again.
 // *grew (optional): the group was reallocated.  pinned: host memory (hipHostMalloc) instead of device memory.
-inline hipError_t grow(std::initializer_list<GrowBuf> bufs, size_t* cap, size_t need, size_t want, bool* grew = nullptr,
+inline hipError_t grow(const GrowBuf* bufs, size_t nbufs, size_t* cap, size_t need, size_t want, bool* grew = nullptr,
                        bool pinned = false) {
   if (grew) *grew = false;
   if (need <= *cap) return hipSuccess;
   *cap = 0;
-  for (const GrowBuf& b : bufs) {
+  for (size_t k = 0; k < nbufs; ++k) {
+    const GrowBuf& b = bufs[k];
     if (*b.p) (void)(pinned ? hipHostFree(*b.p) : hipFree(*b.p));
     *b.p = nullptr;
   }
-  for (const GrowBuf& b : bufs) {
+  for (size_t k = 0; k < nbufs; ++k) {
+    const GrowBuf& b = bufs[k];
     const hipError_t e = pinned ? hipHostMalloc(b.p, want * b.unit, hipHostMallocDefault) : hipMalloc(b.p, want * b.unit);
     if (e != hipSuccess) return e;
   }
   *cap = want;
   if (grew) *grew = true;
   return hipSuccess;
+}
+inline hipError_t grow(std::initializer_list<GrowBuf> bufs, size_t* cap, size_t need, size_t want, bool* grew = nullptr,
+                       bool pinned = false) {
+  return grow(bufs.begin(), bufs.size(), cap, need, want, grew, pinned);
 }
 template <class T>
 inline hipError_t grow(T** p, size_t* cap, size_t need, size_t want, bool* grew = nullptr) {
@@ -313,6 +320,38 @@ inline LanePlan lane_step(LaneState& s, LaneEvent ev) {
   return p;
 }
 
+// ---- the plan of one alignment's launch chain -------------------------------------------------------------------------
+// The numbers every single-pair chain takes (scan or map-to-map, 2D or 3D; the device half is ndt_chain.hpp): launches
+// 0 .. K evaluate, launch k >= 1 solves first.  Launch 0 either stands in front of the graph (`first` = 1: a
+// k_iterate*_first, which carries the per-call arguments) or is the graph's first launch behind a k_begin* (`first` = 0).
+struct ChainPlan {
+  int fixed = 0;         // iterations of a fixed chain, 0: converged mode
+  int K = 0;             // the last launch index: fixed, or max_iterations
+  int first = 0;         // launches enqueued in front of the graph, and so the parity of the graph's first launch
+  bool graph = true;     // one graph replay per chain or chunk; false: plain launches (NDT_TUNE_LAUNCH_GRAPHS = 0)
+  bool chunked = false;  // converged mode on graphs: chunks of launches until the finishing launch raises the host flag
+                         // (chunk_run_begin below) - the only chains whose first launch gets the host state and flag pointers
+  int chunk = 0;         // launches per chunk: even, so that replays keep alternating the parity
+  int launches = 0;      // length of the graph to fetch
+  int poll = 0;          // plain launches in converged mode: fetch the state every `poll` launches (0: never)
+};
+
+// Pure: the only place these decisions live.  fixed_override >= 0 replaces the parameters' fixed_iterations (1: an
+// evaluation); first_in_front: launch 0 is enqueued in front of the graph (map-to-map chains never: theirs is k_begin_d2d*).
+inline ChainPlan chain_plan(int fixed_override, int fixed_iterations, int max_iterations, bool use_graph, int check_every,
+                            bool first_in_front) {
+  ChainPlan p;
+  p.fixed = fixed_override >= 0 ? fixed_override : fixed_iterations;
+  p.K = p.fixed > 0 ? p.fixed : max_iterations;
+  p.first = first_in_front ? 1 : 0;
+  p.graph = use_graph;
+  p.chunked = use_graph && check_every > 0 && p.fixed == 0;
+  p.chunk = check_every + (check_every & 1);
+  p.launches = p.chunked ? p.chunk : p.K + 1 - p.first;
+  p.poll = !use_graph && p.fixed == 0 && check_every > 0 ? check_every : 0;
+  return p;
+}
+
 // The stream and events of a secondary lane (created with the handle, never inside a call that may be timed)
 struct AsyncLane {
   hipStream_t stream = nullptr;
@@ -457,6 +496,24 @@ inline hipError_t run_chunks_until_flag(hipGraphExec_t exec, hipStream_t stream,
   if (e != hipSuccess) { *seen = false; (void)hipStreamSynchronize(stream); return e; }
   return chunk_run_finish(r, stream, flag, seen);
 }
+
+// What a handle's last single-pair alignment left in flight, and so how its final state reaches h_state (2D and 3D:
+// ndt_chain_host.hpp's run_chain_tail records it, finish and fetch_state consume it).
+struct ChainFlight {
+  enum How {
+    kOnHost,    // nothing in flight: h_state holds the result (or no alignment has run)
+    kFetch,     // a chain on `lane` (run, or at least enqueued): fetch_state copies state[parity] of that lane's context
+    kQueued,    // a chain with the copy of its final state enqueued behind it: a stream synchronise brings it
+    kChunkRun,  // a converged-mode loop the host has to keep fed (chunk_run); its finishing launch writes h_state
+    kSmallRun   // a k_align_small launch: it writes h_state, then raises flag[0]
+  };
+  How how = kOnHost;
+  int lane = 0, parity = 0;
+  ChunkRun chunk_run;
+  int call_seq = 0;        // alignments enqueued so far (never 0 once one has run)
+  bool host_fed() const { return how == kChunkRun || how == kSmallRun; }
+  bool waits() const { return host_fed() || how == kQueued; }    // finish has something to wait for
+};
 
 // The buffers of a handle's multi-start chains, allocated on first use: pinned room for `starts` final states and the
 // chains' device context (zeroed on `stream`).

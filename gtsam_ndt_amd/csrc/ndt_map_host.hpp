@@ -14,10 +14,13 @@ constexpr int kMapGraphKey = 0x2000000;      // ChainGraphCache key of the k_ite
 // << 20), multi_align3's are 0x100000 | up to 64 << 8
 constexpr int kMapMultiGraphKey = 0x8000000;
 
-// Per dimension (ndt2d_d2d_api.hpp, ndt3d_d2d_api.hpp).  One alignment of s's component list against t's grid from
-// `pose`, synchronous: the final state is in *t->h_state.  fixed_override: >= 0 replaces the handle's fixed_iterations.
-int32_t align_map_pair(ndt2d_handle* t, ndt2d_handle* s, const double* pose, int fixed_override);
-int32_t align_map_pair(ndt3d_handle* t, ndt3d_handle* s, const double* pose, int fixed_override);
+// Per dimension (ndt2d_d2d_api.hpp, ndt3d_d2d_api.hpp).  The one launch of a single pair's chain that differs, its
+// first (k_begin_d2d, k_begin_d2d3): s's component list against t's covariance records from `pose`, `blocks` workgroups
+// per launch; and the kernel of the launches behind it.
+void launch_begin_map(ndt2d_handle* t, ndt2d_handle* s, int blocks, const double* pose, int fixed, IterState* host_state, int* host_flag);
+void launch_begin_map(ndt3d_handle* t, ndt3d_handle* s, int blocks, const double* pose, int fixed, IterState3* host_state, int* host_flag);
+const void* map_iter_kernel(const ndt2d_handle* t);
+const void* map_iter_kernel(const ndt3d_handle* t);
 // The chain of a multi call whose plan is made: the first launch from sp and sm, then solve and body `K` + 1 times or
 // until every start is through (fixed == 0); the final states are in t->h_state_multi on return.
 int32_t run_map_multi_chain(ndt2d_handle* t, const StartPoses& sp, const StartMaps& sm, int m, int max_blocks, int fixed, int K);
@@ -99,11 +102,10 @@ int32_t check_map_handles(const H* t, H* const* src, int n, const char* who) {
 // target's covariance records.  src[0 .. n): distinct handles, t may be among them.
 template <class H>
 int32_t prepare_map_handles(H* t, H* const* src, int n) {
-  using T = HandleTraits<H>;
   HIP_TRY(hipSetDevice(t->device));
-  { const int32_t fs = T::finish(t); if (fs != NDT_OK) return fs; }
+  { const int32_t fs = finish(t); if (fs != NDT_OK) return fs; }
   for (int j = 0; j < n; ++j)
-    if (src[j] != t) { const int32_t fs = T::finish(src[j]); if (fs != NDT_OK) return fs; }
+    if (src[j] != t) { const int32_t fs = finish(src[j]); if (fs != NDT_OK) return fs; }
   for (int j = 0; j < n; ++j) { const int32_t cs = ensure_components(src[j]); if (cs != NDT_OK) return cs; }
   return ensure_cov_records(t);
 }
@@ -126,6 +128,34 @@ int32_t prepare_map_pair(H* t, H* s, const char* who, const double* pose) {
   return order_after_sources(t, &s, 1);
 }
 
+// One alignment of s's component list against t's grid from `pose`, synchronous: the final state is in *t->h_state, and
+// nothing reads s's list any more.  fixed_override: >= 0 replaces the handle's fixed_iterations.  The loop is the launch
+// chain of ndt*_align_dev (ndt_chain_host.hpp) with the list in the place of a scan: launch 0 is the k_begin_d2d*, so the
+// graph starts at parity 0; lane 0; drained, because the list belongs to the other handle.
+template <class H>
+int32_t align_map_pair(H* t, H* s, const double* pose, int fixed_override) {
+  using T = HandleTraits<H>;
+  using State = typename T::State;
+  TraceRange range(T::kTraceMapPair);
+  { const int32_t ps = prepare_map_pair(t, s, "alignment: both", pose); if (ps != NDT_OK) return ps; }
+  if (s->n_comp < 1 || t->n_valid < 1) {
+    t->flight.how = ChainFlight::kOnHost;
+    *t->h_state = no_cell_state<State>(pose);
+    return NDT_OK;
+  }
+  if (!t->d_map_call) HIP_TRY(hipMalloc((void**)&t->d_map_call, sizeof(*t->d_map_call)));
+  const ChainPlan p = chain_plan(fixed_override, t->prm.fixed_iterations, t->prm.max_iterations, t->use_graph, t->check_every,
+                                 /*first_in_front=*/false);
+  const int blocks = capped_blocks(s->n_comp, kBlock, kMaxBlocks);
+  next_seq(&t->flight.call_seq, t->h_flag);
+  launch_begin_map(t, s, blocks, pose, p.fixed, p.chunked ? t->h_state : (State*)nullptr, p.chunked ? t->h_flag : (int*)nullptr);
+  HIP_TRY(hipGetLastError());
+  const ChainLaunch c{map_iter_kernel(t), dim3(blocks), dim3(kBlock), t->d_static, t->d_map_call, t->d_dyn};
+  { const int32_t cs = run_chain_tail(t, c, kMapGraphKey | t->prm.hessian_mode, 0, t->stream, nullptr, p, /*drain=*/true);
+    if (cs != NDT_OK) return cs; }
+  return fetch_state(t);
+}
+
 // The k_multi_solve* + k_multi_body_d2d* chain of a multi call on t's graph cache: `launches` steps per replay, K + 1
 // in all or, with converged = true, until the chain raises t's flag; the final states arrive in t->h_state_multi.
 template <class H>
@@ -137,7 +167,7 @@ int32_t run_map_multi_graph(H* t, const void* solve, const void* body, int m, in
   HIP_TRY(t->graphs.get2(solve, gs, dim3(kBlock), body, gb, dim3(kBlock), (void*)t->d_static, (void*)t->d_call, (void*)t->d_dyn_multi,
                          launches, kMapMultiGraphKey | ((int)gb.x << 8) | t->prm.hessian_mode, t->stream, &exec));
   bool seen = true;
-  HIP_TRY(run_multi_chain(exec, t->stream, converged ? t->h_flag : nullptr, launches, K + 1, t->call_seq, t->h_state_multi,
+  HIP_TRY(run_multi_chain(exec, t->stream, converged ? t->h_flag : nullptr, launches, K + 1, t->flight.call_seq, t->h_state_multi,
                           t->d_dyn_multi->state[K & 1], T::kMaxStarts * sizeof(typename T::State), &seen));
   if (!seen) { set_error(T::kMapMultiNoEnd); return NDT_ERR_HIP; }
   return NDT_OK;
@@ -176,7 +206,7 @@ int32_t run_align_map_multi(H* t, H* const* sources, const double* init_poses, i
   { const int32_t os = order_after_sources(t, distinct, nd); if (os != NDT_OK) return os; }
   HIP_TRY(ensure_multi_chain(&t->h_state_multi, T::kMaxStarts, &t->d_dyn_multi, t->stream));
   const int fixed = t->prm.fixed_iterations;
-  next_seq(&t->call_seq, t->h_flag);
+  next_seq(&t->flight.call_seq, t->h_flag);
   { const int32_t cs = run_map_multi_chain(t, sp, sm, (int)m, max_blocks, fixed, fixed > 0 ? fixed : t->prm.max_iterations);
     if (cs != NDT_OK) return cs; }
   for (int k = 0; k < m; ++k)

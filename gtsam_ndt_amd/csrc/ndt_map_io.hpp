@@ -123,7 +123,7 @@ int32_t ndt2d_save_map(ndt2d_handle* h, void* buf, size_t capacity, size_t* writ
   if (written) *written = need;
   if (capacity < need) return NDT_ERR_CAPACITY;
   HIP_TRY(hipSetDevice(h->device));
-  { const int32_t fs = finish_chunk_run(h); if (fs != NDT_OK) return fs; }
+  { const int32_t fs = finish(h); if (fs != NDT_OK) return fs; }
   const GridDev& g = h->grid;
   ndt_map_header m{};
   m.magic = NDT_MAP_MAGIC; m.version = kMapVersion;
@@ -148,7 +148,7 @@ int32_t ndt2d_load_map(ndt2d_handle* h, const void* buf, size_t bytes) {
   if (m.ngrid != (h->prm.overlap_grids == 4 ? 4 : 1)) { set_error("map and handle differ in overlap_grids"); return NDT_ERR_INVALID_ARG; }
   { const int32_t cs = check_map_cells2((const char*)buf + sizeof m, (size_t)m.n_cells); if (cs != NDT_OK) return cs; }
   HIP_TRY(hipSetDevice(h->device));
-  { const int32_t fs = finish_chunk_run(h); if (fs != NDT_OK) return fs; }
+  { const int32_t fs = finish(h); if (fs != NDT_OK) return fs; }
   h->has_target = false;
   grid_changed(h);
   GridDev& g = h->grid;
@@ -185,7 +185,7 @@ int32_t ndt3d_save_map(ndt3d_handle* h, void* buf, size_t capacity, size_t* writ
   if (written) *written = need;
   if (capacity < need) return NDT_ERR_CAPACITY;
   HIP_TRY(hipSetDevice(h->device));
-  { const int32_t fs = finish_align3(h); if (fs != NDT_OK) return fs; }
+  { const int32_t fs = finish(h); if (fs != NDT_OK) return fs; }
   const ndt::Grid3Dev& g = h->grid;
   ndt_map_header m{};
   m.magic = NDT_MAP_MAGIC; m.version = kMapVersion;
@@ -211,7 +211,7 @@ int32_t ndt3d_load_map(ndt3d_handle* h, const void* buf, size_t bytes) {
   if (m.ngrid != 1) { set_error("a 3D map has one grid"); return NDT_ERR_INVALID_ARG; }
   { const int32_t cs = check_map_cells3((const char*)buf + sizeof m, (size_t)m.n_cells); if (cs != NDT_OK) return cs; }
   HIP_TRY(hipSetDevice(h->device));
-  { const int32_t fs = finish_align3(h); if (fs != NDT_OK) return fs; }
+  { const int32_t fs = finish(h); if (fs != NDT_OK) return fs; }
   h->has_target = false;
   grid_changed3(h);
   Grid3Dev& g = h->grid;

@@ -262,8 +262,8 @@ int32_t merge_map_impl(H* dst, H* src, const double* pose, size_t* n_outside, in
     if (!std::isfinite(pose[i])) { last_error() = std::string(who) + ": the pose is not finite"; return NDT_ERR_INVALID_ARG; }
   if (!src->has_target || !dst->has_target) { last_error() = std::string(who) + ": a handle holds no target"; return NDT_ERR_NO_TARGET; }
   HIP_TRY(hipSetDevice(dst->device));
-  { const int32_t fs = T::finish(src); if (fs != NDT_OK) return fs; }
-  { const int32_t fs = T::finish(dst); if (fs != NDT_OK) return fs; }
+  { const int32_t fs = finish(src); if (fs != NDT_OK) return fs; }
+  { const int32_t fs = finish(dst); if (fs != NDT_OK) return fs; }
   merge_grid_changed(dst);
   MergeArgs a{};
   merge_geometry(src, dst, &a);

@@ -242,14 +242,10 @@ void launch_point_fit(ndt3d_handle* h, unsigned tiles, const ndt::FitArgs<3>& a)
   hipLaunchKernelGGL((ndt::k_point_fit<3, 1>), dim3(tiles), dim3(ndt::kBlock), 0, h->stream, a);
 }
 // a host scan into the handle's staging arrays (as ndt*_evaluate stages its scan)
-int32_t fit_stage(ndt2d_handle* h, const float* const* s, size_t n, const float** d) {
-  const int32_t ss = stage_source(h, s[0], s[1], n);
-  d[0] = h->d_sx; d[1] = h->d_sy; d[2] = nullptr;
-  return ss;
-}
-int32_t fit_stage(ndt3d_handle* h, const float* const* s, size_t n, const float** d) {
-  const int32_t ss = stage_source3(h, s[0], s[1], s[2], n);
-  for (int a = 0; a < 3; ++a) d[a] = h->d_s[a];
+template <class H>
+int32_t fit_stage(H* h, const float* const* s, size_t n, const float** d) {
+  const int32_t ss = stage_source(h, s, n);
+  for (int a = 0; a < 3; ++a) d[a] = a < HandleTraits<H>::kDim ? h->d_s[a] : nullptr;
   return ss;
 }
 
@@ -287,7 +283,7 @@ int32_t point_fit_impl(H* h, const char* who, const float* const* d_s, size_t n,
   { const int32_t cs = point_fit_check(h, who, d_s, n, pose, max_m, keep, d_o, fit); if (cs != NDT_OK) return cs; }
   std::memset(fit, 0, sizeof(*fit));
   HIP_TRY(hipSetDevice(h->device));
-  { const int32_t fs = T::finish(h); if (fs != NDT_OK) return fs; }
+  { const int32_t fs = finish(h); if (fs != NDT_OK) return fs; }
   PointFitScratch& S = h->fit;
   const size_t tiles = (n + kFitTile - 1) / kFitTile;
   auto no_memory = [&]() {

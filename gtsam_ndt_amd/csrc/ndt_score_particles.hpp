@@ -319,7 +319,7 @@ template <class H>
 int32_t score_particles_enqueue(H* h, const float* const* d_s, size_t n, const double* d_poses, size_t m, float* d_scores,
                                 uint32_t* d_n_hit) {
   HIP_TRY(hipSetDevice(h->device));
-  { const int32_t fs = HandleTraits<H>::finish(h); if (fs != NDT_OK) return fs; }
+  { const int32_t fs = finish(h); if (fs != NDT_OK) return fs; }
   const int team = h->particle_team ? h->particle_team : (m < ndt::kParticleWideBelow ? 256 : 64);
   if (team == 256) launch_score_particles<256>(h, (unsigned)m, d_s, n, d_poses, m, d_scores, d_n_hit);
   else launch_score_particles<64>(h, (unsigned)((m + 3) / 4), d_s, n, d_poses, m, d_scores, d_n_hit);

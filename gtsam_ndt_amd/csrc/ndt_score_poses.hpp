@@ -278,7 +278,7 @@ int32_t score_poses_check(const H* h, const float* const* s, size_t n, const voi
 template <class H>
 int32_t score_poses_enqueue(H* h, const float* const* d_s, size_t n, const double* d_poses, size_t m, float* d_scores) {
   HIP_TRY(hipSetDevice(h->device));
-  { const int32_t fs = HandleTraits<H>::finish(h); if (fs != NDT_OK) return fs; }
+  { const int32_t fs = finish(h); if (fs != NDT_OK) return fs; }
   launch_score_poses(h, (unsigned)((m + ndt::kPoseThreads - 1) / ndt::kPoseThreads), d_s, n, d_poses, m, d_scores);
   HIP_TRY(hipGetLastError());
   return NDT_OK;

@@ -15,7 +15,7 @@
 #include <algorithm>
 #include <vector>
 
-#include "ndt_host.hpp"
+#include "ndt_chain_host.hpp"
 
 namespace ndt {
 
@@ -408,9 +408,9 @@ int32_t search_select(ndt::SearchScratch& s, hipStream_t stream, const float* vo
 }
 
 // What differs between the dimensions in the host code both handles share, specialised next to each handle
-// (ndt2d_api.hip, ndt3d_api.hpp).  Here: Window and Hit (the ABI's), kPose, kMaxStarts, finish (waits for the alignment
-// in flight), window (the searched axes of a Window) and hits_out (the walk's peaks as the ABI's hits).
-template <class Handle> struct HandleTraits;
+// (ndt2d_api.hip, ndt3d_api.hpp).  Here: Window and Hit (the ABI's), kPose, kMaxStarts, window (the searched axes of a
+// Window) and hits_out (the walk's peaks as the ABI's hits).  Declared in ndt_chain_host.hpp, with finish (waits for the
+// alignment in flight).
 
 // (ndt_map_host.hpp) what a map-to-map call refuses and prepares before it enqueues anything
 template <class H> int32_t prepare_map_pair(H* t, H* s, const char* who, const double* pose);
@@ -442,7 +442,7 @@ int32_t search_host_run(H* t, H* s, const typename HandleTraits<H>::Window* win,
   } else {
     if (!t->has_target) return NDT_ERR_NO_TARGET;
     HIP_TRY(hipSetDevice(t->device));
-    { const int32_t fs = T::finish(t); if (fs != NDT_OK) return fs; }
+    { const int32_t fs = finish(t); if (fs != NDT_OK) return fs; }
   }
   { const int32_t us = search_upload_axes(t->srch, t->stream, w, &plan); if (us != NDT_OK) return us; }
   float* vol = nullptr;

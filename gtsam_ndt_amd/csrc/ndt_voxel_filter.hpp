@@ -421,13 +421,12 @@ template <class H>
 int32_t voxel_filter_impl(H* h, const char* who, const float* const* d_s, size_t n, double leaf, uint32_t min_points,
                           float* const* d_o, uint32_t* d_count, size_t capacity, ndt_voxel_filter_info* info) {
   using namespace ndt;
-  using T = HandleTraits<H>;
   constexpr int DIM = std::is_same<H, ndt2d_handle>::value ? 2 : 3;
   { const int32_t cs = voxel_filter_check<DIM>(h, who, d_s, n, leaf, min_points, d_o, d_count, capacity, info); if (cs != NDT_OK) return cs; }
   std::memset(info, 0, sizeof(*info));
   { const int32_t ds = voxel_no_device(who); if (ds != NDT_OK) return ds; }
   HIP_TRY(hipSetDevice(h->device));
-  { const int32_t fs = T::finish(h); if (fs != NDT_OK) return fs; }
+  { const int32_t fs = finish(h); if (fs != NDT_OK) return fs; }
   VoxelFilterScratch& S = h->vox;
   auto no_memory = [&]() {
     (void)hipGetLastError();

@@ -114,7 +114,7 @@ int main() {
   // finish in steady state, between pairs and inside one: nothing new on the handle's stream, no fork
   run("finish in steady state", 2, {{A, 0, true, false}, {A, 1, false, true}, {F, 0, false, false}, {A, 0, false, false}, {A, 1, false, false},
                                     {A, 0, false, false}, {F, 0, false, false}, {A, 0, false, false}, {A, 1, false, false}});
-  // wait_stream keeps the pairing and the state of the fork (run_align's caller makes lane 1 wait for the producer)
+  // wait_stream keeps the pairing and the state of the fork (begin_align's caller makes lane 1 wait for the producer)
   run("wait_stream", 2, {{W, 0, false, false}, {A, 0, true, false}, {W, 0, false, false}, {A, 1, false, true}, {W, 0, false, false},
                          {A, 0, false, false}, {W, 0, false, false}, {A, 1, false, false}});
   // one lane: nothing alternates, nothing is recorded or waited for

@@ -2,7 +2,7 @@
 // lane_step).  No GPU, no HIP call: the rule is a pure function of the sequence of events on a handle.  Exact sequences
 // for three and four lanes first, then a model of the streams over random sequences (fixed seed): every stream is an
 // ordered queue, an event record copies what the tail of its stream is ordered behind, a wait merges that into the
-// waiting stream.  The driver enqueues what ndt2d_api.hip's run_align, ndt2d_wait_stream and ndt2d_set_tuning enqueue for
+// waiting stream.  The driver enqueues what ndt2d_api.hip's begin_align, ndt2d_wait_stream and ndt2d_set_tuning enqueue for
 // a plan.  Prints "ok" and returns 0, or says which expectation failed.
 #include <cstdint>
 #include <cstdio>

@@ -11,31 +11,32 @@ THE KEYS (a slot matches on launches, blocks = the first kernel's grid.x, mode, 
   Fused chain (m < split_from = 12): nh = 1 for m <= 6, else 2; subsets = ceil(m / nh).  m = 1..11 therefore gives NINE keys
   per call kind, not eleven: (nh 1; 1..6 subsets), (2; 4) for m = 7 and 8, (2; 5) for m = 9 and 10, (2; 6) for m = 11.
   Split chain (m >= 12): mg = 16, 32, 64 slots for m = 12, 17, 33, in the key as mg << 8 | mg << 20, and as blocks.
-  align: run_align -> ensure_graph, launches = K = 3 behind k_iterate_first, mode = hessian, lane 0, first_parity 1.
+  align: begin_align -> run_chain_tail (ndt_chain_host.hpp), launches = K = 3 behind k_iterate_first, mode = hessian, lane 0,
+  first_parity 1.
   evaluate: the same with launches = 1.  align_trace: plain launches, no graph.
   test_multi_start_shapes_2d walks S1..S11, C1..C11 (start, scan), the six split keys, align, evaluate: 26 distinct keys.
   Behind the last use of S11 come 9 + 6 + 2 = 17 other keys, behind every earlier S more: each of m = 11..1 in the last
   pass finds its graph evicted and rebuilds it (test_the_key_model_says_every_reuse_is_a_rebuild replays this on an LRU
   of 16).
 
-2D / 3D, run_align_map (ndt2d_d2d_api.hpp, ndt3d_d2d_api.hpp): mode = kMapGraphKey | hessian, launches = K + 1 = 4,
+2D / 3D, align_map_pair (ndt_map_host.hpp) -> run_chain_tail: mode = kMapGraphKey | hessian, launches = K + 1 = 4,
   blocks = min(ceil(n_comp / 256), 256) of the SOURCE.  Twenty sources with at least 17 distinct blocks (asserted from
   components()), aligned twice round: 19 other sources lie between two uses of one key.  run_map_multi_graph: mode =
   kMapMultiGraphKey | pow2(max blocks of the starts) << 8 | hessian, blocks = pow2(m): m = 2, 5, 9, 17 add keys in between.
 
-2D lanes (run_align): the key carries the lane, so after the cache was filled with the 18 fused multi keys, a run of r
+2D lanes (begin_align): the key carries the lane, so after the cache was filled with the 18 fused multi keys, a run of r
   back-to-back align_async calls needs r new keys (lane 0..r-1, launches 30); the call on lane k evicts while the chains of
   lanes 0..k-1 are queued.  ChainGraphCache::victim drains the handle's stream and the lane streams first.
 
 3D, multi_align3 (ndt3d_api.hpp): two-kernel chains, mode = 0x100000 | mg << 8 | graph_mode3 (0x10 with neighbourhood 7),
-  blocks = mg = 1, 2, 4, ..., 64; start and scan calls share keys.  align / evaluate: ensure_graph3, launches 3 / 1, mode =
+  blocks = mg = 1, 2, 4, ..., 64; start and scan calls share keys.  align / evaluate: run_chain_tail, launches 3 / 1, mode =
   graph_mode3.  m = 1, 2, 3, 5, 9, 17, 33 under both neighbourhoods, with align and evaluate: 18 keys per pass, so the
   second pass finds every graph evicted.  The 3D handle has one launch chain: its asynchronous calls follow one another on
   the handle's stream, and the first of a run evicts while nothing of that run is queued yet.
 
 Between align_async and align_finish only further align_async calls are made.  The header says of another call in between
 only that "any other call on the handle finishes a loop in flight first"; it does not say what align_finish returns
-afterwards, so that sequence is left out.
+afterwards, so that sequence is left out (tests/test_gpu_chain_interleave.py pins the call in between).
 
 Wall time on one MI355X: test_multi_start_shapes_2d 0.39 s, test_multi_start_shapes_3d 0.13 s, test_map_to_map_shapes 0.26 s
 (2D) and 0.16 s (3D), test_eviction_while_lanes_are_busy_2d 0.08 s, test_eviction_in_front_of_async_runs_3d 0.08 s,
