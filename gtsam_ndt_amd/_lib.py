@@ -332,6 +332,8 @@ SIGNATURES = {
     "ndt3d_stream": (_vp, [_vp]),
     "ndt3d_set_neighbourhood": (C.c_int32, [_vp, C.c_int32]),
     "ndt3d_neighbourhood": (C.c_int32, [_vp]),
+    "ndt3d_set_map_neighbourhood": (C.c_int32, [_vp, C.c_int32]),
+    "ndt3d_map_neighbourhood": (C.c_int32, [_vp]),
     "ndt3d_align_multi_scan_dev": (C.c_int32, [_vp, _vp, _vp, _vp, _vp, _dp, C.c_int32, _vp]),
     "ndt3d_align_multi_start_dev": (C.c_int32, [_vp, _vp, _vp, _vp, C.c_size_t, _dp, C.c_int32, _vp]),
     "ndt3d_align_trace": (C.c_int32, [_vp, _vp, _vp, _vp, C.c_size_t, _dp, _vp, C.c_int32, C.POINTER(C.c_int32), _vp]),

@@ -761,6 +761,10 @@ template <> struct HandleTraits<ndt2d_handle> {
   static constexpr const char* kTraceMapMulti = "ndt2d_align_map_multi";
   static constexpr const char* kMapMultiNoEnd = "the map-to-map multi-start loop did not report its end";
   static size_t cells(const ndt2d_handle* h) { return (size_t)h->grid.W * h->grid.H; }
+  // a 2D target scores a component against its own cell only (the map neighbourhood is a 3D handle's setting)
+  static int map_neighbourhood(const ndt2d_handle*) { return 1; }
+  static int map_graph_mode(const ndt2d_handle* h) { return h->prm.hessian_mode; }
+  static constexpr const char* kMapNeighbourhoodSetter = "";
   template <class... A> static int32_t begin(A... a) { return begin_align(a...); }
   template <class... A> static ChainLaunch scan_chain(A... a) { return ::scan_chain(a...); }
   template <class... A> static void launch_begin(A... a) { ::launch_begin(a...); }

@@ -66,6 +66,7 @@ struct ndt3d_handle {
   hipEvent_t map_ev = nullptr;                            // orders a target handle's stream behind this handle's (order_after)
   int particle_team = 0;                                  // NDT_TUNE_PARTICLE_TEAM: lanes per pose of ndt3d_score_particles*, 0 = by the list's length
   int neighbourhood = 1;                                  // ndt3d_set_neighbourhood: voxels a point is scored against in the alignment chains (1 or 7)
+  int map_neighbourhood = 1;                              // ndt3d_set_map_neighbourhood: voxels a source component is scored against, this handle as TARGET (1 or 7)
 };
 
 namespace {
@@ -470,6 +471,10 @@ template <> struct HandleTraits<ndt3d_handle> {
   static constexpr const char* kTraceMapMulti = "ndt3d_align_map_multi";
   static constexpr const char* kMapMultiNoEnd = "the 3D map-to-map multi-start loop did not report its end";
   static size_t cells(const ndt3d_handle* h) { return (size_t)h->grid.W * h->grid.H * h->grid.D; }
+  // the handle as a map-to-map TARGET: its map neighbourhood, and what of it (with the Hessian) enters a graph's key
+  static int map_neighbourhood(const ndt3d_handle* h) { return h->map_neighbourhood; }
+  static int map_graph_mode(const ndt3d_handle* h) { return (h->map_neighbourhood == 7 ? 0x10 : 0) | h->prm.hessian_mode; }
+  static constexpr const char* kMapNeighbourhoodSetter = "ndt3d_set_map_neighbourhood";
   template <class... A> static int32_t begin(A... a) { return begin_align(a...); }
   template <class... A> static ChainLaunch scan_chain(A... a) { return ::scan_chain(a...); }
   template <class... A> static void launch_begin(A... a) { ::launch_begin(a...); }
@@ -653,6 +658,28 @@ int32_t ndt3d_set_neighbourhood(ndt3d_handle* h, int32_t n) {
 }
 
 int32_t ndt3d_neighbourhood(const ndt3d_handle* h) { return h ? h->neighbourhood : NDT_ERR_INVALID_ARG; }
+
+// The map-to-map twin, a setting of its own: it selects kernels and graph keys of the calls this handle is the TARGET
+// of, and rebuilds nothing (grid, sums, covariance records and component list do not depend on it).
+int32_t ndt3d_set_map_neighbourhood(ndt3d_handle* h, int32_t n) {
+  if (!h) { ndt::set_error("ndt3d_set_map_neighbourhood: the handle is null"); return NDT_ERR_INVALID_ARG; }
+  if (n != 1 && n != 7) {
+    ndt::set_error("ndt3d_set_map_neighbourhood: the map neighbourhood is 1 (own voxel) or 7 (own voxel and its six face neighbours)");
+    return NDT_ERR_INVALID_ARG;
+  }
+  if (h->flight.waits()) {
+    HIP_TRY(hipSetDevice(h->device));
+    const int32_t fs = finish(h);
+    if (fs != NDT_OK) return fs;
+  }
+  h->map_neighbourhood = n;
+  return NDT_OK;
+}
+
+int32_t ndt3d_map_neighbourhood(const ndt3d_handle* h) {
+  if (!h) { ndt::set_error("ndt3d_map_neighbourhood: the handle is null"); return NDT_ERR_INVALID_ARG; }
+  return h->map_neighbourhood;
+}
 
 int32_t ndt3d_wait_stream(ndt3d_handle* h, void* producer_stream) {
   if (!h) return NDT_ERR_INVALID_ARG;

@@ -1,12 +1,14 @@
 // 3D map-to-map alignment (distribution-to-distribution NDT; docs/ALGORITHM.md section 2.14), the SE(3) twin of
 // ndt2d_d2d.hpp: the source is the list of its own voxel Gaussians, each scored against the target Gaussian of the voxel
-// its transformed mean falls in.  Everything comes from the exact per-voxel sums both handles keep (CellAcc3).
+// its transformed mean falls in (and, with the target's map neighbourhood 7, against those of that voxel's six face
+// neighbours: section 2.26).  Everything comes from the exact per-voxel sums both handles keep (CellAcc3).
 //
 //   k_cov_records3    target side: a second record array, the regularised covariance instead of its inverse
 //   k_comp_offsets    (ndt2d_d2d.hpp, dimension-free) exclusive scan of the per-workgroup counts of valid voxels ...
 //   k_components3     ... and the compaction of the valid voxels into a dense list, in voxel-key order
 //   k_begin_d2d3      per-call part of the context (the twin of k_begin3)
 //   k_iterate_d2d3    one launch per iteration: k_iterate3's prologue and epilogue around a new per-component body
+//                     (<MODE, NB>: the Hessian form and the map neighbourhood, 1 or 7)
 #pragma once
 #include "ndt2d_d2d.hpp"
 #include "ndt3d_kernels.hpp"
@@ -286,11 +288,105 @@ __device__ __forceinline__ void accumulate_component3(const MapPose3& T, const f
   acc[28] += hit ? 1.f : 0.f;
 }
 
+// ---- map neighbourhood 7 (ALGORITHM 2.26): the same terms with a component's work split in two.  The NB = 1 kernels keep
+// the text above untouched, and with it the instructions they compiled to before the option existed;
+// what follows is accumulate_component3's operations on the same operands in the same order, so the own voxel's term is
+// bit for bit that function's.
+// What does not depend on the target voxel (mean -> image p, covariance Sg) - S = R Sg R', R mu = p - t and the three
+// a_k x (R mu) - is formed once per component ...
+struct ComponentFrame3 { float S[6]; V3 j[3]; };
+__device__ __forceinline__ void component_frame3(const MapPose3& T, const float* Sg, float px, float py, float pz, ComponentFrame3& F) {
+  rotate_cov3(T.R, Sg, F.S);
+  const V3 pr{px - T.tx, py - T.ty, pz - T.tz};
+  F.j[0] = axis_cross<0>(T, pr);
+  F.j[1] = axis_cross<1>(T, pr);
+  F.j[2] = axis_cross<2>(T, pr);
+}
+// (rot_terms3 with j = a_k x (R mu) from the frame)
+template <int K>
+__device__ __forceinline__ void rot_terms_of3(const MapPose3& T, const float* S, const float* B, const V3& j, const V3& v,
+                                              const V3& Sv, RotTerms3& o) {
+  o.j = j;
+  o.p = axis_cross<K>(T, v);
+  o.e = axis_cross<K>(T, Sv);
+  o.f = symv(S, o.p);
+  const V3 z{o.e.x - o.f.x, o.e.y - o.f.y, o.e.z - o.f.z};
+  o.r = V3{o.j.x - z.x, o.j.y - z.y, o.j.z - z.z};
+  o.c = dot3(v, o.j) - 0.5f * dot3(v, z);
+  o.U = symv(B, o.r);
+}
+// ... and the rest once per candidate voxel (A4 = its mean and count, B4 and tyz, tzz = its covariance; hit = the
+// candidate is in the grid and its record valid): S + Sigma_j, the cofactor inverse and its one division, v, S v, the
+// rotation terms, the 29 sums.  A miss takes the unit matrix and weighs 0, as above.
+template <int MODE>
+__device__ __forceinline__ void accumulate_pair3(const MapPose3& T, const ComponentFrame3& F, float px, float py, float pz, bool hit,
+                                                 const float4& A4, const float4& B4, float tyz, float tzz, float d1, float d2,
+                                                 float nhd2, float* acc) {
+  const float* S = F.S;
+  const float axx = S[0] + (hit ? B4.x : 1.f), axy = S[1] + (hit ? B4.y : 0.f), axz = S[2] + (hit ? B4.z : 0.f);
+  const float ayy = S[3] + (hit ? B4.w : 1.f), ayz = S[4] + (hit ? tyz : 0.f), azz = S[5] + (hit ? tzz : 1.f);
+  float B[6];
+  V3 v;
+  const float m = mahalanobis_sum3(axx, axy, axz, ayy, ayz, azz, V3{px - A4.x, py - A4.y, pz - A4.z}, B, v);
+  const float s = hit ? d1 * __builtin_amdgcn_exp2f(nhd2 * m) : 0.f;
+  const float w = s * d2;
+  const V3 Sv = symv(S, v);
+  RotTerms3 t[3];
+  rot_terms_of3<0>(T, S, B, F.j[0], v, Sv, t[0]);
+  rot_terms_of3<1>(T, S, B, F.j[1], v, Sv, t[1]);
+  rot_terms_of3<2>(T, S, B, F.j[2], v, Sv, t[2]);
+  const float v3[3] = {v.x, v.y, v.z};
+  {
+    int qq = 0;
+#pragma unroll
+    for (int i = 0; i < 3; ++i)
+#pragma unroll
+      for (int j = i; j < 3; ++j) {
+        float h = B[qq];
+        if (MODE == 1) h = h - d2 * v3[i] * v3[j];
+        acc[qq] = fmaf(w, h, acc[qq]);
+        ++qq;
+      }
+  }
+#pragma unroll
+  for (int k = 0; k < 3; ++k) {
+    const float u3[3] = {t[k].U.x, t[k].U.y, t[k].U.z};
+#pragma unroll
+    for (int r = 0; r < 3; ++r) {
+      float h = u3[r];
+      if (MODE == 1) h = h - d2 * v3[r] * t[k].c;
+      acc[6 + 3 * r + k] = fmaf(w, h, acc[6 + 3 * r + k]);
+    }
+  }
+  {
+    int qq = 15;
+#pragma unroll
+    for (int k = 0; k < 3; ++k)
+#pragma unroll
+      for (int l = k; l < 3; ++l) {
+        float h = dot3(t[k].r, t[l].U);
+        if (MODE == 1) {       // - d2 c_k c_l + v' j_kl - v' Z_kl v / 2, the last two = p_l . (e_k - j_k) - p_k . f_l
+          const V3 ej{t[k].e.x - t[k].j.x, t[k].e.y - t[k].j.y, t[k].e.z - t[k].j.z};
+          h = (h - d2 * t[k].c * t[l].c) + (dot3(t[l].p, ej) - dot3(t[k].p, t[l].f));
+        }
+        acc[qq] = fmaf(w, h, acc[qq]);
+        ++qq;
+      }
+  }
+  acc[21] = fmaf(w, v.x, acc[21]); acc[22] = fmaf(w, v.y, acc[22]); acc[23] = fmaf(w, v.z, acc[23]);
+#pragma unroll
+  for (int k = 0; k < 3; ++k) acc[24 + k] = fmaf(w, t[k].c, acc[24 + k]);
+  acc[27] += s;
+  acc[28] += hit ? 1.f : 0.f;
+}
+
 // Body and epilogue of a map-to-map launch for one alignment, shared by k_iterate_d2d3 and the multi-start chain
 // (k_multi_body_d2d3), in the shape of evaluate_block3: this workgroup's components (i, i + stride, ...; the first one
 // already loaded into ca, cb, cc) under the pose T, each mean looked up as a point is (a voxel of `cov` either way),
 // per-thread sums, the wave's sums through LDS, one partial row entry per sum at partial_col[row * kMaxBlocks].
-template <int MODE>
+// NB = the target's map neighbourhood (ndt3d_set_map_neighbourhood, ALGORITHM 2.26): 1 = the voxel the image of the mean
+// falls into, 7 = and its six face neighbours.
+template <int MODE, int NB>
 __device__ __forceinline__ void evaluate_components3(const Grid3Dev& G, const SolveParams& prm, const MapPose3& T,
                                                      const float4* __restrict__ comp, const float4* __restrict__ cov, int n, int i,
                                                      int stride, float4 ca, float4 cb, float4 cc, float (*s_wave)[kRowsMap3],
@@ -302,6 +398,8 @@ __device__ __forceinline__ void evaluate_components3(const Grid3Dev& G, const So
   float acc[NA];
 #pragma unroll
   for (int j = 0; j < NA; ++j) acc[j] = 0.f;
+  static_assert(NB == 1 || NB == 7, "the map neighbourhood is the own voxel, or the own voxel and its six face neighbours");
+  if constexpr (NB == 1) {
   while (i < n) {
     const int i2 = i + stride;
     float4 na = make_float4(0.f, 0.f, 0.f, 0.f), nb = na, nc = na;
@@ -316,6 +414,44 @@ __device__ __forceinline__ void evaluate_components3(const Grid3Dev& G, const So
     accumulate_component3<MODE>(T, Sg, p.x, p.y, p.z, vox.in, A4, B4, C2, d1, d2, nhd2, acc);
     ca = na; cb = nb; cc = nc; i = i2;
   }
+  } else {
+  // Own voxel and its six face neighbours, in evaluate_block3<MODE, 7>'s order and by its rule: a candidate is taken by
+  // index, and one that leaves the grid loads the own record (an address inside the array) and has no vote.  All seven
+  // records (10 of a record's 12 words each) are requested in front of the first term; a candidate that is off the grid
+  // or empty adds a term of weight zero (no branch: the lanes of a wave disagree on which candidates count).  The frame
+  // - S, R mu and its three cross products - is formed once, under the loads.
+  const int WH = G.W * G.H;
+  while (i < n) {
+    const int i2 = i + stride;
+    float4 na = make_float4(0.f, 0.f, 0.f, 0.f), nb = na, nc = na;
+    if (i2 < n) { na = comp[3 * (size_t)i2]; nb = comp[3 * (size_t)i2 + 1]; nc = comp[3 * (size_t)i2 + 2]; }
+    const V3 p = image3(T.R, T.tx, T.ty, T.tz, ca.x, ca.y, ca.z);
+    const VoxelIndex3 vox = voxel_index3(G, E, p.x, p.y, p.z);
+    const bool in = vox.in;
+    const bool ok[NB] = {in, in && vox.ix > 0, in && vox.ix + 1 < G.W, in && vox.iy > 0, in && vox.iy + 1 < G.H,
+                         in && vox.iz > 0, in && vox.iz + 1 < G.D};
+    const int dk[NB] = {0, -1, 1, -G.W, G.W, -WH, WH};
+    float4 A4[NB], B4[NB];
+    float2 C2[NB];
+#pragma unroll
+    for (int c = 0; c < NB; ++c) {
+      const float4* r = cov + 3 * (size_t)(unsigned int)(vox.key + (ok[c] ? dk[c] : 0));
+      A4[c] = r[0];
+      B4[c] = r[1];
+      C2[c] = *reinterpret_cast<const float2*>(r + 2);
+    }
+    // (left alone, the scheduler sinks the records of four candidates next to their terms to save registers: four more
+    // exposed gather latencies in a launch of one wave per SIMD, which has nothing to hide them under)
+    __builtin_amdgcn_sched_barrier(0);
+    const float Sg[6] = {cb.x, cb.y, cb.z, cb.w, cc.x, cc.y};
+    ComponentFrame3 F;
+    component_frame3(T, Sg, p.x, p.y, p.z, F);
+#pragma unroll
+    for (int c = 0; c < NB; ++c)
+      accumulate_pair3<MODE>(T, F, p.x, p.y, p.z, ok[c] & (A4[c].w > 0.f), A4[c], B4[c], C2[c].x, C2[c].y, d1, d2, nhd2, acc);
+    ca = na; cb = nb; cc = nc; i = i2;
+  }
+  }
   block_reduce3_store<NA, kRowsMap3>(acc, s_t_wave, s_wave, partial_col);
 }
 
@@ -324,7 +460,8 @@ __device__ __forceinline__ void evaluate_components3(const Grid3Dev& G, const So
 // ndt3d_kernels.hpp), with call->blocks workgroups of kBlock threads, a component per lane.  Both Hessian modes carry
 // the same 29 sums:
 // in the map-frame form the second-derivative terms are per-component, there is no M to contract in the prologue.
-template <int MODE>
+// NB (evaluate_components3) changes the body alone: the sums, their fold and the update are the same.
+template <int MODE, int NB>
 __global__ __launch_bounds__(kBlock) void k_iterate_d2d3(const AlignStatic3* __restrict__ st, const MapCall3* __restrict__ call,
                                                          AlignDyn3* __restrict__ dyn, int parity) {
   constexpr int NA = kNumAccMap3, RPW = kRowsMap3 / 4;
@@ -421,7 +558,7 @@ __global__ __launch_bounds__(kBlock) void k_iterate_d2d3(const AlignStatic3* __r
   // ---- body and epilogue: per-component terms at `pose`
   MapPose3 T;
   make_map_pose3(pose, T);
-  evaluate_components3<MODE>(G, prm, T, comp, cov, n, i, stride, ca, cb, cc, s_wave, s_t[wave],
+  evaluate_components3<MODE, NB>(G, prm, T, comp, cov, n, i, stride, ca, cb, cc, s_wave, s_t[wave],
                              &dyn->partials[parity][0][blockIdx.x]);
 }
 

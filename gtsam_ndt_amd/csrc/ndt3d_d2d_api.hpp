@@ -7,8 +7,17 @@
 
 namespace {
 
+// The template arguments of a 3D map-to-map kernel: f(MODE, NB) with the TARGET's Hessian and map neighbourhood (with_mode3
+// for the setting map-to-map alignment has of its own)
+template <class F>
+auto with_map_mode3(const ndt3d_handle* t, F&& f) {
+  return with_mode(t->prm, [&](auto M, auto) {
+    return t->map_neighbourhood == 7 ? f(M, std::integral_constant<int, 7>{}) : f(M, std::integral_constant<int, 1>{});
+  });
+}
+
 const void* map_iter_kernel(const ndt3d_handle* t) {
-  return with_mode(t->prm, [](auto M, auto) { return (const void*)&ndt::k_iterate_d2d3<M>; });
+  return with_map_mode3(t, [](auto M, auto NB) { return (const void*)&ndt::k_iterate_d2d3<M, NB>; });
 }
 
 void launch_begin_map(ndt3d_handle* t, ndt3d_handle* s, int blocks, const double* pose, int fixed, ndt::IterState3* host_state,
@@ -29,7 +38,7 @@ int32_t run_map_multi_chain(ndt3d_handle* t, const ndt::StartPoses3& sp, const n
                      converged_mode ? t->h_flag : (int*)nullptr, t->flight.call_seq);
   HIP_TRY(hipGetLastError());
   const void* solve = (const void*)&k_multi_solve3<0>;
-  const void* body = with_mode(t->prm, [](auto M, auto) { return (const void*)&k_multi_body_d2d3<M>; });
+  const void* body = with_map_mode3(t, [](auto M, auto NB) { return (const void*)&k_multi_body_d2d3<M, NB>; });
   return run_map_multi_graph(t, solve, body, m, max_blocks, converged_mode ? t->check_every : K + 1, converged_mode, K);
 }
 

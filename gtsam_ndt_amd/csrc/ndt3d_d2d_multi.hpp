@@ -92,7 +92,7 @@ __global__ void k_begin_d2d_multi3(AlignCall3* __restrict__ call, AlignDynMulti3
 
 // Grid (>= max_h blocks[h], >= m), kBlock threads.  Reads body[parity][h] (k_multi_solve3's: the float64 pose), writes
 // partials[parity][h][*][b]; workgroups past blocks[h] and those of finished or unused slots return without writing.
-template <int MODE>
+template <int MODE, int NB>
 __global__ __launch_bounds__(kBlock) void k_multi_body_d2d3(const AlignStatic3* __restrict__ st, const AlignCall3* __restrict__ call,
                                                             AlignDynMulti3* __restrict__ dyn, int parity) {
   constexpr int NA = kNumAccMap3;
@@ -122,7 +122,7 @@ __global__ __launch_bounds__(kBlock) void k_multi_body_d2d3(const AlignStatic3* 
   // ---- body and epilogue: the function k_iterate_d2d3 calls
   MapPose3 T;
   make_map_pose3(pose, T);
-  evaluate_components3<MODE>(G, prm, T, comp, cov, n, i, blocks * kBlock, ca, cb, cc, s_wave, s_t[wave],
+  evaluate_components3<MODE, NB>(G, prm, T, comp, cov, n, i, blocks * kBlock, ca, cb, cc, s_wave, s_t[wave],
                              &dyn->partials[parity][h][0][b]);
 }
 

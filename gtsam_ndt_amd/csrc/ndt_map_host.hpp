@@ -8,9 +8,12 @@
 
 namespace {
 
-constexpr int kMapGraphKey = 0x2000000;      // ChainGraphCache key of the k_iterate_d2d / k_iterate_d2d3 chains (| hessian_mode)
+// ChainGraphCache key of the k_iterate_d2d / k_iterate_d2d3 chains (| HandleTraits::map_graph_mode of the target: the
+// Hessian mode in bit 0 and, 3D, the map neighbourhood in bit 4 - the cache compares keys, not kernels, and a handle
+// switched between the neighbourhoods must never replay the other one's graph)
+constexpr int kMapGraphKey = 0x2000000;
 // ... and of the k_multi_solve + k_multi_body_d2d / k_multi_solve3<0> + k_multi_body_d2d3 chains (| the body's grid width
-// << 8 | hessian_mode; the solve's grid is the `blocks` of the key).  Bit 27: multi_align's keys reach bit 26 (64 starts
+// << 8 | map_graph_mode; the solve's grid is the `blocks` of the key).  Bit 27: multi_align's keys reach bit 26 (64 starts
 // << 20), multi_align3's are 0x100000 | up to 64 << 8
 constexpr int kMapMultiGraphKey = 0x8000000;
 
@@ -128,6 +131,23 @@ int32_t prepare_map_pair(H* t, H* s, const char* who, const double* pose) {
   return order_after_sources(t, &s, 1);
 }
 
+// The head of the calls whose kernels score a component against its own voxel only - the map-to-map searches and pose
+// lists (who = "search", "pose list"), the _align forms through them.  The map neighbourhood 7 (ALGORITHM 2.26) is a
+// scoring option of the alignment chains alone; these keep the single-voxel score their contracts name, so with 7 set
+// on the target they refuse instead of answering another question (what single_voxel_only is to the point searches),
+// before any device call.
+template <class H>
+int32_t prepare_single_voxel_map_pair(H* t, H* s, const char* who) {
+  using T = HandleTraits<H>;
+  if (T::map_neighbourhood(t) == 7) {
+    last_error() = std::string("map-to-map ") + who + ": scores a component against its own voxel only; the target's map neighbourhood "
+                   "is 7: call " + T::kMapNeighbourhoodSetter + "(target, 1) first - search with 1, refine with 7 (the map "
+                   "neighbourhood is honoured by evaluate_map, align_map and align_map_multi)";
+    return NDT_ERR_INVALID_ARG;
+  }
+  return prepare_map_pair(t, s, (std::string(who) + ": both").c_str(), nullptr);
+}
+
 // One alignment of s's component list against t's grid from `pose`, synchronous: the final state is in *t->h_state, and
 // nothing reads s's list any more.  fixed_override: >= 0 replaces the handle's fixed_iterations.  The loop is the launch
 // chain of ndt*_align_dev (ndt_chain_host.hpp) with the list in the place of a scan: launch 0 is the k_begin_d2d*, so the
@@ -151,7 +171,7 @@ int32_t align_map_pair(H* t, H* s, const double* pose, int fixed_override) {
   launch_begin_map(t, s, blocks, pose, p.fixed, p.chunked ? t->h_state : (State*)nullptr, p.chunked ? t->h_flag : (int*)nullptr);
   HIP_TRY(hipGetLastError());
   const ChainLaunch c{map_iter_kernel(t), dim3(blocks), dim3(kBlock), t->d_static, t->d_map_call, t->d_dyn};
-  { const int32_t cs = run_chain_tail(t, c, kMapGraphKey | t->prm.hessian_mode, 0, t->stream, nullptr, p, /*drain=*/true);
+  { const int32_t cs = run_chain_tail(t, c, kMapGraphKey | T::map_graph_mode(t), 0, t->stream, nullptr, p, /*drain=*/true);
     if (cs != NDT_OK) return cs; }
   return fetch_state(t);
 }
@@ -165,7 +185,7 @@ int32_t run_map_multi_graph(H* t, const void* solve, const void* body, int m, in
   const dim3 gs(pow2_at_least(m)), gb(pow2_at_least(max_blocks), gs.x);
   hipGraphExec_t exec = nullptr;
   HIP_TRY(t->graphs.get2(solve, gs, dim3(kBlock), body, gb, dim3(kBlock), (void*)t->d_static, (void*)t->d_call, (void*)t->d_dyn_multi,
-                         launches, kMapMultiGraphKey | ((int)gb.x << 8) | t->prm.hessian_mode, t->stream, &exec));
+                         launches, kMapMultiGraphKey | ((int)gb.x << 8) | T::map_graph_mode(t), t->stream, &exec));
   bool seen = true;
   HIP_TRY(run_multi_chain(exec, t->stream, converged ? t->h_flag : nullptr, launches, K + 1, t->flight.call_seq, t->h_state_multi,
                           t->d_dyn_multi->state[K & 1], T::kMaxStarts * sizeof(typename T::State), &seen));

@@ -265,7 +265,8 @@ int32_t score_map_poses_check(const H* t, const H* s, const void* poses, size_t 
   return NDT_OK;
 }
 
-// Every entry point prepares the pair as ndt*_search_map does (prepare_map_pair: the handle errors before any device
+// Every entry point prepares the pair as ndt*_search_map does (prepare_single_voxel_map_pair: the refusal of a target
+// at map neighbourhood 7, then prepare_map_pair: the handle errors before any device
 // call, the alignment in flight finished, the derived data, t's stream behind s's); then the score launch on t's stream.
 template <class H>
 int32_t score_map_poses_enqueue(H* t, H* s, const double* d_poses, size_t m, float* d_scores, uint32_t* d_n_hit) {
@@ -278,7 +279,7 @@ int32_t score_map_poses_enqueue(H* t, H* s, const double* d_poses, size_t m, flo
 template <class H>
 int32_t score_map_poses_dev(H* t, H* s, const double* d_poses, size_t m, float* d_scores, uint32_t* d_n_hit) {
   { const int32_t cs = score_map_poses_check(t, s, d_poses, m, d_scores, false, 0.0, 0.0, 1, nullptr); if (cs != NDT_OK) return cs; }
-  { const int32_t ps = prepare_map_pair(t, s, "pose list: both", nullptr); if (ps != NDT_OK) return ps; }
+  { const int32_t ps = prepare_single_voxel_map_pair(t, s, "pose list"); if (ps != NDT_OK) return ps; }
   { const int32_t es = score_map_poses_enqueue(t, s, d_poses, m, d_scores, d_n_hit); if (es != NDT_OK) return es; }
   HIP_TRY(hipStreamSynchronize(t->stream));
   return NDT_OK;
@@ -290,7 +291,7 @@ int32_t score_map_poses_host(H* t, H* s, const double* poses, size_t m, float* s
   using namespace ndt;
   constexpr int P = HandleTraits<H>::kPose;
   { const int32_t cs = score_map_poses_check(t, s, poses, m, scores, false, 0.0, 0.0, 1, nullptr); if (cs != NDT_OK) return cs; }
-  { const int32_t ps = prepare_map_pair(t, s, "pose list: both", nullptr); if (ps != NDT_OK) return ps; }
+  { const int32_t ps = prepare_single_voxel_map_pair(t, s, "pose list"); if (ps != NDT_OK) return ps; }
   SearchScratch& S = t->srch;
   HIP_TRY(grow(&S.d_list, &S.list_cap, m * P, m * P + m * P / 4));
   HIP_TRY(grow(&S.d_vol, &S.vol_cap, m, m + m / 4));
@@ -309,7 +310,7 @@ int32_t best_map_poses_dev(H* t, H* s, const double* d_poses, size_t m, double m
                            typename HandleTraits<H>::Hit* hits, int32_t* n_hits) {
   using namespace ndt;
   { const int32_t cs = score_map_poses_check(t, s, d_poses, m, hits, true, min_sep_trans, min_sep_rot, k, n_hits); if (cs != NDT_OK) return cs; }
-  { const int32_t ps = prepare_map_pair(t, s, "pose list: both", nullptr); if (ps != NDT_OK) return ps; }
+  { const int32_t ps = prepare_single_voxel_map_pair(t, s, "pose list"); if (ps != NDT_OK) return ps; }
   SearchScratch& S = t->srch;
   HIP_TRY(grow(&S.d_vol, &S.vol_cap, m, m + m / 4));
   { const int32_t es = score_map_poses_enqueue(t, s, d_poses, m, S.d_vol, nullptr); if (es != NDT_OK) return es; }

@@ -413,7 +413,7 @@ int32_t search_select(ndt::SearchScratch& s, hipStream_t stream, const float* vo
 // alignment in flight).
 
 // (ndt_map_host.hpp) what a map-to-map call refuses and prepares before it enqueues anything
-template <class H> int32_t prepare_map_pair(H* t, H* s, const char* who, const double* pose);
+template <class H> int32_t prepare_single_voxel_map_pair(H* t, H* s, const char* who);
 
 // The lattice of an ABI window; *w = its searched axes.  Every centre coordinate has to be finite, the pinned ones too.
 template <class H>
@@ -437,7 +437,7 @@ int32_t search_host_run(H* t, H* s, const typename HandleTraits<H>::Window* win,
   SearchPlan plan;
   { const int32_t ls = search_lattice_of<H>(win, &w, &plan.L); if (ls != NDT_OK) return ls; }
   if (s) {
-    const int32_t ps = prepare_map_pair(t, s, "search: both", nullptr);
+    const int32_t ps = prepare_single_voxel_map_pair(t, s, "search");
     if (ps != NDT_OK) return ps;
   } else {
     if (!t->has_target) return NDT_ERR_NO_TARGET;

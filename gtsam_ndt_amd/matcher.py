@@ -930,13 +930,17 @@ class NdtMatcher3D(_NdtMatcher):
     _dim = _DIM3
     _where_set_target_dev = "set_target_dev"
 
-    def __init__(self, device: int = 0, tuning: dict | None = None, neighbourhood: int = 1, **overrides):
+    def __init__(self, device: int = 0, tuning: dict | None = None, neighbourhood: int = 1, map_neighbourhood: int = 1,
+                 **overrides):
         """tuning: execution-strategy knobs by name (L.TUNING; 3D handles know "single_sync_build",
-        "map_multi_from" and "fused_begin").  neighbourhood: set_neighbourhood() of the new handle."""
+        "map_multi_from" and "fused_begin").  neighbourhood: set_neighbourhood() of the new handle; map_neighbourhood:
+        its set_map_neighbourhood()."""
         self.params = default_params3d(**overrides)
         self._create(device, tuning)
         if neighbourhood != 1:
             self.set_neighbourhood(neighbourhood)
+        if map_neighbourhood != 1:
+            self.set_map_neighbourhood(map_neighbourhood)
 
     def set_neighbourhood(self, n: int):
         """1: a point is scored against the voxel its image lies in; 7: and against that voxel's six face neighbours
@@ -947,6 +951,18 @@ class NdtMatcher3D(_NdtMatcher):
     @property
     def neighbourhood(self) -> int:
         return self._check(self._c.neighbourhood(self._h), "neighbourhood")
+
+    def set_map_neighbourhood(self, n: int):
+        """Map-to-map alignment with this matcher as the TARGET (ndt3d_set_map_neighbourhood).  1: a source component
+        is scored against the voxel the image of its mean falls into; 7: and against that voxel's six face neighbours,
+        which takes the pull towards the identity out of two maps on one lattice.  Honoured by evaluate_map, align_map and
+        align_map_multi; search_map, search_align_map, score_map_poses, best_map_poses and best_map_poses_align raise
+        NdtError while 7 is set: search with 1, refine with 7.  A source's own setting is ignored."""
+        self._check(self._c.set_map_neighbourhood(self._h, int(n)), "set_map_neighbourhood")
+
+    @property
+    def map_neighbourhood(self) -> int:
+        return self._check(self._c.map_neighbourhood(self._h), "map_neighbourhood")
 
     def set_target(self, x, y, z):
         return self._set_target((x, y, z))
@@ -1554,3 +1570,20 @@ class NdtMapPyramid2D(_NdtMapPyramid):
 
 class NdtMapPyramid3D(_NdtMapPyramid):
     _Matcher = NdtMatcher3D
+
+    def __init__(self, fine, levels=PYRAMID_LEVELS, map_neighbourhood: int = 1, _owns_fine: bool = False):
+        """map_neighbourhood: NdtMatcher3D.set_map_neighbourhood() of every level's handle, `fine` included, when it is
+        not 1 (1 leaves `fine` as the caller set it)."""
+        super().__init__(fine, levels, _owns_fine)
+        if map_neighbourhood != 1:
+            for m in self.levels:
+                m.set_map_neighbourhood(map_neighbourhood)
+
+    @classmethod
+    def from_blob(cls, blob, device: int = 0, levels=PYRAMID_LEVELS, map_neighbourhood: int = 1, **params):
+        """_NdtMapPyramid.from_blob, with map_neighbourhood for every level."""
+        pyr = super().from_blob(blob, device, levels, **params)
+        if map_neighbourhood != 1:
+            for m in pyr.levels:
+                m.set_map_neighbourhood(map_neighbourhood)
+        return pyr

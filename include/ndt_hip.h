@@ -1025,6 +1025,32 @@ int32_t ndt3d_align_multi_start_dev(ndt3d_handle* h, const float* d_sx, const fl
  * ndt3d_neighbourhood returns 1 or 7 (a null handle: NDT_ERR_INVALID_ARG). */
 int32_t ndt3d_set_neighbourhood(ndt3d_handle* h, int32_t n);
 int32_t ndt3d_neighbourhood(const ndt3d_handle* h);
+/* The map neighbourhood: the target voxels a source COMPONENT is scored against in 3D map-to-map alignment
+ * (docs/ALGORITHM.md 2.26; Stoyanov et al. 2012 pair a source Gaussian with neighbouring target Gaussians).  n = 1 (a
+ * new handle) is the voxel the image of the component's mean falls into, the objective of 2.14; n = 7 adds that voxel's
+ * six face neighbours, which takes the jumps at the voxel faces out of the score and with them the pull towards the
+ * identity that two maps on one lattice show.  A setting of its own, not ndt3d_set_neighbourhood (points), and the
+ * TARGET handle's, like d1, d2 and the Hessian mode: a source handle's value is ignored.
+ *   The own voxel is found as with 1 (the float32 image of the mean; outside the grid or not finite: the component
+ *   contributes nothing, whatever lies next to it).  Candidates in the order own, -x, +x, -y, +y, -z, +z; one that
+ *   leaves [0, W) x [0, H) x [0, D) is skipped by index (key - 1 from ix = 0 is a voxel of the grid and not a
+ *   neighbour).  Every candidate with a valid covariance record adds one full term of 2.14 with that voxel's mean and
+ *   covariance to the score, g and H (both Hessian modes), in candidate order, and one to n_hit: n_hit counts
+ *   component-voxel pairs, and min_hits is compared with that count.  With target == source and 7 the identity is a
+ *   stationary point up to float32 rounding only (the pairs i->j and j->i cancel in exact arithmetic).
+ *   Honoured by ndt3d_evaluate_map, ndt3d_align_map and ndt3d_align_map_multi (on both sides of
+ *     NDT_TUNE_MAP_MULTI_FROM; results[k] stays bit for bit the single call's).
+ *   Refused while the target's setting is 7 (NDT_ERR_INVALID_ARG, ndt_last_error names ndt3d_set_map_neighbourhood):
+ *     ndt3d_search_map, ndt3d_search_map_scores, ndt3d_search_align_map, ndt3d_score_map_poses*, ndt3d_best_map_poses* -
+ *     their kernels keep the single-voxel score their contracts name.  Search with 1, refine with 7.
+ *   Unaffected: everything that scores points, builds, updates, save / load, coarsen, merge, ndt3d_get_components.
+ * Bit for bit reproducible; with 1 every result is bit for bit what it was before the option existed.
+ * ndt3d_set_map_neighbourhood: n other than 1 or 7, or a null handle: NDT_ERR_INVALID_ARG, ndt_last_error names the
+ * function (the setting stays).  An alignment in flight on the handle is finished first; nothing is rebuilt (grid, sums,
+ * covariance records and component list do not depend on the setting) and no target is needed.
+ * ndt3d_map_neighbourhood returns 1 or 7 (a null handle: NDT_ERR_INVALID_ARG). */
+int32_t ndt3d_set_map_neighbourhood(ndt3d_handle* h, int32_t n);
+int32_t ndt3d_map_neighbourhood(const ndt3d_handle* h);
 /* Exhaustive 3D pose search (docs/ALGORITHM.md "Exhaustive 3D pose search"), the twin of ndt2d_search*: the NDT score of
  * the scan at every pose of an (x, y, yaw) lattice against the cached voxel grid, then the best well-separated peaks - a
  * ground vehicle's relocalisation or loop closure whose guess is metres and tens of degrees off.  z, roll and pitch are

@@ -1,13 +1,17 @@
 """Timing of 3D map-to-map alignment (ndt3d_align_map) next to the point-to-map path it shares its launch chain with.
 
   maps_1m            the config-5 pair as two 1 m voxel maps, from a start 5 cm / 5 mrad off the generating pose
+  maps_1m_zero       maps_1m from the zero guess: the local optimum 0.3 m off with the own voxel alone, the
+                     generating pose with --map-neighbourhood 7
   maps_2m            the same clouds at 2 m voxels, from the zero guess
   coarse_then_fine   maps_2m from the zero guess, then maps_1m from its result: how a caller gets past the local optimum
   point_to_map       ndt3d_align_dev of the config-5 scan against the 1 m grid (the existing path)
 
 Per map case: components, host-call-to-result time of a converged alignment, time per launch of the chain from two
 fixed-iteration runs ((t(K2) - t(K1)) / (K2 - K1)), the one-off cost of the derived data (first call after a grid change
-minus a later one) and the distance of the result to the generating pose.  Prints one JSON line.  Run it under
+minus a later one) and the distance of the result to the generating pose.  --map-neighbourhood 7: every target of the map cases
+scores a component against its own voxel and the six face neighbours (ndt3d_set_map_neighbourhood; default 1).
+Prints one JSON line.  Run it under
 `rocprofv3 --kernel-trace --stats` (with --profile: fewer repetitions) for per-kernel times."""
 import json
 import os
@@ -40,8 +44,11 @@ def per_launch_us(make, run, reps, k1=20, k2=120):
     return (out[1] - out[0]) * 1e3 / (k2 - k1)
 
 
+MAP_NB = int(sys.argv[sys.argv.index("--map-neighbourhood") + 1]) if "--map-neighbourhood" in sys.argv else 1
+
+
 def pair_of_maps(d, cell, **kw):
-    t, s = NdtMatcher3D(cell_size=cell, **kw), NdtMatcher3D(cell_size=cell)
+    t, s = NdtMatcher3D(cell_size=cell, map_neighbourhood=MAP_NB, **kw), NdtMatcher3D(cell_size=cell)
     t.set_target(d["tx"], d["ty"], d["tz"])
     s.set_target(d["sx"], d["sy"], d["sz"])
     return t, s
@@ -79,8 +86,9 @@ def main():
     d = synth3d.make_pair3d()
     zero = (0.0,) * 6
     near = tuple(np.array(d["pose"]) + np.array([0.05, -0.05, 0.02, 0.005, -0.005, 0.005]))
-    out = {"true_pose": list(d["pose"])}
+    out = {"true_pose": list(d["pose"]), "map_neighbourhood": MAP_NB}
     out["maps_1m"] = map_case(d, 1.0, near, reps)
+    out["maps_1m_zero"] = map_case(d, 1.0, zero, reps)
     out["maps_2m"] = map_case(d, 2.0, zero, reps)
     t2, s2 = pair_of_maps(d, 2.0)
     t1, s1 = pair_of_maps(d, 1.0)
